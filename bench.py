@@ -11,6 +11,13 @@ resident in HBM before the timed region.  value = frame pixels * steps / time.
     python bench.py --gpus N              # ONE process drives N GPUs through one bhray_ctx (the reference's host model)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N   # one process per GPU, one ctx each;
                                           # torch.distributed (gloo) only carries the barrier and the 128-byte communicator id
+    python bench.py --full                # + every secondary figure below (roofline, sustained, latency, literal, hand-off, ...)
+    python bench.py --dump-outputs DIR    # + the last timed frame as DIR/frame.npy (float32)
+
+A plain run sets up, warms up (--warmup frames), times ONE block of exactly --steps frames, writes its outputs if asked and prints the
+line: metric, value, unit, ms_per_step (= the block's time / --steps), higher_is_better, dtype and the configuration.  Everything else
+it measures or checks runs only with --full: the counted frame (traced rays, roofline), the sustained block, the latency / literal /
+hand-off / moving-scene / drop-in legs, the CPU baseline and, at N > 1, the byte-for-byte check of the gathered frame.
 
 Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (trace_kernel; averaged over
 all its launches, i.e. the 4 ladder levels, so that it matches the per-kernel average of
@@ -27,8 +34,11 @@ import sys
 import time
 
 # Frames in flight run on separate HIP streams; ROCm maps streams onto 4 hardware queues by default, so 4+ streams
-# would serialise pairwise (measured: 8 queues are not enough once the N>1 path adds its side streams and RCCL's).  Must be set before the HIP runtime initialises; libbhray only READS it (the host owns the process environment).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "64")
+# would serialise pairwise (measured: 8 queues are not enough once the N>1 path adds its side streams and RCCL's).  Must be set before the HIP
+# runtime initialises; libbhray only READS it (the host owns the process environment).  32 is the most a process may open on a shared device;
+# libbhray gives 30 of them to frame slots, more than the 22 frames in flight of the headline.  Set, not defaulted: an environment that
+# exports ROCm's default of 4 would otherwise put the 22 slots on 2 streams and time another pipeline.
+os.environ["GPU_MAX_HW_QUEUES"] = "32"
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -110,6 +120,44 @@ def cpu_baseline(args, tex, cam, bh, det, model):
             "sample": f"CPU oracle (C restatement of ray.wgsl, OpenMP x{O.num_threads()}), one {last[0]}x{last[1]} frame "
                       f"(ladder {cfg.sizes()[0][0]}x{cfg.sizes()[0][1]} x3 x{args.levels}, same camera/scene, adaptive RK), "
                       f"{dt:.2f} s wall"}
+
+
+def differing_pixels(a, b) -> int:
+    """Pixels of two frames (RGBA32F, or the RGBA16F sky image) that differ: bit for bit, except the SIGN of a NaN.  DESIGN.md section 2,
+    "NaN sign": where the shader's arithmetic makes a NaN every build makes it in the same channels, but its sign is specified by neither WGSL
+    nor the contract and differs between builds of the same source (the one-slot latency build against the builds of a ctx with several
+    frame slots).  A NaN where the other frame has none counts, and so does every other bit.  -1 when the shapes differ."""
+    import numpy as np
+    if a.shape != b.shape:
+        return -1
+    word = np.uint16 if a.dtype == np.float16 else np.uint32
+    na, nb = np.isnan(a), np.isnan(b)
+    wa, wb = a.view(word).copy(), b.view(word).copy()
+    wa[na & nb] = 0
+    wb[na & nb] = 0
+    return int((wa != wb).any(axis=-1).sum())
+
+
+DUMP_BYTES = 48 << 20                            # --dump-outputs: a frame above this is written as a seeded sample of its pixels
+
+
+def dump_outputs(out_dir: str, rp, sky: bool = False) -> None:
+    """What the caller of the timed path receives from its last frame: the RGBA32F frame (bhray_read_hdr; at N > 1 the gathered frame on
+    the root), or with BHRAY_F_GATHER_SKY the RGBA16F sky image widened to float32.  The same arguments give the same inputs (seeded
+    textures, the same frame clock), so two builds can be compared array for array.  A frame above DUMP_BYTES keeps a fixed seeded sample
+    of its pixels (frame_sample.npy, pixels x 4) and their flat indices (frame_sample_index.npy, float64: exact)."""
+    import numpy as np
+    img = rp.read_sky().astype(np.float32) if sky else rp.read_hdr()
+    name = "sky" if sky else "frame"
+    os.makedirs(out_dir, exist_ok=True)
+    if img.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(out_dir, name + ".npy"), img)
+        return
+    flat = img.reshape(-1, img.shape[-1])
+    n = DUMP_BYTES // (flat.shape[1] * flat.itemsize + 8)
+    idx = np.sort(np.random.default_rng(20261016).choice(flat.shape[0], size=n, replace=False))
+    np.save(os.path.join(out_dir, name + "_sample.npy"), np.ascontiguousarray(flat[idx]))
+    np.save(os.path.join(out_dir, name + "_sample_index.npy"), idx.astype(np.float64))
 
 
 def auto_frames_per_batch(args, world: int) -> int:
@@ -297,17 +345,28 @@ def main():
                     "gathered (half the bytes over xGMI); the verification then compares sky images")
     ap.add_argument("--no-verify", action="store_true", help="N>1: skip the byte-for-byte comparison of the gathered frame with the frame rendered whole (on by default)")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the isolated / latency / literal / hand-off legs (profiling runs)")
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="the timed block of exactly --steps frames is repeated until this much time has been "
-                    "measured; the MEDIAN block is reported (a 20-step block lasts ~10 ms: one block alone is at the mercy of a clock ramp)")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="0 (default): ONE timed block of exactly --steps frames.  Above 0: the block is repeated until "
+                    "this much time has been measured and the MEDIAN block is reported (a 20-step block lasts ~10 ms: one block alone is at the mercy of a clock ramp; "
+                    "the committed bench lines under profiles/ were taken with 0.5)")
     ap.add_argument("--pmc-json", default="", help="PMC summary (profiles/summarize.py) collected from THIS command in the same session: enables valu.issue")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: the counted frame (traced rays, roofline, valu), "
+                    "the sustained block, the latency / literal / hand-off / moving-scene / drop-in legs, the CPU baseline and, at N > 1, the verification "
+                    "of the gathered frame (each still subject to its own --no-* option)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed block, write the frame the timed path delivered last as DIR/frame.npy "
+                    "(float32, rows x width x RGBA; DIR/sky.npy with --gather-sky); a frame above 48 MB is written as a fixed seeded sample of its pixels")
     args = ap.parse_args()
     if args.literal:
         args.eval = "literal"
     if args.readback is None:
         args.readback = "async"
     eval_kw = {"contract": {}, "literal": {"literal": True}, "fma": {"eval_fma": True}}[args.eval]
-    if args.gpus > 1 and not args.no_verify:
+    if args.gpus > 1 and not args.no_verify and args.full:
         args.verify = True
+    if not args.full:                             # a plain run: set-up, warm-up, the timed block, the outputs, the line
+        args.sustained_steps = 0
+        args.no_extra_legs = True
+        args.no_cpu_baseline = True
+        args.sequence = "none"
 
     lw, lrank, llocal = launcher_env()
     if lw > 1 and lw != args.gpus:
@@ -427,7 +486,7 @@ def main():
         partition_d = {"mode": "interleaved stripes", "stripe_rows": args.stripe_rows}
     counters = None
     rank_counters = None                         # --emulate-world: the work of the ONE rank this process renders (incl. its redundant coarse rows)
-    if lrank == 0:                               # algorithmic work of the frame: an untimed render of the undivided frame
+    if lrank == 0 and args.full:                 # algorithmic work of the frame: an untimed render of the undivided frame
         rpc = make_pass(whole=True, counters=True, frames_in_flight=1)
         rpc.render()
         counters = rpc.counters()
@@ -636,6 +695,8 @@ def main():
         if launcher.reduce(go, op="max")[0] == 0.0:
             break
     elapsed = sorted(blocks)[len(blocks) // 2]   # the median block of exactly --steps frames
+    if args.dump_outputs and rp is not None and info["root_is_local"]:
+        dump_outputs(args.dump_outputs, rp, sky=bool(main_kw.get("gather_sky")))        # before any leg renders another frame into the ctx
     # one long block with the same ctx: what the pass sustains once the pipeline is full (a 20-frame block is fill + drain of a ladder
     # whose dependent launches last as long as their longest rays, however few rays a GPU's row tiles hold: DESIGN.md §4.5)
     sustained = None
@@ -675,9 +736,8 @@ def main():
         rp.set_uniforms(cam.uniform(), bh.uniform(), det.uniform())       # the same frame through the partitioned ctx (the timed frames had their own times)
         rp.render()
         got = rp.read_sky() if sky_mode else rp.read_hdr()
-        word = np.uint16 if sky_mode else np.uint32
-        if got.shape != ref.shape or not np.array_equal(got.view(word), ref.view(word)):
-            bad = int((got.view(word) != ref.view(word)).any(axis=-1).sum()) if got.shape == ref.shape else -1
+        bad = differing_pixels(got, ref)          # (the timed ctx and this one-slot ctx run different builds: a NaN's sign may differ)
+        if bad != 0:
             print(f"bench: rank {lrank}: the gathered frame differs from the frame rendered whole on one GPU ({bad} pixels)", file=sys.stderr)
             sys.exit(3)
         verified = 1
@@ -932,7 +992,7 @@ def main():
             pt_.render(); pl_.render()
             a_, b_ = pt_.read_hdr(), pl_.read_hdr()
             nver_ += 1
-            if a_.shape != b_.shape or not np.array_equal(a_.view(np.uint32), b_.view(np.uint32)):
+            if differing_pixels(a_, b_) != 0:           # (four slots against one: different builds, a NaN's sign may differ)
                 bad_ += 1
         pt_.close(); pl_.close()
         if bad_:
@@ -967,156 +1027,157 @@ def main():
         pixels = args.width * args.height
         ms_per_step = elapsed / args.steps * 1e3
         value = pixels * args.steps / elapsed / 1e6
-        # dominant kernel: trace_kernel, from the launches of the GPU that delivers the frame (at N>1 it traced only its row
-        # tiles: its share of the algorithmic bytes is taken as rows/frame rows of the whole frame's)
-        # `avg_ms` = the kernel's EXECUTION span (first block start -> last block end, stamped by the kernel on the device clock): what
-        # rocprofv3 --kernel-trace reports as its duration.  HIP events around the launch (`enq_ms`) also contain the time the launch
-        # waits for room beside the persistent kernels of the other frames in flight - reported next to it, not used for the roofline.
-        launches = max(1, tm.trace_launches)
-        enq_ms = tm.trace_ms / launches
-        exec_launches = int(tm.trace_exec_launches)
-        avg_ms = tm.trace_exec_ms / exec_launches if exec_launches else enq_ms
-        frames = max(1, tm.frames)
-        share = 1.0
-        if n_gpus > 1:       # the rows the delivering GPU traced itself (its tiles do not travel)
-            wire_row_ = args.width * 8 if main_kw.get("gather_sky") else (3 * args.width + (args.width + 31) // 32) * 4
-            share = info["bytes_received_per_frame"] and 1.0 - info["bytes_received_per_frame"] / float(wire_row_ * args.height)
-        work = rank_counters if rank_counters is not None else counters      # --emulate-world: this rank's own rays, not the whole frame's
-        bytes_per_launch = algorithmic_bytes_trace(work) * share * frames / launches
-        achieved_gbs = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        method = 1 if args.integrator == "rk" else 0
-        flops_per_frame = algorithmic_flops(work, method)     # per GPU when emulating one rank of N
-        # HBM traffic of the same kernel from the committed PMC passes (profiles/collect.sh: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE,
-        # separate passes of the default command); the instruction-issue view only from a PMC summary of THIS session (--pmc-json)
-        traffic, traffic_note, valu_issue = None, None, None
-        default_cmd = args.workload == "disk" and n_gpus == 1 and args.integrator == "rk" and (args.width, args.height) == (1920, 1080) and args.eval == "contract" and not args.emulate_world
-        # the committed PMC summaries (profiles/collect.sh) of the four profiled commands
-        prof_wl = None
-        if n_gpus == 1 and args.eval == "contract" and not args.emulate_world:
-            key = (args.workload, args.integrator, args.width, args.height)
-            prof_wl = {("disk", "rk", 1920, 1080): "default", ("disk", "euler", 1920, 1080): "euler", ("mesh", "rk", 1920, 1080): "mesh", ("disk", "rk", 3840, 2160): "4k"}.get(key)
-        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json" if prof_wl in (None, "default") else f"pmc_traffic_{prof_wl}.json")
-        default_cmd = prof_wl is not None
-        if os.path.exists(tpath) and default_cmd:
-            tj = json.load(open(tpath))
-            traffic = round(tj["bytes_per_launch_corrected"], 1)
-            traffic_note = (f"committed PMC passes of this command (profiles/{tj['tag']}_pmc{'' if prof_wl == 'default' else '_' + prof_wl}.json, not this run): FETCH_SIZE {tj['FETCH_SIZE_KB_per_launch']:.0f} KB x2 "
-                            f"(gfx950 correction) + WRITE_SIZE {tj['WRITE_SIZE_KB_per_launch']:.0f} KB per launch; raw sum {tj['bytes_per_launch_raw']:.0f} B")
-        issue_src = args.pmc_json if (args.pmc_json and os.path.exists(args.pmc_json)) else (tpath if os.path.exists(tpath) else "")
-        if issue_src and default_cmd:
-            tj = json.load(open(issue_src))
-            if "valu_insts_per_launch" in tj:
-                insts_frame = tj["valu_insts_per_launch"] * launches / frames
-                issue_cap = NUM_CUS * 4 * (CLOCK_GHZ * 1e9 / 2.0) * (ms_per_step * 1e-3)
-                valu_issue = {"valu_wave_insts_per_frame": round(insts_frame, 0), "frac_of_issue_rate": round(insts_frame / issue_cap, 4),
-                              "active_lane_fraction": round(tj.get("valu_active_lane_fraction", 0.0), 4) or None,
-                              "source": os.path.relpath(issue_src, ROOT) + ("" if args.pmc_json else " (committed PMC pass of the default command on this tree, not this run)"),
-                              "note": "SQ_INSTS_VALU of trace_kernel (PMC pass of this command) x launches per frame of this run, / "
-                                      "(256 CUs x 4 SIMDs x 1.2e9 wave-instructions/s x wall time per frame)"}
-        valu_tflops = flops_per_frame / (ms_per_step * 1e-3) / 1e12 / n_gpus    # per GPU: (whole-frame | this rank's) flops / wall per frame / GPUs
-        # the same fraction from the COMMITTED rocprofv3 --kernel-trace --stats summary of this command (profiles/<tag>_kernel_stats*.csv):
-        # the kernel's average duration there, so that a reader need not reconcile the in-run span with the CSV
-        frac_from_profiles = None
-        if prof_wl is not None:
-            import csv
-            import glob
-            cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "r0*_kernel_stats" + ("" if prof_wl == "default" else "_" + prof_wl) + ".csv")))
-            if cands:
-                with open(cands[-1]) as fcsv:
-                    rows_ = [r_ for r_ in csv.DictReader(fcsv) if "trace_kernel" in r_["Name"]]
-                if rows_:
-                    calls_ = sum(int(r_["Calls"]) for r_ in rows_)
-                    avg_ns_ = sum(float(r_["TotalDurationNs"]) for r_ in rows_) / max(1, calls_)
-                    gbs_ = bytes_per_launch / (avg_ns_ * 1e-9) / 1e9
-                    frac_from_profiles = {"source": os.path.relpath(cands[-1], ROOT), "avg_launch_ms": round(avg_ns_ * 1e-6, 5), "calls": calls_,
-                                          "achieved": round(gbs_, 4), "frac": round(gbs_ / HBM_PEAK_GBS, 6),
-                                          "note": "algorithmic bytes per launch of THIS run / the trace kernel's average duration in the committed rocprofv3 summary of the same command "
-                                                  "(a profiled run: fewer launches overlap than un-profiled, DESIGN.md §5)"}
-        iso_d = None
-        if iso is not None and iso.trace_launches:
-            iso_ms = iso.trace_ms / iso.trace_launches
-            iso_bytes = algorithmic_bytes_trace(counters) * iso.frames / iso.trace_launches
-            iso_gbs = iso_bytes / (iso_ms * 1e-3) / 1e9
-            iso_d = {"avg_launch_ms": round(iso_ms, 5), "launches": int(iso.trace_launches), "achieved": round(iso_gbs, 4),
-                     "frac": round(iso_gbs / HBM_PEAK_GBS, 6),
-                     "level_trace_ms": [round(iso.level_trace_ms[i] / max(1, iso.frames), 5) for i in range(args.levels)],
-                     "valu_tflops": round(flops_per_frame * iso.frames / (iso.trace_ms * 1e-3) / 1e12, 4),
-                     "note": "same kernels, one frame in flight, nothing else on the device (matches rocprofv3 --stats of `bench.py --frames-in-flight 1`)"}
-        sky_d = None
-        if iso_sky is not None and iso_sky.sky_launches:
-            sky_ms = iso_sky.sky_ms / iso_sky.sky_launches
-            sky_bytes = pixels * 24.0 + counters_sky_taps(counters, pixels) * 16.0
-            sky_d = {"kernel": "sky_kernel (sky.wgsl, rgba32f -> rgba16f)", "avg_launch_ms": round(sky_ms, 5), "launches": int(iso_sky.sky_launches),
-                     "algorithmic_bytes_per_launch": sky_bytes, "achieved": round(sky_bytes / (sky_ms * 1e-3) / 1e9, 2), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(sky_bytes / (sky_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                     "note": "16 B read + 8 B written per pixel + 16 B of sky texels per direction pixel; not part of `value`"}
-        gather_d = None
-        if n_gpus > 1:
-            g = max(1, tm.gathers)
-            gather_d = {"transport": "RCCL grouped ncclSend/ncclRecv inside libbhray (dlopen'ed librccl %d), enqueued by bhray_render" % info["rccl_version"],
-                        "process_model": ("one process, %d GPUs, one bhray_ctx" % n_gpus) if model_ == "single" else "one process per GPU (launcher), one bhray_ctx each",
-                        "process_model_fallback": fallback,
-                        "fallbacks": gather_fallbacks or None,
-                        "devices": devices, "comm_ranks": info["comm_ranks"], "root": info["root"],
-                        "bytes_received_per_frame": info["bytes_received_per_frame"],
-                        "gathered_image": "RGBA16F sky image (BHRAY_F_GATHER_SKY: every partition resolves the sky over its own rows, 8 B per pixel travel)" if main_kw.get("gather_sky") else "RGBA32F frame (travels packed - x, y, z + one bit of alpha, which is exactly 0 or 1: 12.1 B per pixel - and is unpacked by the root's de-interleave: the same bits)",
-                        "batches_gathered": int(tm.gathers), "receive_ms_per_batch": round(tm.gather_ms / g, 5),
-                        "deinterleave_ms_per_batch": round(tm.deinterleave_ms / g, 5),
-                        "note": "receive = first ncclRecv enqueued -> all tiles of the batch arrived (includes waiting for the slowest partition's render); "
-                                "de-interleave = HIP kernel, staging rows -> frame rows, HBM-bound"}
-        # N > 1: what the committed per-rank emulation (every rank of the partition rendered in turn on ONE GPU, before the gather: profiles/r04_emulate_*.json,
-        # profiles/emulate_all_ranks.sh) says this command should scale like, and what the links allow - so that a hardware number can be read against both
-        expected_d = None
-        if n_gpus > 1:
-            tagf = {(1920, 1080): "1080p", (3840, 2160): "4k", (7680, 4320): "8k"}.get((args.width, args.height))
-            epath = os.path.join(ROOT, "profiles", f"r04_emulate_{tagf}.json") if tagf else ""
-            emu = json.load(open(epath)) if epath and os.path.exists(epath) else {}
-            short_, long_ = emu.get(f"{tagf}_n{n_gpus}_short", {}), emu.get(f"{tagf}_n{n_gpus}_long", {})
-            per_link_mb = info["bytes_received_per_frame"] / max(1, n_gpus - 1) / 1e6
-            link_gbs = 48.0
-            # both gathers, whichever this run used: the rows the root receives x the bytes a row has on the wire
-            wire_used_ = args.width * 8 if main_kw.get("gather_sky") else (3 * args.width + (args.width + 31) // 32) * 4
-            rows_received_ = info["bytes_received_per_frame"] / float(wire_used_)
-            n1_ms_ = (emu.get("n1_long", {}).get("ms_per_step") or ms_per_step * n_gpus)
+        if args.full:
+            # dominant kernel: trace_kernel, from the launches of the GPU that delivers the frame (at N>1 it traced only its row
+            # tiles: its share of the algorithmic bytes is taken as rows/frame rows of the whole frame's)
+            # `avg_ms` = the kernel's EXECUTION span (first block start -> last block end, stamped by the kernel on the device clock): what
+            # rocprofv3 --kernel-trace reports as its duration.  HIP events around the launch (`enq_ms`) also contain the time the launch
+            # waits for room beside the persistent kernels of the other frames in flight - reported next to it, not used for the roofline.
+            launches = max(1, tm.trace_launches)
+            enq_ms = tm.trace_ms / launches
+            exec_launches = int(tm.trace_exec_launches)
+            avg_ms = tm.trace_exec_ms / exec_launches if exec_launches else enq_ms
+            frames = max(1, tm.frames)
+            share = 1.0
+            if n_gpus > 1:       # the rows the delivering GPU traced itself (its tiles do not travel)
+                wire_row_ = args.width * 8 if main_kw.get("gather_sky") else (3 * args.width + (args.width + 31) // 32) * 4
+                share = info["bytes_received_per_frame"] and 1.0 - info["bytes_received_per_frame"] / float(wire_row_ * args.height)
+            work = rank_counters if rank_counters is not None else counters      # --emulate-world: this rank's own rays, not the whole frame's
+            bytes_per_launch = algorithmic_bytes_trace(work) * share * frames / launches
+            achieved_gbs = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            method = 1 if args.integrator == "rk" else 0
+            flops_per_frame = algorithmic_flops(work, method)     # per GPU when emulating one rank of N
+            # HBM traffic of the same kernel from the committed PMC passes (profiles/collect.sh: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE,
+            # separate passes of the default command); the instruction-issue view only from a PMC summary of THIS session (--pmc-json)
+            traffic, traffic_note, valu_issue = None, None, None
+            default_cmd = args.workload == "disk" and n_gpus == 1 and args.integrator == "rk" and (args.width, args.height) == (1920, 1080) and args.eval == "contract" and not args.emulate_world
+            # the committed PMC summaries (profiles/collect.sh) of the four profiled commands
+            prof_wl = None
+            if n_gpus == 1 and args.eval == "contract" and not args.emulate_world:
+                key = (args.workload, args.integrator, args.width, args.height)
+                prof_wl = {("disk", "rk", 1920, 1080): "default", ("disk", "euler", 1920, 1080): "euler", ("mesh", "rk", 1920, 1080): "mesh", ("disk", "rk", 3840, 2160): "4k"}.get(key)
+            tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json" if prof_wl in (None, "default") else f"pmc_traffic_{prof_wl}.json")
+            default_cmd = prof_wl is not None
+            if os.path.exists(tpath) and default_cmd:
+                tj = json.load(open(tpath))
+                traffic = round(tj["bytes_per_launch_corrected"], 1)
+                traffic_note = (f"committed PMC passes of this command (profiles/{tj['tag']}_pmc{'' if prof_wl == 'default' else '_' + prof_wl}.json, not this run): FETCH_SIZE {tj['FETCH_SIZE_KB_per_launch']:.0f} KB x2 "
+                                f"(gfx950 correction) + WRITE_SIZE {tj['WRITE_SIZE_KB_per_launch']:.0f} KB per launch; raw sum {tj['bytes_per_launch_raw']:.0f} B")
+            issue_src = args.pmc_json if (args.pmc_json and os.path.exists(args.pmc_json)) else (tpath if os.path.exists(tpath) else "")
+            if issue_src and default_cmd:
+                tj = json.load(open(issue_src))
+                if "valu_insts_per_launch" in tj:
+                    insts_frame = tj["valu_insts_per_launch"] * launches / frames
+                    issue_cap = NUM_CUS * 4 * (CLOCK_GHZ * 1e9 / 2.0) * (ms_per_step * 1e-3)
+                    valu_issue = {"valu_wave_insts_per_frame": round(insts_frame, 0), "frac_of_issue_rate": round(insts_frame / issue_cap, 4),
+                                  "active_lane_fraction": round(tj.get("valu_active_lane_fraction", 0.0), 4) or None,
+                                  "source": os.path.relpath(issue_src, ROOT) + ("" if args.pmc_json else " (committed PMC pass of the default command on this tree, not this run)"),
+                                  "note": "SQ_INSTS_VALU of trace_kernel (PMC pass of this command) x launches per frame of this run, / "
+                                          "(256 CUs x 4 SIMDs x 1.2e9 wave-instructions/s x wall time per frame)"}
+            valu_tflops = flops_per_frame / (ms_per_step * 1e-3) / 1e12 / n_gpus    # per GPU: (whole-frame | this rank's) flops / wall per frame / GPUs
+            # the same fraction from the COMMITTED rocprofv3 --kernel-trace --stats summary of this command (profiles/<tag>_kernel_stats*.csv):
+            # the kernel's average duration there, so that a reader need not reconcile the in-run span with the CSV
+            frac_from_profiles = None
+            if prof_wl is not None:
+                import csv
+                import glob
+                cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "r0*_kernel_stats" + ("" if prof_wl == "default" else "_" + prof_wl) + ".csv")))
+                if cands:
+                    with open(cands[-1]) as fcsv:
+                        rows_ = [r_ for r_ in csv.DictReader(fcsv) if "trace_kernel" in r_["Name"]]
+                    if rows_:
+                        calls_ = sum(int(r_["Calls"]) for r_ in rows_)
+                        avg_ns_ = sum(float(r_["TotalDurationNs"]) for r_ in rows_) / max(1, calls_)
+                        gbs_ = bytes_per_launch / (avg_ns_ * 1e-9) / 1e9
+                        frac_from_profiles = {"source": os.path.relpath(cands[-1], ROOT), "avg_launch_ms": round(avg_ns_ * 1e-6, 5), "calls": calls_,
+                                              "achieved": round(gbs_, 4), "frac": round(gbs_ / HBM_PEAK_GBS, 6),
+                                              "note": "algorithmic bytes per launch of THIS run / the trace kernel's average duration in the committed rocprofv3 summary of the same command "
+                                                      "(a profiled run: fewer launches overlap than un-profiled, DESIGN.md §5)"}
+            iso_d = None
+            if iso is not None and iso.trace_launches:
+                iso_ms = iso.trace_ms / iso.trace_launches
+                iso_bytes = algorithmic_bytes_trace(counters) * iso.frames / iso.trace_launches
+                iso_gbs = iso_bytes / (iso_ms * 1e-3) / 1e9
+                iso_d = {"avg_launch_ms": round(iso_ms, 5), "launches": int(iso.trace_launches), "achieved": round(iso_gbs, 4),
+                         "frac": round(iso_gbs / HBM_PEAK_GBS, 6),
+                         "level_trace_ms": [round(iso.level_trace_ms[i] / max(1, iso.frames), 5) for i in range(args.levels)],
+                         "valu_tflops": round(flops_per_frame * iso.frames / (iso.trace_ms * 1e-3) / 1e12, 4),
+                         "note": "same kernels, one frame in flight, nothing else on the device (matches rocprofv3 --stats of `bench.py --frames-in-flight 1`)"}
+            sky_d = None
+            if iso_sky is not None and iso_sky.sky_launches:
+                sky_ms = iso_sky.sky_ms / iso_sky.sky_launches
+                sky_bytes = pixels * 24.0 + counters_sky_taps(counters, pixels) * 16.0
+                sky_d = {"kernel": "sky_kernel (sky.wgsl, rgba32f -> rgba16f)", "avg_launch_ms": round(sky_ms, 5), "launches": int(iso_sky.sky_launches),
+                         "algorithmic_bytes_per_launch": sky_bytes, "achieved": round(sky_bytes / (sky_ms * 1e-3) / 1e9, 2), "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s", "frac": round(sky_bytes / (sky_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                         "note": "16 B read + 8 B written per pixel + 16 B of sky texels per direction pixel; not part of `value`"}
+            gather_d = None
+            if n_gpus > 1:
+                g = max(1, tm.gathers)
+                gather_d = {"transport": "RCCL grouped ncclSend/ncclRecv inside libbhray (dlopen'ed librccl %d), enqueued by bhray_render" % info["rccl_version"],
+                            "process_model": ("one process, %d GPUs, one bhray_ctx" % n_gpus) if model_ == "single" else "one process per GPU (launcher), one bhray_ctx each",
+                            "process_model_fallback": fallback,
+                            "fallbacks": gather_fallbacks or None,
+                            "devices": devices, "comm_ranks": info["comm_ranks"], "root": info["root"],
+                            "bytes_received_per_frame": info["bytes_received_per_frame"],
+                            "gathered_image": "RGBA16F sky image (BHRAY_F_GATHER_SKY: every partition resolves the sky over its own rows, 8 B per pixel travel)" if main_kw.get("gather_sky") else "RGBA32F frame (travels packed - x, y, z + one bit of alpha, which is exactly 0 or 1: 12.1 B per pixel - and is unpacked by the root's de-interleave: the same bits)",
+                            "batches_gathered": int(tm.gathers), "receive_ms_per_batch": round(tm.gather_ms / g, 5),
+                            "deinterleave_ms_per_batch": round(tm.deinterleave_ms / g, 5),
+                            "note": "receive = first ncclRecv enqueued -> all tiles of the batch arrived (includes waiting for the slowest partition's render); "
+                                    "de-interleave = HIP kernel, staging rows -> frame rows, HBM-bound"}
+            # N > 1: what the committed per-rank emulation (every rank of the partition rendered in turn on ONE GPU, before the gather: profiles/r04_emulate_*.json,
+            # profiles/emulate_all_ranks.sh) says this command should scale like, and what the links allow - so that a hardware number can be read against both
+            expected_d = None
+            if n_gpus > 1:
+                tagf = {(1920, 1080): "1080p", (3840, 2160): "4k", (7680, 4320): "8k"}.get((args.width, args.height))
+                epath = os.path.join(ROOT, "profiles", f"r04_emulate_{tagf}.json") if tagf else ""
+                emu = json.load(open(epath)) if epath and os.path.exists(epath) else {}
+                short_, long_ = emu.get(f"{tagf}_n{n_gpus}_short", {}), emu.get(f"{tagf}_n{n_gpus}_long", {})
+                per_link_mb = info["bytes_received_per_frame"] / max(1, n_gpus - 1) / 1e6
+                link_gbs = 48.0
+                # both gathers, whichever this run used: the rows the root receives x the bytes a row has on the wire
+                wire_used_ = args.width * 8 if main_kw.get("gather_sky") else (3 * args.width + (args.width + 31) // 32) * 4
+                rows_received_ = info["bytes_received_per_frame"] / float(wire_used_)
+                n1_ms_ = (emu.get("n1_long", {}).get("ms_per_step") or ms_per_step * n_gpus)
 
-            def links_for_(wire_row_bytes):
-                mb_ = rows_received_ * wire_row_bytes / max(1, n_gpus - 1) / 1e6
-                return {"mb_per_frame_and_link_into_the_root": round(mb_, 3), "ms_per_frame_on_the_links": round(mb_ / link_gbs, 5),
-                        "link_bound_scaling": round(n1_ms_ / max(1e-9, mb_ / link_gbs), 2)}
-            links_by_gather = {"rgba32f_packed": links_for_((3 * args.width + (args.width + 31) // 32) * 4), "rgba16f_sky": links_for_(args.width * 8),
-                               "used": "rgba16f_sky" if main_kw.get("gather_sky") else "rgba32f_packed",
-                               "why": ("--gather-sky: the RGBA16F image of the sky pass travels (BHRAY_F_GATHER_SKY: 8 bytes per pixel; the RGBA32F frame is never assembled)" if main_kw.get("gather_sky") else
-                                       "the RGBA32F frame is gathered by default because that is what the metric names - north_star: `an RCCL gather over xGMI of the per-tile HDR buffer` of the RAY pass, "
-                                       "the texture RayPipeline::output_view hands to the sky pass (ray_pipeline.rs:297-299) - although the root's links bound it earlier (link_bound_scaling); "
-                                       "a host that only displays the frame gathers the sky pass's RGBA16F image instead: `--gather-sky`, half the bytes, the same pixels on screen (tests/test_gpu_multidevice.py)"),
-                               "assumed_gb_per_s_per_link_one_way": link_gbs, "n1_ms_per_frame": round(n1_ms_, 5)}
-            expected_d = {"source": os.path.relpath(epath, ROOT) if emu else None,
-                          "slowest_rank_scaling_in_blocks_of_%d_frames" % emu.get("n1_short", {}).get("steps", 20): short_.get("scaling"),
-                          "slowest_rank_scaling_sustained": long_.get("scaling"),
-                          "note": "compute only: the slowest rank's time per frame against the undivided frame on one GPU, emulated rank by rank; a block of exactly --steps frames is a chain "
-                                  "of dependent ray generations per batch (chain-bound), a long block is throughput-bound",
-                          "link_bound_scaling": links_by_gather,
-                          "links": {"mb_per_frame_and_link_into_the_root": round(per_link_mb, 3), "assumed_gb_per_s_per_link_one_way": link_gbs,
-                                    "ms_per_frame_on_the_links": round(per_link_mb / link_gbs, 5),
-                                    "scaling_bound_by_the_links": round((emu.get("n1_long", {}).get("ms_per_step") or ms_per_step * n_gpus) / max(1e-9, per_link_mb / link_gbs), 2) if emu else None,
-                                    "note": "every frame's tiles travel to the root over its %d links in parallel; the gather of a batch overlaps the next batch's render, so the links bound the SUSTAINED rate "
-                                            "(and add the last batch's transfer to a short block).  48 GB/s one way per link is what RCCL send/recv typically sustains over xGMI - an assumption here, no "
-                                            "multi-GPU box was available to this build; --gather-sky halves the bytes" % (n_gpus - 1)}}
-        traced_rate = counters["traced"] * args.steps / elapsed / 1e6
-        ref_host_regime = None
-        try:
-            leg_ = dropin["legs"]["async_sky_rgba16f_2_in_flight"]
-            ref_host_regime = {"value": leg_["mrays_per_s"], "ms_per_frame": leg_["ms_per_frame"], "frames_in_flight": leg_["frames_in_flight"], "leg": "dropin.legs.async_sky_rgba16f_2_in_flight",
-                               "frame": dropin.get("frame"), "note": "bhusie_amd/bhray_render --dropin: update + pass + sky pass + hand-off per frame, PCIe-inclusive, without BHRAY_F_TEMPORAL"}
-        except (TypeError, KeyError):
-            pass
-        # the compiler libbhray was (or would be) built with on this box - the kernels' performance is a property of its schedule (VERDICT r5 weak 9;
-        # __graft_entry__.build() refuses another major.minor, tests/test_gpu_perf_guard.py holds the numbers)
-        try:
-            import __graft_entry__ as ge_
-            toolchain_d = dict(ge_.hipcc_version(), pinned_major_minor=ge_.PINNED_HIP)
-        except Exception as e_:                  # never fail the bench line over the version string
-            toolchain_d = {"error": f"{type(e_).__name__}: {e_}"}
+                def links_for_(wire_row_bytes):
+                    mb_ = rows_received_ * wire_row_bytes / max(1, n_gpus - 1) / 1e6
+                    return {"mb_per_frame_and_link_into_the_root": round(mb_, 3), "ms_per_frame_on_the_links": round(mb_ / link_gbs, 5),
+                            "link_bound_scaling": round(n1_ms_ / max(1e-9, mb_ / link_gbs), 2)}
+                links_by_gather = {"rgba32f_packed": links_for_((3 * args.width + (args.width + 31) // 32) * 4), "rgba16f_sky": links_for_(args.width * 8),
+                                   "used": "rgba16f_sky" if main_kw.get("gather_sky") else "rgba32f_packed",
+                                   "why": ("--gather-sky: the RGBA16F image of the sky pass travels (BHRAY_F_GATHER_SKY: 8 bytes per pixel; the RGBA32F frame is never assembled)" if main_kw.get("gather_sky") else
+                                           "the RGBA32F frame is gathered by default because that is what the metric names - north_star: `an RCCL gather over xGMI of the per-tile HDR buffer` of the RAY pass, "
+                                           "the texture RayPipeline::output_view hands to the sky pass (ray_pipeline.rs:297-299) - although the root's links bound it earlier (link_bound_scaling); "
+                                           "a host that only displays the frame gathers the sky pass's RGBA16F image instead: `--gather-sky`, half the bytes, the same pixels on screen (tests/test_gpu_multidevice.py)"),
+                                   "assumed_gb_per_s_per_link_one_way": link_gbs, "n1_ms_per_frame": round(n1_ms_, 5)}
+                expected_d = {"source": os.path.relpath(epath, ROOT) if emu else None,
+                              "slowest_rank_scaling_in_blocks_of_%d_frames" % emu.get("n1_short", {}).get("steps", 20): short_.get("scaling"),
+                              "slowest_rank_scaling_sustained": long_.get("scaling"),
+                              "note": "compute only: the slowest rank's time per frame against the undivided frame on one GPU, emulated rank by rank; a block of exactly --steps frames is a chain "
+                                      "of dependent ray generations per batch (chain-bound), a long block is throughput-bound",
+                              "link_bound_scaling": links_by_gather,
+                              "links": {"mb_per_frame_and_link_into_the_root": round(per_link_mb, 3), "assumed_gb_per_s_per_link_one_way": link_gbs,
+                                        "ms_per_frame_on_the_links": round(per_link_mb / link_gbs, 5),
+                                        "scaling_bound_by_the_links": round((emu.get("n1_long", {}).get("ms_per_step") or ms_per_step * n_gpus) / max(1e-9, per_link_mb / link_gbs), 2) if emu else None,
+                                        "note": "every frame's tiles travel to the root over its %d links in parallel; the gather of a batch overlaps the next batch's render, so the links bound the SUSTAINED rate "
+                                                "(and add the last batch's transfer to a short block).  48 GB/s one way per link is what RCCL send/recv typically sustains over xGMI - an assumption here, no "
+                                                "multi-GPU node has measured it for this project yet; --gather-sky halves the bytes" % (n_gpus - 1)}}
+            traced_rate = counters["traced"] * args.steps / elapsed / 1e6
+            ref_host_regime = None
+            try:
+                leg_ = dropin["legs"]["async_sky_rgba16f_2_in_flight"]
+                ref_host_regime = {"value": leg_["mrays_per_s"], "ms_per_frame": leg_["ms_per_frame"], "frames_in_flight": leg_["frames_in_flight"], "leg": "dropin.legs.async_sky_rgba16f_2_in_flight",
+                                   "frame": dropin.get("frame"), "note": "bhusie_amd/bhray_render --dropin: update + pass + sky pass + hand-off per frame, PCIe-inclusive, without BHRAY_F_TEMPORAL"}
+            except (TypeError, KeyError):
+                pass
+            # the compiler libbhray was (or would be) built with where the bench runs - the kernels' performance is a property of its schedule (VERDICT r5 weak 9;
+            # __graft_entry__.build() refuses another major.minor, tests/test_gpu_perf_guard.py holds the numbers)
+            try:
+                import __graft_entry__ as ge_
+                toolchain_d = dict(ge_.hipcc_version(), pinned_major_minor=ge_.PINNED_HIP)
+            except Exception as e_:                  # never fail the bench line over the version string
+                toolchain_d = {"error": f"{type(e_).__name__}: {e_}"}
         out = {
             "metric": "Mrays/sec at 1920x1080 adaptive-RK4; 1/2/4/8 MI355X + % HBM roofline",
             "value": round(value, 3), "unit": "Mrays/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
@@ -1130,14 +1191,8 @@ def main():
                                 f"GPU_MAX_HW_QUEUES = {os.environ.get('GPU_MAX_HW_QUEUES')} exported before HIP initialises (bench.py does; ROCm's default of 4 "
                                 "serialises the streams pairwise).  The reference host presents every frame (frame latency 2): its regimes are "
                                 "latency_ms_one_frame_in_flight and `dropin`",
-            "traced_mrays_per_s": round(traced_rate, 3),
-            "traced_fraction_of_frame_pixels": round(counters["traced"] / float(pixels), 4),
-            "latency_ms_one_frame_in_flight": round(lat_ms, 4) if lat_ms else None,
-            "latency_ms_one_frame_in_flight_by_mode": lat_modes,
-            "mrays_per_s_one_frame_in_flight": round(pixels / (lat_ms * 1e-3) / 1e6, 2) if lat_ms else None,
             "host_issue_ms_per_step": round(host_issue_ms, 5),
-            "sustained": sustained,
-            "timed_blocks": {"blocks": len(blocks), "steps_per_block": args.steps, "reported": "median block",
+            "timed_blocks": {"blocks": len(blocks), "steps_per_block": args.steps, "reported": "median block" if len(blocks) > 1 else "the one block",
                              "block_ms": {"min": round(min(blocks) * 1e3, 4), "median": round(elapsed * 1e3, 4), "max": round(max(blocks) * 1e3, 4), "first": round(blocks[0] * 1e3, 4)},
                              "note": "every block = exactly --steps frames bracketed by barrier + full device synchronisation (pipeline fill and drain inside)"},
             "config": {
@@ -1152,62 +1207,73 @@ def main():
                 "frames_in_flight": args.frames_in_flight, "frames_per_batch": fpb, "gather_root": (args.gather_root if n_gpus > 1 else None),
                 "verified_frames": verified, "speculative_levels": spec, "superset_levels": args.superset_levels, "readback_to_host": args.readback,
                 "integrator_evaluation": args.eval, "emulated_rank": ([args.emulate_rank, args.emulate_world] if args.emulate_world else None),
+            },
+        }
+        if args.full:
+            out["config"].update({
                 # (repeated here from the top level: the driver's `parsed` record keeps `config` whole and lists the other keys by name only)
                 "mrays_per_s_reference_host_regime": ref_host_regime,
                 "value_literal": literal_d["mrays_per_s"] if literal_d else None,
                 "pixels_beyond_1e-4_vs_shader_text": ({k_: literal_d["distance_of_the_headline_kernel"][k_] for k_ in ("pixels_beyond_1e-4", "pixels", "fraction_beyond_1e-4", "class_differences", "max_rel_err")}
                                                       if literal_d else None),
                 "toolchain": toolchain_d,
-            },
-            "roofline": {
-                "bound": "hbm", "kernel": "trace_kernel", "achieved": round(achieved_gbs, 4), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved_gbs / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_note": traffic_note,
-                "avg_launch_ms": round(avg_ms, 5), "launches": exec_launches or int(tm.trace_launches),
-                "avg_launch_ms_definition": "execution span of the kernel (first block start -> last block end on the device clock, stamped by the kernel: bhray_timing.trace_exec_ms); "
-                                            "agrees with rocprofv3 --kernel-trace --stats of this command (profiles/)" if exec_launches else "HIP events around the launch (no execution spans recorded)",
-                "avg_launch_ms_enqueue_to_complete": round(enq_ms, 5),
-                "algorithmic_bytes_per_launch": round(bytes_per_launch, 1),
-                "concurrency": f"{args.frames_in_flight} frames in flight: a launch shares the device with the kernels it overlaps with; spans and events are taken on "
-                               "every 4th batch of the timed region (every event is a packet in the stream: all of them cost 1.6 %)",
-                "isolated": iso_d,
-                "frac_from_profiles": frac_from_profiles,
-                "secondary": {"bound": "valu", "achieved": round(valu_tflops, 4), "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-                              "frac": round(valu_tflops / VALU_PEAK_TFLOPS, 6)},
-                "note": "the metric names the HBM roofline, so `bound`/`frac` are HBM; the kernel is a VALU-bound f32 ODE march (SURVEY.md F8: ~20 "
-                        "algorithmic bytes per traced ray against ~96 kflop), so the fraction that says something about the kernel is `secondary` (= `valu`)",
-            },
-            "valu": {"achieved": round(valu_tflops, 4), "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(valu_tflops / VALU_PEAK_TFLOPS, 6),
-                     "algorithmic_flops_per_frame": flops_per_frame,
-                     "one_frame_in_flight": ({"achieved": round(flops_per_frame / (lat_ms * 1e-3) / 1e12, 4), "frac": round(flops_per_frame / (lat_ms * 1e-3) / 1e12 / VALU_PEAK_TFLOPS, 6),
-                                              "note": "the same flops / latency_ms_one_frame_in_flight: the reference host's regime, where every launch lasts as long as its longest ray"}
-                                             if lat_ms else None),
-                     "issue": valu_issue,
-                     "note": "algorithmic flops per frame (390 per RK step as the shader text counts them; the kernel issues fewer operations since N9/N10) / "
-                             "wall time per frame of the median block; peak = the FMA rate"},
-            "pass_ms": {"event_total": round(tm.total_ms / frames, 5), "trace": round(tm.trace_ms / frames, 5),
-                        "classify": round(tm.classify_ms / frames, 5),
-                        "level_trace": [round(tm.level_trace_ms[i] / frames, 5) for i in range(args.levels)]},
-            "gather": gather_d,
-            "expected_scaling": expected_d,
-            # the reference host's regime as a second headline: the C++ mirror of the Rust shim - one host thread, the shipped 72x41 x3 x4
-            # ladder, two frames in flight (mod.rs:108 desired_maximum_frame_latency: 2), every frame through the sky pass and handed to pinned host memory as
-            # RGBA16F, NO temporal history - from the `dropin` leg of this run
-            "mrays_per_s_reference_host_regime": ref_host_regime,
-            "value_literal": literal_d["mrays_per_s"] if literal_d else None,
-            "value_literal_definition": ("the same timed blocks rendered by the LITERAL kernel (BHRAY_F_LITERAL: ray.wgsl:401-480 operator by operator, bit-identical to the "
-                                         "executed shader text on every direction pixel): the number that meets north_star's 1e-4 per channel to the letter; `value` is the contract "
-                                         "evaluation (FMA + reassociation, DESIGN.md N7/N9/N10)") if literal_d else None,
-            "pixels_beyond_1e-4_vs_shader_text": literal_d["distance_of_the_headline_kernel"] if literal_d else None,
-            "literal": literal_d,
-            "handoff": handoff_d,
-            "dropin": dropin,
-            "sequence": sequence_d,
-            "mrays_per_s_with_handoff": handoff_d["mrays_per_s_with_handoff"] if handoff_d else None,
-            "sky_resolve": sky_d,
-            "counters": counters,
-            "algorithmic_bytes_per_frame": algorithmic_bytes_frame(counters),
-        }
+            })
+            out.update({
+                "traced_mrays_per_s": round(traced_rate, 3),
+                "traced_fraction_of_frame_pixels": round(counters["traced"] / float(pixels), 4),
+                "latency_ms_one_frame_in_flight": round(lat_ms, 4) if lat_ms else None,
+                "latency_ms_one_frame_in_flight_by_mode": lat_modes,
+                "mrays_per_s_one_frame_in_flight": round(pixels / (lat_ms * 1e-3) / 1e6, 2) if lat_ms else None,
+                "sustained": sustained,
+                "roofline": {
+                    "bound": "hbm", "kernel": "trace_kernel", "achieved": round(achieved_gbs, 4), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved_gbs / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_note": traffic_note,
+                    "avg_launch_ms": round(avg_ms, 5), "launches": exec_launches or int(tm.trace_launches),
+                    "avg_launch_ms_definition": "execution span of the kernel (first block start -> last block end on the device clock, stamped by the kernel: bhray_timing.trace_exec_ms); "
+                                                "agrees with rocprofv3 --kernel-trace --stats of this command (profiles/)" if exec_launches else "HIP events around the launch (no execution spans recorded)",
+                    "avg_launch_ms_enqueue_to_complete": round(enq_ms, 5),
+                    "algorithmic_bytes_per_launch": round(bytes_per_launch, 1),
+                    "concurrency": f"{args.frames_in_flight} frames in flight: a launch shares the device with the kernels it overlaps with; spans and events are taken on "
+                                   "every 4th batch of the timed region (every event is a packet in the stream: all of them cost 1.6 %)",
+                    "isolated": iso_d,
+                    "frac_from_profiles": frac_from_profiles,
+                    "secondary": {"bound": "valu", "achieved": round(valu_tflops, 4), "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                  "frac": round(valu_tflops / VALU_PEAK_TFLOPS, 6)},
+                    "note": "the metric names the HBM roofline, so `bound`/`frac` are HBM; the kernel is a VALU-bound f32 ODE march (SURVEY.md F8: ~20 "
+                            "algorithmic bytes per traced ray against ~96 kflop), so the fraction that says something about the kernel is `secondary` (= `valu`)",
+                },
+                "valu": {"achieved": round(valu_tflops, 4), "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+                         "frac": round(valu_tflops / VALU_PEAK_TFLOPS, 6),
+                         "algorithmic_flops_per_frame": flops_per_frame,
+                         "one_frame_in_flight": ({"achieved": round(flops_per_frame / (lat_ms * 1e-3) / 1e12, 4), "frac": round(flops_per_frame / (lat_ms * 1e-3) / 1e12 / VALU_PEAK_TFLOPS, 6),
+                                                  "note": "the same flops / latency_ms_one_frame_in_flight: the reference host's regime, where every launch lasts as long as its longest ray"}
+                                                 if lat_ms else None),
+                         "issue": valu_issue,
+                         "note": "algorithmic flops per frame (390 per RK step as the shader text counts them; the kernel issues fewer operations since N9/N10) / "
+                                 "wall time per frame of the median block; peak = the FMA rate"},
+                "pass_ms": {"event_total": round(tm.total_ms / frames, 5), "trace": round(tm.trace_ms / frames, 5),
+                            "classify": round(tm.classify_ms / frames, 5),
+                            "level_trace": [round(tm.level_trace_ms[i] / frames, 5) for i in range(args.levels)]},
+                "gather": gather_d,
+                "expected_scaling": expected_d,
+                # the reference host's regime as a second headline: the C++ mirror of the Rust shim - one host thread, the shipped 72x41 x3 x4
+                # ladder, two frames in flight (mod.rs:108 desired_maximum_frame_latency: 2), every frame through the sky pass and handed to pinned host memory as
+                # RGBA16F, NO temporal history - from the `dropin` leg of this run
+                "mrays_per_s_reference_host_regime": ref_host_regime,
+                "value_literal": literal_d["mrays_per_s"] if literal_d else None,
+                "value_literal_definition": ("the same timed blocks rendered by the LITERAL kernel (BHRAY_F_LITERAL: ray.wgsl:401-480 operator by operator, bit-identical to the "
+                                             "executed shader text on every direction pixel): the number that meets north_star's 1e-4 per channel to the letter; `value` is the contract "
+                                             "evaluation (FMA + reassociation, DESIGN.md N7/N9/N10)") if literal_d else None,
+                "pixels_beyond_1e-4_vs_shader_text": literal_d["distance_of_the_headline_kernel"] if literal_d else None,
+                "literal": literal_d,
+                "handoff": handoff_d,
+                "dropin": dropin,
+                "sequence": sequence_d,
+                "mrays_per_s_with_handoff": handoff_d["mrays_per_s_with_handoff"] if handoff_d else None,
+                "sky_resolve": sky_d,
+                "counters": counters,
+                "algorithmic_bytes_per_frame": algorithmic_bytes_frame(counters),
+            })
         if n_gpus == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, tex, cam, bh, det, model)
         print(json.dumps(out), flush=True)

@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$ROOT/gpurun_out/bench_$TAG
 mkdir -p $OUT
 cd $ROOT
-run() { name=$1; shift; timeout 900 python bench.py "$@" 2> $OUT/$name.err | grep '^{' | head -1 > $OUT/${TAG}_$name.json; echo "$name: $(python -c "import json,sys; d=json.load(open('$OUT/${TAG}_$name.json')); print(d['value'], d['unit'], d['ms_per_step'], 'ms/step')" 2>&1)"; }
+run() { name=$1; shift; timeout 900 python bench.py --full --min-seconds 0.5 "$@" 2> $OUT/$name.err | grep '^{' | head -1 > $OUT/${TAG}_$name.json; echo "$name: $(python -c "import json,sys; d=json.load(open('$OUT/${TAG}_$name.json')); print(d['value'], d['unit'], d['ms_per_step'], 'ms/step')" 2>&1)"; }
 run bench_default
 run bench_driver_style --steps 20 --warmup 5
 run bench_euler --integrator euler --no-cpu-baseline

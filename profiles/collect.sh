@@ -8,7 +8,7 @@
 # Outputs go to gpurun_out/prof_<tag>/<workload>/ ; profiles/summarize.py turns them into profiles/<tag>_*.{csv,json}.
 TAG=${1:-r03}
 ROOT=${GRAFT_REPO_ROOT:-$PWD}
-BASE="--steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs"
+BASE="--full --steps 20 --warmup 5 --min-seconds 0.5 --no-cpu-baseline --no-extra-legs"
 cd /tmp && export TMPDIR=/tmp
 prof() {   # workload-name, extra bench args
   W=$1; shift

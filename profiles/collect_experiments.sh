@@ -9,8 +9,8 @@ ROOT=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$ROOT/gpurun_out/prof_exp
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-MESH="--workload mesh --steps 64 --warmup 16 --no-cpu-baseline --min-seconds 0.2"
-DISK="--steps 96 --warmup 24 --no-cpu-baseline --min-seconds 0.2"
+MESH="--full --workload mesh --steps 64 --warmup 16 --no-cpu-baseline --min-seconds 0.2"
+DISK="--full --steps 96 --warmup 24 --no-cpu-baseline --min-seconds 0.2"
 for v in base stk8 top512; do
   LIB=$ROOT/bhusie_amd/libbhray.so; [ $v != base ] && LIB=$ROOT/profiles/variants/libbhray_$v.so
   BHRAY_LIB=$LIB rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/mesh_$v/stats -o bench -- python $ROOT/bench.py $MESH > $OUT/mesh_$v.stats.log 2>&1

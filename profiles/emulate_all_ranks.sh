@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$ROOT/gpurun_out/emulate
 rm -rf $OUT; mkdir -p $OUT
 cd $ROOT
-B="--no-cpu-baseline --no-extra-legs --sustained-steps 0"
+B="--full --min-seconds 0.5 --no-cpu-baseline --no-extra-legs --sustained-steps 0"
 run() { name=$1; shift; timeout 900 python bench.py $B "$@" > $OUT/$name.json 2>> $OUT/err.txt || echo "FAILED $name" >> $OUT/err.txt; }
 emu() {  # tag, world, long-steps, extra args...
   tag=$1; N=$2; LONG=$3; shift 3

@@ -73,7 +73,8 @@ def box():
 def _bench(*flags):
     env = dict(os.environ)
     env.pop("GPU_MAX_HW_QUEUES", None)              # bench.py sets what its frames in flight need
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", *flags],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--min-seconds", "0.5",
+                        "--no-cpu-baseline", *flags],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads(r.stdout.strip().splitlines()[-1])

@@ -13,7 +13,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--verify", "--steps", "13", "--warmup", "5", "--min-seconds", "0.05", "--no-cpu-baseline", "--width", "960", "--height", "540", "--frames-in-flight", "4"]
+COMMON = ["--full", "--verify", "--steps", "13", "--warmup", "5", "--min-seconds", "0.05", "--no-cpu-baseline", "--width", "960", "--height", "540", "--frames-in-flight", "4"]
 
 
 def _port():

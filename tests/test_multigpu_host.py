@@ -123,3 +123,24 @@ def test_frames_per_batch_rule_counts_pixels_and_divides_the_block():
         for world in (2, 4, 8):
             b = fpb(1920, 1080, steps, world)
             assert 1 <= b <= max(1, steps // 4) and (steps % b == 0 or b == steps // 4)
+
+
+def test_bench_frame_comparison_ignores_only_the_sign_of_a_nan():
+    """bench.py's verifications compare frames of different builds (a ctx with several frame slots against a one-slot ctx): bit for bit,
+    except the sign of a NaN, which DESIGN.md section 2 leaves unspecified.  A NaN against a number, -0 against +0 and any other bit count."""
+    sys.path.insert(0, ROOT)
+    import bench
+    pos_nan, neg_nan = (np.array([v], dtype=np.uint32).view(np.float32)[0] for v in (0x7FC00000, 0xFFC00000))
+    a = np.zeros((3, 5, 4), np.float32)
+    a[1, 2] = (pos_nan, pos_nan, pos_nan, 1.0)
+    b = a.copy()
+    b[1, 2, :3] = neg_nan
+    assert bench.differing_pixels(a, b) == 0
+    c = b.copy(); c[1, 2, 0] = 0.0
+    assert bench.differing_pixels(a, c) == 1
+    c = b.copy(); c[0, 4, 1] = -0.0
+    assert bench.differing_pixels(a, c) == 1
+    c = b.copy(); c[2, 0, 3] = np.nextafter(np.float32(0), np.float32(1))
+    assert bench.differing_pixels(a, c) == 1
+    h, g = a.astype(np.float16), b.astype(np.float16)
+    assert bench.differing_pixels(h, g) == 0 and bench.differing_pixels(h, h[:2]) == -1
