@@ -1634,19 +1634,6 @@ int dev_get_work(bhray_dev* c, double* wave_steps_per_frame, double* classify_pi
     return BHRAY_OK;
 }
 
-// diagnostics (not part of include/bhray.h): the entries the last frame's own queue of `level` held (temporal mode: the fix-up set)
-int dev_debug_read_queue(bhray_dev* c, uint32_t level, uint32_t* out, uint32_t cap, uint32_t* count) {
-    if (!c || !count || level >= c->cfg.levels) return BHRAY_E_INVALID;
-    int rc = dev_sync(c);
-    if (rc) return rc;
-    const FrameRes& R = c->slots[(size_t)c->last_slot].fr[(size_t)c->last_sub];
-    uint32_t n = 0;
-    HIPCHK(c, hipMemcpy(&n, R.d_qctl + 2 * level, sizeof n, hipMemcpyDeviceToHost));
-    *count = n;
-    if (out && R.queue[level]) HIPCHK(c, hipMemcpy(out, R.queue[level], (size_t)(n < cap ? n : cap) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return BHRAY_OK;
-}
-
 int dev_get_counters(bhray_dev* c, bhray_counters* out) {
     if (!c || !out) return BHRAY_E_INVALID;
     memset(out, 0, sizeof *out);

@@ -3,14 +3,14 @@
 // A bhray_dev renders ONE row partition of the frame on ONE GPU (bhray_api.hip): ladder levels, frame slots, frame batches,
 // speculative levels.  The public bhray_ctx (bhray_group.hip) owns one bhray_dev per local partition and, when the frame is
 // split over several partitions, the gather of the row tiles to the root partition's GPU (RCCL) and the de-interleave into
-// the frame.  Nothing here is exported; the C ABI is include/bhray.h.
+// the frame.  Nothing here is exported; the C ABI is include/bhray.h (and include/bhray_diag.h for measurement).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
 #include <hip/hip_runtime.h>
 
-#include "../../include/bhray.h"
+#include "../../include/bhray_diag.h"
 
 #include <vector>
 
@@ -81,7 +81,6 @@ int  dev_signal_stream(bhray_dev* c, void* s);
 int  dev_selftest(bhray_dev* c, uint64_t mismatches[3]);
 int  dev_get_level_counters(bhray_dev* c, uint32_t level, bhray_counters* out);
 int  dev_add_row_work(bhray_dev* c, uint32_t level, uint64_t* acc, uint32_t n);   // acc[y] += iterations of the last render's rays of level row y
-int  dev_debug_read_queue(bhray_dev* c, uint32_t level, uint32_t* out, uint32_t cap, uint32_t* count);   // diagnostics only
 int  dev_get_counters(bhray_dev* c, bhray_counters* out);
 int  dev_get_timing(bhray_dev* c, bhray_timing* out);
 // what the frames still held by the slots cost: integrator steps issued by the trace waves (mean per frame) and pixels visited by the classify launches

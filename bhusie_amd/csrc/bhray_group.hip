@@ -1421,31 +1421,6 @@ int bhray_get_work(bhray_ctx* c, double* wave_steps_per_frame, double* classify_
     return BHRAY_OK;
 }
 
-int bhray_get_gather_info(const bhray_ctx* c, bhray_gather_info* out) {
-    if (!c || !out) return BHRAY_E_INVALID;
-    memset(out, 0, sizeof *out);
-    out->partitions = c->world;
-    out->root = c->root;
-    const uint64_t rowb = c->gather_sky ? (uint64_t)c->cfg.frame_w * 8u : (uint64_t)packed_row_words(c->cfg.frame_w) * 4u;    // bytes of one row on the wire
-    for (uint32_t q = 0; q < c->parts.size(); q++) {
-        const Part& p = c->parts[q];
-        if (p.dev) out->local_partitions++;
-        if (!c->gather) continue;
-        if (p.dev && q != c->root) out->bytes_sent_per_frame += p.rows * rowb;
-        if (c->root_local && q != c->root) out->bytes_received_per_frame += p.rows * rowb;
-    }
-    out->root_is_local = c->gather ? (c->root_local ? 1u : 0u) : 1u;
-    out->comm_ranks = c->gather ? c->comm_size : 0;
-    out->rccl_version = g_rccl.so ? (uint32_t)g_rccl.version : 0;
-    return BHRAY_OK;
-}
-
-// diagnostics, not declared in include/bhray.h (scratch experiments read the temporal fix-up sets through it); single-partition ctx only
-int bhray_debug_read_queue(bhray_ctx* c, uint32_t level, uint32_t* out, uint32_t cap, uint32_t* count) {
-    if (!c || !c->single) return BHRAY_E_INVALID;
-    return dev_debug_read_queue(c->parts[0].dev, level, out, cap, count);
-}
-
 // ---- scene state: replicated on every local partition ---------------------------------------
 int bhray_set_texture(bhray_ctx* c, int slot, const uint8_t* rgba8, uint32_t w, uint32_t h) {
     if (!c) return BHRAY_E_INVALID;
@@ -1610,46 +1585,6 @@ int bhray_read_hdr(bhray_ctx* c, float* dst, size_t pitch) {
     if (!dst || pitch < rowb) return gfail(c, BHRAY_E_INVALID, "bad destination / pitch");
     GHIP(c, hipSetDevice(root_part(c)->device));
     GHIP(c, hipMemcpy2D(dst, pitch, c->gslots[(size_t)c->last_slot].dst[c->last_sub], rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost));
-    return BHRAY_OK;
-}
-
-int bhray_read_level(bhray_ctx* c, uint32_t level, float* dst, size_t pitch) {
-    if (!c) return BHRAY_E_INVALID;
-    ENTER(c);
-    if (c->single) { DEV(c, c->parts[0].dev, dev_read_level(c->parts[0].dev, level, dst, pitch)); return BHRAY_OK; }
-    // every partition computed the level rows its stripes depend on: overlay them (unrendered pixels are NaN-filled; pixels
-    // computed by several partitions are identical)
-    if (level >= c->cfg.levels) return gfail(c, BHRAY_E_INVALID, "level out of range");
-    { int rc = group_sync(c); if (rc) return rc; }
-    const size_t w = c->cfg.level_w[level], h = c->cfg.level_h[level], rowb = w * sizeof(float4);
-    if (!dst || pitch < rowb) return gfail(c, BHRAY_E_INVALID, "bad destination / pitch");
-    for (size_t y = 0; y < h; y++) memset((uint8_t*)dst + y * pitch, 0xFF, rowb);
-    std::vector<uint32_t> tmp(w * h * 4);
-    const bool last = level + 1 == c->cfg.levels;
-    for (uint32_t q = 0; q < c->world; q++) {
-        Part& p = c->parts[q];
-        if (!p.dev) continue;
-        if (last) {
-            // a partition's last-level image is its output binding: the root's is the assembled frame, read through the ctx
-            if (q != c->root) continue;
-            std::vector<float> fr(frame_pixels(c) * 4);
-            int rc = bhray_read_hdr(c, fr.data(), (size_t)c->cfg.frame_w * 16);
-            if (rc) return rc;
-            for (size_t y = 0; y < c->cfg.frame_h; y++)
-                memcpy((uint8_t*)dst + (y + c->cfg.crop_y) * pitch + (size_t)c->cfg.crop_x * 16, fr.data() + y * c->cfg.frame_w * 4, (size_t)c->cfg.frame_w * 16);
-            continue;
-        }
-        DEV(c, p.dev, dev_read_level(p.dev, level, (float*)tmp.data(), rowb));
-        for (size_t y = 0; y < h; y++) {
-            const uint32_t* s = tmp.data() + y * w * 4;
-            uint32_t* d = (uint32_t*)((uint8_t*)dst + y * pitch);
-            for (size_t x = 0; x < w; x++) {
-                const uint32_t* px = s + 4 * x;
-                if (px[0] == 0xFFFFFFFFu && px[1] == 0xFFFFFFFFu && px[2] == 0xFFFFFFFFu && px[3] == 0xFFFFFFFFu) continue;
-                memcpy(d + 4 * x, px, 16);
-            }
-        }
-    }
     return BHRAY_OK;
 }
 
@@ -1902,7 +1837,66 @@ int bhray_sky_device_ptr(bhray_ctx* c, void** p, size_t* bytes) {
     return BHRAY_OK;
 }
 
-// ---- measurement -------------------------------------------------------------------------------------
+// ---- measurement and verification: include/bhray_diag.h ----------------------------------------------
+int bhray_get_gather_info(const bhray_ctx* c, bhray_gather_info* out) {
+    if (!c || !out) return BHRAY_E_INVALID;
+    memset(out, 0, sizeof *out);
+    out->partitions = c->world;
+    out->root = c->root;
+    const uint64_t rowb = c->gather_sky ? (uint64_t)c->cfg.frame_w * 8u : (uint64_t)packed_row_words(c->cfg.frame_w) * 4u;    // bytes of one row on the wire
+    for (uint32_t q = 0; q < c->parts.size(); q++) {
+        const Part& p = c->parts[q];
+        if (p.dev) out->local_partitions++;
+        if (!c->gather) continue;
+        if (p.dev && q != c->root) out->bytes_sent_per_frame += p.rows * rowb;
+        if (c->root_local && q != c->root) out->bytes_received_per_frame += p.rows * rowb;
+    }
+    out->root_is_local = c->gather ? (c->root_local ? 1u : 0u) : 1u;
+    out->comm_ranks = c->gather ? c->comm_size : 0;
+    out->rccl_version = g_rccl.so ? (uint32_t)g_rccl.version : 0;
+    return BHRAY_OK;
+}
+
+int bhray_read_level(bhray_ctx* c, uint32_t level, float* dst, size_t pitch) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    if (c->single) { DEV(c, c->parts[0].dev, dev_read_level(c->parts[0].dev, level, dst, pitch)); return BHRAY_OK; }
+    // every partition computed the level rows its stripes depend on: overlay them (unrendered pixels are NaN-filled; pixels
+    // computed by several partitions are identical)
+    if (level >= c->cfg.levels) return gfail(c, BHRAY_E_INVALID, "level out of range");
+    { int rc = group_sync(c); if (rc) return rc; }
+    const size_t w = c->cfg.level_w[level], h = c->cfg.level_h[level], rowb = w * sizeof(float4);
+    if (!dst || pitch < rowb) return gfail(c, BHRAY_E_INVALID, "bad destination / pitch");
+    for (size_t y = 0; y < h; y++) memset((uint8_t*)dst + y * pitch, 0xFF, rowb);
+    std::vector<uint32_t> tmp(w * h * 4);
+    const bool last = level + 1 == c->cfg.levels;
+    for (uint32_t q = 0; q < c->world; q++) {
+        Part& p = c->parts[q];
+        if (!p.dev) continue;
+        if (last) {
+            // a partition's last-level image is its output binding: the root's is the assembled frame, read through the ctx
+            if (q != c->root) continue;
+            std::vector<float> fr(frame_pixels(c) * 4);
+            int rc = bhray_read_hdr(c, fr.data(), (size_t)c->cfg.frame_w * 16);
+            if (rc) return rc;
+            for (size_t y = 0; y < c->cfg.frame_h; y++)
+                memcpy((uint8_t*)dst + (y + c->cfg.crop_y) * pitch + (size_t)c->cfg.crop_x * 16, fr.data() + y * c->cfg.frame_w * 4, (size_t)c->cfg.frame_w * 16);
+            continue;
+        }
+        DEV(c, p.dev, dev_read_level(p.dev, level, (float*)tmp.data(), rowb));
+        for (size_t y = 0; y < h; y++) {
+            const uint32_t* s = tmp.data() + y * w * 4;
+            uint32_t* d = (uint32_t*)((uint8_t*)dst + y * pitch);
+            for (size_t x = 0; x < w; x++) {
+                const uint32_t* px = s + 4 * x;
+                if (px[0] == 0xFFFFFFFFu && px[1] == 0xFFFFFFFFu && px[2] == 0xFFFFFFFFu && px[3] == 0xFFFFFFFFu) continue;
+                memcpy(d + 4 * x, px, 16);
+            }
+        }
+    }
+    return BHRAY_OK;
+}
+
 int bhray_selftest(bhray_ctx* c, uint64_t mismatches[3]) {
     if (!c || !mismatches) return BHRAY_E_INVALID;
     ENTER(c);

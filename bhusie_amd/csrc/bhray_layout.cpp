@@ -7,7 +7,7 @@
 // MaterialUniform material.rs:7-11.
 #include <stddef.h>
 
-#include "../../include/bhray.h"
+#include "../../include/bhray_diag.h"   // bhray.h, and bhray_counters for the size below
 
 #define OFF(T, m, v) static_assert(offsetof(T, m) == (v), #T "." #m " offset")
 #define SZ(T, v) static_assert(sizeof(T) == (v), #T " size")

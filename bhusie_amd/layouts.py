@@ -1,4 +1,4 @@
-"""ctypes mirrors of include/bhray.h (which mirrors the reference's #[repr(C)] structs)."""
+"""ctypes mirrors of include/bhray.h (which mirrors the reference's #[repr(C)] structs) and include/bhray_diag.h."""
 from __future__ import annotations
 
 import ctypes as C
@@ -118,7 +118,6 @@ class BhrayGatherInfo(C.Structure):
 assert C.sizeof(BhrayDetails) == 32 and C.sizeof(BhrayCameraUniform) == 32 and C.sizeof(BhrayBlackHoleUniform) == 132
 assert C.sizeof(BhrayNode) == 32 and C.sizeof(BhrayTriangle) == 24
 
-# every symbol include/bhray.h declares: name -> (restype, argtypes)
 class BhrayRebalanceInfo(C.Structure):
     """bhray_rebalance_info (include/bhray.h)"""
     _fields_ = [("partitions", C.c_uint32), ("applied", C.c_uint32), ("slab_row0", C.c_uint32 * 17), ("part_cost", C.c_float * 16), ("extra_cost", C.c_float * 16),
@@ -133,6 +132,7 @@ class BhrayRebalanceInfo(C.Structure):
 
 P = C.POINTER
 vp, u32, i32, sz = C.c_void_p, C.c_uint32, C.c_int32, C.c_size_t
+# every symbol include/bhray.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "bhray_ladder_from_base": (C.c_int, [u32, u32, u32, u32, P(BhrayConfig)]),
     "bhray_ladder_for_frame": (C.c_int, [u32, u32, u32, u32, P(BhrayConfig)]),
@@ -148,7 +148,6 @@ SYMBOLS = {
     "bhray_config_partition_row_index": (C.c_int, [P(BhrayConfig), u32, u32, P(u32)]),
     "bhray_balance_slabs": (C.c_int, [P(BhrayConfig), P(P(C.c_uint64)), u32, P(u32)]),
     "bhray_comm_unique_id": (C.c_int, [vp]),
-    "bhray_get_gather_info": (C.c_int, [vp, P(BhrayGatherInfo)]),
     "bhray_set_partition": (C.c_int, [vp, P(u32)]),
     "bhray_get_partition": (C.c_int, [vp, P(u32), P(u32)]),
     "bhray_rebalance_slabs": (C.c_int, [u32, u32, P(u32), P(C.c_double), P(C.c_double), C.c_double, P(C.c_double), P(u32), P(C.c_double)]),
@@ -165,7 +164,6 @@ SYMBOLS = {
     "bhray_flush": (C.c_int, [vp]),
     "bhray_sync": (C.c_int, [vp]),
     "bhray_read_hdr": (C.c_int, [vp, vp, sz]),
-    "bhray_read_level": (C.c_int, [vp, u32, vp, sz]),
     "bhray_local_rows": (u32, [vp]),
     "bhray_local_row_index": (C.c_int, [vp, u32, P(u32)]),
     "bhray_hdr_device_ptr": (C.c_int, [vp, P(vp), P(sz)]),
@@ -183,11 +181,6 @@ SYMBOLS = {
     "bhray_wait_stream": (C.c_int, [vp, vp]),
     "bhray_signal_stream": (C.c_int, [vp, vp]),
     "bhray_next_stream": (C.c_int, [vp, P(vp)]),
-    "bhray_get_counters": (C.c_int, [vp, P(BhrayCounters)]),
-    "bhray_get_level_counters": (C.c_int, [vp, u32, P(BhrayCounters)]),
-    "bhray_get_row_work": (C.c_int, [vp, u32, P(C.c_uint64), u32]),
-    "bhray_get_timing": (C.c_int, [vp, P(BhrayTiming)]),
-    "bhray_selftest": (C.c_int, [vp, P(C.c_uint64)]),
     "bhray_camera_uniform_update": (None, [P(BhrayCameraUniform), P(C.c_float), P(C.c_float), C.c_float]),
     "bhray_black_hole_default": (None, [P(BhrayBlackHole)]),
     "bhray_black_hole_uniform_update": (None, [P(BhrayBlackHoleUniform), P(BhrayBlackHole)]),
@@ -207,11 +200,22 @@ SYMBOLS = {
     "bhray_generate_disk_texture": (C.c_int, [u32, vp]),
 }
 
+# every symbol include/bhray_diag.h declares (measurement and verification): name -> (restype, argtypes)
+DIAG_SYMBOLS = {
+    "bhray_get_counters": (C.c_int, [vp, P(BhrayCounters)]),
+    "bhray_get_level_counters": (C.c_int, [vp, u32, P(BhrayCounters)]),
+    "bhray_get_row_work": (C.c_int, [vp, u32, P(C.c_uint64), u32]),
+    "bhray_get_timing": (C.c_int, [vp, P(BhrayTiming)]),
+    "bhray_selftest": (C.c_int, [vp, P(C.c_uint64)]),
+    "bhray_read_level": (C.c_int, [vp, u32, vp, sz]),
+    "bhray_get_gather_info": (C.c_int, [vp, P(BhrayGatherInfo)]),
+}
+
 
 def declare(L):
     import os
     old_build = os.environ.get("BHRAY_AB_OLD_BUILD") == "1"      # kernel A/B against a library built from an earlier tree (profiles/jobs/ab.sh): symbols it lacks are not bound
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in {**SYMBOLS, **DIAG_SYMBOLS}.items():
         if old_build and not hasattr(L, name):
             continue
         f = getattr(L, name)          # AttributeError if the library does not export it

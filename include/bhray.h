@@ -16,6 +16,8 @@
  *     passes `bytemuck::bytes_of(..)` unchanged.
  *   - there is NO CPU fallback: bhray_create fails with BHRAY_E_NO_DEVICE when no gfx950
  *     device is usable.
+ * What exists to measure or verify the library (counters, timing, self-test, level read-back, gather statistics) is declared
+ * in bhray_diag.h, which includes this file; a renderer needs none of it.
  */
 #ifndef BHRAY_H
 #define BHRAY_H
@@ -147,10 +149,9 @@ typedef struct bhray_model_desc {
 #define BHRAY_COMM_ID_BYTES 128        /* an RCCL ncclUniqueId                                         */
 
 enum {                                  /* bhray_config.flags */
-    BHRAY_F_COUNTERS   = 1u << 0,       /* kernels also accumulate bhray_counters (slower)   */
-    BHRAY_F_TIMING     = 1u << 1,       /* record HIP events around every launch             */
-    BHRAY_F_TIMING_SPARSE = 1u << 4,    /* like BHRAY_F_TIMING, but only every 4th batch carries events (a recorded event is a packet in
-                                           the stream: 12 per frame cost a saturated device 1.6 %); bhray_get_timing aggregates those */
+    BHRAY_F_COUNTERS   = 1u << 0,       /* measurement: counting kernels (bhray_diag.h)      */
+    BHRAY_F_TIMING     = 1u << 1,       /* measurement: HIP-event timing (bhray_diag.h)      */
+    BHRAY_F_TIMING_SPARSE = 1u << 4,    /* measurement: timing of every 4th batch (bhray_diag.h) */
     BHRAY_F_TEMPORAL   = 1u << 3,       /* temporal speculation: one launch first traces, at every level, the pixels the previous frame
                                            had to trace; the ladder then only traces what that prediction missed.  Same pixels; the
                                            chain of dependent trace launches collapses when consecutive frames are similar (an
@@ -159,14 +160,8 @@ enum {                                  /* bhray_config.flags */
                                            border pixels: DESIGN.md §4), +8 % rays; 1080p, one frame at a time: 0.78 ms with a static
                                            camera, 0.84-0.87 ms with a moving one, 1.20 ms without the flag.  levels <= 4, no
                                            speculative / superset levels.                                                    */
-    /* (1u << 6 was BHRAY_F_FUSED, the fused ladder of rounds 3-5 - one persistent launch per batch with tile dependencies instead of
-       launch boundaries: measured slower on MI355X, 2.1 against 1.2 ms for one 1080p frame at a time, profiles/EXPERIMENTS.md R3.1 - removed
-       in round 6, kept as a patch: profiles/variants_src/.  bhray_create refuses the bit.)                                              */
-    BHRAY_F_EVAL_FMA   = 1u << 5,       /* a THIRD evaluation of the integrator: the shader text with fused multiply-add contraction only
-                                           (every `x*y + z` of ray.wgsl:401-480 one fma), none of the contract's reassociations (N9/N10).
-                                           Like BHRAY_F_LITERAL it exists for measurement: the pixels on which it differs from the literal
-                                           text by more than 1e-4 are the pixels on which the default evaluation does
-                                           (tests/test_gpu_literal.py).  Ignored when BHRAY_F_LITERAL is set.                        */
+    /* 1u << 6: reserved, refused by bhray_create */
+    BHRAY_F_EVAL_FMA   = 1u << 5,       /* measurement: fma-only evaluation of the integrator (bhray_diag.h) */
     BHRAY_F_GATHER_SKY = 1u << 7,       /* multi-GPU ctx only (device_count >= 2, or gather = BHRAY_GATHER_RCCL): gather the RGBA16F image of the
                                            sky pass instead of the RGBA32F frame - HALF the bytes over xGMI.  Every partition runs the sky
                                            pass (sky.wgsl, per pixel) over its own rows behind its render and sends 8-byte pixels; the root
@@ -176,11 +171,7 @@ enum {                                  /* bhray_config.flags */
                                            bhray_hdr_device_ptr and bhray_bind_output return BHRAY_E_STATE.  For a host that lets the library
                                            run the sky pass.  Same pixels as the sky pass over the assembled frame.  */
     BHRAY_F_ALL        = 0xbfu,         /* every flag above and below: bhray_create refuses any other bit                    */
-    BHRAY_F_LITERAL    = 1u << 2        /* the integrator (ray.wgsl:401-480, 533) operator by operator: one binary32 operation per
-                                           WGSL operator in source order, no fused multiply-add, no reassociation.  Slower; exists
-                                           to MEASURE how far the default evaluation (DESIGN.md §2, N3/N7/N9/N10 — permitted by
-                                           WGSL, cheaper on CDNA4) is from the shader text: tests/test_gpu_literal.py.  Cost: bench.py's
-                                           `literal` entry                                                          */
+    BHRAY_F_LITERAL    = 1u << 2        /* measurement: literal evaluation of the integrator (bhray_diag.h) */
 };
 
 /* The ladder is the reference's chain of RayPipelines (mod.rs:170-207): level 0 traces every
@@ -193,7 +184,7 @@ enum {                                  /* bhray_config.flags */
  * takes as long as its longest ray, however few rays it has).  With speculative_levels = S the pixels of levels
  * 0..S-1 are all traced in ONE launch before any of them is classified; classification then selects, per pixel, the
  * copy / the interpolation / the already traced value exactly as the shader would.  Same pixels, fewer dependent
- * launches, more rays traced (bhray_counters then count the speculative work).  Meant for small per-GPU frames
+ * launches, more rays traced (bhray_counters, bhray_diag.h, then count the speculative work).  Meant for small per-GPU frames
  * (row-tiled multi-GPU); off by default.
  *
  * Superset speculation.  speculative_levels shortens the chain at its coarse end by tracing everything; at the fine end
@@ -224,7 +215,7 @@ enum {                                  /* bhray_config.flags */
  * (r / stripe_rows) % row_world - interleaved stripes, balanced whatever the scene, at the price of coarse ladder rows that
  * several partitions compute (every stripe boundary costs two rows at each coarser level).  partition =
  * BHRAY_PARTITION_SLABS: partition p owns the consecutive rows [slab_row0[p], slab_row0[p + 1]) - one boundary per partition;
- * the bounds come from the host, which balances them by measured work (bhray_get_row_work of a calibration frame ->
+ * the bounds come from the host, which balances them by measured work (bhray_get_row_work of bhray_diag.h on a calibration frame ->
  * bhray_balance_slabs; 1920x1080, 8 partitions, default scene: 2 % of the ray-steps computed twice and 2 % imbalance against
  * 7 % and 8.5 % for stripes of 27, profiles/partition_sim.py).  Either way this ctx renders only rows of partition row_rank
  * and packs them densely, in increasing r, into its output buffer.  row_world = 1 ⇒ the whole frame.
@@ -237,7 +228,7 @@ enum {                                  /* bhray_config.flags */
  *     ncclSend/ncclRecv over xGMI, one message per partition per batch) and the de-interleave of the stripes into the
  *     frame (a HIP kernel on the root GPU).  On the wire a row of the RGBA32F frame is its x, y, z floats plus ONE BIT of alpha per
  *     pixel (alpha is exactly 0 or 1: ray.wgsl:589-594): 12.1 bytes per pixel instead of 16, packed behind the render on the sending
- *     GPU and unpacked by the de-interleave - the assembled frame is the same bits (bhray_gather_info counts the bytes that travel).  Output calls (bhray_read_hdr, bhray_hdr_device_ptr, bhray_bind_output,
+ *     GPU and unpacked by the de-interleave - the assembled frame is the same bits (bhray_gather_info of bhray_diag.h counts the bytes that travel).  Output calls (bhray_read_hdr, bhray_hdr_device_ptr, bhray_bind_output,
  *     bhray_resolve_sky) then refer to the WHOLE frame on the root GPU; bhray_local_rows = frame_h.  row_rank/row_world
  *     are ignored (row_world is set to N).  A device may appear more than once (functional tests on a one-GPU box): its
  *     partitions share one RCCL rank and their tiles travel as send/recv-to-self.
@@ -303,7 +294,7 @@ int bhray_partition_row_index(uint32_t frame_h, uint32_t world, uint32_t stripe_
 /* The same for the partition a bhray_config describes (stripes or slabs; world = device_count when >= 2, else row_world). */
 uint32_t bhray_config_partition_rows(const bhray_config* cfg, uint32_t part);
 int bhray_config_partition_row_index(const bhray_config* cfg, uint32_t part, uint32_t i, uint32_t* frame_row);
-/* Slab bounds balanced by measured work.  row_work[l] points to level_h[l] numbers: the work (ray-steps, bhray_get_row_work) of
+/* Slab bounds balanced by measured work.  row_work[l] points to level_h[l] numbers: the work (ray-steps, bhray_get_row_work: bhray_diag.h) of
  * every row of ladder level l of a calibration frame rendered WHOLE with the speculative_levels the partitions will use.  A
  * partition's work is the work of the level rows its frame rows depend on (every level: the ladder arithmetic of cfg, crop
  * included); the bounds minimise the largest partition's work over all contiguous partitions.  Pure host arithmetic.
@@ -358,18 +349,6 @@ int bhray_get_partition(const bhray_ctx* ctx, uint32_t* slab_row0 /* BHRAY_MAX_D
 
 /* One process per GPU: a fresh communicator id (ncclGetUniqueId); call on ONE rank, hand the bytes to all ranks.  */
 int bhray_comm_unique_id(uint8_t id[BHRAY_COMM_ID_BYTES]);
-/* What a ctx gathers with.                                                                                          */
-typedef struct bhray_gather_info {
-    uint32_t partitions;                /* row partitions of the frame (1 = no tiling)                               */
-    uint32_t local_partitions;          /* partitions rendered by this ctx                                           */
-    uint32_t root;                      /* partition that receives the frame                                         */
-    uint32_t root_is_local;             /* 1: the frame is delivered by this ctx                                     */
-    uint32_t comm_ranks;                /* ranks of the RCCL communicator (0: no gather)                             */
-    uint32_t rccl_version;              /* ncclGetVersion, e.g. 22707 (0: RCCL not loaded)                           */
-    uint64_t bytes_sent_per_frame;      /* by this ctx's non-root partitions                                         */
-    uint64_t bytes_received_per_frame;  /* by the root partition (0 when it is not local)                            */
-} bhray_gather_info;
-int bhray_get_gather_info(const bhray_ctx* ctx, bhray_gather_info* out);
 
 /* Static inputs — replaces the include_bytes! textures (ray_pipeline.rs:63-70) and
  * texture.rs:16-69 semantics: RGBA8 unorm, no sRGB decode, bilinear, clamp-to-edge, 1 mip.  */
@@ -407,8 +386,6 @@ int bhray_sync(bhray_ctx* ctx);
  * row 0 = top, x fastest (textureStore(screen_pos), ray.wgsl:182).  Rows of this ctx's
  * partition only, packed; local_rows = bhray_local_rows().  Synchronises the stream.        */
 int bhray_read_hdr(bhray_ctx* ctx, float* dst_rgba32f, size_t row_pitch_bytes);
-/* Any ladder level, full size level_w×level_h (unrendered pixels are NaN-filled at create).  */
-int bhray_read_level(bhray_ctx* ctx, uint32_t level, float* dst_rgba32f, size_t row_pitch_bytes);
 uint32_t bhray_local_rows(const bhray_ctx* ctx);
 /* frame row index of packed row i (0 ≤ i < local_rows).                                      */
 int bhray_local_row_index(const bhray_ctx* ctx, uint32_t i, uint32_t* frame_row);
@@ -482,69 +459,6 @@ int bhray_next_stream(bhray_ctx* ctx, void** hip_stream);
 int bhray_resolve_sky(bhray_ctx* ctx);
 int bhray_read_sky(bhray_ctx* ctx, uint16_t* dst_rgba16f, size_t row_pitch_bytes);
 int bhray_sky_device_ptr(bhray_ctx* ctx, void** dev_ptr, size_t* bytes);
-
-/* ------------------------------------------------------------------------------------------
- * Measurement
- * ---------------------------------------------------------------------------------------- */
-typedef struct bhray_counters {        /* summed over all levels of the last render          */
-    uint64_t pixels;                   /* pixels written (all levels)                        */
-    uint64_t copied;                   /* grid: copied from the coarser level (ray.wgsl:193) */
-    uint64_t interpolated;             /* grid: bilinear mix of directions (ray.wgsl:217)    */
-    uint64_t traced;                   /* pixels that ran trace_ray                          */
-    uint64_t steps;                    /* relativity iterations (integrator steps)           */
-    uint64_t flat_iters;               /* flat-space iterations                              */
-    uint64_t node_pairs;               /* BVH inner-node visits (2 AABB tests each)          */
-    uint64_t triangles;                /* hit_triangle calls                                 */
-    uint64_t disk_hits;                /* accretion-disk shading events                      */
-    uint64_t sky_samples;              /* in-kernel sky taps (ray.wgsl:587)                  */
-    /* scheduling of the trace kernel (not a property of the frame: depends on frames in flight, batches, the kernel build)   */
-    uint64_t wave_steps;               /* integrator steps issued by waves: `steps` / (64 * wave_steps) = fraction of the lanes
-                                          of a stepping wave that hold a live ray                                            */
-    uint64_t rays_adopted;             /* rays that changed wave through the drain-merging mailbox (dense build)             */
-    uint64_t max_ray_iterations;       /* iterations of the longest ray (a maximum, also over levels): the latency floor of a level
-                                          is its longest ray                                                                  */
-} bhray_counters;
-int bhray_get_counters(bhray_ctx* ctx, bhray_counters* out);   /* needs BHRAY_F_COUNTERS     */
-int bhray_get_level_counters(bhray_ctx* ctx, uint32_t level, bhray_counters* out);
-/* Where the work of the last render lies: out[y] = iterations of all rays traced for row y of ladder level `level` (n = level_h[level]
- * numbers; rows this ctx did not render are 0; a multi-partition ctx sums its local partitions).  Needs BHRAY_F_COUNTERS.
- * The input of bhray_balance_slabs.                                                                                              */
-int bhray_get_row_work(bhray_ctx* ctx, uint32_t level, uint64_t* out, uint32_t n);
-
-/* Device self-test of the properties two exact shortcuts rest on: (i) the integrator computes the correctly
- * rounded 1/x and sqrt(x) with short gfx950 sequences — run against the IEEE lowering on all 2^32 binary32 bit patterns;
- * (ii) the grid classification replaces `acos(c) < threshold` by `c > c*` — the portable acos must be monotone over every
- * binary32 value of [-1, 1].  Returns the number of violating inputs of each (all must be 0).  ~20 ms.              */
-int bhray_selftest(bhray_ctx* ctx, uint64_t mismatches[3]);    /* [0] = 1/x and the step-size power, [1] = sqrt, [2] = acos monotonicity */
-
-/* HIP-event timing of every launch (events recorded on the ctx stream).  bhray_get_timing sums
- * over the batches launched since the previous call (at most BHRAY_TIMING_RING of them).     */
-#define BHRAY_TIMING_RING 128
-typedef struct bhray_timing {
-    uint32_t frames;                   /* frames aggregated                                  */
-    uint32_t batches;                  /* batches aggregated (= frames unless frames_per_batch > 1) */
-    float    total_ms;                 /* Σ (first launch → last launch) per batch           */
-    float    trace_ms;                 /* Σ trace kernels                                    */
-    float    classify_ms;              /* Σ grid classify kernels                            */
-    uint32_t trace_launches;
-    uint32_t classify_launches;
-    float    level_trace_ms[BHRAY_MAX_LEVELS];
-    float    level_classify_ms[BHRAY_MAX_LEVELS];
-    float    sky_ms;                   /* Σ sky resolve kernels                              */
-    uint32_t sky_launches;
-    float    gather_ms;                /* multi-GPU, root: Σ (receive of the row tiles: start → all tiles arrived)   */
-    float    deinterleave_ms;          /* multi-GPU, root: Σ de-interleave kernels                                   */
-    uint32_t gathers;                  /* batches gathered                                                            */
-    float    predicted_trace_ms;       /* BHRAY_F_TEMPORAL: Σ (prediction + the predicted trace launch, all levels): the bulk of such a
-                                          frame; trace_ms / level_trace_ms then hold the fix-up launches only          */
-    uint32_t predicted_launches;
-    float    trace_exec_ms;            /* Σ EXECUTION spans of the trace kernels: first block's start → last block's end on the device's
-                                          constant-rate clock, stamped by the kernel itself.  trace_ms (HIP events in the stream) also
-                                          contains the time a launch waits for room beside the persistent kernels of the other frames
-                                          in flight; this is what `rocprofv3 --kernel-trace` reports as the kernel's duration          */
-    uint32_t trace_exec_launches;
-} bhray_timing;
-int bhray_get_timing(bhray_ctx* ctx, bhray_timing* out);       /* needs BHRAY_F_TIMING       */
 
 /* ------------------------------------------------------------------------------------------
  * Host-side scene helpers (C++ behind this ABI; mirror the Rust host code on the path)

@@ -1,0 +1,129 @@
+/*
+ * bhray_diag.h — measurement and verification entry points of libbhray.
+ *
+ * bhray.h is what a renderer calls (a RayPipeline shim; the C++ host, host/renderer.hpp).  This header
+ * adds what exists to MEASURE or VERIFY the library rather than to render a frame: the counters and the row work of the
+ * counting build, the HIP-event timing, the device self-test, the read-back of any ladder level and the gather statistics.
+ * The tests, bench.py and the profiling scripts use them; a product host needs none.  It includes bhray.h, so a diagnostic
+ * consumer includes this file only.  The conventions of bhray.h hold here too.
+ */
+#ifndef BHRAY_DIAG_H
+#define BHRAY_DIAG_H
+
+#include "bhray.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ------------------------------------------------------------------------------------------
+ * Measurement flags of bhray_config.flags (the values are bhray.h's BHRAY_F_* enum)
+ *
+ * BHRAY_F_COUNTERS       kernels also accumulate bhray_counters (slower).
+ * BHRAY_F_TIMING         record HIP events around every launch.
+ * BHRAY_F_TIMING_SPARSE  like BHRAY_F_TIMING, but only every 4th batch carries events (a recorded event is a packet in
+ *                        the stream: 12 per frame cost a saturated device 1.6 %); bhray_get_timing aggregates those.
+ * BHRAY_F_LITERAL        the integrator (ray.wgsl:401-480, 533) operator by operator: one binary32 operation per
+ *                        WGSL operator in source order, no fused multiply-add, no reassociation.  Slower; exists
+ *                        to MEASURE how far the default evaluation (DESIGN.md §2, N3/N7/N9/N10 — permitted by
+ *                        WGSL, cheaper on CDNA4) is from the shader text: tests/test_gpu_literal.py.  Cost: bench.py's
+ *                        `literal` entry.
+ * BHRAY_F_EVAL_FMA       a THIRD evaluation of the integrator: the shader text with fused multiply-add contraction only
+ *                        (every `x*y + z` of ray.wgsl:401-480 one fma), none of the contract's reassociations (N9/N10).
+ *                        Like BHRAY_F_LITERAL it exists for measurement: the pixels on which it differs from the literal
+ *                        text by more than 1e-4 are the pixels on which the default evaluation does
+ *                        (tests/test_gpu_literal.py).  Ignored when BHRAY_F_LITERAL is set.
+ * ---------------------------------------------------------------------------------------- */
+
+/* ------------------------------------------------------------------------------------------
+ * Counters (BHRAY_F_COUNTERS)
+ * ---------------------------------------------------------------------------------------- */
+typedef struct bhray_counters {        /* summed over all levels of the last render          */
+    uint64_t pixels;                   /* pixels written (all levels)                        */
+    uint64_t copied;                   /* grid: copied from the coarser level (ray.wgsl:193) */
+    uint64_t interpolated;             /* grid: bilinear mix of directions (ray.wgsl:217)    */
+    uint64_t traced;                   /* pixels that ran trace_ray                          */
+    uint64_t steps;                    /* relativity iterations (integrator steps)           */
+    uint64_t flat_iters;               /* flat-space iterations                              */
+    uint64_t node_pairs;               /* BVH inner-node visits (2 AABB tests each)          */
+    uint64_t triangles;                /* hit_triangle calls                                 */
+    uint64_t disk_hits;                /* accretion-disk shading events                      */
+    uint64_t sky_samples;              /* in-kernel sky taps (ray.wgsl:587)                  */
+    /* scheduling of the trace kernel (not a property of the frame: depends on frames in flight, batches, the kernel build)   */
+    uint64_t wave_steps;               /* integrator steps issued by waves: `steps` / (64 * wave_steps) = fraction of the lanes
+                                          of a stepping wave that hold a live ray                                            */
+    uint64_t rays_adopted;             /* rays that changed wave through the drain-merging mailbox (dense build)             */
+    uint64_t max_ray_iterations;       /* iterations of the longest ray (a maximum, also over levels): the latency floor of a level
+                                          is its longest ray                                                                  */
+} bhray_counters;
+int bhray_get_counters(bhray_ctx* ctx, bhray_counters* out);   /* needs BHRAY_F_COUNTERS     */
+int bhray_get_level_counters(bhray_ctx* ctx, uint32_t level, bhray_counters* out);
+/* Where the work of the last render lies: out[y] = iterations of all rays traced for row y of ladder level `level` (n = level_h[level]
+ * numbers; rows this ctx did not render are 0; a multi-partition ctx sums its local partitions).  Needs BHRAY_F_COUNTERS.
+ * The input of bhray_balance_slabs.                                                                                              */
+int bhray_get_row_work(bhray_ctx* ctx, uint32_t level, uint64_t* out, uint32_t n);
+
+/* ------------------------------------------------------------------------------------------
+ * Timing (BHRAY_F_TIMING, BHRAY_F_TIMING_SPARSE)
+ * ---------------------------------------------------------------------------------------- */
+/* HIP-event timing of every launch (events recorded on the ctx stream).  bhray_get_timing sums
+ * over the batches launched since the previous call (at most BHRAY_TIMING_RING of them).     */
+#define BHRAY_TIMING_RING 128
+typedef struct bhray_timing {
+    uint32_t frames;                   /* frames aggregated                                  */
+    uint32_t batches;                  /* batches aggregated (= frames unless frames_per_batch > 1) */
+    float    total_ms;                 /* Σ (first launch → last launch) per batch           */
+    float    trace_ms;                 /* Σ trace kernels                                    */
+    float    classify_ms;              /* Σ grid classify kernels                            */
+    uint32_t trace_launches;
+    uint32_t classify_launches;
+    float    level_trace_ms[BHRAY_MAX_LEVELS];
+    float    level_classify_ms[BHRAY_MAX_LEVELS];
+    float    sky_ms;                   /* Σ sky resolve kernels                              */
+    uint32_t sky_launches;
+    float    gather_ms;                /* multi-GPU, root: Σ (receive of the row tiles: start → all tiles arrived)   */
+    float    deinterleave_ms;          /* multi-GPU, root: Σ de-interleave kernels                                   */
+    uint32_t gathers;                  /* batches gathered                                                            */
+    float    predicted_trace_ms;       /* BHRAY_F_TEMPORAL: Σ (prediction + the predicted trace launch, all levels): the bulk of such a
+                                          frame; trace_ms / level_trace_ms then hold the fix-up launches only          */
+    uint32_t predicted_launches;
+    float    trace_exec_ms;            /* Σ EXECUTION spans of the trace kernels: first block's start → last block's end on the device's
+                                          constant-rate clock, stamped by the kernel itself.  trace_ms (HIP events in the stream) also
+                                          contains the time a launch waits for room beside the persistent kernels of the other frames
+                                          in flight; this is what `rocprofv3 --kernel-trace` reports as the kernel's duration          */
+    uint32_t trace_exec_launches;
+} bhray_timing;
+int bhray_get_timing(bhray_ctx* ctx, bhray_timing* out);       /* needs BHRAY_F_TIMING       */
+
+/* ------------------------------------------------------------------------------------------
+ * Verification
+ * ---------------------------------------------------------------------------------------- */
+/* Device self-test of the properties two exact shortcuts rest on: (i) the integrator computes the correctly
+ * rounded 1/x and sqrt(x) with short gfx950 sequences — run against the IEEE lowering on all 2^32 binary32 bit patterns;
+ * (ii) the grid classification replaces `acos(c) < threshold` by `c > c*` — the portable acos must be monotone over every
+ * binary32 value of [-1, 1].  Returns the number of violating inputs of each (all must be 0).  ~20 ms.              */
+int bhray_selftest(bhray_ctx* ctx, uint64_t mismatches[3]);    /* [0] = 1/x and the step-size power, [1] = sqrt, [2] = acos monotonicity */
+
+/* Any ladder level, full size level_w×level_h (unrendered pixels are NaN-filled at create).  */
+int bhray_read_level(bhray_ctx* ctx, uint32_t level, float* dst_rgba32f, size_t row_pitch_bytes);
+
+/* ------------------------------------------------------------------------------------------
+ * Gather statistics (multi-GPU)
+ * ---------------------------------------------------------------------------------------- */
+/* What a ctx gathers with.                                                                                          */
+typedef struct bhray_gather_info {
+    uint32_t partitions;                /* row partitions of the frame (1 = no tiling)                               */
+    uint32_t local_partitions;          /* partitions rendered by this ctx                                           */
+    uint32_t root;                      /* partition that receives the frame                                         */
+    uint32_t root_is_local;             /* 1: the frame is delivered by this ctx                                     */
+    uint32_t comm_ranks;                /* ranks of the RCCL communicator (0: no gather)                             */
+    uint32_t rccl_version;              /* ncclGetVersion, e.g. 22707 (0: RCCL not loaded)                           */
+    uint64_t bytes_sent_per_frame;      /* by this ctx's non-root partitions                                         */
+    uint64_t bytes_received_per_frame;  /* by the root partition (0 when it is not local)                            */
+} bhray_gather_info;
+int bhray_get_gather_info(const bhray_ctx* ctx, bhray_gather_info* out);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* BHRAY_DIAG_H */

@@ -2,60 +2,24 @@
 """Evidence behind the latency work of round 2 (run on the GPU box from the repo root; writes gpurun_out/latency_experiments.json,
 copied to profiles/r02_latency_experiments.json).
 
- 1. lone_wave_phases   where one wave's time goes in a latency-bound launch (level 0 of the 1080p ladder alone, 2 993 rays dealt out
-                       3 per wave): per-phase and per-iteration clocks written by a timing-only build of the SAME sources
-                           make -C bhusie_amd/csrc OUT=../../profiles/variants/libbhray_prof.so  OBJDIR=_obj_prof  EXTRA=-DBHRAY_EXP_PROFILE
-                           make -C bhusie_amd/csrc OUT=../../profiles/variants/libbhray_prof2.so OBJDIR=_obj_prof2 EXTRA="-DBHRAY_EXP_PROFILE -DBHRAY_EXP_PROFILE_FINE"
-                       (clock64 ticks = shader clocks, 0.42 ns on the box: profiles/ubench/lone_wave.hip; every clock read costs ~70).
- 2. temporal_prediction  BHRAY_F_TEMPORAL with a moving camera: rays the per-level fix-up launches had to trace (= what the prediction
-                       missed) and the latency of one frame at a time, for the prediction parameters BHRAY_TEMPORAL_MARGIN /
-                       BHRAY_TEMPORAL_RADIUS="last[,below]" (the library's defaults are 0.8 and 1,4).
+temporal_prediction  BHRAY_F_TEMPORAL with a moving camera: rays the per-level fix-up launches had to trace (= what the prediction
+                     missed) and the latency of one frame at a time, for the prediction parameters BHRAY_TEMPORAL_MARGIN /
+                     BHRAY_TEMPORAL_RADIUS="last[,below]" (the library's defaults are 0.8 and 1,4).
+
+The recorded file also holds lone_wave_phases / lone_wave_phases_fine: where one wave's time goes in a latency-bound launch (level 0
+of the 1080p ladder alone, 2 993 rays dealt out 3 per wave), per-phase and per-iteration clocks written by a timing-only build of
+round 2 (-DBHRAY_EXP_PROFILE; clock64 ticks = shader clocks, 0.42 ns on the box: profiles/ubench/lone_wave.hip; every clock read
+costs ~70).  That build option and its read-back export are gone, and so is the part of this script that used them.
 """
-import ctypes as C
 import json
 import math
 import os
-import subprocess
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, "gpurun_out", "latency_experiments.json")
-
-
-def lone_wave(fine):
-    import numpy as np
-    import bhusie_amd as B
-    from bhusie_amd import assets
-    tex = (assets.temp_lut(256), assets.reference_disk_texture(1000), assets.sky_texture(4096, 2048, seed=2))
-    L = C.CDLL(B.LIB_PATH)
-    L.bhray_debug_read_profile.argtypes = [C.c_void_p, C.c_size_t]
-    cfg = B.ladder_from_base((73, 41), 3, 1)
-    u = (B.Camera().uniform(), B.BlackHole().uniform(), B.RayDetails(integration_method=1).uniform())
-    rp = B.RayPass(cfg, frames_in_flight=1, timing=True)
-    rp.set_textures(*tex); rp.set_uniforms(*u)
-    for _ in range(3):
-        rp.render()
-    rp.sync(); rp.timing()
-    rp.render(); rp.sync()
-    tm = rp.timing()
-    buf = np.zeros(8192 * 16, np.int64)
-    L.bhray_debug_read_profile(buf.ctypes.data, buf.size)
-    d = buf.reshape(8192, 16)
-    act = d[d[:, 2] > 0]
-    it = act[:, 2].astype(float)
-    out = {"launch_ms": tm.trace_ms / tm.frames, "waves_with_rays": int(len(act)), "rays": 73 * 41,
-           "iterations_of_the_longest_wave": int(act[:, 2].max()), "ticks_total_longest_wave": int(act[:, 0].max()),
-           "mean_ticks_per_wave": {"refill": float(act[:, 3].mean()), "disk_shading": float(act[:, 4].mean()), "flat_phase": float(act[:, 5].mean()),
-                                   "epilogue": float(act[:, 6].mean()), "step_batches": float(act[:, 7].mean())},
-           "ticks_per_iteration_step_batches": float((act[:, 7] / it).mean())}
-    if fine:
-        out["ticks_per_iteration_fine"] = {"between_iterations_and_phases": float((act[:, 8] / it).mean()), "integrator_step": float((act[:, 9] / it).mean()),
-                                           "distance_and_culls": float((act[:, 10] / it).mean()), "rare_path_branch_and_count": float((act[:, 11] / it).mean()),
-                                           "note": "each bucket includes one clock read (~70 ticks)"}
-    rp.close()
-    return out
 
 
 def temporal():
@@ -106,18 +70,7 @@ def temporal():
 
 
 if __name__ == "__main__":
-    what = sys.argv[1] if len(sys.argv) > 1 else "all"
-    if what == "lone":
-        print(json.dumps(lone_wave(bool(os.environ.get("FINE")))))
-        sys.exit(0)
-    res = {}
-    env = dict(os.environ)
-    for key, lib, fine in (("lone_wave_phases", "profiles/variants/libbhray_prof.so", ""), ("lone_wave_phases_fine", "profiles/variants/libbhray_prof2.so", "1")):
-        if os.path.exists(os.path.join(ROOT, lib)):
-            r = subprocess.run([sys.executable, __file__, "lone"], capture_output=True, text=True, env=dict(env, BHRAY_LIB=os.path.join(ROOT, lib), FINE=fine), cwd=ROOT)
-            line = [l for l in r.stdout.splitlines() if l.startswith("{")]
-            res[key] = json.loads(line[-1]) if line else {"error": r.stderr[-500:]}
-    res["temporal_prediction"] = temporal()
+    res = {"temporal_prediction": temporal()}
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
     json.dump(res, open(OUT, "w"), indent=1)
     print("wrote", OUT)

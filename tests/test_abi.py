@@ -1,4 +1,4 @@
-"""CPU: the C-ABI library loads, exports every symbol include/bhray.h declares, and its layouts are the
+"""CPU: the C-ABI library loads, exports every symbol include/bhray.h and include/bhray_diag.h declare, and its layouts are the
 reference's #[repr(C)] layouts.  No compute calls (there is no GPU here and no CPU path in the library)."""
 import ctypes as C
 import os
@@ -12,20 +12,51 @@ from bhusie_amd import layouts
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def header_functions():
-    text = open(os.path.join(ROOT, "include", "bhray.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    names = re.findall(r"\b(bhray_[a-z0-9_]+)\s*\(", text)
-    return sorted(set(names))
+# what exists to measure or verify the library: declared in include/bhray_diag.h, never in the renderer's include/bhray.h
+DIAG_ONLY = ("bhray_counters", "bhray_get_counters", "bhray_get_level_counters", "bhray_get_row_work", "BHRAY_TIMING_RING", "bhray_timing",
+             "bhray_get_timing", "bhray_selftest", "bhray_read_level", "bhray_gather_info", "bhray_get_gather_info")
+
+
+def header_code(header):
+    """include/<header> without its comments"""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
+
+
+def header_functions(header):
+    return sorted(set(re.findall(r"\b(bhray_[a-z0-9_]+)\s*\(", header_code(header))))
 
 
 def test_every_declared_symbol_is_exported_and_bound():
     L = B.lib()
-    declared = header_functions()
-    assert len(declared) >= 40
+    product, diag = header_functions("bhray.h"), header_functions("bhray_diag.h")
+    assert len(product) >= 40 and len(diag) >= 7
+    assert not set(product) & set(diag), f"declared in both headers: {sorted(set(product) & set(diag))}"
+    declared = sorted(set(product) | set(diag))
     for name in declared:
-        assert hasattr(L, name), f"{name} declared in include/bhray.h but not exported by libbhray.so"
-    assert sorted(layouts.SYMBOLS) == declared, "python bindings and header disagree"
+        assert hasattr(L, name), f"{name} declared in include/bhray.h or include/bhray_diag.h but not exported by libbhray.so"
+    assert sorted(layouts.SYMBOLS) == product, "python bindings (layouts.SYMBOLS) and include/bhray.h disagree"
+    assert sorted(layouts.DIAG_SYMBOLS) == diag, "python bindings (layouts.DIAG_SYMBOLS) and include/bhray_diag.h disagree"
+    assert sorted(set(layouts.SYMBOLS) | set(layouts.DIAG_SYMBOLS)) == declared
+
+
+def test_measurement_entry_points_live_in_the_diagnostic_header_only():
+    """include/bhray.h is what a renderer includes: it declares none of the measurement surface and does not pull it in."""
+    product, diag = header_code("bhray.h"), header_code("bhray_diag.h")
+    for name in DIAG_ONLY:
+        assert not re.search(r"\b%s\b" % name, product), f"{name} is declared in include/bhray.h"
+        assert re.search(r"\b%s\b" % name, diag), f"{name} is not declared in include/bhray_diag.h"
+    assert not re.search(r"#\s*include\s*[<\"][^>\"]*bhray_diag\.h", product), "include/bhray.h includes bhray_diag.h"
+    assert re.search(r'#\s*include\s*"bhray\.h"', diag), "include/bhray_diag.h must include bhray.h"
+
+
+def test_every_exported_function_is_declared_in_a_header():
+    import subprocess
+    so = os.path.join(ROOT, "bhusie_amd", "libbhray.so")
+    nm = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
+    exported = sorted(set(re.findall(r"^\S+ T (bhray_[a-z0-9_]+)$", nm, flags=re.M)))
+    assert len(exported) >= 60
+    declared = set(header_functions("bhray.h")) | set(header_functions("bhray_diag.h"))
+    assert [n for n in exported if n not in declared] == [], "exported by libbhray.so but declared in no header"
 
 
 def test_layout_sizes_match_reference_structs():
