@@ -17,8 +17,8 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 
 from ._lib import lib, LibraryMissing, LIB_PATH  # noqa: F401
 from .layouts import (BhrayConfig, BhrayCounters, BhrayTiming, BhrayDetails, BhrayCameraUniform,  # noqa: F401
-                      BhrayBlackHoleUniform, BhrayBlackHole, BhrayModelDesc, BhrayNode, BhrayTriangle,
+                      BhrayBlackHoleUniform, BhrayBlackHole, BhrayFxaaDetails, BhrayMixDetails, BhrayModelDesc, BhrayNode, BhrayTriangle,
                       BhrayError, check)
 from .scene import Camera, BlackHole, RayDetails  # noqa: F401
 from .model import Model, load_model  # noqa: F401
-from .renderer import RayPass, Renderer, PinnedFrame, ladder_from_base, ladder_for_frame, comm_unique_id, partition_rows, config_partition_rows, balance_slabs, rebalance_slabs  # noqa: F401
+from .renderer import RayPass, Renderer, PinnedFrame, ladder_from_base, ladder_for_frame, comm_unique_id, post_defaults, bloom_sizes, partition_rows, config_partition_rows, balance_slabs, rebalance_slabs  # noqa: F401

@@ -68,6 +68,8 @@ struct FrameRes {
     float4* out = nullptr;              // where this frame is written (own_out or a bound buffer)
     uint2* sky_out = nullptr;           // RGBA16F image of the sky resolve pass (allocated on first use)
     uint64_t sky_frame_id = ~0ull;      // frame_id of the frame sky_out was resolved from (a slot position is reused: an older frame's image is stale)
+    uint32_t* disp_out = nullptr;       // RGBA8 sRGB image of the display pass (allocated on first use)
+    uint64_t disp_frame_id = ~0ull;     // frame_id of the frame disp_out was resolved from (the sky image's rule)
     uint64_t frame_id = 0;              // frame_counter value of the frame held here
     int row_variant = -1;               // which ordering of the level rows this frame classifies in (Level::d_rows_near), -1: ascending
 };
@@ -91,6 +93,7 @@ struct Slot {
     uint8_t* d_args = nullptr;
     size_t args_cap = 0;
     uint64_t batch_id = 0;              // batch_counter value of the batch this slot holds
+    uint2* post_scratch = nullptr;      // display pass: bloom levels + tone-mapped image (allocated on first use; the frames of a slot run in stream order)
 };
 
 struct ModelStore {
@@ -374,7 +377,9 @@ void dev_destroy(bhray_dev* c) {
             if (R.own_out) (void)hipFree(R.own_out);
             if (R.d_row_work) (void)hipFree(R.d_row_work);
             if (R.sky_out) (void)hipFree(R.sky_out);
+            if (R.disp_out) (void)hipFree(R.disp_out);
         }
+        if (S.post_scratch) (void)hipFree(S.post_scratch);
         if (S.d_qctl) (void)hipFree(S.d_qctl);
         if (S.d_counters) (void)hipFree(S.d_counters);
         if (S.h_args) (void)hipHostFree(S.h_args);
@@ -1504,6 +1509,88 @@ int dev_sky_device_ptr(bhray_dev* c, void** p, size_t* bytes) {
     if (!c->local_rows.empty() && (!R.sky_out || R.sky_frame_id != R.frame_id)) return fail(c, BHRAY_E_STATE, "dev_resolve_sky has not been called for this frame");
     *p = R.sky_out;
     if (bytes) *bytes = c->local_rows.size() * (size_t)c->cfg.frame_w * sizeof(uint2);
+    return BHRAY_OK;
+}
+
+// ---- display pass (bhray_post.hip): the sky image's rules, for the RGBA8 image --------------------------------
+static int display_whole_frame(bhray_dev* c) {
+    if (c->local_rows.size() != (size_t)c->cfg.frame_h)
+        return fail(c, BHRAY_E_STATE, "the display pass needs the whole frame: this ctx renders %zu of %u rows (BHRAY_GATHER_NONE)", c->local_rows.size(), c->cfg.frame_h);
+    if (display_scratch_bytes(c->cfg.frame_w, c->cfg.frame_h) == 0) return fail(c, BHRAY_E_INVALID, "the display pass needs a frame of at least 32 x 32 pixels");
+    return BHRAY_OK;
+}
+
+int dev_resolve_display(bhray_dev* c, const bhray_fxaa_details* fx, const bhray_mix_details* mx) {
+    if (!c || !fx || !mx) return BHRAY_E_INVALID;
+    if (!c->rendered) return fail(c, BHRAY_E_STATE, "nothing rendered yet");
+    { int rc = display_whole_frame(c); if (rc) return rc; }
+    Slot& S = c->slots[(size_t)c->last_slot];
+    FrameRes& R = S.fr[(size_t)c->last_sub];
+    if (!R.sky_out || R.sky_frame_id != R.frame_id) { int rc = dev_resolve_sky(c); if (rc) return rc; }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = launch_batch(c); if (rc) return rc; }
+    const size_t npix = (size_t)c->cfg.frame_w * c->cfg.frame_h;
+    if (!S.post_scratch) HIPCHK(c, hipMalloc(&S.post_scratch, display_scratch_bytes(c->cfg.frame_w, c->cfg.frame_h)));
+    if (!R.disp_out) HIPCHK(c, hipMalloc(&R.disp_out, npix * sizeof(uint32_t)));
+    HIPCHK(c, launch_display(R.sky_out, S.post_scratch, R.disp_out, c->cfg.frame_w, c->cfg.frame_h, *fx, *mx, S.stream));
+    R.disp_frame_id = R.frame_id;
+    HIPCHK(c, hipEventRecord(S.done, S.stream));
+    return BHRAY_OK;
+}
+
+int dev_read_display(bhray_dev* c, uint8_t* dst, size_t pitch) {
+    if (!c) return BHRAY_E_INVALID;
+    const size_t rowb = (size_t)c->cfg.frame_w * 4;
+    { int rc = display_whole_frame(c); if (rc) return rc; }
+    if (!dst || pitch < rowb) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
+    const FrameRes& R = c->slots[(size_t)c->last_slot].fr[(size_t)c->last_sub];
+    if (!c->rendered || !R.disp_out || R.disp_frame_id != R.frame_id) return fail(c, BHRAY_E_STATE, "bhray_resolve_display has not been called for this frame");
+    int rc = dev_sync(c);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpy2D(dst, pitch, R.disp_out, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost));
+    return BHRAY_OK;
+}
+
+int dev_read_display_async(bhray_dev* c, uint8_t* dst, size_t pitch, uint64_t* ticket) {
+    if (!c || !ticket) return BHRAY_E_INVALID;
+    const size_t rowb = (size_t)c->cfg.frame_w * 4;
+    if (!c->rendered) return fail(c, BHRAY_E_STATE, "nothing rendered yet");
+    { int rc = display_whole_frame(c); if (rc) return rc; }
+    if (!dst || pitch < rowb) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
+    HIPCHK(c, hipSetDevice(c->device));
+    Slot& S = c->slots[(size_t)c->last_slot];
+    FrameRes& R = S.fr[(size_t)c->last_sub];
+    if (!R.disp_out || R.disp_frame_id != R.frame_id) return fail(c, BHRAY_E_STATE, "bhray_resolve_display has not been called for this frame");
+    { int rc = launch_batch(c); if (rc) return rc; }
+    const uint64_t t = c->read_tickets;
+    hipEvent_t& ev = c->read_ev[t % BHRAY_READ_RING];
+    if (!ev) HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    else if (t >= BHRAY_READ_RING) HIPCHK(c, hipEventSynchronize(ev));
+    if (pitch == rowb) HIPCHK(c, hipMemcpyAsync(dst, R.disp_out, (size_t)c->cfg.frame_h * rowb, hipMemcpyDeviceToHost, S.stream));
+    else HIPCHK(c, hipMemcpy2DAsync(dst, pitch, R.disp_out, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost, S.stream));
+    HIPCHK(c, hipEventRecord(ev, S.stream));
+    HIPCHK(c, hipEventRecord(S.done, S.stream));
+    *ticket = t;
+    c->read_tickets = t + 1;
+    return BHRAY_OK;
+}
+
+int dev_display_device_ptr(bhray_dev* c, void** p, size_t* bytes) {
+    if (!c || !p) return BHRAY_E_INVALID;
+    *p = nullptr;
+    { int rc = display_whole_frame(c); if (rc) return rc; }
+    const FrameRes& R = c->slots[(size_t)c->last_slot].fr[(size_t)c->last_sub];
+    if (!c->rendered || !R.disp_out || R.disp_frame_id != R.frame_id) return fail(c, BHRAY_E_STATE, "bhray_resolve_display has not been called for this frame");
+    *p = R.disp_out;
+    if (bytes) *bytes = (size_t)c->cfg.frame_w * c->cfg.frame_h * 4;
+    return BHRAY_OK;
+}
+
+// the display pass of a gathered frame on the root (bhray_group.hip): sky image -> RGBA8 on the caller's stream
+int dev_launch_display(bhray_dev* c, const void* sky, void* scratch, void* dst, const bhray_fxaa_details* fx, const bhray_mix_details* mx, hipStream_t stream) {
+    if (!c || !fx || !mx) return BHRAY_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_display((const uint2*)sky, (uint2*)scratch, (uint32_t*)dst, c->cfg.frame_w, c->cfg.frame_h, *fx, *mx, stream));
     return BHRAY_OK;
 }
 

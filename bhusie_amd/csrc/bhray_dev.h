@@ -75,6 +75,11 @@ int  dev_bind_output(bhray_dev* c, void* p, size_t bytes);     // destination of
 int  dev_resolve_sky(bhray_dev* c);
 int  dev_read_sky(bhray_dev* c, uint16_t* dst, size_t pitch);
 int  dev_sky_device_ptr(bhray_dev* c, void** p, size_t* bytes);
+int  dev_resolve_display(bhray_dev* c, const bhray_fxaa_details* fxaa, const bhray_mix_details* mix);   // display pass (bhray_post.hip) behind the last frame
+int  dev_read_display(bhray_dev* c, uint8_t* dst, size_t pitch);
+int  dev_read_display_async(bhray_dev* c, uint8_t* dst, size_t pitch, uint64_t* ticket);
+int  dev_display_device_ptr(bhray_dev* c, void** p, size_t* bytes);
+int  dev_launch_display(bhray_dev* c, const void* sky, void* scratch, void* dst, const bhray_fxaa_details* fxaa, const bhray_mix_details* mix, hipStream_t stream);
 int  dev_wait_event(bhray_dev* c, hipEvent_t ev);             // the next render's launches start after ev (ev is owned by the caller)
 int  dev_next_stream(bhray_dev* c, void** s);
 int  dev_signal_stream(bhray_dev* c, void* s);

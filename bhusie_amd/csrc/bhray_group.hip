@@ -229,6 +229,8 @@ struct GroupSlot {                 // per batch slot (same index as the devices'
     uint2* sky[BHRAY_MAX_FRAMES_PER_BATCH];   // root: RGBA16F images of bhray_resolve_sky (allocated on first use)
     uint64_t frame_no[BHRAY_MAX_FRAMES_PER_BATCH] = {};       // serial of the frame staged in each place (1-based), and of the frame its sky
     uint64_t sky_frame_no[BHRAY_MAX_FRAMES_PER_BATCH] = {};   // image was resolved from: a sky image is current only while the two agree
+    uint32_t* disp[BHRAY_MAX_FRAMES_PER_BATCH] = {};          // root: RGBA8 images of bhray_resolve_display (allocated on first use) ...
+    uint64_t disp_frame_no[BHRAY_MAX_FRAMES_PER_BATCH] = {};  // ... and the frame each was resolved from (the sky image's rule)
     hipEvent_t tev[3] = {nullptr, nullptr, nullptr};   // timing: before receive, after receive, after de-interleave
     bool timed = false;
 };
@@ -298,6 +300,9 @@ struct bhray_ctx {
     double hole_row = 0.0, hole_row_prev = 0.0; bool hole_row_valid = false, hole_row_prev_valid = false;   // frame row the hole projects to: at the last render / at the last rebalance
     float* d_xchg = nullptr;               // one process per GPU: 2 + 2 * partitions floats on this rank's GPU (the all-gather of bhray_rebalance)
     float4* bound = nullptr;               // bhray_bind_output: destination of the next frame (one-shot)
+    bhray_fxaa_details post_fxaa{};        // display pass uniforms (bhray_set_post_uniforms), used by the next bhray_resolve_display
+    bhray_mix_details post_mix{};
+    uint2* post_scratch = nullptr;         // root of a gathering ctx: the display pass's bloom levels and tone-mapped image (all on the root's communication stream)
     hipEvent_t read_ev[64] = {nullptr};
     uint64_t read_tickets = 0;
     std::vector<void*> external;           // bhray_import_external_fd: hipExternalMemory_t handles, by mapped pointer (pairs: ptr, handle)
@@ -660,8 +665,10 @@ void group_free(bhray_ctx* c) {
             if (G.frame_done) (void)hipEventDestroy(G.frame_done);
             for (auto& e : G.tev) if (e) (void)hipEventDestroy(e);
             for (auto& s : G.sky) if (s) (void)hipFree(s);
+            for (auto& d : G.disp) if (d) (void)hipFree(d);
         }
         if (c->d_table) (void)hipFree(c->d_table);
+        if (c->post_scratch) (void)hipFree(c->post_scratch);
     }
     for (CommRank& r : c->ranks) {
         (void)hipSetDevice(r.device);
@@ -1021,6 +1028,7 @@ int bhray_create(const bhray_config* cfg_in, bhray_ctx** out) {
     bhray_ctx* c = new (std::nothrow) bhray_ctx();
     if (!c) return gfail(nullptr, BHRAY_E_NOMEM, "host allocation failed");
     c->cfg = *cfg;
+    (void)bhray_post_defaults(&c->post_fxaa, &c->post_mix);
     const bool multi_dev = cfg->device_count >= 2;                                   // one process, N GPUs
     const bool multi_proc = !multi_dev && cfg->gather == BHRAY_GATHER_RCCL && cfg->row_world > 1;   // one process per GPU
     c->gather = multi_dev || multi_proc;
@@ -1785,10 +1793,7 @@ int bhray_signal_stream(bhray_ctx* c, void* s) {
 }
 
 // ---- sky resolve -----------------------------------------------------------------------------------
-int bhray_resolve_sky(bhray_ctx* c) {
-    if (!c) return BHRAY_E_INVALID;
-    ENTER(c);
-    if (c->single) { DEV(c, c->parts[0].dev, dev_resolve_sky(c->parts[0].dev)); return BHRAY_OK; }
+static int group_resolve_sky(bhray_ctx* c) {
     if (!c->rendered) return gfail(c, BHRAY_E_STATE, "nothing rendered yet");
     { int rc = group_flush(c); if (rc) return rc; }
     if (c->gather_sky) return BHRAY_OK;              // the partitions resolved their rows behind the render; the gather assembled the image
@@ -1805,6 +1810,13 @@ int bhray_resolve_sky(bhray_ctx* c) {
     // group_gather enqueued captured the EARLIER record of frame_done, behind the de-interleave): order it behind this one
     GHIP(c, hipStreamWaitEvent(dev_slot_stream(rp.dev, c->last_slot), G.frame_done, 0));
     return BHRAY_OK;
+}
+
+int bhray_resolve_sky(bhray_ctx* c) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    if (c->single) { DEV(c, c->parts[0].dev, dev_resolve_sky(c->parts[0].dev)); return BHRAY_OK; }
+    return group_resolve_sky(c);
 }
 
 int bhray_read_sky(bhray_ctx* c, uint16_t* dst, size_t pitch) {
@@ -1834,6 +1846,97 @@ int bhray_sky_device_ptr(bhray_ctx* c, void** p, size_t* bytes) {
     }
     *p = c->root_local ? (void*)c->gslots[(size_t)c->last_slot].sky[c->last_sub] : nullptr;
     if (bytes) *bytes = c->root_local ? frame_pixels(c) * sizeof(uint2) : 0;
+    return BHRAY_OK;
+}
+
+// ---- display pass (bhray_post.hip) ---------------------------------------------------------------------------
+int bhray_set_post_uniforms(bhray_ctx* c, const void* fxaa16, const void* mix4) {
+    if (!c || !fxaa16 || !mix4) return BHRAY_E_INVALID;
+    bhray_fxaa_details f; bhray_mix_details m;
+    memcpy(&f, fxaa16, sizeof f); memcpy(&m, mix4, sizeof m);
+    if (f.iterations > BHRAY_FXAA_MAX_ITERATIONS) return gfail(c, BHRAY_E_INVALID, "fxaa iterations %d > BHRAY_FXAA_MAX_ITERATIONS (%d)", f.iterations, BHRAY_FXAA_MAX_ITERATIONS);
+    c->post_fxaa = f; c->post_mix = m;
+    return BHRAY_OK;
+}
+
+// the root's RGBA8 image of the most recently staged frame, if it was resolved for that frame
+static uint32_t* group_display(bhray_ctx* c) {
+    const GroupSlot& GS = c->gslots[(size_t)c->last_slot];
+    uint32_t* d = GS.disp[c->last_sub];
+    return (d && GS.disp_frame_no[c->last_sub] == GS.frame_no[c->last_sub]) ? d : nullptr;
+}
+
+int bhray_resolve_display(bhray_ctx* c) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    if (c->single) { DEV(c, c->parts[0].dev, dev_resolve_display(c->parts[0].dev, &c->post_fxaa, &c->post_mix)); return BHRAY_OK; }
+    if (!c->rendered) return gfail(c, BHRAY_E_STATE, "nothing rendered yet");
+    if (display_scratch_bytes(c->cfg.frame_w, c->cfg.frame_h) == 0) return gfail(c, BHRAY_E_INVALID, "the display pass needs a frame of at least 32 x 32 pixels");
+    { int rc = group_flush(c); if (rc) return rc; }
+    if (!c->root_local) return BHRAY_OK;                        // the frame lives on another rank
+    GroupSlot& G = c->gslots[(size_t)c->last_slot];
+    if (!G.sky[c->last_sub] || G.sky_frame_no[c->last_sub] != G.frame_no[c->last_sub]) { int rc = group_resolve_sky(c); if (rc) return rc; }
+    Part& rp = *root_part(c);
+    CommRank* rr = rank_of(c, rp);
+    GHIP(c, hipSetDevice(rp.device));
+    if (!c->post_scratch) GHIP(c, hipMalloc(&c->post_scratch, display_scratch_bytes(c->cfg.frame_w, c->cfg.frame_h)));
+    if (!G.disp[c->last_sub]) GHIP(c, hipMalloc(&G.disp[c->last_sub], frame_pixels(c) * sizeof(uint32_t)));
+    // behind the sky image on the root's communication stream (the gather's de-interleave, or bhray_resolve_sky's pass)
+    DEV(c, rp.dev, dev_launch_display(rp.dev, G.sky[c->last_sub], c->post_scratch, G.disp[c->last_sub], &c->post_fxaa, &c->post_mix, rr->stream));
+    G.disp_frame_no[c->last_sub] = G.frame_no[c->last_sub];
+    return BHRAY_OK;
+}
+
+int bhray_read_display(bhray_ctx* c, uint8_t* dst, size_t pitch) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    if (c->single) { DEV(c, c->parts[0].dev, dev_read_display(c->parts[0].dev, dst, pitch)); return BHRAY_OK; }
+    { int rc = group_sync(c); if (rc) return rc; }
+    if (!c->root_local) return BHRAY_OK;
+    const size_t rowb = (size_t)c->cfg.frame_w * 4;
+    if (!dst || pitch < rowb) return gfail(c, BHRAY_E_INVALID, "bad destination / pitch");
+    uint32_t* src = c->rendered ? group_display(c) : nullptr;
+    if (!src) return gfail(c, BHRAY_E_STATE, "bhray_resolve_display has not been called for this frame");
+    GHIP(c, hipSetDevice(root_part(c)->device));
+    GHIP(c, hipMemcpy2D(dst, pitch, src, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost));
+    return BHRAY_OK;
+}
+
+int bhray_read_display_async(bhray_ctx* c, uint8_t* dst, size_t pitch, uint64_t* ticket) {
+    if (!c || !ticket) return BHRAY_E_INVALID;
+    ENTER(c);
+    if (c->single) { DEV(c, c->parts[0].dev, dev_read_display_async(c->parts[0].dev, dst, pitch, ticket)); return BHRAY_OK; }
+    if (!c->rendered) return gfail(c, BHRAY_E_STATE, "nothing rendered yet");
+    const uint64_t t = c->read_tickets;
+    if (!c->root_local) { *ticket = t; c->read_tickets = t + 1; return BHRAY_OK; }
+    const size_t rowb = (size_t)c->cfg.frame_w * 4;
+    if (!dst || pitch < rowb) return gfail(c, BHRAY_E_INVALID, "bad destination / pitch");
+    uint32_t* src = group_display(c);
+    if (!src) return gfail(c, BHRAY_E_STATE, "bhray_resolve_display has not been called for this frame");
+    Part& rp = *root_part(c);
+    CommRank* rr = rank_of(c, rp);
+    GHIP(c, hipSetDevice(rp.device));
+    hipEvent_t& ev = c->read_ev[t % 64];
+    if (!ev) GHIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    else if (t >= 64) { GHIP(c, hipEventSynchronize(ev)); WATCH_CHECK(c); }
+    if (pitch == rowb) GHIP(c, hipMemcpyAsync(dst, src, rowb * c->cfg.frame_h, hipMemcpyDeviceToHost, rr->stream));     // behind the display pass, in stream order
+    else GHIP(c, hipMemcpy2DAsync(dst, pitch, src, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost, rr->stream));
+    GHIP(c, hipEventRecord(ev, rr->stream));
+    *ticket = t; c->read_tickets = t + 1;
+    return BHRAY_OK;
+}
+
+int bhray_display_device_ptr(bhray_ctx* c, void** p, size_t* bytes) {
+    if (!c || !p) return BHRAY_E_INVALID;
+    if (c->single) { DEV(c, c->parts[0].dev, dev_display_device_ptr(c->parts[0].dev, p, bytes)); return BHRAY_OK; }
+    ENTER(c);
+    *p = nullptr;
+    if (c->root_local) {
+        uint32_t* d = c->rendered ? group_display(c) : nullptr;
+        if (!d) return gfail(c, BHRAY_E_STATE, "bhray_resolve_display has not been called for this frame");
+        *p = d;
+    }
+    if (bytes) *bytes = c->root_local ? frame_pixels(c) * 4 : 0;
     return BHRAY_OK;
 }
 

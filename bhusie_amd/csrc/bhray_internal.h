@@ -148,4 +148,19 @@ hipError_t launch_predict(const FrameParams* Pb, const FrameLaunch* Fb, int nb, 
 hipError_t launch_selftest(unsigned long long* bad3, hipStream_t s);   // [0]: 1/x mismatches, [1]: sqrt mismatches, [2]: places where bh_acos increases
 hipError_t launch_sky(const TexDev& sky, const float4* src, uint2* dst_rgba16f, size_t npix, hipStream_t s);
 
+// display pass (bhray_post.hip): bloom down x5 / up x5, mix, ACES, FXAA into RGBA8 sRGB
+#define BHRAY_BLOOM_LEVELS 10
+struct PostArgs {                        // fxaa_kernel's arguments: the uniform block, and the sRGB encoding's decision thresholds (copied to LDS)
+    float srgb_thr[255];                 // increasing: byte = number of thresholds <= the value
+    float edge_min, edge_max;
+    int iterations;
+    float subpix;
+    float one_twelfth;                   // fxaa.wgsl's `1.0 / 12.0` (an abstract-float constant, rounded to f32 once)
+};
+int bloom_sizes(uint32_t frame_w, uint32_t frame_h, uint32_t w[BHRAY_BLOOM_LEVELS], uint32_t h[BHRAY_BLOOM_LEVELS]);   // BHRAY_E_INVALID: a level would be empty
+size_t display_scratch_bytes(uint32_t frame_w, uint32_t frame_h);                  // device bytes launch_display needs besides its input and output; 0: frame too small
+// the 11 launches of the display pass on stream s: RGBA16F sky image (frame_w x frame_h) -> RGBA8 sRGB image
+hipError_t launch_display(const uint2* sky, uint2* scratch, uint32_t* dst_rgba8, uint32_t frame_w, uint32_t frame_h,
+                          const bhray_fxaa_details& fxaa, const bhray_mix_details& mix, hipStream_t s);
+
 }  // namespace bhray

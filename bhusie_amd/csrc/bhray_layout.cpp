@@ -52,6 +52,13 @@ static_assert(BHRAY_MODEL_OFF_LOOKUP + 4u * BHRAY_MAX_MODEL_VERTICES + 28u == BH
 static_assert(BHRAY_MODEL_UNIFORM_BYTES == 48234572u, "ModelUniform size (triangle.rs:268-285)");
 static_assert(BHRAY_MAX_MODELS == 1 && BHRAY_MAX_MATERIALS == 8, "triangle.rs:6, material.rs:3");
 
+// FXAADetailsUniform (fxaa_pipline.rs:76-83) and MixDetails (mix_pipeline.rs:5-7): the display pass's uniform blocks
+SZ(bhray_fxaa_details, 16);
+OFF(bhray_fxaa_details, edge_threshold_min, 0); OFF(bhray_fxaa_details, edge_threshold_max, 4); OFF(bhray_fxaa_details, iterations, 8);
+OFF(bhray_fxaa_details, subpixel_quality, 12);
+SZ(bhray_mix_details, 4);
+OFF(bhray_mix_details, mix_ratio, 0);
+
 // not reference layouts, but ABI the bindings restate (bhusie_amd/layouts.py)
 static_assert(sizeof(bhray_counters) == 104, "bhray_counters");
 static_assert(BHRAY_COMM_ID_BYTES == 128, "ncclUniqueId");

@@ -65,7 +65,9 @@ private:
 enum class Handoff {
     Sync,        // finish() = bhray_read_hdr of the frame just rendered: the naive binding, one frame at a time
     AsyncHdr,    // pass() also enqueues the RGBA32F copy into pinned memory (bhray_read_hdr_async); finish() hands over the OLDEST frame in flight
-    AsyncSky     // pass() also runs the sky pass in the library (sky.wgsl) and enqueues the copy of its RGBA16F image: half the bytes
+    AsyncSky,    // pass() also runs the sky pass in the library (sky.wgsl) and enqueues the copy of its RGBA16F image: half the bytes
+    AsyncDisplay // pass() also runs the display pass (bloom, mix, ACES, FXAA: DESIGN.md §10) and enqueues the copy of its RGBA8 sRGB image:
+                 // the finished picture, a quarter of the RGBA32F bytes - the host uploads it raw into the texture its ScreenPipeline samples
 };
 
 // The chain of RayPipelines of one frame (mod.rs:181-207) as one object.
@@ -113,7 +115,7 @@ public:
     // (mod.rs:415-417), finish() where the host needs the pixels (before sky_pipeline.pass(), mod.rs:419)
     void enable_handoff(Handoff h, uint32_t frames_in_flight) {
         handoff_ = h; ring_ = frames_in_flight < 1 ? 1 : frames_in_flight;
-        const size_t bytes = (size_t)cfg_.frame_w * cfg_.frame_h * (h == Handoff::AsyncSky ? 8 : 16);
+        const size_t bytes = (size_t)cfg_.frame_w * cfg_.frame_h * (h == Handoff::AsyncDisplay ? 4 : (h == Handoff::AsyncSky ? 8 : 16));
         for (uint32_t i = 0; i < ring_; i++) { void* p = nullptr; check(bhray_host_alloc(bytes, &p)); staging_.push_back(p); }
         tickets_.assign(ring_, 0); pending_.assign(ring_, false);
     }
@@ -126,6 +128,9 @@ public:
         } else if (handoff_ == Handoff::AsyncSky) {
             resolve_sky();
             check(bhray_read_sky_async(ctx_, (uint16_t*)staging_[k], (size_t)cfg_.frame_w * 8, &tickets_[k]), ctx_); pending_[k] = true;
+        } else if (handoff_ == Handoff::AsyncDisplay) {
+            resolve_display();
+            check(bhray_read_display_async(ctx_, (uint8_t*)staging_[k], (size_t)cfg_.frame_w * 4, &tickets_[k]), ctx_); pending_[k] = true;
         }
         frame_++;
     }
@@ -156,6 +161,9 @@ public:
     void pass() { check(bhray_render(ctx_), ctx_); }                                            // ray_pipeline.rs:301-309
     void flush() { check(bhray_flush(ctx_), ctx_); }
     void resolve_sky() { check(bhray_resolve_sky(ctx_), ctx_); }                                // sky_pipeline.rs pass
+    // bloom / mix / hdr / fxaa passes (mod.rs:425-431), with the uniforms Renderer::render uploads unless set_post_uniforms changed them
+    void resolve_display() { check(bhray_resolve_display(ctx_), ctx_); }
+    void set_post_uniforms(const bhray_fxaa_details& f, const bhray_mix_details& m) { check(bhray_set_post_uniforms(ctx_, &f, &m), ctx_); }
     std::vector<float> output() {                                                               // output_view + read-back
         std::vector<float> out((size_t)cfg_.frame_w * cfg_.frame_h * 4);
         check(bhray_read_hdr(ctx_, out.data(), (size_t)cfg_.frame_w * 16), ctx_);

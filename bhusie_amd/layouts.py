@@ -18,6 +18,7 @@ F_TIMING_SPARSE = 16
 F_EVAL_FMA = 32
 F_GATHER_SKY = 128
 TEX_TEMP_LUT, TEX_DISK, TEX_SKY = 0, 1, 2
+FXAA_MAX_ITERATIONS = 1024
 
 
 class BhrayError(RuntimeError):
@@ -57,6 +58,14 @@ class BhrayNode(C.Structure):               # triangle.rs:45-52
 
 class BhrayTriangle(C.Structure):           # triangle.rs:54-63
     _fields_ = [(n, C.c_int32) for n in ("p1", "p2", "p3", "n1", "n2", "n3")]
+
+
+class BhrayFxaaDetails(C.Structure):       # fxaa_pipline.rs:76-83 (FXAADetailsUniform)
+    _fields_ = [("edge_threshold_min", C.c_float), ("edge_threshold_max", C.c_float), ("iterations", C.c_int32), ("subpixel_quality", C.c_float)]
+
+
+class BhrayMixDetails(C.Structure):         # mix_pipeline.rs:5-7 (MixDetails)
+    _fields_ = [("mix_ratio", C.c_float)]
 
 
 class BhrayModelDesc(C.Structure):
@@ -178,6 +187,13 @@ SYMBOLS = {
     "bhray_resolve_sky": (C.c_int, [vp]),
     "bhray_read_sky": (C.c_int, [vp, vp, sz]),
     "bhray_sky_device_ptr": (C.c_int, [vp, P(vp), P(sz)]),
+    "bhray_post_defaults": (C.c_int, [P(BhrayFxaaDetails), P(BhrayMixDetails)]),
+    "bhray_bloom_sizes": (C.c_int, [u32, u32, P(u32), P(u32)]),
+    "bhray_set_post_uniforms": (C.c_int, [vp, vp, vp]),
+    "bhray_resolve_display": (C.c_int, [vp]),
+    "bhray_read_display": (C.c_int, [vp, vp, sz]),
+    "bhray_read_display_async": (C.c_int, [vp, vp, sz, P(C.c_uint64)]),
+    "bhray_display_device_ptr": (C.c_int, [vp, P(vp), P(sz)]),
     "bhray_wait_stream": (C.c_int, [vp, vp]),
     "bhray_signal_stream": (C.c_int, [vp, vp]),
     "bhray_next_stream": (C.c_int, [vp, P(vp)]),

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import lib
-from .layouts import (PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters,
+from .layouts import (BhrayFxaaDetails, BhrayMixDetails, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters,
                       BhrayGatherInfo, BhrayRebalanceInfo, BhrayTiming, check)
 from .model import Model
 from .scene import BlackHole, Camera, RayDetails
@@ -29,6 +29,20 @@ def ladder_for_frame(frame=(1920, 1080), multiplier=3, levels=4) -> BhrayConfig:
     cfg = BhrayConfig()
     check(lib().bhray_ladder_for_frame(frame[0], frame[1], multiplier, levels, C.byref(cfg)))
     return cfg
+
+
+def post_defaults():
+    """(BhrayFxaaDetails, BhrayMixDetails): the display pass's uniforms as Renderer::render uploads them (bhray_post_defaults)."""
+    f, m = BhrayFxaaDetails(), BhrayMixDetails()
+    check(lib().bhray_post_defaults(C.byref(f), C.byref(m)))
+    return f, m
+
+
+def bloom_sizes(frame_w: int, frame_h: int):
+    """[(w, h)] of the 10 bloom targets (5 down, 5 up) of a frame_w x frame_h frame (bhray_bloom_sizes: host arithmetic)."""
+    w, h = (C.c_uint32 * 10)(), (C.c_uint32 * 10)()
+    check(lib().bhray_bloom_sizes(int(frame_w), int(frame_h), w, h))
+    return [(int(a), int(b)) for a, b in zip(w, h)]
 
 
 def comm_unique_id() -> bytes:
@@ -289,6 +303,39 @@ class RayPass:
         check(self._L.bhray_read_sky(self._h, out.ctypes.data, int(self.cfg.frame_w) * 8), self._h, self._L)
         return out
 
+    # -- display pass: bloom, mix, ACES, FXAA into the RGBA8 sRGB image
+    def set_post_uniforms(self, fxaa: BhrayFxaaDetails | bytes | None = None, mix: BhrayMixDetails | bytes | float | None = None):
+        """The FXAA (16 B) and mix (4 B) uniform blocks, applied from the next resolve_display; None = the reference's defaults."""
+        df, dm = post_defaults()
+        f = bytes(fxaa) if fxaa is not None else bytes(df)
+        m = bytes(BhrayMixDetails(float(mix))) if isinstance(mix, (int, float)) else (bytes(mix) if mix is not None else bytes(dm))
+        assert len(f) == 16 and len(m) == 4
+        check(self._L.bhray_set_post_uniforms(self._h, f, m), self._h, self._L)
+
+    def resolve_display(self):
+        """The display pass behind the last frame (runs the sky pass first if it has not run for that frame)."""
+        check(self._L.bhray_resolve_display(self._h), self._h, self._L)
+
+    def read_display(self) -> np.ndarray:
+        """uint8 [H, W, 4]: R, G, B sRGB-encoded, A unorm.  On a rank that does not hold the frame (a non-root rank of a one-process-per-GPU
+        ctx: bhray_local_rows is 0) the library delivers nothing and this returns a [0, W, 4] array."""
+        w = int(self.cfg.frame_w)
+        h = int(self.cfg.frame_h) if int(self._L.bhray_local_rows(self._h)) > 0 else 0
+        out = np.empty((h, w, 4), dtype=np.uint8)
+        check(self._L.bhray_read_display(self._h, out.ctypes.data if h else None, w * 4), self._h, self._L)
+        return out
+
+    def read_display_async(self, dst: "PinnedFrame") -> int:
+        """The RGBA8 image (resolve_display first) into pinned memory (a PinnedFrame(rows, width, rgba8=True)); returns a ticket."""
+        t = C.c_uint64()
+        check(self._L.bhray_read_display_async(self._h, C.c_void_p(dst.ptr), int(self.cfg.frame_w) * 4, C.byref(t)), self._h, self._L)
+        return int(t.value)
+
+    def display_device_ptr(self):
+        p, n = C.c_void_p(), C.c_size_t()
+        check(self._L.bhray_display_device_ptr(self._h, C.byref(p), C.byref(n)), self._h, self._L)
+        return p.value, n.value
+
     def device_ptr(self):
         p, n = C.c_void_p(), C.c_size_t()
         check(self._L.bhray_hdr_device_ptr(self._h, C.byref(p), C.byref(n)), self._h, self._L)
@@ -341,14 +388,18 @@ class RayPass:
 
 
 class PinnedFrame:
-    """Pinned host memory for one RGBA32F frame (bhray_host_alloc), viewed as a (rows, width, 4) float32 array."""
+    """Pinned host memory for one RGBA32F frame (bhray_host_alloc), viewed as a (rows, width, 4) float32 array
+    (channels16: RGBA16F, float16; rgba8: the display image, uint8)."""
 
-    def __init__(self, rows: int, width: int, channels16: bool = False):
+    def __init__(self, rows: int, width: int, channels16: bool = False, rgba8: bool = False):
+        assert not (channels16 and rgba8)
         p = C.c_void_p()
-        self.nbytes = rows * width * (8 if channels16 else 16)
+        self.nbytes = rows * width * (4 if rgba8 else (8 if channels16 else 16))
         check(lib().bhray_host_alloc(self.nbytes, C.byref(p)))
         self.ptr = p.value
-        if channels16:          # RGBA16F (the sky pass's image)
+        if rgba8:               # RGBA8 sRGB (the display pass's image)
+            self.array = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(rows, width, 4))
+        elif channels16:        # RGBA16F (the sky pass's image)
             self.array = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint16)), shape=(rows, width, 4)).view(np.float16)
         else:
             self.array = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(rows, width, 4))
@@ -388,3 +439,12 @@ class Renderer:
 
     def read_hdr(self):
         return self.ray_pass.read_hdr()
+
+    def save_image(self, path):
+        """The reference's Save Image (mod.rs:473-482): the display pass's RGBA8 image of the last frame, written with alpha 255
+        (PIL picks the format from the file name; PNG as the reference does)."""
+        from PIL import Image
+        self.ray_pass.resolve_display()
+        img = self.ray_pass.read_display()
+        img[..., 3] = 255
+        Image.fromarray(img, "RGBA").save(path)

@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 #define BHRAY_VERSION_MAJOR 0
-#define BHRAY_VERSION_MINOR 4
+#define BHRAY_VERSION_MINOR 5
 
 /* ------------------------------------------------------------------------------------------
  * Error codes
@@ -459,6 +459,42 @@ int bhray_next_stream(bhray_ctx* ctx, void** hip_stream);
 int bhray_resolve_sky(bhray_ctx* ctx);
 int bhray_read_sky(bhray_ctx* ctx, uint16_t* dst_rgba16f, size_t row_pitch_bytes);
 int bhray_sky_device_ptr(bhray_ctx* ctx, void** dev_ptr, size_t* bytes);
+
+/* Display pass — the rest of the reference's GPU frame after the sky pass (mod.rs:209-324, run at 425-431): 5 bloom-down and
+ * 5 bloom-up passes (bloom_down.wgsl, bloom_up.wgsl), mix (mix.wgsl), ACES tone mapping (hdr.wgsl) and FXAA (fxaa.wgsl) into the
+ * Rgba8UnormSrgb target the reference's `Save Image` copies out (texture_to_output_buffer, mod.rs:491-526): frame_w x frame_h x 4
+ * bytes, row 0 = top, bytes R, G, B (sRGB-encoded) and A (unorm).  Opt-in: nothing runs unless bhray_resolve_display is called.
+ * Semantics (bloom sizes, filters, arithmetic, the exact sRGB encoding): DESIGN.md §10.
+ *
+ * bhray_resolve_display enqueues the pass behind the most recently enqueued frame (same slot, same stream), running the sky pass
+ * first if it has not run for this frame (with BHRAY_F_GATHER_SKY: the gathered image), into that slot's RGBA8 image.  The image
+ * follows the sky image's rules: after the next bhray_render the reads return BHRAY_E_STATE until bhray_resolve_display has run for
+ * the new frame (a copy enqueued with bhray_read_display_async before that render still delivers the earlier frame).  Multi-GPU
+ * ctx: the pass runs on the root over the whole frame; a non-root rank of a one-process-per-GPU ctx gets BHRAY_OK and nothing.  A
+ * row-partitioned ctx with BHRAY_GATHER_NONE does not hold the whole frame: BHRAY_E_STATE.  A frame narrower or lower than 32
+ * pixels has an empty bloom level: BHRAY_E_INVALID.  bhray_read_display_async shares its tickets with the other asynchronous reads. */
+typedef struct bhray_fxaa_details {     /* FXAADetailsUniform — fxaa_pipline.rs:76-83  ⇄  fxaa.wgsl `Details` */
+    float   edge_threshold_min;
+    float   edge_threshold_max;
+    int32_t iterations;                 /* at most BHRAY_FXAA_MAX_ITERATIONS (bhray_set_post_uniforms refuses more) */
+    float   subpixel_quality;
+} bhray_fxaa_details;                   /* 16 B */
+typedef struct bhray_mix_details {      /* MixDetails — mix_pipeline.rs:5-7  ⇄  mix.wgsl `Details` */
+    float   mix_ratio;
+} bhray_mix_details;                    /* 4 B */
+#define BHRAY_FXAA_MAX_ITERATIONS 1024   /* a longer edge search walks off any frame; the bound keeps a bad uniform from hanging the GPU */
+/* The values Renderer::render uploads every frame (EdgeThresholdMin/Max::Ultra, 12 iterations, 0.75; mix 0.7).  Either may be NULL. */
+int bhray_post_defaults(bhray_fxaa_details* fxaa, bhray_mix_details* mix);
+/* Sizes of the 10 bloom targets (5 down, then 5 up; the last is frame_w x frame_h).  Pure host arithmetic.  BHRAY_E_INVALID when a
+ * level would be empty (frame_w or frame_h < 32). */
+int bhray_bloom_sizes(uint32_t frame_w, uint32_t frame_h, uint32_t w[10], uint32_t h[10]);
+/* The uniform blocks by bytes (16 and 4), as the host's queue.write_buffer would upload them; applied from the next
+ * bhray_resolve_display.  A ctx starts with bhray_post_defaults. */
+int bhray_set_post_uniforms(bhray_ctx* ctx, const void* fxaa_details_16, const void* mix_details_4);
+int bhray_resolve_display(bhray_ctx* ctx);
+int bhray_read_display(bhray_ctx* ctx, uint8_t* dst_rgba8, size_t row_pitch_bytes);
+int bhray_read_display_async(bhray_ctx* ctx, uint8_t* dst_rgba8, size_t row_pitch_bytes, uint64_t* ticket);
+int bhray_display_device_ptr(bhray_ctx* ctx, void** dev_ptr, size_t* bytes);
 
 /* ------------------------------------------------------------------------------------------
  * Host-side scene helpers (C++ behind this ABI; mirror the Rust host code on the path)
