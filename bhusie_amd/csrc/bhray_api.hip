@@ -253,6 +253,8 @@ void derive_frame(const bhray_dev* c, FrameParams& P) {
     P.acos_cstar = acos_threshold(P.thr);
     P.acos_cstar_near = c->temporal_margin < 1.0f ? acos_threshold(P.thr * c->temporal_margin) : P.acos_cstar;
     int mc = d.model_count; if (mc < 0) mc = 0; if (mc > BHRAY_MAX_MODELS) mc = BHRAY_MAX_MODELS;
+    // Every slot below model_count is built; one never uploaded, one with 0 triangles and an invisible one get visible = 0 (the kernels
+    // skip it, as ray.wgsl:378 skips a default ModelUniform).  The kernels loop to the highest such slot that is visible, + 1.
     int usable = 0;
     for (int i = 0; i < mc; i++) {
         const ModelStore& m = c->models[i];
@@ -262,12 +264,9 @@ void derive_frame(const bhray_dev* c, FrameParams& P) {
         md.points = m.points; md.normals = m.normals; md.triangles = m.triangles; md.nodes = m.nodes; md.lookup = m.lookup; md.leaf = m.leaf;
         md.node_count = m.node_count;
         md.root_cull = m.root_cull; memcpy(md.root_lo, m.root_lo, 12); memcpy(md.root_hi, m.root_hi, 12);
-        usable = i + 1;
+        if (md.visible != 0) usable = i + 1;
     }
-    P.model_count = usable;
-    bool any_visible = false;
-    for (int i = 0; i < usable; i++) any_visible |= P.models[i].visible != 0;
-    if (!any_visible) P.model_count = 0;     // nothing to traverse: the no-mesh kernel variant is exact
+    P.model_count = usable;                  // 0 when no slot is visible: nothing to traverse, the no-mesh kernel variant is exact
     TexDev* t[3] = {&P.temp, &P.disk, &P.sky};
     for (int i = 0; i < 3; i++) { t[i]->rgba = c->tex[i]; t[i]->w = c->tex_w[i]; t[i]->h = c->tex_h[i]; }
 }

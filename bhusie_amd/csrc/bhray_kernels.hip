@@ -1361,29 +1361,34 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
         // traversal (it parks 37-47 dwords of ~70) and, at the register budget of six waves per SIMD, spill inside the traversal's loops.
         Hit mesh_r; F3 mesh_nrm = f3(0, 0, 0);
         mesh_r.hit = false; mesh_r.t = t_max; mesh_r.color = f3(0, 0, 0); mesh_r.opacity = 0.0f;
+        // Several models (ray.wgsl:377-389 with MAX_MODELS = 8): the march is parked ONCE per flat phase, the models are traversed in
+        // index order inside the region, each from t_max (the reference passes t_max to every model: no model's hit bounds another's
+        // traversal), and the winner is the strictly nearer hit - on a tie the lower index stays.  `want` holds one bit per model whose
+        // root box this lane's ray does not miss; the region is skipped when no lane has any.
         if (MESH_PARK) {
-            static_assert(BHRAY_MAX_MODELS == 1, "the parked traversal handles the reference's one model");
-            bool want = false;
+            static_assert(BHRAY_MAX_MODELS <= 32, "one bit per model in `want`");
+            uint32_t want = 0u;
             if (__builtin_expect(run_flat && __any(mode == M_FLAT), 0)) {
-                if (mode == M_FLAT && it < H.max_iter && P.model_count > 0 && P.models[0].visible != 0) {
-                    bool skip = false;
-                    if (P.models[0].root_cull != 0) {
-                        const F3 inv = f3(1.0f / cdir.x, 1.0f / cdir.y, 1.0f / cdir.z);
-                        if (fabsf(inv.x) < INFINITY && fabsf(inv.y) < INFINITY && fabsf(inv.z) < INFINITY) {
-                            const ModelDev& Md = P.models[0];
+                if (mode == M_FLAT && it < H.max_iter) {
+                    const F3 inv = f3(1.0f / cdir.x, 1.0f / cdir.y, 1.0f / cdir.z);
+                    const bool finite = fabsf(inv.x) < INFINITY && fabsf(inv.y) < INFINITY && fabsf(inv.z) < INFINITY;
+                    for (int mi = 0; mi < P.model_count; mi++) {
+                        const ModelDev& Md = P.models[mi];
+                        if (Md.visible == 0) continue;
+                        bool skip = false;
+                        if (Md.root_cull != 0 && finite) {
                             const float d0 = hit_aabb(cpos, inv, make_float4(Md.root_lo[0], Md.root_lo[1], Md.root_lo[2], 0.0f),
                                                       make_float4(Md.root_hi[0], Md.root_hi[1], Md.root_hi[2], 0.0f), ld3(Md.pos));
                             skip = d0 > t_max;
                             if (COUNT && skip) cnt[6]++;
                         }
+                        if (!skip) want |= 1u << mi;
                     }
-                    want = !skip;
                 }
-                if (__any(want)) {
+                if (__any(want != 0u)) {
                     float pk[40];
                     float* pkp = pk;
                     const F3 tpos = cpos, tdir = cdir;
-                    pk[0] = cpos.x; pk[1] = cpos.y; pk[2] = cpos.z; pk[3] = cdir.x; pk[4] = cdir.y; pk[5] = cdir.z;
                     pk[6] = ppos.x; pk[7] = ppos.y; pk[8] = ppos.z; pk[9] = pdir.x; pk[10] = pdir.y; pk[11] = pdir.z;
                     pk[12] = rkpos.x; pk[13] = rkpos.y; pk[14] = rkpos.z; pk[15] = rkdir.x; pk[16] = rkdir.y; pk[17] = rkdir.z;
                     pk[18] = rkh; pk[19] = amount; pk[20] = closest; pk[21] = dist_c; pk[22] = cpos_dist;
@@ -1393,9 +1398,22 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                       pk[29] = __uint_as_float(cold.pix()); pk[30] = cc_.x; pk[31] = cc_.y; pk[32] = cc_.z;
                       pk[33] = rd_.x; pk[34] = rd_.y; pk[35] = rd_.z; pk[36] = cold.pend_t(); }
                     asm volatile("" : "+v"(pkp) : : "memory");         // what was stored may be read and changed behind the compiler's back: nothing above stays in a register
-                    if (want) trace_ray_model<COUNT, BVH_WW>(P.models[0], bvh_lds, tpos, tdir, t_min, t_max, mesh_r, mesh_nrm, cnt, &err);
+                    // the nearest hit so far stays parked too: t in pk[37], colour and face normal in pk[0..5] (cpos / cdir come back from the
+                    // traversal's own tpos / tdir, live through every traversal anyway).  Kept in registers across the next model's traversal it
+                    // cost the region 19 more spilled VGPRs.  Only a hit is stored, and a hit has t < t_max: pk[37] < t_max <=> some model hit.
+                    pk[37] = t_max;
+                    for (int mi = 0; mi < P.model_count; mi++) {
+                        if (want & (1u << mi)) {
+                            Hit r; F3 nrm;
+                            trace_ray_model<COUNT, BVH_WW>(P.models[mi], bvh_lds, tpos, tdir, t_min, t_max, r, nrm, cnt, &err);
+                            if (r.hit && r.t < pkp[37]) {
+                                pkp[37] = r.t; pkp[0] = r.color.x; pkp[1] = r.color.y; pkp[2] = r.color.z;
+                                pkp[3] = nrm.x; pkp[4] = nrm.y; pkp[5] = nrm.z;
+                            }
+                        }
+                    }
                     asm volatile("" : "+v"(pkp) : : "memory");
-                    cpos = f3(pkp[0], pkp[1], pkp[2]); cdir = f3(pkp[3], pkp[4], pkp[5]);
+                    cpos = tpos; cdir = tdir;
                     ppos = f3(pkp[6], pkp[7], pkp[8]); pdir = f3(pkp[9], pkp[10], pkp[11]);
                     rkpos = f3(pkp[12], pkp[13], pkp[14]); rkdir = f3(pkp[15], pkp[16], pkp[17]);
                     rkh = pkp[18]; amount = pkp[19]; closest = pkp[20]; dist_c = pkp[21]; cpos_dist = pkp[22];
@@ -1403,6 +1421,10 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                     it = __float_as_int(pkp[26]); hit = __float_as_int(pkp[27]); mode = __float_as_int(pkp[28]);
                     cold.set_pix(__float_as_uint(pkp[29])); cold.set_color(f3(pkp[30], pkp[31], pkp[32]));
                     cold.set_rdir(f3(pkp[33], pkp[34], pkp[35])); cold.set_pend_t(pkp[36]);
+                    if (pkp[37] < t_max) {
+                        mesh_r.hit = true; mesh_r.t = pkp[37]; mesh_r.color = f3(pkp[0], pkp[1], pkp[2]); mesh_r.opacity = 1.0f;
+                        mesh_nrm = f3(pkp[3], pkp[4], pkp[5]);
+                    }
                 }
             }
         }

@@ -50,7 +50,7 @@ static_assert(BHRAY_MODEL_OFF_NODES == 29360176u, "nodes = triangles + 24 * 5242
 static_assert(BHRAY_MODEL_OFF_LOOKUP == 46137392u, "bvh_lookup = nodes + 32 * 524288");
 static_assert(BHRAY_MODEL_OFF_LOOKUP + 4u * BHRAY_MAX_MODEL_VERTICES + 28u == BHRAY_MODEL_UNIFORM_BYTES, "ModelUniform size");
 static_assert(BHRAY_MODEL_UNIFORM_BYTES == 48234572u, "ModelUniform size (triangle.rs:268-285)");
-static_assert(BHRAY_MAX_MODELS == 1 && BHRAY_MAX_MATERIALS == 8, "triangle.rs:6, material.rs:3");
+static_assert(BHRAY_MAX_MODELS == 8 && BHRAY_MAX_MATERIALS == 8, "ray.wgsl:2 MAX_MODELS raised from 1 (bhray.h), material.rs:3");
 
 // FXAADetailsUniform (fxaa_pipline.rs:76-83) and MixDetails (mix_pipeline.rs:5-7): the display pass's uniform blocks
 SZ(bhray_fxaa_details, 16);

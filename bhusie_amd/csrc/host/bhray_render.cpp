@@ -1,7 +1,8 @@
 // bhray_render — minimal C++ host program over renderer.hpp: renders one frame of the reference's default scene
 // (camera (0,0,-19), hole at the origin, disk 2..10, R = 20; camera.rs:10-16, blackhole.rs:16-28) and writes the HDR frame
 // as raw little-endian f32 RGBA (row 0 = top).  Usage:
-//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj] [--devices 0,1,2,...]
+//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--devices 0,1,2,...]
+// --obj: repeatable; the i-th mesh goes to model slot i (Renderer::add_model), at the position its OBJ loader gives it.
 // --devices: row-tile the frame over several GPUs from this one process (RCCL gather to the first one, inside libbhray).
 //   bhray_render --handoff sync|hdr|sky|sky1|sky-temporal|display FRAMES OUT.bin [--rk] [--base W H] [--levels N]
 //   bhray_render --dropin FRAMES [--rk] [--base W H] [--levels N]
@@ -134,17 +135,17 @@ int main(int argc, char** argv) {
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
         return 0;
     }
-    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj] [--devices 0,1,...]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--devices 0,1,...]\n", argv[0]); return 2; }
     uint32_t bw = 72, bh = 41, levels = 4, disk = 256;
     bool rk = false;
-    const char* obj = nullptr;
+    std::vector<const char*> objs;
     std::vector<int> devices;
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--rk")) rk = true;
         else if (!std::strcmp(argv[i], "--base") && i + 2 < argc) { bw = (uint32_t)std::atoi(argv[++i]); bh = (uint32_t)std::atoi(argv[++i]); }
         else if (!std::strcmp(argv[i], "--levels") && i + 1 < argc) levels = (uint32_t)std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--disk-size") && i + 1 < argc) disk = (uint32_t)std::atoi(argv[++i]);
-        else if (!std::strcmp(argv[i], "--obj") && i + 1 < argc) obj = argv[++i];
+        else if (!std::strcmp(argv[i], "--obj") && i + 1 < argc) objs.push_back(argv[++i]);
         else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) { for (const char* p = argv[++i]; *p; ) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p) p++; } }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
@@ -157,8 +158,8 @@ int main(int argc, char** argv) {
         const uint8_t grey[4] = {160, 160, 160, 255};
         r.ray_pipeline().set_texture(BHRAY_TEX_TEMP_LUT, grey, 1, 1);
         r.ray_pipeline().set_texture(BHRAY_TEX_SKY, grey, 1, 1);
-        std::unique_ptr<bhusie::Model> model;
-        if (obj) { model.reset(new bhusie::Model(obj)); r.set_model(*model); }
+        std::vector<bhusie::Model> models;
+        for (const char* obj : objs) { models.emplace_back(obj); r.add_model(models.back()); }
         r.ray_details.integration_method = rk ? 1 : 0;
         r.render(0.0f);
         const std::vector<float> out = r.ray_pipeline().output();

@@ -155,7 +155,8 @@ public:
     void drain() { for (uint32_t k = 0; k < ring_; k++) if (pending_.size() > k && pending_[k]) { check(bhray_wait_read(ctx_, tickets_[k]), ctx_); pending_[k] = false; } }
     std::pair<uint32_t, uint32_t> resolution() const { return {cfg_.frame_w, cfg_.frame_h}; }
     void set_texture(int slot, const uint8_t* rgba8, uint32_t w, uint32_t h) { check(bhray_set_texture(ctx_, slot, rgba8, w, h), ctx_); }
-    void upload_model(const Model& m) { bhray_model_desc d = m.desc(); check(bhray_upload_model(ctx_, 0, &d), ctx_); }
+    void upload_model(const Model& m, uint32_t index = 0) { bhray_model_desc d = m.desc(); check(bhray_upload_model(ctx_, index, &d), ctx_); }
+    void set_model_transform(uint32_t index, const float position[3], int32_t visible) { check(bhray_set_model_transform(ctx_, index, position, visible), ctx_); }
     void set_materials(const void* material_uniforms_128) { check(bhray_set_materials(ctx_, material_uniforms_128, 128), ctx_); }   // mod.rs:389 (ignored by the shader)
     void set_uniforms(const bhray_camera_uniform& c, const bhray_black_hole_uniform& b, const bhray_details& d) { check(bhray_set_uniforms(ctx_, &c, &b, &d), ctx_); }
     void pass() { check(bhray_render(ctx_), ctx_); }                                            // ray_pipeline.rs:301-309
@@ -196,7 +197,15 @@ public:
         ray_pipeline_.enable_handoff(h, frames_in_flight);
     }
     RayPipeline& ray_pipeline() { return ray_pipeline_; }
-    void set_model(const Model& m) { ray_pipeline_.upload_model(m); ray_details.model_count = 1; }   // mod.rs:384
+    // scene.models: slot i holds the i-th model; model_count = how many (mod.rs:384).  set_model replaces slot 0, add_model takes the next
+    // slot and returns its index (BHRAY_MAX_MODELS slots).
+    void set_model(const Model& m) { ray_pipeline_.upload_model(m, 0); if (models_ == 0) models_ = 1; ray_details.model_count = (int32_t)models_; }
+    uint32_t add_model(const Model& m) {
+        if (models_ >= BHRAY_MAX_MODELS) throw std::runtime_error("add_model: the ctx holds BHRAY_MAX_MODELS models");
+        ray_pipeline_.upload_model(m, models_);
+        ray_details.model_count = (int32_t)++models_;
+        return models_ - 1;
+    }
     void render(float dt) {                                                                     // mod.rs:378-420
         ray_details.time += dt;                                                                 // mod.rs:382
         ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);        // mod.rs:386-388
@@ -215,6 +224,7 @@ public:
     }
 private:
     RayPipeline ray_pipeline_;
+    uint32_t models_ = 0;
 };
 
 }  // namespace bhusie

@@ -9,6 +9,7 @@ COMM_ID_BYTES = 128
 GATHER_NONE, GATHER_RCCL = 0, 1
 PARTITION_STRIPES, PARTITION_SLABS = 0, 1
 MAX_MODEL_VERTICES = 524288
+MAX_MODELS = 8                       # BHRAY_MAX_MODELS: model slots per ctx (ray.wgsl:2 raised from 1)
 MODEL_UNIFORM_BYTES = 48234572
 F_COUNTERS = 1
 F_TIMING = 2

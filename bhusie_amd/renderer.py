@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import lib
-from .layouts import (BhrayFxaaDetails, BhrayMixDetails, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters,
+from .layouts import (BhrayFxaaDetails, BhrayMixDetails, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters,
                       BhrayGatherInfo, BhrayRebalanceInfo, BhrayTiming, check)
 from .model import Model
 from .scene import BlackHole, Camera, RayDetails
@@ -425,12 +425,30 @@ class Renderer:
         self.black_hole = BlackHole()
         self.ray_details = RayDetails()                      # mod.rs:116-121
         self.ray_pass = RayPass(cfg if cfg is not None else ladder_from_base((72, 41), 3, 4), device=device, **kw)
-        self.model: Model | None = None
+        self.models: list[Model] = []                        # scene.models: slot i of the ctx holds models[i]
+
+    @property
+    def model(self) -> Model | None:
+        return self.models[0] if self.models else None
 
     def set_model(self, model: Model):
-        self.model = model
+        """Model slot 0 (replaced if it is there)."""
         self.ray_pass.upload_model(model, 0)
-        self.ray_details.model_count = 1                     # mod.rs:384 (scene.models.size())
+        if self.models:
+            self.models[0] = model
+        else:
+            self.models.append(model)
+        self.ray_details.model_count = len(self.models)      # mod.rs:384 (scene.models.size())
+
+    def add_model(self, model: Model) -> int:
+        """One more model in the next slot (up to MAX_MODELS); returns its index, the model_index of RayPass.set_model_transform."""
+        index = len(self.models)
+        if index >= MAX_MODELS:
+            raise ValueError(f"add_model: the ctx holds {MAX_MODELS} models")
+        self.ray_pass.upload_model(model, index)
+        self.models.append(model)
+        self.ray_details.model_count = len(self.models)      # mod.rs:384 (scene.models.size())
+        return index
 
     def render(self, dt: float = 0.0):
         self.ray_details.time += dt                          # mod.rs:382

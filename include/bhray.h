@@ -105,7 +105,10 @@ typedef struct bhray_triangle {
 /* ModelUniform — src/renderer/triangle.rs:268-285; the storage buffer bound at ray.wgsl:9.
  * Fixed capacity arrays; every size and offset below is static_assert-ed in bhusie_amd/csrc/bhray_layout.cpp. */
 #define BHRAY_MAX_MODEL_VERTICES 524288  /* triangle.rs:7, ray.wgsl:1 */
-#define BHRAY_MAX_MODELS         1       /* triangle.rs:6, ray.wgsl:2 */
+/* Model slots per ctx.  The reference fixes MAX_MODELS = 1 (triangle.rs:6, ray.wgsl:2) only because each of its ModelUniforms is a
+ * 48 MB fixed-capacity image uploaded whole every frame; its shader already loops over details.model_count (ray.wgsl:377-389).  Here a
+ * model is a compact upload, so the shader's loop runs with the constant raised to 8: slots 0-7, model_count clamped to 8. */
+#define BHRAY_MAX_MODELS         8
 #define BHRAY_MAX_MATERIALS      8       /* material.rs:3, ray.wgsl:3 */
 #define BHRAY_MODEL_UNIFORM_BYTES 48234572u
 #define BHRAY_MODEL_OFF_POINTS    48u
@@ -358,7 +361,10 @@ enum { BHRAY_TEX_TEMP_LUT = 0,   /* binding 7  color.png */
 int bhray_set_texture(bhray_ctx* ctx, int slot, const uint8_t* rgba8, uint32_t w, uint32_t h);
 
 /* Model upload — replaces `scene.models.create_buffer/update_buffer` (mod.rs:114,391,
- * array_buffer.rs:71-89).  Either the exact 48 234 572-byte ModelUniform or the compact form. */
+ * array_buffer.rs:71-89).  Either the exact 48 234 572-byte ModelUniform or the compact form.
+ * model_index 0 .. BHRAY_MAX_MODELS-1 (else BHRAY_E_INVALID); uploading to a slot again replaces it.  Slots
+ * 0 .. model_count-1 are traced in index order, the strictly nearest hit wins (a tie keeps the lower index); an
+ * invisible slot, one never uploaded and one with 0 triangles are skipped. */
 int bhray_upload_model_uniform(bhray_ctx* ctx, uint32_t model_index, const void* bytes, size_t size);
 int bhray_upload_model(bhray_ctx* ctx, uint32_t model_index, const bhray_model_desc* desc);
 /* Per-frame model state without re-uploading 48 MB (the reference re-uploads, mod.rs:391).  */
