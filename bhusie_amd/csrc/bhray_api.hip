@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "bhray_bvh_core.h"
 #include "bhray_dev.h"
 #include "bhray_internal.h"
 #include "bhray_math.h"
@@ -104,6 +105,11 @@ struct ModelStore {
     int point_count = 0, normal_count = 0, triangle_count = 0, node_count = 0;
     int root_cull = 0; float root_lo[3] = {0, 0, 0}, root_hi[3] = {0, 0, 0};   // union of the root's child boxes (ModelDev)
     bool loaded = false;
+    // a slot built on the device (dev_upload_model_build): the builder's scratch, kept for dev_update_model_vertices; nodes has room for 2 T - 1
+    BvhBuild* build = nullptr;
+    BvhResult* d_result = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};     // before the copies, between copies and build, behind the build
+    bhray_model_build_info info{};
 };
 
 }  // namespace
@@ -288,6 +294,9 @@ void free_model(ModelStore& m) {
     if (m.nodes) (void)hipFree(m.nodes);
     if (m.lookup) (void)hipFree(m.lookup);
     if (m.leaf) (void)hipFree(m.leaf);
+    if (m.d_result) (void)hipFree(m.d_result);
+    bvh_build_destroy(m.build);
+    for (hipEvent_t e : m.ev) if (e) (void)hipEventDestroy(e);
     m = ModelStore();
 }
 
@@ -794,6 +803,117 @@ int dev_upload_model(bhray_dev* c, uint32_t mi, const bhray_model_desc* d) {
         }
     }
     m.loaded = true;
+    return BHRAY_OK;
+}
+
+namespace {
+// The build of slot `m` from the points, normals and triangles it holds, on the engine's first stream, timed; then the 64 bytes of result.
+// `copies` enqueues the host-to-device copies of this call between the first two events.
+template <class Copies>
+int build_on_device(bhray_dev* c, ModelStore& m, Copies copies) {
+    hipStream_t s = c->slots[0].stream;
+    HIPCHK(c, hipEventRecord(m.ev[0], s));
+    { int rc = copies(s); if (rc) return rc; }
+    HIPCHK(c, hipEventRecord(m.ev[1], s));
+    HIPCHK(c, launch_bvh_build(m.build, m.points, m.normals, m.triangles, m.nodes, m.lookup, m.leaf, m.d_result, s));
+    HIPCHK(c, hipEventRecord(m.ev[2], s));
+    BvhResult r;
+    HIPCHK(c, hipMemcpyAsync(&r, m.d_result, sizeof r, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (r.max_depth == 0 || r.max_depth > BHRAY_LBVH_MAX_PASSES || r.nodes < 1 || r.nodes > 2u * (uint32_t)m.triangle_count - 1u)
+        return fail(c, BHRAY_E_BVH_DEPTH, "device BVH build: the box passes did not reach the root (%u nodes, depth %u)", r.nodes, r.max_depth);
+    m.node_count = (int)r.nodes;
+    m.root_cull = r.root_cull; memcpy(m.root_lo, r.root_lo, 12); memcpy(m.root_hi, r.root_hi, 12);
+    m.info.built_on_device = 1; m.info.triangles = (uint32_t)m.triangle_count; m.info.nodes = r.nodes; m.info.leaves = r.leaves;
+    m.info.max_leaf = r.max_leaf; m.info.max_depth = r.max_depth;
+    HIPCHK(c, hipEventElapsedTime(&m.info.upload_ms, m.ev[0], m.ev[1]));
+    HIPCHK(c, hipEventElapsedTime(&m.info.build_ms, m.ev[1], m.ev[2]));
+    return BHRAY_OK;
+}
+}  // namespace
+
+int dev_upload_model_build(bhray_dev* c, uint32_t mi, const bhray_model_desc* d) {
+    if (!c) return BHRAY_E_INVALID;
+    if (mi >= BHRAY_MAX_MODELS || !d) return fail(c, BHRAY_E_INVALID, "bad model arguments");
+    if (d->point_count < 0 || d->normal_count < 0 || d->triangle_count < 0 || d->point_count > BHRAY_MAX_MODEL_VERTICES ||
+        d->normal_count > BHRAY_MAX_MODEL_VERTICES || d->triangle_count > BHRAY_MAX_MODEL_VERTICES)
+        return fail(c, BHRAY_E_CAPACITY, "model exceeds MAX_MODEL_VERTICES (triangle.rs:7)");
+    if (d->triangle_count > 0 && (!d->points || !d->normals || !d->triangles)) return fail(c, BHRAY_E_INVALID, "model arrays missing");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = launch_batch(c); if (rc) return rc; }          // staged frames hold the old model's addresses
+    HIPCHK(c, sync_all(c));
+    ModelStore n;                                             // built beside the slot: a refused model leaves the slot as it was
+    memcpy(n.pos, d->position, 12);
+    n.visible = d->visible;
+    n.point_count = d->point_count; n.normal_count = d->normal_count; n.triangle_count = d->triangle_count;
+    n.info.triangles = (uint32_t)d->triangle_count;
+    if (d->triangle_count > 0) {
+        const size_t T = (size_t)d->triangle_count;
+        hipStream_t s = c->slots[0].stream;
+        int rc = BHRAY_OK, bad = 0;
+        auto hip = [&](hipError_t e, const char* what) { if (rc == BHRAY_OK && e != hipSuccess) rc = fail(c, BHRAY_E_HIP, "%s: %s", what, hipGetErrorString(e)); return rc == BHRAY_OK; };
+        // index 0 of an empty points / normals array cannot be valid; one element keeps the allocations non-empty
+        hip(hipMalloc(&n.points, (size_t)std::max(d->point_count, 1) * 16), "hipMalloc(points)") && hip(hipMalloc(&n.normals, (size_t)std::max(d->normal_count, 1) * 16), "hipMalloc(normals)") &&
+            hip(hipMalloc(&n.triangles, T * 24), "hipMalloc(triangles)") && hip(hipMalloc(&n.nodes, (2 * T - 1) * 32), "hipMalloc(nodes)") &&
+            hip(hipMalloc(&n.lookup, T * 4), "hipMalloc(lookup)") && hip(hipMalloc(&n.leaf, T * 96), "hipMalloc(leaf)") &&
+            hip(hipMalloc(&n.d_result, sizeof(BvhResult)), "hipMalloc(result)") && hip(bvh_build_create(d->triangle_count, &n.build), "device BVH scratch");
+        for (hipEvent_t& e : n.ev) if (rc == BHRAY_OK) hip(hipEventCreate(&e), "hipEventCreate");
+        if (rc == BHRAY_OK) hip(hipMemcpyAsync(n.triangles, d->triangles, T * 24, hipMemcpyHostToDevice, s), "triangle upload");
+        if (rc == BHRAY_OK) hip(launch_bvh_validate(n.build, n.triangles, d->point_count, d->normal_count, &bad, s), "index validation");
+        if (rc == BHRAY_OK && bad != 0) rc = fail(c, BHRAY_E_INVALID, "a triangle has an index out of range");
+        if (rc == BHRAY_OK)
+            rc = build_on_device(c, n, [&](hipStream_t st) {
+                HIPCHK(c, hipMemcpyAsync(n.points, d->points, (size_t)d->point_count * 16, hipMemcpyHostToDevice, st));
+                HIPCHK(c, hipMemcpyAsync(n.normals, d->normals, (size_t)d->normal_count * 16, hipMemcpyHostToDevice, st));
+                return (int)BHRAY_OK;
+            });
+        if (rc != BHRAY_OK) { std::string keep = c->err; (void)hipStreamSynchronize(s); free_model(n); c->err = keep; return rc; }
+    }
+    n.loaded = true;
+    free_model(c->models[mi]);
+    c->models[mi] = n;
+    return BHRAY_OK;
+}
+
+int dev_update_model_vertices(bhray_dev* c, uint32_t mi, const float* points, int32_t point_count, const float* normals, int32_t normal_count) {
+    if (!c) return BHRAY_E_INVALID;
+    if (mi >= BHRAY_MAX_MODELS) return fail(c, BHRAY_E_INVALID, "bad model arguments");
+    ModelStore& m = c->models[mi];
+    if (!m.loaded || !m.build) return fail(c, BHRAY_E_STATE, "bhray_update_model_vertices: slot %u was not built by bhray_upload_model_build", mi);
+    if ((points && point_count != m.point_count) || (normals && normal_count != m.normal_count))
+        return fail(c, BHRAY_E_INVALID, "bhray_update_model_vertices: the slot holds %d points and %d normals", m.point_count, m.normal_count);
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = launch_batch(c); if (rc) return rc; }          // staged frames show the old geometry
+    HIPCHK(c, sync_all(c));                                   // and the frames in flight read the buffers that are rewritten here
+    return build_on_device(c, m, [&](hipStream_t st) {
+        if (points) HIPCHK(c, hipMemcpyAsync(m.points, points, (size_t)m.point_count * 16, hipMemcpyHostToDevice, st));
+        if (normals) HIPCHK(c, hipMemcpyAsync(m.normals, normals, (size_t)m.normal_count * 16, hipMemcpyHostToDevice, st));
+        return (int)BHRAY_OK;
+    });
+}
+
+int dev_get_model_build_info(bhray_dev* c, uint32_t mi, bhray_model_build_info* out) {
+    if (!c) return BHRAY_E_INVALID;
+    if (mi >= BHRAY_MAX_MODELS || !out) return fail(c, BHRAY_E_INVALID, "bad model arguments");
+    const ModelStore& m = c->models[mi];
+    if (!m.loaded) return fail(c, BHRAY_E_STATE, "model slot %u is empty", mi);
+    *out = m.info;
+    out->triangles = (uint32_t)m.triangle_count; out->nodes = (uint32_t)m.node_count;
+    return BHRAY_OK;
+}
+
+int dev_read_model_bvh(bhray_dev* c, uint32_t mi, bhray_node* nodes, uint32_t node_cap, int32_t* lookup, uint32_t lookup_cap, uint32_t* node_count, uint32_t* triangle_count) {
+    if (!c) return BHRAY_E_INVALID;
+    if (mi >= BHRAY_MAX_MODELS) return fail(c, BHRAY_E_INVALID, "bad model arguments");
+    const ModelStore& m = c->models[mi];
+    if (!m.loaded) return fail(c, BHRAY_E_STATE, "model slot %u is empty", mi);
+    const uint32_t nn = m.triangle_count > 0 ? (uint32_t)m.node_count : 0u, nt = (uint32_t)m.triangle_count;
+    if (node_count) *node_count = nn;
+    if (triangle_count) *triangle_count = nt;
+    if (nn > node_cap || nt > lookup_cap || (nn > 0 && !nodes) || (nt > 0 && !lookup)) return fail(c, BHRAY_E_INVALID, "bhray_read_model_bvh: the slot holds %u nodes and %u triangles", nn, nt);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (nn > 0) HIPCHK(c, hipMemcpy(nodes, m.nodes, (size_t)nn * 32, hipMemcpyDeviceToHost));
+    if (nt > 0) HIPCHK(c, hipMemcpy(lookup, m.lookup, (size_t)nt * 4, hipMemcpyDeviceToHost));
     return BHRAY_OK;
 }
 

@@ -56,6 +56,10 @@ void dev_destroy(bhray_dev* c);
 int  dev_set_texture(bhray_dev* c, int slot, const uint8_t* rgba8, uint32_t w, uint32_t h);
 int  dev_upload_model_uniform(bhray_dev* c, uint32_t model_index, const void* bytes, size_t size);
 int  dev_upload_model(bhray_dev* c, uint32_t model_index, const bhray_model_desc* desc);
+int  dev_upload_model_build(bhray_dev* c, uint32_t model_index, const bhray_model_desc* desc);    // tree built on the device (bhray_bvh.hip)
+int  dev_update_model_vertices(bhray_dev* c, uint32_t model_index, const float* points, int32_t point_count, const float* normals, int32_t normal_count);
+int  dev_get_model_build_info(bhray_dev* c, uint32_t model_index, bhray_model_build_info* out);
+int  dev_read_model_bvh(bhray_dev* c, uint32_t model_index, bhray_node* nodes, uint32_t node_cap, int32_t* lookup, uint32_t lookup_cap, uint32_t* node_count, uint32_t* triangle_count);
 int  dev_set_model_transform(bhray_dev* c, uint32_t model_index, const float position[3], int32_t visible);
 int  dev_set_uniforms(bhray_dev* c, const void* cam32, const void* bh132, const void* det32);
 // another row partition (bhray_config.partition / stripe_rows / slab_row0 / row_rank / row_world) for the same frame; synchronises the engine

@@ -1456,6 +1456,35 @@ int bhray_upload_model(bhray_ctx* c, uint32_t mi, const bhray_model_desc* d) {
     if (mi < BHRAY_MAX_MODELS && d) { c->m_usable[mi] = d->triangle_count > 0; c->m_vis[mi] = d->visible; memcpy(c->m_pos[mi], d->position, 12); c->m_dirty[mi] = false; }
     return BHRAY_OK;
 }
+// every local partition's device builds its own copy of the tree; the build is deterministic, so the copies are equal
+int bhray_upload_model_build(bhray_ctx* c, uint32_t mi, const bhray_model_desc* d) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    if (c->gather) { int rc = group_sync(c); if (rc) return rc; }
+    for (Part& p : c->parts) if (p.dev) DEV(c, p.dev, dev_upload_model_build(p.dev, mi, d));
+    if (mi < BHRAY_MAX_MODELS && d) { c->m_usable[mi] = d->triangle_count > 0; c->m_vis[mi] = d->visible; memcpy(c->m_pos[mi], d->position, 12); c->m_dirty[mi] = false; }
+    return BHRAY_OK;
+}
+int bhray_update_model_vertices(bhray_ctx* c, uint32_t mi, const float* points, int32_t point_count, const float* normals, int32_t normal_count) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    if (c->gather) { int rc = group_sync(c); if (rc) return rc; }
+    for (Part& p : c->parts) if (p.dev) DEV(c, p.dev, dev_update_model_vertices(p.dev, mi, points, point_count, normals, normal_count));
+    return BHRAY_OK;
+}
+int bhray_get_model_build_info(bhray_ctx* c, uint32_t mi, bhray_model_build_info* out) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    for (Part& p : c->parts) if (p.dev) { DEV(c, p.dev, dev_get_model_build_info(p.dev, mi, out)); return BHRAY_OK; }
+    return gfail(c, BHRAY_E_STATE, "no local partition");
+}
+int bhray_read_model_bvh(bhray_ctx* c, uint32_t mi, bhray_node* nodes, uint32_t node_cap, int32_t* lookup, uint32_t lookup_cap, uint32_t* node_count, uint32_t* triangle_count) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    if (c->gather) { int rc = group_sync(c); if (rc) return rc; }
+    for (Part& p : c->parts) if (p.dev) { DEV(c, p.dev, dev_read_model_bvh(p.dev, mi, nodes, node_cap, lookup, lookup_cap, node_count, triangle_count)); return BHRAY_OK; }
+    return gfail(c, BHRAY_E_STATE, "no local partition");
+}
 int bhray_set_model_transform(bhray_ctx* c, uint32_t mi, const float position[3], int32_t visible) {
     if (!c) return BHRAY_E_INVALID;
     if (c->threaded) {               // travels with the next frame (the engines belong to their issue threads)

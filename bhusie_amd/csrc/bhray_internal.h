@@ -163,4 +163,21 @@ size_t display_scratch_bytes(uint32_t frame_w, uint32_t frame_h);               
 hipError_t launch_display(const uint2* sky, uint2* scratch, uint32_t* dst_rgba8, uint32_t frame_w, uint32_t frame_h,
                           const bhray_fxaa_details& fxaa, const bhray_mix_details& mix, hipStream_t s);
 
+// mesh BVH built on the device (bhray_bvh.hip)
+struct BvhBuild;                         // scratch of one model slot's builder: allocated once per upload, reused by every vertex update
+struct BvhResult {                       // what a build reports: 64 bytes read back behind it
+    uint32_t nodes, leaves, max_leaf, max_depth;   // max_depth: nodes on the longest path root -> leaf; 0 = the fit passes did not reach the root
+    int32_t root_cull;                   // as ModelDev
+    float root_lo[3], root_hi[3];
+    uint32_t pad[5];
+};
+static_assert(sizeof(BvhResult) == 64, "BvhResult");
+hipError_t bvh_build_create(int triangle_count, BvhBuild** out);          // triangle_count >= 1
+void bvh_build_destroy(BvhBuild* b);
+// every p* < point_count and n* < normal_count (and >= 0)?  *host_error != 0: no.  Synchronises s.
+hipError_t launch_bvh_validate(BvhBuild* b, const int32_t* triangles, int point_count, int normal_count, int* host_error, hipStream_t s);
+// nodes: room for 2 T - 1 nodes; lookup: T; leaf: 6 T float4.  Enqueues only.
+hipError_t launch_bvh_build(BvhBuild* b, const float4* points, const float4* normals, const int32_t* triangles, float4* nodes, int32_t* lookup, float4* leaf,
+                            BvhResult* d_result, hipStream_t s);
+
 }  // namespace bhray

@@ -156,6 +156,11 @@ public:
     std::pair<uint32_t, uint32_t> resolution() const { return {cfg_.frame_w, cfg_.frame_h}; }
     void set_texture(int slot, const uint8_t* rgba8, uint32_t w, uint32_t h) { check(bhray_set_texture(ctx_, slot, rgba8, w, h), ctx_); }
     void upload_model(const Model& m, uint32_t index = 0) { bhray_model_desc d = m.desc(); check(bhray_upload_model(ctx_, index, &d), ctx_); }
+    // the tree built on the GPU from the model's points, normals and triangles; update_model_vertices then moves them without a host build
+    void upload_model_build(const Model& m, uint32_t index = 0) { bhray_model_desc d = m.desc(); check(bhray_upload_model_build(ctx_, index, &d), ctx_); }
+    void update_model_vertices(uint32_t index, const float* points, int32_t point_count, const float* normals, int32_t normal_count) {
+        check(bhray_update_model_vertices(ctx_, index, points, point_count, normals, normal_count), ctx_);
+    }
     void set_model_transform(uint32_t index, const float position[3], int32_t visible) { check(bhray_set_model_transform(ctx_, index, position, visible), ctx_); }
     void set_materials(const void* material_uniforms_128) { check(bhray_set_materials(ctx_, material_uniforms_128, 128), ctx_); }   // mod.rs:389 (ignored by the shader)
     void set_uniforms(const bhray_camera_uniform& c, const bhray_black_hole_uniform& b, const bhray_details& d) { check(bhray_set_uniforms(ctx_, &c, &b, &d), ctx_); }
@@ -200,9 +205,10 @@ public:
     // scene.models: slot i holds the i-th model; model_count = how many (mod.rs:384).  set_model replaces slot 0, add_model takes the next
     // slot and returns its index (BHRAY_MAX_MODELS slots).
     void set_model(const Model& m) { ray_pipeline_.upload_model(m, 0); if (models_ == 0) models_ = 1; ray_details.model_count = (int32_t)models_; }
-    uint32_t add_model(const Model& m) {
+    uint32_t add_model(const Model& m, bool build_on_device = false) {
         if (models_ >= BHRAY_MAX_MODELS) throw std::runtime_error("add_model: the ctx holds BHRAY_MAX_MODELS models");
-        ray_pipeline_.upload_model(m, models_);
+        if (build_on_device) ray_pipeline_.upload_model_build(m, models_);
+        else ray_pipeline_.upload_model(m, models_);
         ray_details.model_count = (int32_t)++models_;
         return models_ - 1;
     }

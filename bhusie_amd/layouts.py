@@ -125,6 +125,15 @@ class BhrayGatherInfo(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class BhrayModelBuildInfo(C.Structure):
+    """bhray_model_build_info (include/bhray_diag.h)"""
+    _fields_ = [(n, C.c_uint32) for n in ("built_on_device", "triangles", "nodes", "leaves", "max_leaf", "max_depth")] + \
+               [("upload_ms", C.c_float), ("build_ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: (float if t is C.c_float else int)(getattr(self, n)) for n, t in self._fields_}
+
+
 assert C.sizeof(BhrayDetails) == 32 and C.sizeof(BhrayCameraUniform) == 32 and C.sizeof(BhrayBlackHoleUniform) == 132
 assert C.sizeof(BhrayNode) == 32 and C.sizeof(BhrayTriangle) == 24
 
@@ -168,6 +177,8 @@ SYMBOLS = {
     "bhray_set_texture": (C.c_int, [vp, C.c_int, vp, u32, u32]),
     "bhray_upload_model_uniform": (C.c_int, [vp, u32, vp, sz]),
     "bhray_upload_model": (C.c_int, [vp, u32, P(BhrayModelDesc)]),
+    "bhray_upload_model_build": (C.c_int, [vp, u32, P(BhrayModelDesc)]),
+    "bhray_update_model_vertices": (C.c_int, [vp, u32, vp, i32, vp, i32]),
     "bhray_set_model_transform": (C.c_int, [vp, u32, P(C.c_float), i32]),
     "bhray_set_uniforms": (C.c_int, [vp, vp, vp, vp]),
     "bhray_render": (C.c_int, [vp]),
@@ -226,6 +237,8 @@ DIAG_SYMBOLS = {
     "bhray_selftest": (C.c_int, [vp, P(C.c_uint64)]),
     "bhray_read_level": (C.c_int, [vp, u32, vp, sz]),
     "bhray_get_gather_info": (C.c_int, [vp, P(BhrayGatherInfo)]),
+    "bhray_get_model_build_info": (C.c_int, [vp, u32, P(BhrayModelBuildInfo)]),
+    "bhray_read_model_bvh": (C.c_int, [vp, u32, vp, u32, vp, u32, P(u32), P(u32)]),
 }
 
 

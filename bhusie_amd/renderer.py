@@ -14,8 +14,8 @@ import numpy as np
 
 from ._lib import lib
 from .layouts import (BhrayFxaaDetails, BhrayMixDetails, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters,
-                      BhrayGatherInfo, BhrayRebalanceInfo, BhrayTiming, check)
-from .model import Model
+                      BhrayGatherInfo, BhrayModelBuildInfo, BhrayModelDesc, BhrayRebalanceInfo, BhrayTiming, check)
+from .model import NODE_DTYPE, Model
 from .scene import BlackHole, Camera, RayDetails
 
 
@@ -170,6 +170,46 @@ class RayPass:
     def upload_model(self, model: Model, index=0):
         d = model.desc()
         check(self._L.bhray_upload_model(self._h, index, C.byref(d)), self._h, self._L)
+
+    def upload_model_build(self, model, index=0):
+        """Points, normals and triangles of `model` (a Model, or a dict shaped like Model.arrays(): its nodes / bvh_lookup are not read);
+        the tree is built on the GPU (bhray_upload_model_build)."""
+        if isinstance(model, Model):
+            d = model.desc()
+        else:
+            keep = [np.ascontiguousarray(model["points"], dtype=np.float32), np.ascontiguousarray(model["normals"], dtype=np.float32),
+                    np.ascontiguousarray(model["triangles"], dtype=np.int32)]
+            assert keep[0].ndim == 2 and keep[0].shape[1] == 4 and keep[1].ndim == 2 and keep[1].shape[1] == 4 and keep[2].ndim == 2 and keep[2].shape[1] == 6
+            d = BhrayModelDesc()
+            d.position = (C.c_float * 3)(*[float(x) for x in model.get("position", (0.0, 0.0, 0.0))])
+            d.visible = int(model.get("visible", 1))
+            d.points, d.normals, d.triangles = keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data
+            d.point_count, d.normal_count, d.triangle_count = len(keep[0]), len(keep[1]), len(keep[2])
+        check(self._L.bhray_upload_model_build(self._h, index, C.byref(d)), self._h, self._L)
+
+    def update_model_vertices(self, points=None, normals=None, index=0):
+        """New points and / or normals ((n, 4) float32, the counts the slot holds) for a slot built by upload_model_build; the tree is rebuilt
+        on the GPU in the slot's own buffers (bhray_update_model_vertices)."""
+        p = np.ascontiguousarray(points, dtype=np.float32) if points is not None else None
+        n = np.ascontiguousarray(normals, dtype=np.float32) if normals is not None else None
+        for a in (p, n):
+            assert a is None or (a.ndim == 2 and a.shape[1] == 4)
+        check(self._L.bhray_update_model_vertices(self._h, index, p.ctypes.data if p is not None else None, len(p) if p is not None else 0,
+                                                  n.ctypes.data if n is not None else None, len(n) if n is not None else 0), self._h, self._L)
+
+    def read_model_bvh(self, index=0) -> dict:
+        """dict(nodes, bvh_lookup) - the shape of Model.arrays() - of the tree slot `index` holds on the device, in the device's numbering."""
+        nn, nt = C.c_uint32(), C.c_uint32()
+        self._L.bhray_read_model_bvh(self._h, index, None, 0, None, 0, C.byref(nn), C.byref(nt))      # sizes first (BHRAY_E_INVALID unless both are 0)
+        nodes, lookup = np.zeros(nn.value, dtype=NODE_DTYPE), np.zeros(nt.value, dtype=np.int32)
+        check(self._L.bhray_read_model_bvh(self._h, index, nodes.ctypes.data, nn.value, lookup.ctypes.data, nt.value, C.byref(nn), C.byref(nt)), self._h, self._L)
+        return dict(nodes=nodes, bvh_lookup=lookup)
+
+    def model_build_info(self, index=0) -> dict:
+        """built_on_device, triangles, nodes, leaves, max_leaf, max_depth, upload_ms, build_ms of slot `index` (bhray_get_model_build_info)"""
+        info = BhrayModelBuildInfo()
+        check(self._L.bhray_get_model_build_info(self._h, index, C.byref(info)), self._h, self._L)
+        return info.as_dict()
 
     def upload_model_uniform(self, blob: bytes, index=0):
         check(self._L.bhray_upload_model_uniform(self._h, index, blob, len(blob)), self._h, self._L)
@@ -440,12 +480,18 @@ class Renderer:
             self.models.append(model)
         self.ray_details.model_count = len(self.models)      # mod.rs:384 (scene.models.size())
 
-    def add_model(self, model: Model) -> int:
-        """One more model in the next slot (up to MAX_MODELS); returns its index, the model_index of RayPass.set_model_transform."""
+    def add_model(self, model: Model, build: str = "host") -> int:
+        """One more model in the next slot (up to MAX_MODELS); returns its index, the model_index of RayPass.set_model_transform.
+        build="device": the tree is built on the GPU (RayPass.upload_model_build) and the model's own tree is not read."""
         index = len(self.models)
         if index >= MAX_MODELS:
             raise ValueError(f"add_model: the ctx holds {MAX_MODELS} models")
-        self.ray_pass.upload_model(model, index)
+        if build not in ("host", "device"):
+            raise ValueError(f"add_model: build must be 'host' or 'device', got {build!r}")
+        if build == "device":
+            self.ray_pass.upload_model_build(model, index)
+        else:
+            self.ray_pass.upload_model(model, index)
         self.models.append(model)
         self.ray_details.model_count = len(self.models)      # mod.rs:384 (scene.models.size())
         return index

@@ -120,7 +120,8 @@ typedef struct bhray_triangle {
 typedef struct bhray_model_header {     /* first 48 bytes of ModelUniform (Rust field order) */
     float    position[3];
     int32_t  visible;
-    float    rotation[3];               /* uploaded, never applied by the shader (ray.wgsl:56) */
+    float    rotation[3];               /* uploaded, never applied by the shader (ray.wgsl:56); a host that wants a rotated or
+                                           deforming model sends the moved vertices through bhray_update_model_vertices */
     uint32_t pad3;
     int32_t  point_count;
     int32_t  normal_count;
@@ -367,6 +368,17 @@ int bhray_set_texture(bhray_ctx* ctx, int slot, const uint8_t* rgba8, uint32_t w
  * invisible slot, one never uploaded and one with 0 triangles are skipped. */
 int bhray_upload_model_uniform(bhray_ctx* ctx, uint32_t model_index, const void* bytes, size_t size);
 int bhray_upload_model(bhray_ctx* ctx, uint32_t model_index, const bhray_model_desc* desc);
+/* Upload points, normals and triangles and build the tree on the GPU.  desc->nodes,
+ * desc->bvh_lookup and desc->node_count are ignored.  Same slot rules, error codes and synchronisation
+ * as bhray_upload_model (staged frames are launched first and keep the old model).  An index out of range is
+ * BHRAY_E_INVALID, found on the device before anything reads through it; the slot then keeps what it held. */
+int bhray_upload_model_build(bhray_ctx* ctx, uint32_t model_index, const bhray_model_desc* desc);
+/* New vertex data for a slot built by bhray_upload_model_build: same counts, same triangles.  Copies the two
+ * arrays into the buffers the slot already owns (no allocation) and rebuilds on the device.  The result is
+ * byte for byte what bhray_upload_model_build of the same data gives.  Either pointer may be NULL (keep).
+ * BHRAY_E_STATE for a slot that was not built on the device, BHRAY_E_INVALID when a count differs. */
+int bhray_update_model_vertices(bhray_ctx* ctx, uint32_t model_index, const float* points, int32_t point_count,
+                                const float* normals, int32_t normal_count);
 /* Per-frame model state without re-uploading 48 MB (the reference re-uploads, mod.rs:391).  */
 int bhray_set_model_transform(bhray_ctx* ctx, uint32_t model_index, const float position[3], int32_t visible);
 

@@ -108,6 +108,21 @@ int bhray_selftest(bhray_ctx* ctx, uint64_t mismatches[3]);    /* [0] = 1/x and 
 int bhray_read_level(bhray_ctx* ctx, uint32_t level, float* dst_rgba32f, size_t row_pitch_bytes);
 
 /* ------------------------------------------------------------------------------------------
+ * Device-built trees (bhray_upload_model_build)
+ * ---------------------------------------------------------------------------------------- */
+/* What the last build of a slot produced (first local partition).  A host-built slot: built_on_device 0, triangles and nodes
+ * filled, the rest 0.  An empty slot: BHRAY_E_STATE.                                                                  */
+typedef struct bhray_model_build_info {
+    uint32_t built_on_device, triangles, nodes, leaves, max_leaf, max_depth;
+    float    upload_ms, build_ms;   /* HIP events around the copies / the build kernels of the last build */
+} bhray_model_build_info;
+int bhray_get_model_build_info(bhray_ctx* ctx, uint32_t model_index, bhray_model_build_info* out);
+/* The tree a slot holds on the device (any slot, host-built ones too; first local partition): node_count nodes in
+ * the device's numbering and triangle_count lookup entries.  Caps too small: BHRAY_E_INVALID, counts still written. */
+int bhray_read_model_bvh(bhray_ctx* ctx, uint32_t model_index, bhray_node* nodes, uint32_t node_cap, int32_t* lookup,
+                         uint32_t lookup_cap, uint32_t* node_count, uint32_t* triangle_count);
+
+/* ------------------------------------------------------------------------------------------
  * Gather statistics (multi-GPU)
  * ---------------------------------------------------------------------------------------- */
 /* What a ctx gathers with.                                                                                          */
