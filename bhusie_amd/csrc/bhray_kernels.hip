@@ -1053,6 +1053,14 @@ enum : int { M_EMPTY = 0, M_REL = 1, M_FLAT = 2, M_FINISH = 3, M_SHADE_REL = 4, 
 #define BHRAY_PRIO_2_HI 16.0f
 #define BHRAY_PRIO_1_HI 40.0f
 #endif
+#ifndef BHRAY_PHASE_ORDER
+#define BHRAY_PHASE_ORDER 1      // the order of a round's phases in trace_kernel and quad_march (scheduling only: every ray is the same operations on the same values in the same order).
+                                 // 0: refill, shade, flat, epilogue, march - a ray that leaves the sphere waits the rest of its batch, comes back from its flat iteration for ONE general
+                                 // step, leaves again and idles a whole batch until the next flat phase, and the lane its epilogue frees idles another until the next refill.
+                                 // 1: refill, march, shade, flat, epilogue - the epilogue's lanes are refilled at once - and, in the no-mesh contract RK kernels, the general step taken
+                                 // behind the flat phase with a second flat pass for the lanes it threw out: an exit is finished in one visit (profiles/EXPERIMENTS.md R9.1).
+                                 // `make phase0` builds the earlier order's text as libbhray_phase0.so for tests/test_gpu_phase_order.py.
+#endif
 #ifndef BHRAY_MESH_COLD_LDS
 #define BHRAY_MESH_COLD_LDS 0    // mesh variant: the cold per-lane state in LDS as in the dense build
 #endif
@@ -1143,6 +1151,8 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
     constexpr bool MESH_PARK = MESH_DENSE && !COLD_LDS;   // its traversal in a region of its own (see the flat phase)
     constexpr bool FLAT_COLD = MESH_DENSE;                // ... the flat phase marked unlikely
     constexpr bool BVH_WW = MESH_DENSE;                   // ... and the while-while traversal
+    constexpr bool ROTATE = BHRAY_PHASE_ORDER != 0;                        // the march behind the refill (per build: a build that measures slower keeps the earlier order here)
+    constexpr bool FLAT2 = ROTATE && UNIFIED && !MODELS && METHOD == 1;    // ... and an exit finished in one visit: general step + second flat pass behind the flat phase
     constexpr bool WAVE_PRIO = ((BHRAY_WAVE_PRIO & 1) != 0 && !DENSE && !MODELS) || ((BHRAY_WAVE_PRIO & 2) != 0 && DENSE);   // (the mesh variant's lone launches wait for their traversals: nothing, measured)
     __shared__ float cold_lds[COLD_LDS ? (8 + BHRAY_HIT_LDS + (WAVE_PRIO ? 1 : 0)) * BHRAY_TRACE_THREADS : 1];
     // Integrator steps this wave issues for the frames of the batch -> Fb[0].work at the kernel's end.  Wave-uniform: a scalar register.
@@ -1326,6 +1336,12 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
             }
             if (!__any(mode != M_EMPTY)) break;
         }
+#if BHRAY_PHASE_ORDER
+        // (BHRAY_PHASE_ORDER: the march here, so that the lanes the epilogue frees at the round's end meet the refill before the next batch, not behind it)
+        if constexpr (ROTATE) {
+#include "bhray_march.inc"
+        }
+#endif
         // ---- deferred disk shading (ray.wgsl:612-663 and the hit bookkeeping of 537-552) for lanes that paused on a disk hit
         if (__any(mode >= M_SHADE_REL)) {
             if (mode >= M_SHADE_REL) {
@@ -1429,6 +1445,13 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
             }
         }
         // (FLAT_COLD: the flat phase marked unlikely, so that the register allocator weighs the step loop above the traversal's loops)
+#if BHRAY_PHASE_ORDER
+        // FLAT2: two passes.  A lane that the first pass sends back into the sphere is "odd" (its hit-test ray starts at the entry point, not at the integrator's position:
+        // see bhray_march.inc) and owes one general step, which for an escaping ray ends outside the sphere again: the step is taken here and the second pass runs that
+        // lane's last flat iteration, instead of the lane idling through the next batch for it.  A lane whose FIRST exit came in this general step is odd again behind the
+        // second pass: the odd test in front of the pairs catches it.
+        for (int flat_pass = 0; flat_pass < (FLAT2 ? 2 : 1); flat_pass++) {
+#endif
         const bool flat_now = run_flat && __any(mode == M_FLAT);
         if (FLAT_COLD ? __builtin_expect(flat_now, 0) : flat_now) {
             if (mode == M_FLAT) {
@@ -1497,6 +1520,21 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                 }
             }
         }
+#if BHRAY_PHASE_ORDER
+        if constexpr (FLAT2) {
+            if (flat_pass == 0) {
+                const bool odd = (mode == M_REL) & ((cpos.x != rkpos.x) | (cpos.y != rkpos.y) | (cpos.z != rkpos.z) | (cpos_dist != dist_c));     // (the condition in front of the pairs)
+                if (!__any(odd)) break;
+                work_steps += 1u;
+                {
+#define BHRAY_STEP_LEAN 1
+#include "bhray_step.inc"
+#undef BHRAY_STEP_LEAN
+                }
+            }
+        }
+        }
+#endif
 
         // ---- epilogue (ray.wgsl:583-595) for lanes whose loop ended
         if (__any(mode == M_FINISH)) {
@@ -1553,73 +1591,11 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
             }
         }
 
-        // ---- a batch of integrator steps (ray.wgsl:522-553) for lanes inside the sphere
-        if (__any(mode == M_REL)) work_steps += (unsigned)REL_BATCH;
-        if constexpr (UNIFIED) {
-            // The unified march (bhray_step_u.inc): pairs of steps over two position register sets, the state that only the rare paths and the other
-            // phases read (cpos / cdir / ppos / pdir apart from the integrator's own) written when a lane LEAVES the march, not on every step.
-            // RK: the integrator runs on rkpos / rkdir and the hit test's segment starts at cpos, which differs from rkpos for one step after a
-            // disk hit or a sphere entry moved it (ray.wgsl keeps two rays) - a wave that holds such a lane takes one step of the general form first.
-            if (METHOD == 1) {
-                const bool odd = (mode == M_REL) & ((cpos.x != rkpos.x) | (cpos.y != rkpos.y) | (cpos.z != rkpos.z) | (cpos_dist != dist_c));
-                if (__any(odd)) {
-                    work_steps += 1u;
-                    {                                        // (the lean text in both builds: the dense text leaves a step with `continue`)
-#define BHRAY_STEP_LEAN 1
-#include "bhray_step.inc"
-#undef BHRAY_STEP_LEAN
-                    }
-                }
-            }
-            if (mode == M_REL && it >= H.max_iter) mode = M_FINISH;      // the iteration limit (ray.wgsl:522) in front of the pairs; inside them it is tested where `it` changes
-            F3& upos = METHOD == 0 ? cpos : rkpos;      // the integrator's position and direction
-            F3& udir = METHOD == 0 ? cdir : rkdir;
-            // (the hole at the origin - all three words +0, wave-uniform: a scalar test - marches without forming position - bpos: see bhray_step_u.inc)
-            if (!MODELS && (BHRAY_ORIGIN_PATH & (1 << METHOD)) != 0 && ((__float_as_uint(H.bh.x) | __float_as_uint(H.bh.y) | __float_as_uint(H.bh.z)) == 0u)) {
-#define BHRAY_U_ORIGIN 1
-                for (int k = 0; k < REL_BATCH; k += 2) {
-                    if (!__any(mode == M_REL)) break;
-#define BHRAY_U_FIRST 1
-#include "bhray_step_u.inc"
-#undef BHRAY_U_FIRST
-#define BHRAY_U_FIRST 0
-#include "bhray_step_u.inc"
-#undef BHRAY_U_FIRST
-                }
-                if (mode == M_REL) qrel = upos;
-#undef BHRAY_U_ORIGIN
-            } else {
-#define BHRAY_U_ORIGIN 0
-            for (int k = 0; k < REL_BATCH; k += 2) {
-                if (!__any(mode == M_REL)) break;
-#define BHRAY_U_FIRST 1
-#include "bhray_step_u.inc"
-#undef BHRAY_U_FIRST
-#define BHRAY_U_FIRST 0
-#include "bhray_step_u.inc"
-#undef BHRAY_U_FIRST
-            }
-#undef BHRAY_U_ORIGIN
-            }
-            if (mode == M_REL) {                         // between batches every lane's state is exactly the general step's (after the second step of a pair ppos
-                if (METHOD == 1) { cpos = rkpos; cdir = rkdir; }   // is the previous position already): a general step, the iteration limit inside it, the other phases read it
-                pdir = udir;
-                cpos_dist = dist_c;
-            }
-        } else {
-        for (int k = 0; k < REL_BATCH; k++) {       // (unrolled by 2 / 4 to let prev = curr become renaming: -1 % / 0 %, measured)
-            if (!__any(mode == M_REL)) break;
-            if (COUNT && lane == 0) cnt[10]++;
-            if (DENSE || MODELS) {                    // see bhray_step.inc
-#define BHRAY_STEP_LEAN 0
-#include "bhray_step.inc"
-#undef BHRAY_STEP_LEAN
-            } else {
-#define BHRAY_STEP_LEAN 1
-#include "bhray_step.inc"
-#undef BHRAY_STEP_LEAN
-            }
-        }
+#if BHRAY_PHASE_ORDER
+        if constexpr (!ROTATE)
+#endif
+        {
+#include "bhray_march.inc"
         }
     }
 
