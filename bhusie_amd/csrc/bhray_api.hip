@@ -167,6 +167,8 @@ struct bhray_dev {
     int quad_wps = -1;                     // BHRAY_QUAD: waves per SIMD the quad march may use for a short queue (bhray_quad.inc); 0 = the scalar thin shares only; -1 = the measured default (RK 2, Euler 1)
     int dense_override = -1;               // BHRAY_TRACE_DENSE=0/1 (tuning experiments only)
     int coarse_build = -1;                 // BHRAY_COARSE_BUILD=0/1 (experiment): the build of the trace launches below the ladder's last level (-1: the batch's build)
+    int origin_kernel = 1;                 // BHRAY_ORIGIN_KERNEL=0: never the ORIGIN builds of the trace kernels (the A/B of EXPERIMENTS R10.1; the same pixels)
+    uint64_t origin_launches = 0, general_launches = 0;      // trace launches enqueued with an ORIGIN build / with any other (dev_get_trace_builds)
     bool rendered = false;
     // asynchronous hand-off (dev_read_hdr_async)
     hipEvent_t read_ev[BHRAY_READ_RING] = {nullptr};     // ticket t -> read_ev[t % BHRAY_READ_RING]
@@ -587,6 +589,7 @@ int dev_create(const bhray_config* cfg, const bhray::DevOptions& opt, bhray_dev*
     }
     if (const char* e = getenv("BHRAY_TRACE_DENSE")) c->dense_override = atoi(e) != 0;
     if (const char* e = getenv("BHRAY_COARSE_BUILD")) c->coarse_build = atoi(e);
+    if (const char* e = getenv("BHRAY_ORIGIN_KERNEL")) c->origin_kernel = atoi(e) != 0;
     if (const char* e = getenv("BHRAY_DYNAMIC_DENSE")) c->dynamic_dense = atoi(e);
     const uint32_t nslots = cfg->frames_in_flight ? cfg->frames_in_flight : 4;
     c->cfg.frames_in_flight = nslots;
@@ -1010,6 +1013,7 @@ struct BatchPlan {
     const uint32_t nb, nl;             // frames staged, ladder levels
     const bool count;                  // BHRAY_F_COUNTERS
     const int literal;                 // the integrator's evaluation (launch_trace's `eval`)
+    const bool origin;                 // every frame of the batch has the hole at +0, +0, +0 (launch_trace's `origin`)
     const int grid;                    // persistent trace blocks of the ctx's trace build
     hipStream_t st;
     size_t args_used;
@@ -1148,7 +1152,7 @@ struct BatchPlan {
             // trace launch (2 persistent blocks per CU: `grid`) - a full-device persistent grid keeps the next batch's small kernels
             // (its prediction, its fix-up classification) waiting until it has drained, and two batches then run one after the other
             // (rank 3 of an 8-way 1080p partition, 20-frame blocks of a moving sequence: 0.0995 -> 0.0736 ms per frame, EXPERIMENTS R4.12)
-            seq.push_back({1, d, shared_device ? grid : c->num_cus * trace_blocks_per_cu(S.method, S.models, count, 1, literal), count, {}, {(int)(3 * nl + 3)}, 1});
+            seq.push_back({1, d, shared_device ? grid : c->num_cus * trace_blocks_per_cu(S.method, S.models, count, 1, literal, origin), count, {}, {(int)(3 * nl + 3)}, 1});
         }
         for (uint32_t l = 0; l < nl; l++) {
             FrameLaunch* h; const FrameLaunch* d; next_launch(h, d);
@@ -1162,7 +1166,7 @@ struct BatchPlan {
                 h[k].row_work = (count && R.d_row_work) ? R.d_row_work + c->row_work_off[l] : nullptr;
             }
             seq.push_back({0, d, classify_blocks(l), count, {(int)(3 * l)}, {(int)(3 * l + 1)}, -1, true});
-            seq.push_back({1, d, shared_device ? grid : c->num_cus * trace_blocks_per_cu(S.method, S.models, count, 0, literal), count, {}, {(int)(3 * l + 2)}, 0});
+            seq.push_back({1, d, shared_device ? grid : c->num_cus * trace_blocks_per_cu(S.method, S.models, count, 0, literal, origin), count, {}, {(int)(3 * l + 2)}, 0});
         }
         first_normal = nl;
         return BHRAY_OK;
@@ -1290,7 +1294,16 @@ int launch_batch(bhray_dev* c) {
     const bool dense = c->dense_override >= 0 ? c->dense_override != 0
                                               : ((double)nb * weight >= 2.5 || (double)(in_flight * (size_t)c->batch) * weight >= (double)(dyn > 0 ? dyn : 4));
     const int literal = (c->cfg.flags & BHRAY_F_LITERAL) ? 1 : ((c->cfg.flags & BHRAY_F_EVAL_FMA) ? 2 : 0);   // the integrator's evaluation (launch_trace's `eval`)
-    int bpc = trace_blocks_per_cu(S.method, S.models, count, dense, literal);
+    // The hole at the scene's origin - the three position words of EVERY frame staged in this batch are zero bits (a -0 is not: x - (-0) is not x for x = -0) - selects the ORIGIN
+    // builds of the trace kernels (bhray_kernels.hip: no position - bpos in the march) for every trace launch of the batch and for the occupancy query that sizes their grids.
+    // Per batch, from the uniform words staged with each frame: a scene whose hole moves changes builds from one batch to the next, with the same pixels.
+    bool origin = c->origin_kernel != 0;
+    for (uint32_t k = 0; k < nb && origin; k++) {
+        uint32_t w[3];
+        memcpy(w, ((const FrameParams*)S.h_args)[k].bh, sizeof w);
+        origin = (w[0] | w[1] | w[2]) == 0u;
+    }
+    int bpc = trace_blocks_per_cu(S.method, S.models, count, dense, literal, origin);
     if (c->slots.size() > 1 && bpc > 1) bpc = bpc > 4 ? 2 : (bpc / 2 > 1 ? bpc / 2 : 1);     // measured: 2 blocks per CU is best at 8-16 slots
     if (c->bpc_override > 0) bpc = c->bpc_override;
     int grid = c->num_cus * bpc;
@@ -1299,7 +1312,7 @@ int launch_batch(bhray_dev* c) {
     // (profiles/r05_ab_euler_grid.txt, EXPERIMENTS.md R5.9)
     if (S.method == 0 && c->slots.size() >= 8 && bpc == 2 && c->bpc_override <= 0) grid = c->num_cus * 3 / 2;      // (measured at 22 slots only: from 8 slots on)
     if (c->grid_override > 0) grid = c->grid_override;
-    BatchPlan plan{c, S, nb, nl, count, literal, grid, st, (size_t)B * sizeof(FrameParams)};
+    BatchPlan plan{c, S, nb, nl, count, literal, origin, grid, st, (size_t)B * sizeof(FrameParams)};
     const uint32_t ns = c->cfg.speculative_levels;
     const bool any_rows = !c->levels[nl - 1].rows.empty();    // a partition without rows has nothing to launch (then no level has rows)
     const bool temporal = (c->cfg.flags & BHRAY_F_TEMPORAL) != 0;
@@ -1362,7 +1375,11 @@ int launch_batch(bhray_dev* c) {
         if (timing) for (int e : Ln.ev_before) HIPCHK(c, hipEventRecord(fev[e], st));
         if (Ln.kind == 2) HIPCHK(c, launch_predict(dP, Ln.d, (int)nb, Ln.levels, Ln.blocks, st));
         else if (Ln.kind == 0) HIPCHK(c, launch_classify(dP, Ln.d, (int)nb, Ln.blocks, Ln.count, Ln.fixup, st));
-        else HIPCHK(c, launch_trace(dP, Ln.d, (int)nb, S.method, S.models, Ln.count, Ln.build < 0 ? dense : Ln.build != 0, literal, c->d_err, Ln.blocks, st));
+        else {
+            const bool ln_dense = Ln.build < 0 ? dense : Ln.build != 0;
+            HIPCHK(c, launch_trace(dP, Ln.d, (int)nb, S.method, S.models, Ln.count, ln_dense, literal, origin, c->d_err, Ln.blocks, st));
+            if (origin && trace_origin_build(S.method, S.models, Ln.count, ln_dense, literal)) c->origin_launches++; else c->general_launches++;
+        }
         if (timing) for (int e : Ln.ev_after) HIPCHK(c, hipEventRecord(fev[e], st));
     }
     HIPCHK(c, hipEventRecord(S.done, st));
@@ -1771,6 +1788,12 @@ int dev_signal_stream(bhray_dev* c, void* s) {
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = launch_batch(c); if (rc) return rc; }
     HIPCHK(c, hipStreamWaitEvent((hipStream_t)s, c->slots[(size_t)c->last_slot].done, 0));
+    return BHRAY_OK;
+}
+
+int dev_get_trace_builds(bhray_dev* c, uint64_t launches[2]) {
+    if (!c || !launches) return BHRAY_E_INVALID;
+    launches[0] = c->origin_launches; launches[1] = c->general_launches;
     return BHRAY_OK;
 }
 

@@ -2043,6 +2043,20 @@ int bhray_selftest(bhray_ctx* c, uint64_t mismatches[3]) {
     return BHRAY_OK;
 }
 
+int bhray_get_trace_builds(bhray_ctx* c, uint64_t launches[2]) {
+    if (!c || !launches) return BHRAY_E_INVALID;
+    ENTER(c);
+    uint64_t sum[2] = {0, 0};
+    for (Part& p : c->parts) {
+        if (!p.dev) continue;
+        uint64_t m[2];
+        DEV(c, p.dev, dev_get_trace_builds(p.dev, m));
+        sum[0] += m[0]; sum[1] += m[1];
+    }
+    launches[0] = sum[0]; launches[1] = sum[1];
+    return BHRAY_OK;
+}
+
 int bhray_get_level_counters(bhray_ctx* c, uint32_t level, bhray_counters* out) {
     if (!c || !out) return BHRAY_E_INVALID;
     ENTER(c);

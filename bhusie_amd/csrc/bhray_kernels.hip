@@ -142,10 +142,12 @@ __device__ __forceinline__ float pin_sgpr(float v) { asm volatile("" : "+s"(v));
 __device__ __forceinline__ int pin_sgpr(int v) { asm volatile("" : "+s"(v)); return v; }
 __device__ __forceinline__ const uint8_t* pin_sgpr(const uint8_t* v) { asm volatile("" : "+s"(v)); return v; }
 __device__ __forceinline__ TexDev pin_sgpr(const TexDev& t) { TexDev r; r.rgba = pin_sgpr(t.rgba); r.w = pin_sgpr(t.w); r.h = pin_sgpr(t.h); return r; }
-template <bool FOLDED_CULLS = false>
+// ORIGIN: the hole's position is the constant +0 vector (the host launches such a kernel only for frames whose three position words are zero bits), not three SGPRs
+template <bool FOLDED_CULLS = false, bool ORIGIN = false>
 __device__ __forceinline__ HotParams load_hot(const FrameParams& P) {
     HotParams H;
-    H.bh = f3(pin_sgpr(P.bh[0]), pin_sgpr(P.bh[1]), pin_sgpr(P.bh[2]));
+    if (ORIGIN) H.bh = f3(0.0f, 0.0f, 0.0f);
+    else H.bh = f3(pin_sgpr(P.bh[0]), pin_sgpr(P.bh[1]), pin_sgpr(P.bh[2]));
     H.bn = f3(pin_sgpr(P.bn[0]), pin_sgpr(P.bn[1]), pin_sgpr(P.bn[2]));
     H.bn_len = pin_sgpr(P.bn_len);
     H.inner = pin_sgpr(P.inner); H.outer = pin_sgpr(P.outer); H.R = pin_sgpr(P.R);
@@ -1024,8 +1026,15 @@ enum : int { M_EMPTY = 0, M_REL = 1, M_FLAT = 2, M_FINISH = 3, M_SHADE_REL = 4, 
 #ifndef BHRAY_PNUMER_EARLY
 #define BHRAY_PNUMER_EARLY 1
 #endif
+#ifndef BHRAY_ORIGIN_KERNEL
+#define BHRAY_ORIGIN_KERNEL 1    // the hole at the scene's origin (all three position words +0) is a property of a kernel BUILD, chosen by the host per launch (trace_kernel's ORIGIN): such a
+                                 // build holds only the origin text of the unified pairs (no position - bpos per step, bhray_step_u.inc) and the constant +0 for bpos everywhere, every other
+                                 // build only the general text.  0 (`make origin0`: libbhray_origin0.so, what tests/test_gpu_origin_kernel.py and the A/B of EXPERIMENTS R10.1 compare with): no such
+                                 // build; the choice is the wave-uniform test inside the kernel that BHRAY_ORIGIN_PATH describes - the kernel text before the ORIGIN builds.
+#endif
 #ifndef BHRAY_ORIGIN_PATH
-#define BHRAY_ORIGIN_PATH 1      // bit 0: Euler, bit 1: RK - a second copy of the unified pairs for a hole at the scene's origin (no position - bpos per step): Euler +1.7 %; RK -1.8 % (the doubled loop costs its kernel 48 bytes of scratch in the phases): Euler only
+#define BHRAY_ORIGIN_PATH 1      // (BHRAY_ORIGIN_KERNEL 0 only) bit 0: Euler, bit 1: RK - a second copy of the unified pairs for a hole at the scene's origin inside ONE kernel, behind a scalar test:
+                                 // Euler +1.7 %; RK -1.8 % (the doubled loop costs its kernel 48 bytes of scratch in the phases): Euler only
 #endif
 #ifndef BHRAY_UNIFIED_MESH
 #define BHRAY_UNIFIED_MESH 1    // ... and the mesh variant's kernels too (RK +1.5-2.2 %, Euler +3.5 % on configs[2]; profiles/EXPERIMENTS.md R6.10)
@@ -1128,7 +1137,7 @@ namespace bhray {
 #ifndef BHRAY_TRACE_KERNEL_ATTR
 #define BHRAY_TRACE_KERNEL_ATTR      // (experiments: e.g. __attribute__((amdgpu_num_sgpr(88))))
 #endif
-template <int METHOD, bool MODELS, bool COUNT, bool DENSE, int EVAL = 0>
+template <int METHOD, bool MODELS, bool COUNT, bool DENSE, int EVAL = 0, bool ORIGIN = false>
 __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS ? (DENSE ? BHRAY_TRACE_WAVES_MESH_DENSE : BHRAY_TRACE_WAVES_MESH) : (DENSE ? BHRAY_TRACE_WAVES_DENSE : BHRAY_TRACE_WAVES)) void trace_kernel(const FrameParams* __restrict__ Pb, const FrameLaunch* __restrict__ Fb, const int nb, int* __restrict__ err_flag) {
     const int lane = threadIdx.x & 63;
     int err = 0;
@@ -1219,7 +1228,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
         }
         if (thin_share != 0u && fi != 0) continue;
     }
-    const HotParams H = load_hot<MODELS>(P);
+    const HotParams H = load_hot<MODELS, ORIGIN>(P);
     // The quad march (bhray_quad.inc): a queue that fits 16 rays per wave on the waves the host allows it (bits 2-4 of probe_empty: waves per
     // SIMD; 0 = off) is marched with one ray per QUAD of lanes - x, y, z on three lanes - instead of one per lane: fewer instructions per
     // iteration of the launch's longest ray, the same operations per ray.  Dealt out once like a scalar thin share; whole rounds of one wave per SIMD.
@@ -1804,7 +1813,8 @@ hipError_t launch_classify(const FrameParams* Pb, const FrameLaunch* Fb, int nb,
     return hipGetLastError();
 }
 
-// Which builds of trace_kernel<METHOD, MODELS, COUNT, DENSE, EVAL> exist (x 2 integrators = 32 instantiations; 48 in round 5, 72 in round 3).
+// Which builds of trace_kernel<METHOD, MODELS, COUNT, DENSE, EVAL, ORIGIN> exist (12 x 2 integrators general builds + 2 x 2 ORIGIN builds = 36 instantiations; 32 in round 9, 48 in round 5,
+// 72 in round 3).
 // eval: 0 the numerics contract, 1 BHRAY_F_LITERAL, 2 BHRAY_F_EVAL_FMA.  Every variant has a build for lone launches (the latency build);
 // the build for a saturated device (dense) exists where throughput is reported: not for counting kernels (BHRAY_F_COUNTERS is a diagnosis
 // mode: the same counts whichever build marches) and, of the two measurement-only evaluations, not for the mesh variant.  A launch that
@@ -1812,44 +1822,62 @@ hipError_t launch_classify(const FrameParams* Pb, const FrameLaunch* Fb, int nb,
 constexpr bool trace_variant_exists(int eval, bool models, bool dense, bool count) {
     return !(count && dense) && !(eval != 0 && models && dense);
 }
-template <int METHOD, bool MODELS, bool COUNT, bool DENSE, int EVAL>
+// ... and which of them also have an ORIGIN build - the hole's position the constant +0 vector, the unified pairs without position - bpos (bhray_march.inc) - for launches whose
+// frames all have the hole at the scene's origin: the no-mesh, non-counting contract kernels (RK and Euler, latency and dense: four).  None where there is no origin text to hold
+// (-DBHRAY_UNIFIED=0) and none in the stand-in for the kernels before them (-DBHRAY_ORIGIN_KERNEL=0).  A launch whose variant has none gets the general build: the same pixels.
+constexpr bool trace_origin_variant_exists(int eval, bool models, bool dense, bool count) {
+    return BHRAY_ORIGIN_KERNEL != 0 && BHRAY_UNIFIED != 0 && eval == 0 && !models && !count && trace_variant_exists(eval, models, dense, count);
+}
+template <int METHOD, bool MODELS, bool COUNT, bool DENSE, int EVAL, bool ORIGIN>
 static const void* trace_kernel_ptr_t() {
-    if constexpr (trace_variant_exists(EVAL, MODELS, DENSE, COUNT)) return (const void*)trace_kernel<METHOD, MODELS, COUNT, DENSE, EVAL>;
-    else return trace_kernel_ptr_t<METHOD, MODELS, COUNT, false, EVAL>();
+    if constexpr (ORIGIN && !trace_origin_variant_exists(EVAL, MODELS, DENSE, COUNT)) return trace_kernel_ptr_t<METHOD, MODELS, COUNT, DENSE, EVAL, false>();
+    else if constexpr (trace_variant_exists(EVAL, MODELS, DENSE, COUNT)) return (const void*)trace_kernel<METHOD, MODELS, COUNT, DENSE, EVAL, ORIGIN>;
+    else return trace_kernel_ptr_t<METHOD, MODELS, COUNT, false, EVAL, ORIGIN>();
+}
+template <int METHOD, int EVAL, bool ORIGIN>
+static const void* trace_kernel_ptr_meo(bool models, bool count, bool dense) {
+    if (models) {
+        if (dense) return count ? trace_kernel_ptr_t<METHOD, true, true, true, EVAL, ORIGIN>() : trace_kernel_ptr_t<METHOD, true, false, true, EVAL, ORIGIN>();
+        return count ? trace_kernel_ptr_t<METHOD, true, true, false, EVAL, ORIGIN>() : trace_kernel_ptr_t<METHOD, true, false, false, EVAL, ORIGIN>();
+    }
+    if (dense) return count ? trace_kernel_ptr_t<METHOD, false, true, true, EVAL, ORIGIN>() : trace_kernel_ptr_t<METHOD, false, false, true, EVAL, ORIGIN>();
+    return count ? trace_kernel_ptr_t<METHOD, false, true, false, EVAL, ORIGIN>() : trace_kernel_ptr_t<METHOD, false, false, false, EVAL, ORIGIN>();
 }
 template <int METHOD, int EVAL>
-static const void* trace_kernel_ptr_me(bool models, bool count, bool dense) {
-    if (models) {
-        if (dense) return count ? trace_kernel_ptr_t<METHOD, true, true, true, EVAL>() : trace_kernel_ptr_t<METHOD, true, false, true, EVAL>();
-        return count ? trace_kernel_ptr_t<METHOD, true, true, false, EVAL>() : trace_kernel_ptr_t<METHOD, true, false, false, EVAL>();
-    }
-    if (dense) return count ? trace_kernel_ptr_t<METHOD, false, true, true, EVAL>() : trace_kernel_ptr_t<METHOD, false, false, true, EVAL>();
-    return count ? trace_kernel_ptr_t<METHOD, false, true, false, EVAL>() : trace_kernel_ptr_t<METHOD, false, false, false, EVAL>();
+static const void* trace_kernel_ptr_me(bool models, bool count, bool dense, bool origin) {
+    return origin ? trace_kernel_ptr_meo<METHOD, EVAL, true>(models, count, dense) : trace_kernel_ptr_meo<METHOD, EVAL, false>(models, count, dense);
 }
-static const void* trace_kernel_ptr(int method, bool models, bool count, bool dense, int eval) {
+static const void* trace_kernel_ptr(int method, bool models, bool count, bool dense, int eval, bool origin) {
     if (method == 0) {
-        if (eval == 1) return trace_kernel_ptr_me<0, 1>(models, count, dense);
-        if (eval == 2) return trace_kernel_ptr_me<0, 2>(models, count, dense);
-        return trace_kernel_ptr_me<0, 0>(models, count, dense);
+        if (eval == 1) return trace_kernel_ptr_me<0, 1>(models, count, dense, origin);
+        if (eval == 2) return trace_kernel_ptr_me<0, 2>(models, count, dense, origin);
+        return trace_kernel_ptr_me<0, 0>(models, count, dense, origin);
     }
-    if (eval == 1) return trace_kernel_ptr_me<1, 1>(models, count, dense);
-    if (eval == 2) return trace_kernel_ptr_me<1, 2>(models, count, dense);
-    return trace_kernel_ptr_me<1, 0>(models, count, dense);
+    if (eval == 1) return trace_kernel_ptr_me<1, 1>(models, count, dense, origin);
+    if (eval == 2) return trace_kernel_ptr_me<1, 2>(models, count, dense, origin);
+    return trace_kernel_ptr_me<1, 0>(models, count, dense, origin);
 }
 static size_t trace_dyn_lds(bool models) { return models ? (size_t)BHRAY_BVH_LDS_STACK * BHRAY_TRACE_THREADS * 8 : 0; }   // trace_ray_model's traversal ring
 
-hipError_t launch_trace(const FrameParams* Pb, const FrameLaunch* Fb, int nb, int method, bool models, bool count, bool dense, int eval, int* err_flag,
+// `origin`: every frame of the batch has the hole at +0, +0, +0 (the host's test of the uniform words: bhray_api.hip) - the ORIGIN build where the variant has one
+bool trace_origin_build(int method, bool models, bool count, bool dense, int eval) {
+    (void)method;
+    if (!trace_variant_exists(eval, models, dense, count)) dense = false;
+    return trace_origin_variant_exists(eval, models, dense, count);
+}
+
+hipError_t launch_trace(const FrameParams* Pb, const FrameLaunch* Fb, int nb, int method, bool models, bool count, bool dense, int eval, bool origin, int* err_flag,
                         int grid_blocks, hipStream_t s) {
     if (nb <= 0) return hipSuccess;
     (void)hipGetLastError();
     void* args[] = {(void*)&Pb, (void*)&Fb, (void*)&nb, (void*)&err_flag};
-    return hipLaunchKernel(trace_kernel_ptr(method, models, count, dense, eval), dim3((grid_blocks * 256 + BHRAY_TRACE_THREADS - 1) / BHRAY_TRACE_THREADS),
+    return hipLaunchKernel(trace_kernel_ptr(method, models, count, dense, eval, origin), dim3((grid_blocks * 256 + BHRAY_TRACE_THREADS - 1) / BHRAY_TRACE_THREADS),
                            dim3(BHRAY_TRACE_THREADS), args, trace_dyn_lds(models), s);
 }
 
-int trace_blocks_per_cu(int method, int has_models, int count, int dense, int eval) {
+int trace_blocks_per_cu(int method, int has_models, int count, int dense, int eval, int origin) {
     int n = 0;
-    const void* f = trace_kernel_ptr(method, has_models != 0, count != 0, dense != 0, eval);
+    const void* f = trace_kernel_ptr(method, has_models != 0, count != 0, dense != 0, eval, origin != 0);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, BHRAY_TRACE_THREADS, trace_dyn_lds(has_models != 0)) != hipSuccess || n < 1) n = 2;
     n = n * BHRAY_TRACE_THREADS / 256;            // in units of 256 threads (the grid is sized in those)
     return n < 1 ? 1 : n;

@@ -22,8 +22,13 @@
             if (mode == M_REL && it >= H.max_iter) mode = M_FINISH;      // the iteration limit (ray.wgsl:522) in front of the pairs; inside them it is tested where `it` changes
             F3& upos = METHOD == 0 ? cpos : rkpos;      // the integrator's position and direction
             F3& udir = METHOD == 0 ? cdir : rkdir;
-            // (the hole at the origin - all three words +0, wave-uniform: a scalar test - marches without forming position - bpos: see bhray_step_u.inc)
+            // (the hole at the origin - all three words +0 - marches without forming position - bpos: see bhray_step_u.inc.  A property of the BUILD, chosen by the host per launch: an
+            // ORIGIN build holds the first loop only, every other build the second; BHRAY_ORIGIN_KERNEL 0, the earlier text: both loops in one kernel behind a wave-uniform scalar test)
+#if BHRAY_ORIGIN_KERNEL
+            if constexpr (ORIGIN) {
+#else
             if (!MODELS && (BHRAY_ORIGIN_PATH & (1 << METHOD)) != 0 && ((__float_as_uint(H.bh.x) | __float_as_uint(H.bh.y) | __float_as_uint(H.bh.z)) == 0u)) {
+#endif
 #define BHRAY_U_ORIGIN 1
                 for (int k = 0; k < REL_BATCH; k += 2) {
                     if (!__any(mode == M_REL)) break;

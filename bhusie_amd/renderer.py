@@ -421,6 +421,12 @@ class RayPass:
         check(self._L.bhray_selftest(self._h, m), self._h, self._L)
         return int(m[0]), int(m[1]), int(m[2])
 
+    def trace_builds(self):
+        """(trace launches enqueued so far with an ORIGIN build - the hole at +0, +0, +0 in every frame of the batch -, with any other build): bhray_get_trace_builds"""
+        m = (C.c_uint64 * 2)()
+        check(self._L.bhray_get_trace_builds(self._h, m), self._h, self._L)
+        return int(m[0]), int(m[1])
+
     def timing(self) -> BhrayTiming:
         t = BhrayTiming()
         check(self._L.bhray_get_timing(self._h, C.byref(t)), self._h, self._L)

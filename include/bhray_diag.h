@@ -104,6 +104,12 @@ int bhray_get_timing(bhray_ctx* ctx, bhray_timing* out);       /* needs BHRAY_F_
  * binary32 value of [-1, 1].  Returns the number of violating inputs of each (all must be 0).  ~20 ms.              */
 int bhray_selftest(bhray_ctx* ctx, uint64_t mismatches[3]);    /* [0] = 1/x and the step-size power, [1] = sqrt, [2] = acos monotonicity */
 
+/* Which build of the trace kernels the launches got: launches[0] = trace launches enqueued since create with an ORIGIN build (the hole at
+ * +0, +0, +0 in every frame of the batch: the march without position - hole), launches[1] = with any other build; summed over the local
+ * partitions.  Frames staged but not yet launched (frames_per_batch > 1) are not counted: bhray_flush or bhray_sync first.  The pixels do
+ * not depend on the build; BHRAY_ORIGIN_KERNEL=0 in the environment at create: never an ORIGIN build.                      */
+int bhray_get_trace_builds(bhray_ctx* ctx, uint64_t launches[2]);
+
 /* Any ladder level, full size level_w×level_h (unrendered pixels are NaN-filled at create).  */
 int bhray_read_level(bhray_ctx* ctx, uint32_t level, float* dst_rgba32f, size_t row_pitch_bytes);
 
