@@ -1818,8 +1818,21 @@ int dev_get_level_counters(bhray_dev* c, uint32_t level, bhray_counters* out) {
     if (level >= c->cfg.levels) return fail(c, BHRAY_E_INVALID, "level out of range");
     int rc = dev_sync(c);
     if (rc) return rc;
-    static_assert(sizeof(bhray_counters) == sizeof(Counters64), "counter layout");
-    HIPCHK(c, hipMemcpy(out, c->slots[(size_t)c->last_slot].fr[(size_t)c->last_sub].d_counters + level, sizeof(Counters64), hipMemcpyDeviceToHost));
+    static_assert(sizeof(bhray_counters) == 13 * sizeof(unsigned long long) && sizeof(Counters64) == 16 * sizeof(unsigned long long), "counter layout");
+    HIPCHK(c, hipMemcpy(out, c->slots[(size_t)c->last_slot].fr[(size_t)c->last_sub].d_counters + level, sizeof(bhray_counters), hipMemcpyDeviceToHost));
+    return BHRAY_OK;
+}
+
+// The RK error-estimate bound's counters of the last render (Counters64::v[13..15], summed over the levels): wave-steps, wave-steps whose active lanes all passed, violations
+int dev_get_err_skip(bhray_dev* c, uint64_t out[3]) {
+    if (!c || !out) return BHRAY_E_INVALID;
+    if (!(c->cfg.flags & BHRAY_F_COUNTERS)) return fail(c, BHRAY_E_STATE, "ctx created without BHRAY_F_COUNTERS");
+    int rc = dev_sync(c);
+    if (rc) return rc;
+    Counters64 t[BHRAY_MAX_LEVELS];
+    HIPCHK(c, hipMemcpy(t, c->slots[(size_t)c->last_slot].fr[(size_t)c->last_sub].d_counters, (size_t)c->cfg.levels * sizeof(Counters64), hipMemcpyDeviceToHost));
+    out[0] = out[1] = out[2] = 0;
+    for (uint32_t l = 0; l < c->cfg.levels; l++) for (int k = 0; k < 3; k++) out[k] += t[l].v[13 + k];
     return BHRAY_OK;
 }
 

@@ -92,6 +92,7 @@ int  dev_get_trace_builds(bhray_dev* c, uint64_t launches[2]);   // trace launch
 int  dev_get_level_counters(bhray_dev* c, uint32_t level, bhray_counters* out);
 int  dev_add_row_work(bhray_dev* c, uint32_t level, uint64_t* acc, uint32_t n);   // acc[y] += iterations of the last render's rays of level row y
 int  dev_get_counters(bhray_dev* c, bhray_counters* out);
+int  dev_get_err_skip(bhray_dev* c, uint64_t out[3]);   // the RK error-estimate bound in the counting kernels: wave-steps, wave-steps whose lanes all pass, violations
 int  dev_get_timing(bhray_dev* c, bhray_timing* out);
 // what the frames still held by the slots cost: integrator steps issued by the trace waves (mean per frame) and pixels visited by the classify launches
 int  dev_get_work(bhray_dev* c, double* wave_steps_per_frame, double* classify_pixels_per_frame, uint32_t* frames, int* method);   // method: the integrator of the current uniforms (1 = RK)

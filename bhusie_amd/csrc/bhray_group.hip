@@ -2057,6 +2057,21 @@ int bhray_get_trace_builds(bhray_ctx* c, uint64_t launches[2]) {
     return BHRAY_OK;
 }
 
+int bhray_get_err_skip(bhray_ctx* c, uint64_t out[3]) {
+    if (!c || !out) return BHRAY_E_INVALID;
+    ENTER(c);
+    if (c->gather) { int rc = group_sync(c); if (rc) return rc; }
+    uint64_t sum[3] = {0, 0, 0};
+    for (Part& p : c->parts) {
+        if (!p.dev) continue;
+        uint64_t m[3];
+        DEV(c, p.dev, dev_get_err_skip(p.dev, m));
+        for (int k = 0; k < 3; k++) sum[k] += m[k];
+    }
+    for (int k = 0; k < 3; k++) out[k] = sum[k];
+    return BHRAY_OK;
+}
+
 int bhray_get_level_counters(bhray_ctx* c, uint32_t level, bhray_counters* out) {
     if (!c || !out) return BHRAY_E_INVALID;
     ENTER(c);

@@ -101,7 +101,7 @@ struct SpecLevel { int w, h; float4* out; int out_pitch; int out_x0; const int32
                    unsigned long long* row_work; };   // counting builds: as FrameLaunch::row_work, for this level
 struct SpecLevels { int n; SpecLevel l[BHRAY_MAX_SPEC_LEVELS]; };   // n == 0: one level, described by LevelParams
 
-struct Counters64 { unsigned long long v[13]; };   // order = bhray_counters
+struct Counters64 { unsigned long long v[16]; };   // [0..12]: order = bhray_counters; [13..15]: the RK error-estimate bound (bhray_get_err_skip: wave-steps, all lanes pass, violations)
 
 // One frame's share of one launch.  A launch covers the `nb` frames of a batch: classify uses blockIdx.y as the frame
 // index, the persistent trace blocks start on frame blockIdx.x % nb and move on to the other frames when theirs runs dry.

@@ -646,8 +646,36 @@ __device__ constexpr float DB1 = KF(37.0 / 378.0 - 2825.0 / 27648.0),
 // (FAST: the short 1/x and sqrt sequences WITHOUT their range tests and the step size's common arm only; the return value says for which lanes that is
 // not the exact step - an operand outside a sequence's range, or an error estimate above the threshold: the one-test step of bhray_step_u.inc runs the exact
 // form again for those, behind the test every step has anyway.  A wave that runs alone pays ~35 cycles for every test of its own - profiles/EXPERIMENTS.md R6.12.)
-template <bool FAST>
-__device__ __forceinline__ bool next_ray_rk_t(const F3 q0, const F3 p0, F3& pos, F3& dir, float& h_io, float dist) {
+//
+// SKIP (BHRAY_ERR_SKIP, per build: trace_kernel's ERR_SKIP): the error estimate e = sum DB_i K_i only decides between the step size's two arms, h * 1.0001 and the
+// power arm behind e_max > 0.00002, and a bound formed from two values the step already holds proves the common answer without forming it:
+//
+//     b = fma(sh * sh, dist, sh * sh) = (dist + 1) * sh^2 <= ERR_SKIP_C = 3.6e-5     =>     e_max <= 1.0e-5 < 0.00002.
+//
+// Proof.  Write g = |sh|, D = |q0|_inf, |.| the largest component.  D <= |q0|_2 <= dist * (1 + 4u), u = 2^-24 (dist is the rounded length of q0, fused dot + correctly
+// rounded sqrt).  b <= C gives g^2 <= C, so g <= 0.006, and dist * g^2 <= C.
+//  (1) The stages.  K_1 = q0 * sh, K_i = (q0 + sum_j a_ij K_j) * sh, so with R_i = sum_j |a_ij| (R_2..R_6 = 0.2, 0.3, 2.4, 6.593, 0.875; K4 takes K2 twice, -9/10 and 6/5)
+//      and k = max_i |K_i| / (D g):  k <= 1 + 6.593 g k, k <= 1 / (1 - 6.593 * 0.006) = 1.0412.
+//  (2) The estimate in exact arithmetic.  sum_i DB_i = 0 for the exact weights (both Cash-Karp rows sum to 1; the five rounded constants sum to -1.4e-9), so e = (sum DB_i) q0 sh + sh sum_i DB_i sum_j a_ij K_j and
+//      |e| <= 1.5e-9 D g + g * (sum_i |DB_i| R_i) * k D g = 1.5e-9 D g + 0.2492 * 1.0412 * D g^2 = 1.5e-9 D g + 0.2595 D g^2
+//      (|DB_1,3,4,5,6| = 0.004294, 0.018669, 0.034155, 0.019322, 0.039103; DB_1 has R_1 = 0; 0.00560 + 0.08197 + 0.12738 + 0.03422 = 0.2492).
+//  (3) Rounding.  A stage's sum is at most five fused operations on values <= 1.05 D, each off by at most u * 1.05 D, and its product with sh one more; the e chain is one
+//      product and four fused operations on values <= sum |DB_i| * 1.0412 D g = 0.1203 D g.  Against (2) the computed e moves by at most
+//      g * sum |DB_i| * 6 * 1.05 u D + 5 u * 0.1203 D g <= 1.4 u D g (what a rounded stage hands to the later ones comes back times |a_ij| g <= 0.04: under 5 % of it) < 1e-7 D g.  Denormal results (flushed or not) move it by less than 1e-37.
+//  (4) Together |e| <= 0.2595 * (1 + 4u) * dist g^2 + 1.015e-7 * (1 + 4u) * dist g <= 0.2596 C + 1.02e-7 * sqrt(C dist) (dist g = sqrt(dist) * sqrt(dist g^2))
+//      = 9.35e-6 + 6.1e-10 * sqrt(dist) <= 1.0e-5 for every dist <= 1e6.  Assumed range: dist <= 1e6 - a lane marches inside the relativity sphere only (its radius R is a
+//      scene unit of order 10-1e3; dist^5 overflows binary32 above 6e7, long before which the exact step itself has lost its meaning); above it the slack to the threshold
+//      itself (2e-5) still holds up to dist = 3e8, where dist^5 has long been +inf and sh an exact zero or a NaN.
+//  (5) The test's own rounding: b is two roundings above (dist + 1) g^2, so the real quantity is at most C (1 + 3u): a relative 1.8e-7, inside the upward rounding of the figures of (4).
+//  (6) NaN, inf: a NaN in dist or sh makes b a NaN (fma and the product propagate it; no max / min, which would drop one) and an overflow makes it +inf: `b <= C` is
+//      false for both, the lane fails the bound and its wave runs the full text.  sh^2 underflowing to 0 means g < 1e-22: e is then 0 to 1e-20.
+// The branch is wave-uniform: when EVERY active lane passes, the e chain, the maximum, the compare and the power arm are not executed and h_io = h * 1.0001 - what the full text
+// computes for such lanes; when one lane fails, all lanes run the full text as before.  Same values either way: byte-identical frames (tests/test_gpu_err_skip.py against
+// libbhray_errskip0.so; the bound itself: tests/test_err_bound_cpu.py).  SKIP 2 (the counting kernels): the full text always, and three counters - cnt[13] wave-steps, cnt[14]
+// wave-steps whose active lanes all passed, cnt[15] lane-steps that passed with e_max above the threshold (the proof's claim on the device: must be 0) - bhray_get_err_skip.
+__device__ constexpr float ERR_SKIP_C = 3.6e-5f;
+template <bool FAST, int SKIP = 0>
+__device__ __forceinline__ bool next_ray_rk_t(const F3 q0, const F3 p0, F3& pos, F3& dir, float& h_io, float dist, unsigned long long* cnt = nullptr) {
     const F3 d0 = dir;                     // q0 = p0 - bpos (N9), carried by the caller together with dist = flength(q0)
     const F3 cr = fcross(p0, d0);
     const float h2 = fdot(cr, cr);                   // N3: pow(length(v), 2.0) = dot(v, v)
@@ -662,8 +690,40 @@ __device__ __forceinline__ bool next_ray_rk_t(const F3 q0, const F3 p0, F3& pos,
     const F3 K4 = fmadd3(K2, A43, fmadd3(K2, A42, fmadd3(K1, A41, q0))) * sh;
     const F3 K5 = fmadd3(K4, A54, fmadd3(K3, A53, fmadd3(K2, A52, fmadd3(K1, A51, q0)))) * sh;
     const F3 K6 = fmadd3(K5, A65, fmadd3(K4, A64, fmadd3(K3, A63, fmadd3(K2, A62, fmadd3(K1, A61, q0))))) * sh;
+    if constexpr (SKIP == 1) {
+        const float sh2 = sh * sh;
+        const bool calm = __builtin_fmaf(sh2, dist, sh2) <= ERR_SKIP_C;          // NaN: false
+        // the small terms are summed first and added to the unit-length direction once (one rounding at magnitude 1)
+        const F3 ds = fmadd3(K6, BA6, fmadd3(K5, BA5, fmadd3(K4, BA4, fmadd3(K3, BA3, K1 * BA1))));
+        float hn = h * 1.0001f;
+        bool over = false;
+        if (__ballot(!calm) != 0ull) {                                          // a lane the bound does not cover: today's text for every lane of the wave
+            const F3 e = fmadd3(K6, DB6, fmadd3(K5, DB5, fmadd3(K4, DB4, fmadd3(K3, DB3, K1 * DB1))));
+            const float e_max = max3_abs(e.x, e.y, e.z);
+            if constexpr (FAST) over = e_max > 0.00002f;
+            else if (e_max > 0.00002f) hn = h * (0.9f * pow_m001_step(e_max));
+        }
+        pos = fmadd3(d0, h, p0);
+        h_io = hn;
+        if constexpr (FAST) {
+            const F3 v = d0 + ds;
+            const float nn = fdot(v, v);
+            dir = v * rcp_newton(sqrt_corrected(nn));
+            return !rcp_in_range(d5) | !sqrt_in_range(nn) | over;
+        } else {
+            dir = fnormalize_rn(d0 + ds);
+            return false;
+        }
+    } else {
     const F3 e = fmadd3(K6, DB6, fmadd3(K5, DB5, fmadd3(K4, DB4, fmadd3(K3, DB3, K1 * DB1))));
     const float e_max = max3_abs(e.x, e.y, e.z);
+    if constexpr (SKIP == 2) {
+        const float sh2 = sh * sh;
+        const bool calm = __builtin_fmaf(sh2, dist, sh2) <= ERR_SKIP_C;
+        const unsigned long long active = __ballot(true), passed = __ballot(calm);
+        if ((int)(threadIdx.x & 63u) == (int)__builtin_ctzll(active)) { cnt[13]++; if (passed == active) cnt[14]++; }
+        if (calm && e_max > 0.00002f) cnt[15]++;
+    }
     // the small terms are summed first and added to the unit-length direction once (one rounding at magnitude 1)
     const F3 ds = fmadd3(K6, BA6, fmadd3(K5, BA5, fmadd3(K4, BA4, fmadd3(K3, BA3, K1 * BA1))));
     if constexpr (FAST) {
@@ -680,11 +740,13 @@ __device__ __forceinline__ bool next_ray_rk_t(const F3 q0, const F3 p0, F3& pos,
         else h_io = h * 1.0001f;
         return false;
     }
+    }
 }
 __device__ __forceinline__ void next_ray_rk_to(const F3 q0, const F3 p0, F3& pos, F3& dir, float& h_io, float dist) { (void)next_ray_rk_t<false>(q0, p0, pos, dir, h_io, dist); }
-__device__ __forceinline__ void next_ray_rk(F3 q0, F3& pos, F3& dir, float& h_io, float dist) {
+template <int SKIP = 0>
+__device__ __forceinline__ void next_ray_rk(F3 q0, F3& pos, F3& dir, float& h_io, float dist, unsigned long long* cnt = nullptr) {
     const F3 p0 = pos;
-    next_ray_rk_to(q0, p0, pos, dir, h_io, dist);
+    (void)next_ray_rk_t<false, SKIP>(q0, p0, pos, dir, h_io, dist, cnt);
 }
 
 // next_ray_euler, ray.wgsl:467-480 (N7, N9).
@@ -1026,6 +1088,12 @@ enum : int { M_EMPTY = 0, M_REL = 1, M_FLAT = 2, M_FINISH = 3, M_SHADE_REL = 4, 
 #ifndef BHRAY_PNUMER_EARLY
 #define BHRAY_PNUMER_EARLY 1
 #endif
+#ifndef BHRAY_ERR_SKIP
+#define BHRAY_ERR_SKIP 1        // the Cash-Karp step without its error estimate where a bound proves the estimate below the step-size controller's threshold for every active lane of the wave
+                                // (next_ray_rk_t's SKIP: the proof stands there) - bit 0: the dense no-mesh builds (the flagship's: profiles/EXPERIMENTS.md R11.1), bit 1: the latency no-mesh
+                                // builds, bit 2: the mesh builds (bits 1 and 2: built, byte-identical, not measured to win - off).  Any bit set: the counting kernels count how often the bound
+                                // holds (bhray_get_err_skip).  0 (`make errskip0`: libbhray_errskip0.so, what tests/test_gpu_err_skip.py and the A/B of R11.1 compare with): the kernel text before.
+#endif
 #ifndef BHRAY_ORIGIN_KERNEL
 #define BHRAY_ORIGIN_KERNEL 1    // the hole at the scene's origin (all three position words +0) is a property of a kernel BUILD, chosen by the host per launch (trace_kernel's ORIGIN): such a
                                  // build holds only the origin text of the unified pairs (no position - bpos per step, bhray_step_u.inc) and the constant +0 for bpos everywhere, every other
@@ -1155,6 +1223,9 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
     constexpr int REFILL_MIN = (METHOD == 0 && DENSE && !MODELS) ? BHRAY_REFILL_MIN_EULER_DENSE : BHRAY_REFILL_MIN;
     constexpr bool UNIFIED = BHRAY_UNIFIED != 0 && EVAL == 0 && (!MODELS || BHRAY_UNIFIED_MESH != 0) && !COUNT;           // the unified march (bhray_step_u.inc) in the contract kernels that do not count
     constexpr bool ONE_TEST = UNIFIED && !MODELS && (((BHRAY_ONE_TEST & 1) != 0 && !DENSE) || ((BHRAY_ONE_TEST & 2) != 0 && DENSE));
+    // the RK step's error estimate behind a wave-uniform bound (next_ray_rk_t): 0 the full text, 1 skipped where the bound holds, 2 the full text and the bound's counters
+    constexpr int ERR_SKIP = (METHOD != 1 || EVAL != 0 || BHRAY_ERR_SKIP == 0) ? 0 : COUNT ? 2
+                           : (MODELS ? (BHRAY_ERR_SKIP & 4) != 0 : DENSE ? (BHRAY_ERR_SKIP & 1) != 0 : (BHRAY_ERR_SKIP & 2) != 0) ? 1 : 0;
     constexpr bool COLD_LDS = (DENSE && !MODELS) || (MODELS && BHRAY_MESH_COLD_LDS != 0);
     constexpr bool MESH_DENSE = MODELS && DENSE;                                              // the mesh variant's build for a saturated device
     constexpr bool MESH_PARK = MESH_DENSE && !COLD_LDS;   // its traversal in a region of its own (see the flat phase)
@@ -1277,8 +1348,9 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
 #define HIT_GET() (HIT_IN_LDS ? cold.hit() : (bool)hit)
     bool exhausted = false;
     int flat_round = 0;
-    unsigned long long cnt[13];           // [0..9] = bhray_counters' frame counters, [10] wave steps (lane 0), [11] unused (rays adopted by the drain merging of round 2), [12] longest ray
-    if (COUNT) { for (int k = 0; k < 13; k++) cnt[k] = 0; }
+    unsigned long long cnt[16];           // [0..9] = bhray_counters' frame counters, [10] wave steps (lane 0), [11] unused (rays adopted by the drain merging of round 2), [12] longest ray,
+                                          // [13..15] the RK step's error-estimate bound (next_ray_rk_t, SKIP 2): wave-steps, wave-steps whose lanes all pass it, lane-steps that pass it above the threshold
+    if (COUNT) { for (int k = 0; k < 16; k++) cnt[k] = 0; }
 
     for (;;) {
         // ---- refill finished lanes from the queue (wave ballot + prefix popcount)
@@ -1618,6 +1690,13 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
             unsigned long long v = cnt[12];
             for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_down(v, off); v = o > v ? o : v; }
             if (lane == 0 && v) atomicMax(&counters->v[12], v);
+        }
+        if constexpr (ERR_SKIP == 2) {
+            for (int k = 13; k < 16; k++) {
+                unsigned long long v = cnt[k];
+                for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+                if (lane == 0 && v) atomicAdd(&counters->v[k], v);
+            }
         }
     }
     }   // frames of the batch

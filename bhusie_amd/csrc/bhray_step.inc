@@ -36,7 +36,7 @@
                     if (METHOD == 0) {
                         next_ray_euler(qrel, cpos, cdir, H.step_size, dist_c);
                     } else {
-                        next_ray_rk(qrel, rkpos, rkdir, rkh, dist_c);
+                        next_ray_rk<ERR_SKIP>(qrel, rkpos, rkdir, rkh, dist_c, cnt);
                         cpos = rkpos; cdir = rkdir;
                     }
                     qrel = cpos - bpos;
@@ -113,7 +113,7 @@
                     if (METHOD == 0) {
                         next_ray_euler(qrel, cpos, cdir, H.step_size, dist_c);
                     } else {
-                        next_ray_rk(qrel, rkpos, rkdir, rkh, dist_c);
+                        next_ray_rk<ERR_SKIP>(qrel, rkpos, rkdir, rkh, dist_c, cnt);
                         cpos = rkpos; cdir = rkdir;
                     }
                     qrel = cpos - bpos;

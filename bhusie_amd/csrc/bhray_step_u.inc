@@ -44,7 +44,7 @@
                     float cd;
                     if (ONE_TEST) {
                         if (METHOD == 0) redo = next_ray_euler_t<true>(U_QIN, U_PIN, U_POUT, udir, H.step_size, dist_c);
-                        else redo = next_ray_rk_t<true>(U_QIN, U_PIN, U_POUT, udir, rkh, dist_c);
+                        else redo = next_ray_rk_t<true, ERR_SKIP>(U_QIN, U_PIN, U_POUT, udir, rkh, dist_c);
                         if (!BHRAY_U_ORIGIN) qrel = U_POUT - bpos;
                         const float qq = fdot(U_QOUT, U_QOUT);
                         cd = sqrt_corrected(qq);
@@ -52,7 +52,7 @@
                         if (BHRAY_ONE_TEST & 4) redo |= ((((unsigned)it * 2654435761u) ^ (cold.pix() * 40503u)) & 0x1c0u) == 0u;     // (test build: an eighth of the steps)
                     } else {
                         if (METHOD == 0) next_ray_euler_to(U_QIN, U_PIN, U_POUT, udir, H.step_size, dist_c);
-                        else next_ray_rk_to(U_QIN, U_PIN, U_POUT, udir, rkh, dist_c);
+                        else (void)next_ray_rk_t<false, ERR_SKIP>(U_QIN, U_PIN, U_POUT, udir, rkh, dist_c);
                         if (!BHRAY_U_ORIGIN) qrel = U_POUT - bpos;
                         cd = sqrt_rn(fdot(U_QOUT, U_QOUT));                 // N7: the integrator's distance (ray.wgsl:533)
                     }

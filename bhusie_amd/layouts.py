@@ -236,6 +236,7 @@ DIAG_SYMBOLS = {
     "bhray_get_timing": (C.c_int, [vp, P(BhrayTiming)]),
     "bhray_selftest": (C.c_int, [vp, P(C.c_uint64)]),
     "bhray_get_trace_builds": (C.c_int, [vp, P(C.c_uint64)]),
+    "bhray_get_err_skip": (C.c_int, [vp, P(C.c_uint64)]),
     "bhray_read_level": (C.c_int, [vp, u32, vp, sz]),
     "bhray_get_gather_info": (C.c_int, [vp, P(BhrayGatherInfo)]),
     "bhray_get_model_build_info": (C.c_int, [vp, u32, P(BhrayModelBuildInfo)]),

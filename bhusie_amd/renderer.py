@@ -427,6 +427,13 @@ class RayPass:
         check(self._L.bhray_get_trace_builds(self._h, m), self._h, self._L)
         return int(m[0]), int(m[1])
 
+    def err_skip(self):
+        """(RK wave-steps of the last render, those whose active lanes all satisfied the error-estimate bound, lane-steps that satisfied it with an estimate above the
+        step-size threshold - must be 0): bhray_get_err_skip (needs counters=True)"""
+        m = (C.c_uint64 * 3)()
+        check(self._L.bhray_get_err_skip(self._h, m), self._h, self._L)
+        return int(m[0]), int(m[1]), int(m[2])
+
     def timing(self) -> BhrayTiming:
         t = BhrayTiming()
         check(self._L.bhray_get_timing(self._h, C.byref(t)), self._h, self._L)

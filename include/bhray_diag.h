@@ -110,6 +110,13 @@ int bhray_selftest(bhray_ctx* ctx, uint64_t mismatches[3]);    /* [0] = 1/x and 
  * not depend on the build; BHRAY_ORIGIN_KERNEL=0 in the environment at create: never an ORIGIN build.                      */
 int bhray_get_trace_builds(bhray_ctx* ctx, uint64_t launches[2]);
 
+/* The Cash-Karp step skips its error estimate where a bound on it - (dist + 1) * (s*h)^2 <= 3.6e-5, proved above next_ray_rk_t in bhray_kernels.hip - shows every active
+ * lane of the wave below the step-size controller's threshold.  The counting kernels (BHRAY_F_COUNTERS) always form the estimate and count, for the RK
+ * steps of the last render, summed over levels and local partitions: out[0] = wave-steps, out[1] = wave-steps whose active lanes all satisfied the bound (what a
+ * skipping build skips), out[2] = lane-steps that satisfied the bound with an estimate ABOVE the threshold - the proof's claim measured on the device: must be 0.
+ * All 0 for Euler, the literal / fma evaluations and a library built with -DBHRAY_ERR_SKIP=0.                                                                      */
+int bhray_get_err_skip(bhray_ctx* ctx, uint64_t out[3]);       /* needs BHRAY_F_COUNTERS     */
+
 /* Any ladder level, full size level_w×level_h (unrendered pixels are NaN-filled at create).  */
 int bhray_read_level(bhray_ctx* ctx, uint32_t level, float* dst_rgba32f, size_t row_pitch_bytes);
 
