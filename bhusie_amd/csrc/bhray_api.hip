@@ -86,7 +86,7 @@ struct Slot {
     bool used = false;                  // `uploaded` has been recorded at least once
     std::vector<FrameRes> fr;
     uint32_t pending = 0;               // frames staged and not launched yet
-    int method = 0; bool models = false;   // kernel variant of the staged frames (a batch is homogeneous)
+    int method = 0; int models = 0;        // kernel variant of the staged frames (a batch is homogeneous); models: 0 none, 1 in flat space only, 2 lensed (launch_trace)
     uint32_t* d_qctl = nullptr;         // [frames_per_batch][BHRAY_QCTL_WORDS]
     uint32_t launched_frames = 0;       // frames of the batch launched last from this slot (their work counters are valid once it has completed)
     Counters64* d_counters = nullptr;   // [frames_per_batch][BHRAY_MAX_LEVELS]
@@ -142,6 +142,7 @@ struct bhray_dev {
     bhray_black_hole_uniform bh{};
     bhray_details det{};
     bool have_uniforms = false;
+    bool mesh_lensing = false;             // dev_set_mesh_lensing: models are tested on every step inside the relativity sphere too (from the next dev_render)
     std::vector<hipEvent_t> events;        // ring: [BHRAY_TIMING_RING][3 * levels + 4]: per level (before classify, before trace, after trace), 2 around the sky pass, 2 around the temporal mode's prediction + predicted trace
     uint64_t frame_counter = 0, timing_begin = 0;   // timing_begin: first batch not yet reported by dev_get_timing
     uint8_t sky_recorded[BHRAY_TIMING_RING] = {0};
@@ -967,6 +968,15 @@ int dev_set_model_transform(bhray_dev* c, uint32_t mi, const float position[3], 
     return BHRAY_OK;
 }
 
+// Per-frame state like the uniforms: applies from the next dev_render; frames staged for the other kernel variant are launched first, there (a batch is homogeneous).
+int dev_set_mesh_lensing(bhray_dev* c, int32_t on) {
+    if (!c) return BHRAY_E_INVALID;
+    if (on != 0 && (c->cfg.flags & (BHRAY_F_LITERAL | BHRAY_F_EVAL_FMA)))
+        return fail(c, BHRAY_E_STATE, "mesh lensing has no kernel for BHRAY_F_LITERAL / BHRAY_F_EVAL_FMA (no executed shader text to pin one against)");
+    c->mesh_lensing = on != 0;
+    return BHRAY_OK;
+}
+
 int dev_set_uniforms(bhray_dev* c, const void* cam32, const void* bh132, const void* det32) {
     if (!c) return BHRAY_E_INVALID;
     if (!cam32 || !bh132 || !det32) return fail(c, BHRAY_E_INVALID, "null uniform block");
@@ -1393,13 +1403,13 @@ int launch_batch(bhray_dev* c) {
 }
 
 // kernel variant the current uniforms and scene need (same rule as derive_frame: a mesh only when one is usable and visible)
-void frame_variant(const bhray_dev* c, int& method, bool& models) {
+void frame_variant(const bhray_dev* c, int& method, int& models) {
     method = c->det.integration_method != 0 ? 1 : 0;
     int mc = c->det.model_count; if (mc < 0) mc = 0; if (mc > BHRAY_MAX_MODELS) mc = BHRAY_MAX_MODELS;
-    models = false;
+    models = 0;
     for (int i = 0; i < mc; i++) {
         const ModelStore& m = c->models[i];
-        if (m.loaded && m.triangle_count > 0 && m.visible != 0) models = true;
+        if (m.loaded && m.triangle_count > 0 && m.visible != 0) models = c->mesh_lensing ? 2 : 1;
     }
 }
 }  // namespace
@@ -1415,16 +1425,17 @@ int dev_render(bhray_dev* c) {
     HIPCHK(c, hipSetDevice(c->device));
     FrameParams P;
     derive_frame(c, P);
+    const int models = P.model_count > 0 ? (c->mesh_lensing ? 2 : 1) : 0;      // (frame_variant's rule; no usable visible model: the no-mesh kernels, lensing or not)
     {   // a batch runs one kernel variant: launch what is staged if this frame needs another
         Slot& S0 = c->slots[(size_t)(c->batch_counter % c->slots.size())];
-        if (S0.pending > 0 && (S0.method != P.method || S0.models != (P.model_count > 0))) { int rc = launch_batch(c); if (rc) return rc; }
+        if (S0.pending > 0 && (S0.method != P.method || S0.models != models)) { int rc = launch_batch(c); if (rc) return rc; }
     }
     const int si = (int)(c->batch_counter % c->slots.size());
     Slot& S = c->slots[(size_t)si];
     if (S.pending == 0) {
         // the slot's previous argument block must have reached the device before the pinned copy is rewritten
         if (S.used && hipEventQuery(S.uploaded) != hipSuccess) HIPCHK(c, hipEventSynchronize(S.uploaded));
-        S.method = P.method; S.models = P.model_count > 0;
+        S.method = P.method; S.models = models;
     }
     for (hipEvent_t ev : c->waits) HIPCHK(c, hipStreamWaitEvent(S.stream, ev, 0));
     c->waits.clear();
@@ -1742,7 +1753,7 @@ int dev_next_position(bhray_dev* c, int* slot, uint32_t* sub) {
     if (!c || !slot || !sub) return BHRAY_E_INVALID;
     Slot& S0 = c->slots[(size_t)(c->batch_counter % c->slots.size())];
     if (S0.pending > 0) {
-        int method; bool models;
+        int method, models;
         frame_variant(c, method, models);
         if (S0.method != method || S0.models != models) { int rc = launch_batch(c); if (rc) return rc; }
     }
@@ -1751,7 +1762,7 @@ int dev_next_position(bhray_dev* c, int* slot, uint32_t* sub) {
     return BHRAY_OK;
 }
 
-void dev_peek_position(const bhray_dev* c, uint64_t* batch_counter, uint32_t* pending, int* method, bool* models) {
+void dev_peek_position(const bhray_dev* c, uint64_t* batch_counter, uint32_t* pending, int* method, int* models) {
     const Slot& S = c->slots[(size_t)(c->batch_counter % c->slots.size())];
     *batch_counter = c->batch_counter; *pending = S.pending; *method = S.method; *models = S.models;
 }

@@ -62,6 +62,7 @@ int  dev_get_model_build_info(bhray_dev* c, uint32_t model_index, bhray_model_bu
 int  dev_read_model_bvh(bhray_dev* c, uint32_t model_index, bhray_node* nodes, uint32_t node_cap, int32_t* lookup, uint32_t lookup_cap, uint32_t* node_count, uint32_t* triangle_count);
 int  dev_set_model_transform(bhray_dev* c, uint32_t model_index, const float position[3], int32_t visible);
 int  dev_set_uniforms(bhray_dev* c, const void* cam32, const void* bh132, const void* det32);
+int  dev_set_mesh_lensing(bhray_dev* c, int32_t on);       // from the next dev_render; BHRAY_E_STATE for on != 0 on a BHRAY_F_LITERAL / BHRAY_F_EVAL_FMA engine
 // another row partition (bhray_config.partition / stripe_rows / slab_row0 / row_rank / row_world) for the same frame; synchronises the engine
 int  dev_set_partition(bhray_dev* c, uint32_t partition, uint32_t stripe_rows, const uint32_t* slab_row0, uint32_t row_rank, uint32_t row_world);
 int  dev_render(bhray_dev* c);
@@ -104,7 +105,7 @@ int  dev_device(const bhray_dev* c);
 int  dev_next_position(bhray_dev* c, int* slot, uint32_t* sub);
 // The same state read without side effects: batches launched so far (the staging slot is that number modulo the slots), frames staged
 // in that slot and the kernel variant they were staged for.  For the caller's mirror of the staging position (issue threads).
-void dev_peek_position(const bhray_dev* c, uint64_t* batch_counter, uint32_t* pending, int* method, bool* models);
+void dev_peek_position(const bhray_dev* c, uint64_t* batch_counter, uint32_t* pending, int* method, int* models);   // models: 0 none, 1 flat space only, 2 lensed
 // True when launches were enqueued since the last call; reports the slot and the number of frames of the (last) launched batch.
 bool dev_take_launched(bhray_dev* c, int* slot, uint32_t* frames);
 int* dev_err_flag(bhray_dev* c);                              // the engine's device-side error word (checked by dev_sync)

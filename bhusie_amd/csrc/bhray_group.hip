@@ -249,6 +249,7 @@ struct GroupSlot {                 // per batch slot (same index as the devices'
 struct RenderCmd {
     uint8_t cam[32], bh[132], det[32];
     float mpos[BHRAY_MAX_MODELS][3]; int32_t mvis[BHRAY_MAX_MODELS]; bool mset[BHRAY_MAX_MODELS];
+    int32_t lensing;                       // bhray_set_mesh_lensing as of this frame
     int si; uint32_t sub;                  // where the caller's mirror of the staging position says this frame goes
     float4* bound;                         // bhray_bind_output (root only)
     uint64_t serial;                       // 1-based frame number
@@ -276,8 +277,9 @@ struct bhray_ctx {
     int async_rc = 0;
     // the caller's mirror of the engines' staging position (the engines themselves are only touched by their issue thread)
     bool mirror_stale = true;
-    uint64_t st_counter = 0; uint32_t st_pending = 0; int st_method = 0; bool st_models = false;
+    uint64_t st_counter = 0; uint32_t st_pending = 0; int st_method = 0; int st_models = 0;
     uint8_t u_cam[32] = {0}, u_bh[132] = {0}, u_det[32] = {0}; bool have_uniforms = false;
+    bool mesh_lensing = false;             // bhray_set_mesh_lensing (part of the kernel variant: ctx_variant)
     float m_pos[BHRAY_MAX_MODELS][3] = {{0}}; int32_t m_vis[BHRAY_MAX_MODELS] = {0}; bool m_dirty[BHRAY_MAX_MODELS] = {false}, m_usable[BHRAY_MAX_MODELS] = {false};
     bool single = true;                    // one partition, no gather: every call goes straight to parts[0].dev
     bool gather = false;
@@ -768,6 +770,7 @@ int worker_render(bhray_ctx* c, const CommRank* cr, const RenderCmd& cmd) {
     for (Part& p : c->parts) {
         if (!p.dev || p.rank != cr->rank) continue;
         DEV(c, p.dev, dev_set_uniforms(p.dev, cmd.cam, cmd.bh, cmd.det));
+        DEV(c, p.dev, dev_set_mesh_lensing(p.dev, cmd.lensing));
         for (uint32_t mi = 0; mi < BHRAY_MAX_MODELS; mi++) if (cmd.mset[mi]) DEV(c, p.dev, dev_set_model_transform(p.dev, mi, cmd.mpos[mi], cmd.mvis[mi]));
         int s; uint32_t k;
         DEV(c, p.dev, dev_next_position(p.dev, &s, &k));
@@ -871,12 +874,12 @@ void track_hole_row(bhray_ctx* c, const void* cam32, const void* bh132) {
 }
 
 // kernel variant of the frame the current uniforms describe (the rule of the engines: bhray_api.hip frame_variant)
-void ctx_variant(const bhray_ctx* c, int& method, bool& models) {
+void ctx_variant(const bhray_ctx* c, int& method, int& models) {
     bhray_details d; memcpy(&d, c->u_det, sizeof d);
     method = d.integration_method != 0 ? 1 : 0;
     int mc = d.model_count; if (mc < 0) mc = 0; if (mc > BHRAY_MAX_MODELS) mc = BHRAY_MAX_MODELS;
-    models = false;
-    for (int i = 0; i < mc; i++) if (c->m_usable[i] && c->m_vis[i] != 0) models = true;
+    models = 0;
+    for (int i = 0; i < mc; i++) if (c->m_usable[i] && c->m_vis[i] != 0) models = c->mesh_lensing ? 2 : 1;
 }
 
 }  // namespace
@@ -1500,6 +1503,16 @@ int bhray_set_materials(bhray_ctx* c, const void* bytes, size_t size) {
     if (!bytes || size != 16u * BHRAY_MAX_MATERIALS) return gfail(c, BHRAY_E_INVALID, "materials must be %u bytes (MaterialUniform x %d)", 16u * BHRAY_MAX_MATERIALS, BHRAY_MAX_MATERIALS);
     return BHRAY_OK;                      // bound at binding 3, never read by the shader (ray.wgsl:8)
 }
+// Lensed meshes: part of what decides the kernel variant (ctx_variant), so every engine gets it - with issue threads it travels with the next frame.
+int bhray_set_mesh_lensing(bhray_ctx* c, int32_t on) {
+    if (!c) return BHRAY_E_INVALID;
+    if (on != 0 && (c->cfg.flags & (BHRAY_F_LITERAL | BHRAY_F_EVAL_FMA)))
+        return gfail(c, BHRAY_E_STATE, "mesh lensing has no kernel for BHRAY_F_LITERAL / BHRAY_F_EVAL_FMA (no executed shader text to pin one against)");
+    c->mesh_lensing = on != 0;
+    if (c->threaded) return BHRAY_OK;
+    for (Part& p : c->parts) if (p.dev) DEV(c, p.dev, dev_set_mesh_lensing(p.dev, on));
+    return BHRAY_OK;
+}
 int bhray_set_uniforms(bhray_ctx* c, const void* cam32, const void* bh132, const void* det32) {
     if (!c) return BHRAY_E_INVALID;
     if (c->gather && cam32 && bh132) track_hole_row(c, cam32, bh132);
@@ -1532,19 +1545,20 @@ int bhray_render(bhray_ctx* c) {
         if (c->mirror_stale) {       // the threads are idle (every call but this one waits for them): read the staging position back
             for (Part& p : c->parts) {
                 if (!p.dev) continue;
-                int m; bool md;
+                int m, md;
                 dev_peek_position(p.dev, &c->st_counter, &c->st_pending, &m, &md);
                 c->st_method = m; c->st_models = md;
                 break;
             }
             c->mirror_stale = false;
         }
-        int method; bool models;
+        int method, models;
         ctx_variant(c, method, models);
         if (c->st_pending > 0 && (method != c->st_method || models != c->st_models)) { c->st_counter++; c->st_pending = 0; }   // the engines launch the staged frames first
         if (c->st_pending == 0) { c->st_method = method; c->st_models = models; }
         RenderCmd cmd;
         memcpy(cmd.cam, c->u_cam, 32); memcpy(cmd.bh, c->u_bh, 132); memcpy(cmd.det, c->u_det, 32);
+        cmd.lensing = c->mesh_lensing ? 1 : 0;
         for (uint32_t mi = 0; mi < BHRAY_MAX_MODELS; mi++) { memcpy(cmd.mpos[mi], c->m_pos[mi], 12); cmd.mvis[mi] = c->m_vis[mi]; cmd.mset[mi] = c->m_dirty[mi]; c->m_dirty[mi] = false; }
         cmd.si = (int)(c->st_counter % c->nslots); cmd.sub = c->st_pending;
         cmd.bound = c->bound; c->bound = nullptr;

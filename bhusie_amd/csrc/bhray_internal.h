@@ -138,10 +138,12 @@ struct FrameLaunch {
 // launchers (bhray_kernels.hip); Pb / Fb are device arrays of nb entries
 hipError_t launch_classify(const FrameParams* Pb, const FrameLaunch* Fb, int nb, int blocks, bool count, bool fixup, hipStream_t s);
 // origin: every frame of the batch has the hole at +0, +0, +0 - the ORIGIN build of the variant where it has one (trace_origin_build), the general build otherwise
-hipError_t launch_trace(const FrameParams* Pb, const FrameLaunch* Fb, int nb, int method, bool models, bool count, bool dense, int eval, bool origin, int* err_flag,
+// models / has_models: 0 no usable visible model (the no-mesh kernels), 1 models tested in flat space only (the shader's behaviour), 2 also on every step inside the
+// relativity sphere (bhray_set_mesh_lensing: the lensed-mesh kernels)
+hipError_t launch_trace(const FrameParams* Pb, const FrameLaunch* Fb, int nb, int method, int models, bool count, bool dense, int eval, bool origin, int* err_flag,
                         int grid_blocks, hipStream_t s);
 int trace_blocks_per_cu(int method, int has_models, int count, int dense, int eval, int origin);   // eval: 0 contract, 1 BHRAY_F_LITERAL, 2 BHRAY_F_EVAL_FMA
-bool trace_origin_build(int method, bool models, bool count, bool dense, int eval);   // does a launch of this variant with `origin` set get an ORIGIN build?
+bool trace_origin_build(int method, int models, bool count, bool dense, int eval);   // does a launch of this variant with `origin` set get an ORIGIN build?
 // copies n16 16-byte words from pinned host memory to device memory with a kernel (stays on the compute queue: a DMA copy
 // between the launches of a stream costs a cross-engine handshake each time)
 // and zeroes `nzero` 32-bit words at `zero` (the queue control words of the batch) in the same launch

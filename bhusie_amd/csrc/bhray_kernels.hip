@@ -1044,8 +1044,36 @@ __global__ __launch_bounds__(BHRAY_CLASSIFY_THREADS) void classify_kernel(const 
 // trace: ray.wgsl:269-285 + 482-596
 // ------------------------------------------------------------------------------------------
 enum : int { M_EMPTY = 0, M_REL = 1, M_FLAT = 2, M_FINISH = 3, M_SHADE_REL = 4, M_SHADE_FLAT = 5 };   // M_SHADE_x: a disk hit waits for its shading, then continues in mode x
+// Lensed meshes (bhray_set_mesh_lensing; trace_kernel's LENSED): inside the relativity sphere every step's segment - the previous position with the new
+// direction, range (t_min, seg) - is tested against the models as well (ray.wgsl:541 with render_triangles = true).  A lane whose segment may touch a model pauses in a
+// NEGATIVE mode - no test of the other phases (mode == M_x, mode >= M_SHADE_REL, mode != M_EMPTY keeps the wave alive) sees it as theirs - that records what the step's
+// black-hole test found and where the ray goes on:  mode = -(1 + flat + 2 * kind),  flat: the step left the sphere (M_FLAT next, else M_REL),  kind: 0 nothing, 1 the
+// horizon, 2 the disk (the black hole's t in the cold state's pend_t for 1 and 2).  ppos / pdir stay what the step left them - the segment's ray.
+__device__ __forceinline__ int lens_pause_mode(bool flat, int kind) { return -(1 + (flat ? 1 : 0) + 2 * kind); }
+__device__ __forceinline__ bool lens_mode_flat(int mode) { return ((-mode - 1) & 1) != 0; }
+__device__ __forceinline__ int lens_mode_kind(int mode) { return (-mode - 1) >> 1; }
+// Can the traversal of model Md for the segment (pos, dir, (t_min, seg)) test a triangle at all?  false only by the flat phase's root-box argument with seg in place of t_max:
+// the root is an inner node (root_cull), every 1/dir is finite, and hit_aabb of the union of the root's two child boxes exceeds seg - then both children's own hit_aabb
+// exceed seg = closest.t (the slab test is monotone in the box for finite 1/dir; a miss is 1e8), the first visit pops with nothing pending and the traversal ends.
+// The operations are hit_aabb's own on the traversal's own operands (rcp_rn(x) == 1.0f / x on every input): nothing is estimated, so rounding has no say.
+__device__ __forceinline__ bool lens_model_reachable(const ModelDev& Md, F3 pos, F3 inv, bool finite, float seg) {
+    if (Md.root_cull == 0 || !finite) return true;
+    const float d0 = hit_aabb(pos, inv, make_float4(Md.root_lo[0], Md.root_lo[1], Md.root_lo[2], 0.0f),
+                              make_float4(Md.root_hi[0], Md.root_hi[1], Md.root_hi[2], 0.0f), ld3(Md.pos));
+    return !(d0 > seg);
+}
+__device__ __forceinline__ bool lens_near_mesh(const FrameParams& P, F3 pos, F3 dir, float seg) {
+    const F3 inv = f3(rcp_rn(dir.x), rcp_rn(dir.y), rcp_rn(dir.z));
+    const bool finite = fabsf(inv.x) < INFINITY && fabsf(inv.y) < INFINITY && fabsf(inv.z) < INFINITY;
+    bool near = false;
+    for (int mi = 0; mi < P.model_count; mi++) {
+        const ModelDev& Md = P.models[mi];
+        if (Md.visible != 0 && lens_model_reachable(Md, pos, inv, finite, seg)) near = true;
+    }
+    return near;
+}
 #ifndef BHRAY_THIN_WAVES
-#define BHRAY_THIN_WAVES 1024    // latency build: a short queue is dealt out evenly over this many waves (MI355X: 256 CUs x 4 SIMDs); 0 = off
+#define BHRAY_THIN_WAVES 1024   // latency build: a short queue is dealt out evenly over this many waves (MI355X: 256 CUs x 4 SIMDs); 0 = off
 #endif
 #ifndef BHRAY_REL_BATCH
 #define BHRAY_REL_BATCH 16       // integrator steps between refill / flat / epilogue phases
@@ -1205,7 +1233,7 @@ namespace bhray {
 #ifndef BHRAY_TRACE_KERNEL_ATTR
 #define BHRAY_TRACE_KERNEL_ATTR      // (experiments: e.g. __attribute__((amdgpu_num_sgpr(88))))
 #endif
-template <int METHOD, bool MODELS, bool COUNT, bool DENSE, int EVAL = 0, bool ORIGIN = false>
+template <int METHOD, bool MODELS, bool COUNT, bool DENSE, int EVAL = 0, bool ORIGIN = false, bool LENSED = false>
 __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS ? (DENSE ? BHRAY_TRACE_WAVES_MESH_DENSE : BHRAY_TRACE_WAVES_MESH) : (DENSE ? BHRAY_TRACE_WAVES_DENSE : BHRAY_TRACE_WAVES)) void trace_kernel(const FrameParams* __restrict__ Pb, const FrameLaunch* __restrict__ Fb, const int nb, int* __restrict__ err_flag) {
     const int lane = threadIdx.x & 63;
     int err = 0;
@@ -1221,7 +1249,8 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
 #endif
     constexpr int REL_BATCH = (METHOD == 0 && DENSE && !MODELS) ? BHRAY_REL_BATCH_EULER_DENSE : BHRAY_REL_BATCH;
     constexpr int REFILL_MIN = (METHOD == 0 && DENSE && !MODELS) ? BHRAY_REFILL_MIN_EULER_DENSE : BHRAY_REFILL_MIN;
-    constexpr bool UNIFIED = BHRAY_UNIFIED != 0 && EVAL == 0 && (!MODELS || BHRAY_UNIFIED_MESH != 0) && !COUNT;           // the unified march (bhray_step_u.inc) in the contract kernels that do not count
+    static_assert(!LENSED || (MODELS && !DENSE && EVAL == 0 && !ORIGIN), "the lensed-mesh kernels: mesh variant, latency build, the contract's evaluation, general hole position");
+    constexpr bool UNIFIED = BHRAY_UNIFIED != 0 && EVAL == 0 && (!MODELS || BHRAY_UNIFIED_MESH != 0) && !COUNT && !LENSED;           // the unified march (bhray_step_u.inc) in the contract kernels that do not count (the lensed-mesh kernels: the general step, whose ppos / pdir a paused lane keeps)
     constexpr bool ONE_TEST = UNIFIED && !MODELS && (((BHRAY_ONE_TEST & 1) != 0 && !DENSE) || ((BHRAY_ONE_TEST & 2) != 0 && DENSE));
     // the RK step's error estimate behind a wave-uniform bound (next_ray_rk_t): 0 the full text, 1 skipped where the bound holds, 2 the full text and the bound's counters
     constexpr int ERR_SKIP = (METHOD != 1 || EVAL != 0 || BHRAY_ERR_SKIP == 0) ? 0 : COUNT ? 2
@@ -1348,6 +1377,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
 #define HIT_GET() (HIT_IN_LDS ? cold.hit() : (bool)hit)
     bool exhausted = false;
     int flat_round = 0;
+    [[maybe_unused]] int lens_round = 0;      // (lensed-mesh kernels) rounds since the lens phase ran
     unsigned long long cnt[16];           // [0..9] = bhray_counters' frame counters, [10] wave steps (lane 0), [11] unused (rays adopted by the drain merging of round 2), [12] longest ray,
                                           // [13..15] the RK step's error-estimate bound (next_ray_rk_t, SKIP 2): wave-steps, wave-steps whose lanes all pass it, lane-steps that pass it above the threshold
     if (COUNT) { for (int k = 0; k < 16; k++) cnt[k] = 0; }
@@ -1423,6 +1453,58 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
 #include "bhray_march.inc"
         }
 #endif
+        // ---- lensed meshes: the models of hit_ray (ray.wgsl:376-389) for the lanes whose step paused on a segment that may touch one (bhray_step.inc).
+        // Batched like the flat phase - a traversal is executed by the whole wave for the lanes that need it: the phase runs when enough lanes wait, when nobody
+        // is integrating, or every BHRAY_FLAT_DEFER-th round at the latest.  EVERY paused lane leaves its pause mode here, whatever the traversals find: to the
+        // epilogue (a mesh or the horizon won: opacity 1), to the shade phase below (the disk won) or back to M_REL / M_FLAT.  Each ray still sees its own
+        // iterations in order, and a paused lane's state is touched by no other phase (their tests are on the non-negative modes): results do not depend on when it runs.
+        if constexpr (LENSED) {
+            const unsigned long long ml = __ballot(mode < 0);
+            lens_round++;
+            if (ml != 0ull && (__popcll(ml) >= BHRAY_FLAT_MIN_LANES || !__any(mode == M_REL) || lens_round >= BHRAY_FLAT_DEFER)) {
+                lens_round = 0;
+                if (mode < 0) {
+                    it--;                                                       // the step text counted the paused step (bhray_step.inc); from here on as a disk hit's pause: counted when the ray goes on
+                    const float seg = METHOD == 0 ? H.step_size : rkh;          // the paused step's segment length: rkh changes only in a step
+                    const int kind = lens_mode_kind(mode);
+                    const bool flat = lens_mode_flat(mode);
+                    // closest_render_state after the black hole (ray.wgsl:367-374): its t where it hit (always < seg), else t_max = seg
+                    Hit rs; rs.hit = kind != 0; rs.t = kind != 0 ? cold.pend_t() : seg; rs.color = f3(0.0f, 0.0f, 0.0f); rs.opacity = kind != 0 ? 1.0f : 0.0f;
+                    bool mesh_won = false;
+                    const F3 inv = f3(rcp_rn(pdir.x), rcp_rn(pdir.y), rcp_rn(pdir.z));
+                    const bool finite = fabsf(inv.x) < INFINITY && fabsf(inv.y) < INFINITY && fabsf(inv.z) < INFINITY;
+                    for (int mi = 0; mi < P.model_count; mi++) {
+                        if (P.models[mi].visible != 0) {
+                            Hit r; F3 nrm;
+                            r.hit = false;
+                            // every model with the full range (t_min, seg): no model's hit (nor the black hole's) bounds another's traversal
+                            if (lens_model_reachable(P.models[mi], ppos, inv, finite, seg)) trace_ray_model<COUNT, BVH_WW>(P.models[mi], bvh_lds, ppos, pdir, t_min, seg, r, nrm, cnt, &err);
+                            else if (COUNT) cnt[6]++;                             // counted as the visit it replaces (as in the flat phase)
+                            if (r.hit && r.t < rs.t) {                            // strictly nearer; on a tie the earlier candidate stays
+                                rs = r; mesh_won = true;
+                                const F3 light = normalize(f3(0.2f, 0.2f, -1.0f));
+                                rs.color = rs.color * dot(nrm, light);
+                            }
+                        }
+                    }
+                    if (!mesh_won && kind == 2) {
+                        mode = flat ? M_SHADE_FLAT : M_SHADE_REL;                 // the disk stays the nearest: shaded below (pend_t is its t)
+                    } else {
+                        mode = flat ? M_FLAT : M_REL;
+                        if (rs.hit) {                                             // a mesh, or the horizon (colour 0): ray.wgsl:571-576
+                            cpos = cpos + pdir * rs.t;
+                            cpos_dist = fdistance(cpos, bpos);
+                            if (METHOD == 0) { dist_c = cpos_dist; qrel = cpos - bpos; }
+                            const F3 cc = f3(clamp_(rs.color.x, 0.0f, 1.0f), clamp_(rs.color.y, 0.0f, 1.0f), clamp_(rs.color.z, 0.0f, 1.0f));
+                            cold.set_color(cold.color() + cc * (amount * rs.opacity));
+                            amount *= 1.0f - rs.opacity;
+                            HIT_SET(1);
+                        }
+                        if (amount < 0.005f) mode = M_FINISH; else it++;
+                    }
+                }
+            }
+        }
         // ---- deferred disk shading (ray.wgsl:612-663 and the hit bookkeeping of 537-552) for lanes that paused on a disk hit
         if (__any(mode >= M_SHADE_REL)) {
             if (mode >= M_SHADE_REL) {
@@ -1892,8 +1974,8 @@ hipError_t launch_classify(const FrameParams* Pb, const FrameLaunch* Fb, int nb,
     return hipGetLastError();
 }
 
-// Which builds of trace_kernel<METHOD, MODELS, COUNT, DENSE, EVAL, ORIGIN> exist (12 x 2 integrators general builds + 2 x 2 ORIGIN builds = 36 instantiations; 32 in round 9, 48 in round 5,
-// 72 in round 3).
+// Which builds of trace_kernel<METHOD, MODELS, COUNT, DENSE, EVAL, ORIGIN, LENSED> exist (12 x 2 integrators general builds + 2 x 2 ORIGIN builds + 2 x 2 lensed-mesh builds - trace_lensed_ptr -
+// = 40 instantiations; 36 in round 11, 32 in round 9, 48 in round 5, 72 in round 3).
 // eval: 0 the numerics contract, 1 BHRAY_F_LITERAL, 2 BHRAY_F_EVAL_FMA.  Every variant has a build for lone launches (the latency build);
 // the build for a saturated device (dense) exists where throughput is reported: not for counting kernels (BHRAY_F_COUNTERS is a diagnosis
 // mode: the same counts whichever build marches) and, of the two measurement-only evaluations, not for the mesh variant.  A launch that
@@ -1926,7 +2008,16 @@ template <int METHOD, int EVAL>
 static const void* trace_kernel_ptr_me(bool models, bool count, bool dense, bool origin) {
     return origin ? trace_kernel_ptr_meo<METHOD, EVAL, true>(models, count, dense) : trace_kernel_ptr_meo<METHOD, EVAL, false>(models, count, dense);
 }
-static const void* trace_kernel_ptr(int method, bool models, bool count, bool dense, int eval, bool origin) {
+// The lensed-mesh kernels (trace_kernel's LENSED; `models` == 2): the contract's evaluation, both integrators, the latency build, counting or not - four instantiations.  A request
+// for the dense build or the ORIGIN build gets these (the same pixels, as with every build that does not exist); another evaluation has no lensed kernel and is refused at
+// bhray_set_mesh_lensing - asked for here all the same it gets the variant that tests models in flat space only.
+static const void* trace_lensed_ptr(int method, bool count) {
+    if (method == 0) return count ? (const void*)trace_kernel<0, true, true, false, 0, false, true> : (const void*)trace_kernel<0, true, false, false, 0, false, true>;
+    return count ? (const void*)trace_kernel<1, true, true, false, 0, false, true> : (const void*)trace_kernel<1, true, false, false, 0, false, true>;
+}
+static const void* trace_kernel_ptr(int method, int models_mode, bool count, bool dense, int eval, bool origin) {
+    if (models_mode == 2 && eval == 0) return trace_lensed_ptr(method, count);       // (dense, origin: no such builds)
+    const bool models = models_mode != 0;
     if (method == 0) {
         if (eval == 1) return trace_kernel_ptr_me<0, 1>(models, count, dense, origin);
         if (eval == 2) return trace_kernel_ptr_me<0, 2>(models, count, dense, origin);
@@ -1939,24 +2030,26 @@ static const void* trace_kernel_ptr(int method, bool models, bool count, bool de
 static size_t trace_dyn_lds(bool models) { return models ? (size_t)BHRAY_BVH_LDS_STACK * BHRAY_TRACE_THREADS * 8 : 0; }   // trace_ray_model's traversal ring
 
 // `origin`: every frame of the batch has the hole at +0, +0, +0 (the host's test of the uniform words: bhray_api.hip) - the ORIGIN build where the variant has one
-bool trace_origin_build(int method, bool models, bool count, bool dense, int eval) {
+bool trace_origin_build(int method, int models_mode, bool count, bool dense, int eval) {
     (void)method;
+    if (models_mode == 2 && eval == 0) return false;
+    const bool models = models_mode != 0;
     if (!trace_variant_exists(eval, models, dense, count)) dense = false;
     return trace_origin_variant_exists(eval, models, dense, count);
 }
 
-hipError_t launch_trace(const FrameParams* Pb, const FrameLaunch* Fb, int nb, int method, bool models, bool count, bool dense, int eval, bool origin, int* err_flag,
+hipError_t launch_trace(const FrameParams* Pb, const FrameLaunch* Fb, int nb, int method, int models, bool count, bool dense, int eval, bool origin, int* err_flag,
                         int grid_blocks, hipStream_t s) {
     if (nb <= 0) return hipSuccess;
     (void)hipGetLastError();
     void* args[] = {(void*)&Pb, (void*)&Fb, (void*)&nb, (void*)&err_flag};
     return hipLaunchKernel(trace_kernel_ptr(method, models, count, dense, eval, origin), dim3((grid_blocks * 256 + BHRAY_TRACE_THREADS - 1) / BHRAY_TRACE_THREADS),
-                           dim3(BHRAY_TRACE_THREADS), args, trace_dyn_lds(models), s);
+                           dim3(BHRAY_TRACE_THREADS), args, trace_dyn_lds(models != 0), s);
 }
 
 int trace_blocks_per_cu(int method, int has_models, int count, int dense, int eval, int origin) {
     int n = 0;
-    const void* f = trace_kernel_ptr(method, has_models != 0, count != 0, dense != 0, eval, origin != 0);
+    const void* f = trace_kernel_ptr(method, has_models, count != 0, dense != 0, eval, origin != 0);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, BHRAY_TRACE_THREADS, trace_dyn_lds(has_models != 0)) != hipSuccess || n < 1) n = 2;
     n = n * BHRAY_TRACE_THREADS / 256;            // in units of 256 threads (the grid is sized in those)
     return n < 1 ? 1 : n;

@@ -51,8 +51,10 @@
                     const float seg = METHOD == 0 ? H.step_size : rkh;
                     bool near_horizon, near_disk;
                     black_hole_culls<MODELS>(H, ppos, ppos_dist, seg, near_horizon, near_disk);
+                    bool near_mesh = false;                          // lensed-mesh kernels only: may the segment touch a model? (lens_near_mesh)
+                    if constexpr (LENSED) near_mesh = lens_near_mesh(P, ppos, pdir, seg);
                     it++;                                          // the plain march; the rare paths that do not count the step take it back
-                    if (near_horizon || near_disk || cd > H.R) {
+                    if (near_horizon || near_disk || cd > H.R || near_mesh) {
                     Hit crs; float td;
                     const bool disk = hit_black_hole_geom(H, ppos, pdir, near_horizon, near_disk, t_min, seg, crs, td);
                     if (cd > H.R) {
@@ -63,14 +65,25 @@
                         const float m = lin * lin;
                         cdir = mix3(cdir, cold.rdir(), m);
                     }
-                    if (disk) {
+                    // Lensed meshes: hit_ray's models come after its black hole (ray.wgsl:369-389).  The lane pauses with ppos / pdir / seg (the uniform step, or rkh) and what
+                    // the black hole's test found intact - none of the arms below is its own - and the lens phase traverses the models and merges in hit_ray's order
+                    // (trace_kernel).  Both forms of this text count the step for such a lane (`it`); the lens phase takes that back first.
+                    bool lens_paused = false;
+                    if constexpr (LENSED) {
+                        if (near_mesh) {
+                            cold.set_pend_t(disk ? td : crs.t);
+                            mode = lens_pause_mode(mode == M_FLAT, disk ? 2 : (crs.hit ? 1 : 0));
+                            lens_paused = true;
+                        }
+                    }
+                    if (disk && !lens_paused) {
                         // The shading of a disk hit (~700 instructions, needed by 1-5 lanes of a stepping wave) is deferred to the
                         // shade phase: the lane pauses with ppos / pdir / td intact and resumes in the mode it has now.
                         cold.set_pend_t(td);
                         mode = (mode == M_FLAT) ? M_SHADE_FLAT : M_SHADE_REL;
                         it--;                                    // the shade phase counts this step when the ray goes on
                     } else {
-                    if (crs.hit) {                               // horizon: colour 0, opacity 1
+                    if (crs.hit && !lens_paused) {               // horizon: colour 0, opacity 1
                         cpos = cpos + pdir * crs.t;
                         cpos_dist = fdistance(cpos, bpos);
                         if (METHOD == 0) { dist_c = cpos_dist; qrel = cpos - bpos; }
@@ -128,7 +141,9 @@
                     const float seg = METHOD == 0 ? H.step_size : rkh;
                     bool near_horizon, near_disk;
                     black_hole_culls<MODELS>(H, ppos, ppos_dist, seg, near_horizon, near_disk);
-                    if (near_horizon || near_disk || cd > H.R) {
+                    bool near_mesh = false;                          // lensed-mesh kernels only: may the segment touch a model? (lens_near_mesh)
+                    if constexpr (LENSED) near_mesh = lens_near_mesh(P, ppos, pdir, seg);
+                    if (near_horizon || near_disk || cd > H.R || near_mesh) {
                     Hit crs; float td;
                     const bool disk = hit_black_hole_geom(H, ppos, pdir, near_horizon, near_disk, t_min, seg, crs, td);
                     if (cd > H.R) {
@@ -139,14 +154,25 @@
                         const float m = lin * lin;
                         cdir = mix3(cdir, cold.rdir(), m);
                     }
-                    if (disk) {
+                    // Lensed meshes: hit_ray's models come after its black hole (ray.wgsl:369-389).  The lane pauses with ppos / pdir / seg (the uniform step, or rkh) and what
+                    // the black hole's test found intact - none of the arms below is its own - and the lens phase traverses the models and merges in hit_ray's order
+                    // (trace_kernel).  Both forms of this text count the step for such a lane (`it`); the lens phase takes that back first.
+                    bool lens_paused = false;
+                    if constexpr (LENSED) {
+                        if (near_mesh) {
+                            cold.set_pend_t(disk ? td : crs.t);
+                            mode = lens_pause_mode(mode == M_FLAT, disk ? 2 : (crs.hit ? 1 : 0));
+                            lens_paused = true;
+                        }
+                    }
+                    if (disk && !lens_paused) {
                         // The shading of a disk hit (~700 instructions, needed by 1-5 lanes of a stepping wave) is deferred to the
                         // shade phase: the lane pauses with ppos / pdir / td intact and resumes in the mode it has now.
                         cold.set_pend_t(td);
                         mode = (mode == M_FLAT) ? M_SHADE_FLAT : M_SHADE_REL;
                         continue;
                     }
-                    if (crs.hit) {                               // horizon: colour 0, opacity 1
+                    if (crs.hit && !lens_paused) {               // horizon: colour 0, opacity 1
                         cpos = cpos + pdir * crs.t;
                         cpos_dist = fdistance(cpos, bpos);
                         if (METHOD == 0) { dist_c = cpos_dist; qrel = cpos - bpos; }

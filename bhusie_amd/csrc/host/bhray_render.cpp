@@ -1,7 +1,8 @@
 // bhray_render — minimal C++ host program over renderer.hpp: renders one frame of the reference's default scene
 // (camera (0,0,-19), hole at the origin, disk 2..10, R = 20; camera.rs:10-16, blackhole.rs:16-28) and writes the HDR frame
 // as raw little-endian f32 RGBA (row 0 = top).  Usage:
-//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--devices 0,1,2,...]
+//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--lensed-mesh] [--devices 0,1,2,...]
+// --lensed-mesh: the meshes are tested on every step inside the relativity sphere too (bhray_set_mesh_lensing): a mesh inside the sphere is visible.
 // --bvh device: every mesh's tree is built on the GPU (bhray_upload_model_build) instead of by the reference's host builder (the default).
 // --obj: repeatable; the i-th mesh goes to model slot i (Renderer::add_model), at the position its OBJ loader gives it.
 // --devices: row-tile the frame over several GPUs from this one process (RCCL gather to the first one, inside libbhray).
@@ -136,9 +137,9 @@ int main(int argc, char** argv) {
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
         return 0;
     }
-    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--devices 0,1,...]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--lensed-mesh] [--devices 0,1,...]\n", argv[0]); return 2; }
     uint32_t bw = 72, bh = 41, levels = 4, disk = 256;
-    bool rk = false, bvh_device = false;
+    bool rk = false, bvh_device = false, lensed = false;
     std::vector<const char*> objs;
     std::vector<int> devices;
     for (int i = 2; i < argc; i++) {
@@ -148,6 +149,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--disk-size") && i + 1 < argc) disk = (uint32_t)std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--obj") && i + 1 < argc) objs.push_back(argv[++i]);
         else if (!std::strcmp(argv[i], "--bvh") && i + 1 < argc && (!std::strcmp(argv[i + 1], "device") || !std::strcmp(argv[i + 1], "reference"))) bvh_device = !std::strcmp(argv[++i], "device");
+        else if (!std::strcmp(argv[i], "--lensed-mesh")) lensed = true;
         else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) { for (const char* p = argv[++i]; *p; ) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p) p++; } }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
@@ -163,6 +165,7 @@ int main(int argc, char** argv) {
         std::vector<bhusie::Model> models;
         for (const char* obj : objs) { models.emplace_back(obj); r.add_model(models.back(), bvh_device); }
         r.ray_details.integration_method = rk ? 1 : 0;
+        r.mesh_lensing = lensed;
         r.render(0.0f);
         const std::vector<float> out = r.ray_pipeline().output();
         auto res = r.ray_pipeline().resolution();

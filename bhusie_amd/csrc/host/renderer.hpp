@@ -162,6 +162,7 @@ public:
         check(bhray_update_model_vertices(ctx_, index, points, point_count, normals, normal_count), ctx_);
     }
     void set_model_transform(uint32_t index, const float position[3], int32_t visible) { check(bhray_set_model_transform(ctx_, index, position, visible), ctx_); }
+    void set_mesh_lensing(bool on) { check(bhray_set_mesh_lensing(ctx_, on ? 1 : 0), ctx_); }   // lensed meshes: from the next pass on
     void set_materials(const void* material_uniforms_128) { check(bhray_set_materials(ctx_, material_uniforms_128, 128), ctx_); }   // mod.rs:389 (ignored by the shader)
     void set_uniforms(const bhray_camera_uniform& c, const bhray_black_hole_uniform& b, const bhray_details& d) { check(bhray_set_uniforms(ctx_, &c, &b, &d), ctx_); }
     void pass() { check(bhray_render(ctx_), ctx_); }                                            // ray_pipeline.rs:301-309
@@ -193,6 +194,7 @@ public:
     Camera camera;
     BlackHole black_hole;
     RayDetails ray_details;
+    bool mesh_lensing = false;      // lensed meshes (bhray_set_mesh_lensing): models are tested inside the relativity sphere too; applied before each render
     explicit Renderer(int device = 0) : ray_pipeline_({72, 41}, 3, 4, device) {}               // mod.rs:177-179
     Renderer(std::pair<uint32_t, uint32_t> base, uint32_t multiplier, uint32_t levels, int device = 0) : ray_pipeline_(base, multiplier, levels, device) {}
     Renderer(std::pair<uint32_t, uint32_t> base, uint32_t multiplier, uint32_t levels, const std::vector<int>& devices) : ray_pipeline_(base, multiplier, levels, devices) {}
@@ -217,6 +219,7 @@ public:
         ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);        // mod.rs:386-388
         const float materials[32] = {0};
         ray_pipeline_.set_materials(materials);                                                 // mod.rs:389
+        apply_lensing();
         ray_pipeline_.pass();
     }
     // the same frame through the drop-in shim: update + pass_handoff (mod.rs:378-417), then finish() where the sky pass would start
@@ -225,12 +228,15 @@ public:
         ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);
         const float materials[32] = {0};
         ray_pipeline_.set_materials(materials);
+        apply_lensing();
         ray_pipeline_.pass_handoff();
         return ray_pipeline_.finish();
     }
 private:
+    void apply_lensing() { if (mesh_lensing != lensing_applied_) { ray_pipeline_.set_mesh_lensing(mesh_lensing); lensing_applied_ = mesh_lensing; } }
     RayPipeline ray_pipeline_;
     uint32_t models_ = 0;
+    bool lensing_applied_ = false;  // what the ctx was last told (its default: off)
 };
 
 }  // namespace bhusie

@@ -181,6 +181,7 @@ SYMBOLS = {
     "bhray_update_model_vertices": (C.c_int, [vp, u32, vp, i32, vp, i32]),
     "bhray_set_model_transform": (C.c_int, [vp, u32, P(C.c_float), i32]),
     "bhray_set_uniforms": (C.c_int, [vp, vp, vp, vp]),
+    "bhray_set_mesh_lensing": (C.c_int, [vp, i32]),
     "bhray_render": (C.c_int, [vp]),
     "bhray_flush": (C.c_int, [vp]),
     "bhray_sync": (C.c_int, [vp]),

@@ -268,6 +268,11 @@ class RayPass:
     def set_model_transform(self, position, visible=1, index=0):
         check(self._L.bhray_set_model_transform(self._h, index, (C.c_float * 3)(*[float(x) for x in position]), int(visible)), self._h, self._L)
 
+    def set_mesh_lensing(self, on):
+        """Lensed meshes (bhray_set_mesh_lensing): from the next render on, models are also tested on every integrator step inside the
+        relativity sphere.  Off by default; BhrayError (BHRAY_E_STATE) for on on a literal / eval_fma ctx."""
+        check(self._L.bhray_set_mesh_lensing(self._h, 1 if on else 0), self._h, self._L)
+
     # -- per frame
     def set_uniforms(self, camera: bytes, black_hole: bytes, details: bytes):
         assert len(camera) == 32 and len(black_hole) == 132 and len(details) == 32
@@ -479,6 +484,8 @@ class Renderer:
         self.ray_details = RayDetails()                      # mod.rs:116-121
         self.ray_pass = RayPass(cfg if cfg is not None else ladder_from_base((72, 41), 3, 4), device=device, **kw)
         self.models: list[Model] = []                        # scene.models: slot i of the ctx holds models[i]
+        self.mesh_lensing = False                            # lensed meshes (RayPass.set_mesh_lensing): applied before each render
+        self._lensing_applied = False                        # what the ctx was last told (its default: off)
 
     @property
     def model(self) -> Model | None:
@@ -512,6 +519,9 @@ class Renderer:
     def render(self, dt: float = 0.0):
         self.ray_details.time += dt                          # mod.rs:382
         self.ray_pass.set_uniforms(self.camera.uniform(), self.black_hole.uniform(), self.ray_details.uniform())
+        if bool(self.mesh_lensing) != self._lensing_applied:
+            self.ray_pass.set_mesh_lensing(self.mesh_lensing)
+            self._lensing_applied = bool(self.mesh_lensing)
         self.ray_pass.render()
 
     def read_hdr(self):

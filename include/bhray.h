@@ -391,6 +391,17 @@ int bhray_set_materials(bhray_ctx* ctx, const void* material_uniforms_128, size_
 int bhray_set_uniforms(bhray_ctx* ctx, const void* camera_uniform_32,
                        const void* black_hole_uniform_132, const void* ray_details_32);
 
+/* Lensed meshes (not in the reference, whose shader tests models in flat space only: ray.wgsl:541 passes
+ * render_triangles = false).  on != 0: every integrator step inside the relativity sphere also tests its segment - the
+ * previous position with the new direction, range (1e-8, step length) - against models 0 .. model_count-1 in
+ * hit_ray's order, so a model inside the sphere is visible and one behind the hole shows its lensed image.  Per-frame
+ * state like bhray_set_uniforms: applies from the next bhray_render, default off; frames staged for the other setting
+ * are launched first (a batch runs one kernel variant).  Off, and on with no usable visible model, every frame keeps
+ * the bits it has without this call.  BHRAY_E_STATE for on != 0 on a ctx created with BHRAY_F_LITERAL or
+ * BHRAY_F_EVAL_FMA (no executed shader text exists to pin such a kernel against).  With one process per GPU every
+ * rank calls it alike.  bhray_rebalance's wave-step measure does not see the traversal work of lensed frames.       */
+int bhray_set_mesh_lensing(bhray_ctx* ctx, int32_t on);
+
 /* Dispatch — replaces `for rp in ray_pipelines { rp.pass() }` (mod.rs:415-417,
  * ray_pipeline.rs:301-309).  Asynchronous on the ctx stream; levels ordered.                 */
 int bhray_render(bhray_ctx* ctx);
