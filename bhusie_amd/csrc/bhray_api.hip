@@ -95,7 +95,13 @@ struct Slot {
     size_t args_cap = 0;
     uint64_t batch_id = 0;              // batch_counter value of the batch this slot holds
     uint2* post_scratch = nullptr;      // display pass: bloom levels + tone-mapped image (allocated on first use; the frames of a slot run in stream order)
+    // trace grids by queue length (launch_batch): [frames_per_batch][BHRAY_LEVEL_GRID_LAUNCHES] words in pinned memory, written by the trace launches (FrameLaunch::qlen):
+    // the rays the queue of that slot position and ladder launch held the last time it ran; QLEN_NONE: nothing reported
+    uint32_t* h_qlen = nullptr;
+    int qlen_method = -1, qlen_models = -1;             // the kernel variant the words were reported by (another variant: they are reset)
+    bhray_level_grid_info grids{};                      // the batch launched last from this slot (dev_get_level_grids; the totals are the ctx's)
 };
+constexpr uint32_t QLEN_NONE = 0xFFFFFFFFu;
 
 struct ModelStore {
     float pos[3] = {0, 0, 0};
@@ -169,6 +175,9 @@ struct bhray_dev {
     int dense_override = -1;               // BHRAY_TRACE_DENSE=0/1 (tuning experiments only)
     int coarse_build = -1;                 // BHRAY_COARSE_BUILD=0/1 (experiment): the build of the trace launches below the ladder's last level (-1: the batch's build)
     int origin_kernel = 1;                 // BHRAY_ORIGIN_KERNEL=0: never the ORIGIN builds of the trace kernels (the A/B of EXPERIMENTS R10.1; the same pixels)
+    // BHRAY_LEVEL_GRID / _GEN / _MARGIN / _FLOOR: dense ladder trace launches get a grid sized by the rays their queues held last time (bhray_trace_grid_for)
+    int level_grid = 1; uint32_t level_grid_gen = 256, level_grid_margin = 25, level_grid_floor = 64;
+    uint64_t grid_launches = 0, grid_blocks = 0, grid_ceiling_launches = 0;   // ladder trace launches enqueued, their blocks, those with the ctx's grid (dev_get_level_grids)
     uint64_t origin_launches = 0, general_launches = 0;      // trace launches enqueued with an ORIGIN build / with any other (dev_get_trace_builds)
     bool rendered = false;
     // asynchronous hand-off (dev_read_hdr_async)
@@ -394,6 +403,7 @@ void dev_destroy(bhray_dev* c) {
         if (S.d_qctl) (void)hipFree(S.d_qctl);
         if (S.d_counters) (void)hipFree(S.d_counters);
         if (S.h_args) (void)hipHostFree(S.h_args);
+        if (S.h_qlen) (void)hipHostFree(S.h_qlen);
         if (S.d_args) (void)hipFree(S.d_args);
         if (S.done) (void)hipEventDestroy(S.done);
         if (S.uploaded) (void)hipEventDestroy(S.uploaded);
@@ -592,6 +602,10 @@ int dev_create(const bhray_config* cfg, const bhray::DevOptions& opt, bhray_dev*
     if (const char* e = getenv("BHRAY_COARSE_BUILD")) c->coarse_build = atoi(e);
     if (const char* e = getenv("BHRAY_ORIGIN_KERNEL")) c->origin_kernel = atoi(e) != 0;
     if (const char* e = getenv("BHRAY_DYNAMIC_DENSE")) c->dynamic_dense = atoi(e);
+    if (const char* e = getenv("BHRAY_LEVEL_GRID")) c->level_grid = atoi(e) != 0;
+    if (const char* e = getenv("BHRAY_LEVEL_GRID_GEN")) { const int v = atoi(e); if (v > 0) c->level_grid_gen = (uint32_t)v; }
+    if (const char* e = getenv("BHRAY_LEVEL_GRID_MARGIN")) { const int v = atoi(e); if (v >= 0) c->level_grid_margin = (uint32_t)v; }
+    if (const char* e = getenv("BHRAY_LEVEL_GRID_FLOOR")) { const int v = atoi(e); if (v >= 0) c->level_grid_floor = (uint32_t)v; }
     const uint32_t nslots = cfg->frames_in_flight ? cfg->frames_in_flight : 4;
     c->cfg.frames_in_flight = nslots;
     c->slots.resize(nslots);
@@ -626,6 +640,8 @@ int dev_create(const bhray_config* cfg, const bhray::DevOptions& opt, bhray_dev*
         S.args_cap = (B * (sizeof(FrameParams) + nlaunch * sizeof(FrameLaunch) + 16) + 15) & ~(size_t)15;
         CHK(hipHostMalloc((void**)&S.h_args, S.args_cap, hipHostMallocDefault));
         CHK(hipMalloc(&S.d_args, S.args_cap));
+        CHK(hipHostMalloc((void**)&S.h_qlen, B * BHRAY_LEVEL_GRID_LAUNCHES * sizeof(uint32_t), hipHostMallocDefault));
+        for (size_t i = 0; i < B * BHRAY_LEVEL_GRID_LAUNCHES; i++) S.h_qlen[i] = QLEN_NONE;
         S.fr.resize(B);
         for (size_t k = 0; k < B; k++) {
             FrameRes& R = S.fr[k];
@@ -1006,6 +1022,7 @@ int dev_set_partition(bhray_dev* c, uint32_t partition, uint32_t stripe_rows, co
     HIPCHK(c, sync_all(c));
     c->cfg = n;
     for (Slot& S : c->slots) S.launched_frames = 0;           // the work the slots' frames counted belongs to the rows this engine had then (dev_get_work)
+    for (Slot& S : c->slots) for (size_t i = 0; i < (size_t)c->batch * BHRAY_LEVEL_GRID_LAUNCHES; i++) S.h_qlen[i] = QLEN_NONE;   // ... and so do the queue lengths their launches reported
     { int rc = build_row_tables(c); if (rc) return rc; }
     return ensure_frame_buffers(c, true);
 }
@@ -1015,7 +1032,7 @@ int dev_set_partition(bhray_dev* c, uint32_t partition, uint32_t stripe_rows, co
 // launch, in the slot's pinned staging) and the launch sequence, one method per ladder mode; launch_batch enqueues it.
 // ------------------------------------------------------------------------------------------
 namespace {
-struct Launch { int kind; const FrameLaunch* d; int blocks; bool count; std::vector<int> ev_before, ev_after; int build = -1; bool fixup = false; int levels = 1; FrameLaunch* h = nullptr; };   // kind 0 classify, 1 trace; timing events recorded around it; build: -1 the ctx's trace build, 0 latency, 1 dense
+struct Launch { int kind; const FrameLaunch* d; int blocks; bool count; std::vector<int> ev_before, ev_after; int build = -1; bool fixup = false; int levels = 1; FrameLaunch* h = nullptr; int fb = -1; };   // fb: a ladder trace launch's id in bhray_level_grid_info (launch_batch sizes its grid by queue length); kind 0 classify, 1 trace; timing events recorded around it; build: -1 the ctx's trace build, 0 latency, 1 dense
 
 struct BatchPlan {
     bhray_dev* c;
@@ -1094,6 +1111,7 @@ struct BatchPlan {
                 h[k].queue = R.spec_queue; h[k].qctl = R.d_qctl; h[k].counters = count ? R.d_counters : nullptr;
             }
             seq.push_back({1, d, grid, count, {}, {2}});
+            seq.back().fb = 0;
             if (ns < nl) seq.back().build = c->coarse_build;
         }
         for (uint32_t l = 1; l < ns; l++) {
@@ -1163,6 +1181,7 @@ struct BatchPlan {
             // (its prediction, its fix-up classification) waiting until it has drained, and two batches then run one after the other
             // (rank 3 of an 8-way 1080p partition, 20-frame blocks of a moving sequence: 0.0995 -> 0.0736 ms per frame, EXPERIMENTS R4.12)
             seq.push_back({1, d, shared_device ? grid : c->num_cus * trace_blocks_per_cu(S.method, S.models, count, 1, literal, origin), count, {}, {(int)(3 * nl + 3)}, 1});
+            seq.back().fb = 0;
         }
         for (uint32_t l = 0; l < nl; l++) {
             FrameLaunch* h; const FrameLaunch* d; next_launch(h, d);
@@ -1177,6 +1196,7 @@ struct BatchPlan {
             }
             seq.push_back({0, d, classify_blocks(l), count, {(int)(3 * l)}, {(int)(3 * l + 1)}, -1, true});
             seq.push_back({1, d, shared_device ? grid : c->num_cus * trace_blocks_per_cu(S.method, S.models, count, 0, literal, origin), count, {}, {(int)(3 * l + 2)}, 0});
+            seq.back().fb = 1 + (int)l;
         }
         first_normal = nl;
         return BHRAY_OK;
@@ -1194,6 +1214,7 @@ struct BatchPlan {
             }
             seq.push_back({0, d, classify_blocks(l), count, {(int)(3 * l)}, {(int)(3 * l + 1)}});
             seq.push_back({1, d, grid, count, {}, {(int)(3 * l + 2)}});
+            seq.back().fb = 1 + (int)l;
             if (l + 1 < nl) seq.back().build = c->coarse_build;
         }
         return BHRAY_OK;
@@ -1236,6 +1257,7 @@ struct BatchPlan {
                 h[k].queue = R.super_queue; h[k].qctl = R.d_qctl + 2 * u0; h[k].counters = count ? R.d_counters + u0 : nullptr;
             }
             seq.push_back({1, d, grid, count, {}, {(int)(3 * u0 + 2)}});
+            seq.back().fb = BHRAY_MAX_LEVELS + 1;
         }
         for (uint32_t l = u0; l < nl; l++) {
             FrameLaunch* h; const FrameLaunch* d; next_launch(h, d);
@@ -1372,6 +1394,47 @@ int launch_batch(bhray_dev* c) {
         if (c->wave_prio >= 0 ? c->wave_prio != 0 : (nb == 1 && c->slots.size() <= 1)) for (uint32_t k = 0; k < nb; k++) hl[k].probe_empty |= 32;
         const int quad_wps = c->quad_wps >= 0 ? c->quad_wps : ((nb == 1 && c->slots.size() <= 2) ? (S.method == 0 ? 1 : 2) : 0);
         for (uint32_t k = 0; k < nb; k++) hl[k].probe_empty |= (quad_wps & 7) << 2;
+    }
+    // Trace grids by queue length.  Every ladder trace launch reports the rays its queues held (FrameLaunch::qlen -> S.h_qlen, one word per slot
+    // position and launch); the next batch staged here gives the same launch enough blocks for that many rays plus a margin instead of the ctx's grid: a launch of the
+    // coarse levels finds a few hundred waves' worth of rays, and every further wave of a full grid takes a wave slot, loads its arguments and fails an atomic on the
+    // queue head only to leave.  Launches that RUN a dense build only (trace_dense_build: a lensed-mesh launch, or a mesh launch of the literal / fma evaluations, asks for
+    // one and gets the latency build, which sizes its thin shares, strided dealing and quad march from gridDim), not the temporal mode's
+    // launches (their own rule, R4.10 / R4.12), not a counting ctx.  A word read here was written by the previous batch of this slot if that has run its trace launches
+    // already, by the one before it otherwise (dev_render waited for the previous batch's upload, which follows the older batch's kernels in the stream): either is
+    // an estimate, and a wrong estimate costs time only - persistent waves pull until the queues are exhausted, whatever the grid.  For the same reason the reset on
+    // a change of kernel variant below is best effort: the slot's previous batch, of the old variant, may still be in flight and report behind it.
+    {
+        const bool report = !count && !temporal;
+        if (S.qlen_method != S.method || S.qlen_models != S.models) {
+            for (size_t i = 0; i < (size_t)B * BHRAY_LEVEL_GRID_LAUNCHES; i++) S.h_qlen[i] = QLEN_NONE;
+            S.qlen_method = S.method; S.qlen_models = S.models;
+        }
+        bhray_level_grid_info& G = S.grids;
+        memset(&G, 0, sizeof G);
+        for (int i = 0; i < BHRAY_LEVEL_GRID_LAUNCHES; i++) G.expected_rays[i] = BHRAY_LEVEL_GRID_NO_FEEDBACK;
+        G.enabled = (report && c->level_grid) ? 1u : 0u; G.frames = nb; G.ctx_grid = (uint32_t)grid; G.dense = trace_dense_build(S.method, S.models, count, dense, literal) ? 1u : 0u;
+        for (Launch& Ln : seq) {
+            if (Ln.kind != 1 || Ln.fb < 0) continue;
+            const bool ln_dense = trace_dense_build(S.method, S.models, Ln.count, Ln.build < 0 ? dense : Ln.build != 0, literal);    // the build launch_trace will run
+            const int unsized = Ln.blocks;
+            uint64_t expected = BHRAY_LEVEL_GRID_NO_FEEDBACK;
+            if (report) {
+                FrameLaunch* fl = (FrameLaunch*)(S.h_args + ((const uint8_t*)Ln.d - S.d_args));
+                uint64_t sum = 0; bool all = true;
+                for (uint32_t k = 0; k < nb; k++) {
+                    uint32_t* w = S.h_qlen + (size_t)k * BHRAY_LEVEL_GRID_LAUNCHES + (size_t)Ln.fb;
+                    const uint32_t v = __atomic_load_n(w, __ATOMIC_RELAXED);
+                    if (v == QLEN_NONE) all = false; else sum += v;
+                    fl[k].qlen = w;
+                }
+                if (all && c->level_grid && ln_dense) expected = sum;
+            }
+            if (expected != BHRAY_LEVEL_GRID_NO_FEEDBACK)
+                Ln.blocks = (int)bhray_trace_grid_for(expected, nb, (uint32_t)Ln.blocks, c->level_grid_gen, c->level_grid_margin, c->level_grid_floor);
+            G.expected_rays[Ln.fb] = expected; G.blocks[Ln.fb] = (uint32_t)Ln.blocks;
+            c->grid_launches++; c->grid_blocks += (uint64_t)Ln.blocks; if (Ln.blocks >= unsized) c->grid_ceiling_launches++;
+        }
     }
     S.launched_frames = nb;
     // enqueue
@@ -1799,6 +1862,18 @@ int dev_signal_stream(bhray_dev* c, void* s) {
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = launch_batch(c); if (rc) return rc; }
     HIPCHK(c, hipStreamWaitEvent((hipStream_t)s, c->slots[(size_t)c->last_slot].done, 0));
+    return BHRAY_OK;
+}
+
+int dev_get_level_grids(bhray_dev* c, uint32_t slot, bhray_level_grid_info* out) {
+    if (!c || !out) return BHRAY_E_INVALID;
+    if (slot >= c->slots.size()) return fail(c, BHRAY_E_INVALID, "slot %u of %zu", slot, c->slots.size());
+    *out = c->slots[slot].grids;
+    if (out->frames == 0) {                              // nothing launched from this slot yet
+        for (int i = 0; i < BHRAY_LEVEL_GRID_LAUNCHES; i++) out->expected_rays[i] = BHRAY_LEVEL_GRID_NO_FEEDBACK;
+        out->enabled = (c->level_grid && !(c->cfg.flags & (BHRAY_F_COUNTERS | BHRAY_F_TEMPORAL))) ? 1u : 0u;
+    }
+    out->total_launches = c->grid_launches; out->total_blocks = c->grid_blocks; out->total_ceiling_launches = c->grid_ceiling_launches;
     return BHRAY_OK;
 }
 

@@ -90,6 +90,7 @@ int  dev_next_stream(bhray_dev* c, void** s);
 int  dev_signal_stream(bhray_dev* c, void* s);
 int  dev_selftest(bhray_dev* c, uint64_t mismatches[3]);
 int  dev_get_trace_builds(bhray_dev* c, uint64_t launches[2]);   // trace launches enqueued so far with an ORIGIN build / with any other
+int  dev_get_level_grids(bhray_dev* c, uint32_t slot, bhray_level_grid_info* out);   // trace grids by queue length: the batch `slot` launched last, and this engine's totals
 int  dev_get_level_counters(bhray_dev* c, uint32_t level, bhray_counters* out);
 int  dev_add_row_work(bhray_dev* c, uint32_t level, uint64_t* acc, uint32_t n);   // acc[y] += iterations of the last render's rays of level row y
 int  dev_get_counters(bhray_dev* c, bhray_counters* out);

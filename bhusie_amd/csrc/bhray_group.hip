@@ -2071,6 +2071,23 @@ int bhray_get_trace_builds(bhray_ctx* c, uint64_t launches[2]) {
     return BHRAY_OK;
 }
 
+int bhray_get_level_grids(bhray_ctx* c, uint32_t slot, bhray_level_grid_info* out) {
+    if (!c || !out) return BHRAY_E_INVALID;
+    ENTER(c);
+    bool first = true;
+    uint64_t sum[3] = {0, 0, 0};
+    for (Part& p : c->parts) {
+        if (!p.dev) continue;
+        bhray_level_grid_info t;
+        DEV(c, p.dev, dev_get_level_grids(p.dev, slot, &t));
+        sum[0] += t.total_launches; sum[1] += t.total_blocks; sum[2] += t.total_ceiling_launches;
+        if (first) { *out = t; first = false; }
+    }
+    if (first) return BHRAY_E_STATE;
+    out->total_launches = sum[0]; out->total_blocks = sum[1]; out->total_ceiling_launches = sum[2];
+    return BHRAY_OK;
+}
+
 int bhray_get_err_skip(bhray_ctx* c, uint64_t out[3]) {
     if (!c || !out) return BHRAY_E_INVALID;
     ENTER(c);

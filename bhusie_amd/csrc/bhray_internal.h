@@ -124,6 +124,8 @@ struct FrameLaunch {
     unsigned long long* work; // trace, entry 0 of a launch: work[blockIdx & (BHRAY_WORK_WORDS - 1)] += integrator steps this wave ISSUED for the frames of the batch
                               // (a step costs the wave the same whether 1 or 64 of its lanes march): what the batch's rays cost this GPU, whatever else shares
                               // it - the measure bhray_rebalance balances.  Counted in whole batches of BHRAY_REL_BATCH steps.
+    uint32_t* qlen;           // trace: *qlen = qctl[0], the rays this frame's queue held for this launch, in pinned host memory: what the host sizes the NEXT launch of this
+                              // slot position and ladder launch from (bhray_trace_grid_for; launch_batch).  One plain store by block 0; nullptr: not reported
 };
 #define BHRAY_WORK_WORDS 16      // counters per frame (the waves of a launch spread over them: one word would serialise 2 048 atomics at every launch's end)
 #define BHRAY_QCTL_WORDS (2 * BHRAY_MAX_LEVELS + 2 * BHRAY_WORK_WORDS)   // 32-bit words of a frame's control block: queue counts / heads, then the work counters (64-bit)
@@ -143,6 +145,7 @@ hipError_t launch_classify(const FrameParams* Pb, const FrameLaunch* Fb, int nb,
 hipError_t launch_trace(const FrameParams* Pb, const FrameLaunch* Fb, int nb, int method, int models, bool count, bool dense, int eval, bool origin, int* err_flag,
                         int grid_blocks, hipStream_t s);
 int trace_blocks_per_cu(int method, int has_models, int count, int dense, int eval, int origin);   // eval: 0 contract, 1 BHRAY_F_LITERAL, 2 BHRAY_F_EVAL_FMA
+bool trace_dense_build(int method, int models, bool count, bool dense, int eval);    // does a launch of this variant that asks for the dense build get one? (no: the latency build of the same variant)
 bool trace_origin_build(int method, int models, bool count, bool dense, int eval);   // does a launch of this variant with `origin` set get an ORIGIN build?
 // copies n16 16-byte words from pinned host memory to device memory with a kernel (stays on the compute queue: a DMA copy
 // between the launches of a stream costs a cross-engine handshake each time)

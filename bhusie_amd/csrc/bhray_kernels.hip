@@ -1244,6 +1244,12 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
 #ifndef BHRAY_NO_SPAN
     if (Fb[0].span && threadIdx.x == 0) atomicMax(&Fb[0].span[0], ~(unsigned long long)wall_clock64());
 #endif
+    // The queue lengths of this launch, one per frame of the batch, to the host (FrameLaunch::qlen, pinned memory): lane k of block 0 reports frame k (nb <= 32).
+    // They are final here - the classify launch that filled the queues precedes this one in its stream - and nothing on the device reads them back.
+    if (!COUNT && blockIdx.x == 0 && threadIdx.x < (unsigned)nb) {             // (a counting ctx's launches are not sized: its kernels stay as they were)
+        const FrameLaunch& Fk = Fb[threadIdx.x];
+        if (Fk.qlen) *Fk.qlen = Fk.qctl[0];
+    }
 #ifdef BHRAY_WAVE_LOG
     const unsigned long long wl_t0 = wall_clock64();
 #endif
@@ -2036,6 +2042,14 @@ bool trace_origin_build(int method, int models_mode, bool count, bool dense, int
     const bool models = models_mode != 0;
     if (!trace_variant_exists(eval, models, dense, count)) dense = false;
     return trace_origin_variant_exists(eval, models, dense, count);
+}
+
+// `dense`: the dense build is asked for - and is it what trace_kernel_ptr hands out?  Not for the lensed-mesh kernels, a counting launch, or the mesh variant under
+// BHRAY_F_LITERAL / BHRAY_F_EVAL_FMA: those get the latency build, whose thin shares are sized from gridDim (the host sizes only real dense builds by queue length).
+bool trace_dense_build(int method, int models_mode, bool count, bool dense, int eval) {
+    (void)method;
+    if (models_mode == 2 && eval == 0) return false;
+    return dense && trace_variant_exists(eval, models_mode != 0, true, count);
 }
 
 hipError_t launch_trace(const FrameParams* Pb, const FrameLaunch* Fb, int nb, int method, int models, bool count, bool dense, int eval, bool origin, int* err_flag,

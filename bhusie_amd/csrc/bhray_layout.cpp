@@ -71,3 +71,24 @@ OFF(bhray_config, comm_id, 12 + 8 * BHRAY_MAX_LEVELS + 52 + 4 * BHRAY_MAX_DEVICE
 OFF(bhray_config, partition, 12 + 8 * BHRAY_MAX_LEVELS + 52 + 4 * BHRAY_MAX_DEVICES + 8 + BHRAY_COMM_ID_BYTES);
 OFF(bhray_config, slab_row0, 12 + 8 * BHRAY_MAX_LEVELS + 52 + 4 * BHRAY_MAX_DEVICES + 8 + BHRAY_COMM_ID_BYTES + 4);
 SZ(bhray_config, 12 + 8 * BHRAY_MAX_LEVELS + 52 + 4 * BHRAY_MAX_DEVICES + 8 + BHRAY_COMM_ID_BYTES + 4 + 4 * (BHRAY_MAX_DEVICES + 1));
+SZ(bhray_level_grid_info, 12 * BHRAY_LEVEL_GRID_LAUNCHES + 24 + 16);
+OFF(bhray_level_grid_info, total_launches, 8 * BHRAY_LEVEL_GRID_LAUNCHES); OFF(bhray_level_grid_info, blocks, 8 * BHRAY_LEVEL_GRID_LAUNCHES + 24);
+OFF(bhray_level_grid_info, enabled, 12 * BHRAY_LEVEL_GRID_LAUNCHES + 24);
+
+// The persistent grid of one ladder trace launch from the rays its queues held the last time (bhray_diag.h): enough blocks to hold the expected rays
+// plus a margin in `rays_per_block_generation` rays per block, at least one block per frame of the batch (blockIdx % frames picks a block's own frame) and at least
+// `floor_blocks`, never more than the ctx's grid.  Scheduling only: the waves of a trace launch are persistent and pull until every queue of the batch is exhausted,
+// so an estimate that is too small - a scene cut - costs that launch time and no pixel; the floor bounds how much.  Pure host arithmetic, in 64 bits: the sum of 32 frames'
+// 32-bit queue lengths is below 2^37, the margin is capped at 1000 %, so nothing overflows.
+extern "C" uint32_t bhray_trace_grid_for(uint64_t expected_rays, uint32_t frames_in_batch, uint32_t ctx_grid, uint32_t rays_per_block_generation,
+                                         uint32_t margin_percent, uint32_t floor_blocks) {
+    if (expected_rays == BHRAY_LEVEL_GRID_NO_FEEDBACK || rays_per_block_generation == 0) return ctx_grid;    // nothing to size from: the ctx's grid
+    if (expected_rays > ((uint64_t)1 << 40)) return ctx_grid;                                                  // (no sum of 32-bit queue lengths gets here)
+    if (margin_percent > 1000u) margin_percent = 1000u;
+    const uint64_t with_margin = (expected_rays * (100ull + (uint64_t)margin_percent) + 99ull) / 100ull;
+    uint64_t blocks = (with_margin + rays_per_block_generation - 1) / rays_per_block_generation;
+    const uint64_t lo = frames_in_batch > floor_blocks ? frames_in_batch : floor_blocks;
+    if (blocks < lo) blocks = lo;
+    if (blocks > ctx_grid) blocks = ctx_grid;                                                                  // the ceiling wins: no launch gets a larger grid than before
+    return (uint32_t)blocks;
+}

@@ -137,6 +137,27 @@ class BhrayModelBuildInfo(C.Structure):
 assert C.sizeof(BhrayDetails) == 32 and C.sizeof(BhrayCameraUniform) == 32 and C.sizeof(BhrayBlackHoleUniform) == 132
 assert C.sizeof(BhrayNode) == 32 and C.sizeof(BhrayTriangle) == 24
 
+LEVEL_GRID_LAUNCHES = MAX_LEVELS + 2
+LEVEL_GRID_NO_FEEDBACK = 2 ** 64 - 1
+
+
+class BhrayLevelGridInfo(C.Structure):
+    """bhray_level_grid_info (include/bhray_diag.h): trace grids sized by queue length.  Launch ids: 0 the speculative levels' merged launch, 1 + l level l,
+    MAX_LEVELS + 1 the superset launch."""
+    _fields_ = [("expected_rays", C.c_uint64 * LEVEL_GRID_LAUNCHES), ("total_launches", C.c_uint64), ("total_blocks", C.c_uint64), ("total_ceiling_launches", C.c_uint64),
+                ("blocks", C.c_uint32 * LEVEL_GRID_LAUNCHES), ("enabled", C.c_uint32), ("frames", C.c_uint32), ("ctx_grid", C.c_uint32), ("dense", C.c_uint32)]
+
+    def as_dict(self):
+        """launches: {id: (blocks, expected rays or None)} of the trace launches the batch had"""
+        return {"enabled": bool(self.enabled), "frames": int(self.frames), "ctx_grid": int(self.ctx_grid), "dense": bool(self.dense),
+                "launches": {i: (int(self.blocks[i]), None if int(self.expected_rays[i]) == LEVEL_GRID_NO_FEEDBACK else int(self.expected_rays[i]))
+                             for i in range(LEVEL_GRID_LAUNCHES) if int(self.blocks[i])},
+                "total_launches": int(self.total_launches), "total_blocks": int(self.total_blocks), "total_ceiling_launches": int(self.total_ceiling_launches)}
+
+
+assert C.sizeof(BhrayLevelGridInfo) == 12 * LEVEL_GRID_LAUNCHES + 40
+
+
 class BhrayRebalanceInfo(C.Structure):
     """bhray_rebalance_info (include/bhray.h)"""
     _fields_ = [("partitions", C.c_uint32), ("applied", C.c_uint32), ("slab_row0", C.c_uint32 * 17), ("part_cost", C.c_float * 16), ("extra_cost", C.c_float * 16),
@@ -238,6 +259,8 @@ DIAG_SYMBOLS = {
     "bhray_selftest": (C.c_int, [vp, P(C.c_uint64)]),
     "bhray_get_trace_builds": (C.c_int, [vp, P(C.c_uint64)]),
     "bhray_get_err_skip": (C.c_int, [vp, P(C.c_uint64)]),
+    "bhray_trace_grid_for": (u32, [C.c_uint64, u32, u32, u32, u32, u32]),
+    "bhray_get_level_grids": (C.c_int, [vp, u32, P(BhrayLevelGridInfo)]),
     "bhray_read_level": (C.c_int, [vp, u32, vp, sz]),
     "bhray_get_gather_info": (C.c_int, [vp, P(BhrayGatherInfo)]),
     "bhray_get_model_build_info": (C.c_int, [vp, u32, P(BhrayModelBuildInfo)]),

@@ -432,6 +432,14 @@ class RayPass:
         check(self._L.bhray_get_trace_builds(self._h, m), self._h, self._L)
         return int(m[0]), int(m[1])
 
+    def level_grids(self, slot: int = 0) -> dict:
+        """Trace grids sized by queue length (bhray_get_level_grids): for the batch frame slot `slot` launched last, the blocks each ladder trace launch got and the
+        rays it was sized from (None: not sized - it got `ctx_grid`); and the ctx's totals of ladder trace launches, their blocks, and launches at the ceiling."""
+        from .layouts import BhrayLevelGridInfo
+        g = BhrayLevelGridInfo()
+        check(self._L.bhray_get_level_grids(self._h, slot, C.byref(g)), self._h, self._L)
+        return g.as_dict()
+
     def err_skip(self):
         """(RK wave-steps of the last render, those whose active lanes all satisfied the error-estimate bound, lane-steps that satisfied it with an estimate above the
         step-size threshold - must be 0): bhray_get_err_skip (needs counters=True)"""

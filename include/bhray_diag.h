@@ -110,6 +110,33 @@ int bhray_selftest(bhray_ctx* ctx, uint64_t mismatches[3]);    /* [0] = 1/x and 
  * not depend on the build; BHRAY_ORIGIN_KERNEL=0 in the environment at create: never an ORIGIN build.                      */
 int bhray_get_trace_builds(bhray_ctx* ctx, uint64_t launches[2]);
 
+/* Trace grids sized by queue length.  Every dense-build trace launch of the ladder - the speculative levels' merged launch, each plain level, the
+ * superset launch - reports the rays its queues held to the host, and the next batch staged at the same slot sizes that launch's persistent grid from it:
+ *   blocks = ceil(expected_rays * (100 + margin_percent) / 100 / rays_per_block_generation), clamped to [max(frames_in_batch, floor_blocks), ctx_grid].
+ * expected_rays = BHRAY_LEVEL_GRID_NO_FEEDBACK (nothing reported yet: a new ctx, a new partition, another kernel variant): ctx_grid, the grid every launch had before.
+ * The ceiling wins over the floor.  Scheduling only: persistent waves pull until the queues are exhausted, so a grid that is too small makes a launch longer and
+ * changes no pixel.  Environment at create: BHRAY_LEVEL_GRID=0 off (every launch gets ctx_grid), BHRAY_LEVEL_GRID_GEN (256), BHRAY_LEVEL_GRID_MARGIN (25),
+ * BHRAY_LEVEL_GRID_FLOOR (64).  Never sized: latency-build launches, the temporal mode's launches, counting ctxs.                                               */
+#define BHRAY_LEVEL_GRID_NO_FEEDBACK UINT64_MAX
+uint32_t bhray_trace_grid_for(uint64_t expected_rays, uint32_t frames_in_batch, uint32_t ctx_grid, uint32_t rays_per_block_generation,
+                              uint32_t margin_percent, uint32_t floor_blocks);
+/* What the rule did.  Launch ids: 0 the speculative levels' merged launch, 1 + l the plain launch of level l, BHRAY_MAX_LEVELS + 1 the superset launch. */
+#define BHRAY_LEVEL_GRID_LAUNCHES (BHRAY_MAX_LEVELS + 2)
+typedef struct bhray_level_grid_info {
+    uint64_t expected_rays[BHRAY_LEVEL_GRID_LAUNCHES];  /* the batch `slot` launched last: what each trace launch was sized from (summed over the batch's frames);
+                                                           BHRAY_LEVEL_GRID_NO_FEEDBACK: not sized (no feedback, the rule off, or a launch the rule leaves alone)   */
+    uint64_t total_launches;           /* since create, local partitions summed: ladder trace launches enqueued ...                                                  */
+    uint64_t total_blocks;             /* ... the blocks they had together ...                                                                                       */
+    uint64_t total_ceiling_launches;   /* ... and how many of them kept their unsized grid                                                                              */
+    uint32_t blocks[BHRAY_LEVEL_GRID_LAUNCHES];         /* blocks each trace launch of that batch got; 0: the batch had no such launch                               */
+    uint32_t enabled;                  /* 1: this ctx sizes its dense ladder launches (not BHRAY_LEVEL_GRID=0, no counters, not temporal)                            */
+    uint32_t frames;                   /* frames of that batch (0: the slot has launched nothing)                                                                    */
+    uint32_t ctx_grid;                 /* the ceiling of that batch                                                                                                  */
+    uint32_t dense;                    /* 1: the batch's trace launches RAN dense builds                                                                             */
+} bhray_level_grid_info;
+/* slot < frames_in_flight; per-batch fields from the first local partition.  Host state only: no synchronisation. */
+int bhray_get_level_grids(bhray_ctx* ctx, uint32_t slot, bhray_level_grid_info* out);
+
 /* The Cash-Karp step skips its error estimate where a bound on it - (dist + 1) * (s*h)^2 <= 3.6e-5, proved above next_ray_rk_t in bhray_kernels.hip - shows every active
  * lane of the wave below the step-size controller's threshold.  The counting kernels (BHRAY_F_COUNTERS) always form the estimate and count, for the RK
  * steps of the last render, summed over levels and local partitions: out[0] = wave-steps, out[1] = wave-steps whose active lanes all satisfied the bound (what a
