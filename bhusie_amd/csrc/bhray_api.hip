@@ -33,6 +33,16 @@ thread_local std::string g_create_error;
 
 #define BHRAY_READ_RING 64
 constexpr int SPAN_MAX = BHRAY_MAX_LEVELS + 2;      // trace launches per batch (per-level, + speculative / predicted)
+// Timing events of one batch (one entry of the ring bhray_dev::events), nl = ladder levels: three per level - before its classify, between classify and trace, behind its
+// trace (a level without a trace launch of its own records the last two together) -, two around the sky pass, two around the temporal mode's prediction + predicted trace
+constexpr int ev_level_begin(uint32_t l) { return (int)(3 * l); }
+constexpr int ev_level_classified(uint32_t l) { return (int)(3 * l + 1); }
+constexpr int ev_level_traced(uint32_t l) { return (int)(3 * l + 2); }
+constexpr int ev_sky_begin(uint32_t nl) { return (int)(3 * nl); }
+constexpr int ev_sky_end(uint32_t nl) { return (int)(3 * nl + 1); }
+constexpr int ev_predicted_begin(uint32_t nl) { return (int)(3 * nl + 2); }
+constexpr int ev_predicted_end(uint32_t nl) { return (int)(3 * nl + 3); }
+constexpr size_t events_per_batch(uint32_t nl) { return 3 * (size_t)nl + 4; }
 
 #ifndef BHRAY_ROW_VARIANTS
 #define BHRAY_ROW_VARIANTS 9         // orderings of a level's rows kept on the device (centre rows at 0, 1/8, ... 1 of the height); < 2 = ascending only
@@ -149,10 +159,11 @@ struct bhray_dev {
     bhray_details det{};
     bool have_uniforms = false;
     bool mesh_lensing = false;             // dev_set_mesh_lensing: models are tested on every step inside the relativity sphere too (from the next dev_render)
-    std::vector<hipEvent_t> events;        // ring: [BHRAY_TIMING_RING][3 * levels + 4]: per level (before classify, before trace, after trace), 2 around the sky pass, 2 around the temporal mode's prediction + predicted trace
+    std::vector<hipEvent_t> events;        // ring: [BHRAY_TIMING_RING][events_per_batch(levels)], indexed by ev_* (batch_events)
     uint64_t frame_counter = 0, timing_begin = 0;   // timing_begin: first batch not yet reported by dev_get_timing
     uint8_t sky_recorded[BHRAY_TIMING_RING] = {0};
     uint8_t ring_frames[BHRAY_TIMING_RING] = {0};   // frames of the batch held by each timing-ring entry
+    uint8_t ring_own_trace[BHRAY_TIMING_RING] = {0};   // ... and its levels that had a trace launch of their own (bit l; BatchPlan::own_trace)
     // execution spans of the trace launches of timed batches (FrameLaunch::span): [BHRAY_TIMING_RING][SPAN_MAX][2] device words
     unsigned long long* d_span = nullptr;
     uint8_t ring_spans[BHRAY_TIMING_RING] = {0};    // trace launches of each timing-ring entry
@@ -187,6 +198,8 @@ struct bhray_dev {
 };
 
 namespace {
+
+hipEvent_t* batch_events(bhray_dev* c, size_t ring) { return &c->events[ring * events_per_batch(c->cfg.levels)]; }
 
 int fail(bhray_dev* ctx, int code, const char* fmt, ...) {
     char buf[512];
@@ -618,7 +631,11 @@ int dev_create(const bhray_config* cfg, const bhray::DevOptions& opt, bhray_dev*
     for (uint32_t l = 0; l < nl; l++) c->row_work_off[l + 1] = c->row_work_off[l] + (size_t)cfg->level_h[l];
     // rows of the frame owned by this partition, the level rows they depend on, their device tables
     { int rc_ = build_row_tables(c); if (rc_) { g_create_error = c->err; dev_destroy(c); return rc_; } }
-    const size_t nlaunch = 5 * (size_t)nl + 3;                            // upper bound of launches per batch
+    // Argument blocks (FrameLaunch[B] each, BatchPlan::next_launch) a batch can need, by builder: speculative 2 ns (ns tentative classifies, the trace, ns - 1 classifies),
+    // temporal 2 nl + 1 (nl predictions, the predicted trace, nl fix-up pairs that share a block), levels one per level, superset 2 nu + 1.  The modes a config can combine
+    // (speculative + levels + superset; temporal alone) stay within 2 nl + 1; the worst BatchPlan::build could ever string together is speculative plus temporal,
+    // 2 (nl - 1) + 2 nl + 1 < 4 nl + 1.  next_launch refuses the block that would not fit.
+    const size_t nlaunch = 5 * (size_t)nl + 3;
     // Streams beyond the hardware queues ROCm maps them onto (GPU_MAX_HW_QUEUES, default 4; two are left to the null stream and a
     // communication stream) do not add concurrency, they alias - and a device with MORE streams than queues collapses (24 slots on 24
     // queues: 5 580 -> 4 380 Mrays/s, and a 20-frame block from 8.5 to 73 ms, measured).  The library only READS the variable: the slots
@@ -693,7 +710,7 @@ int dev_create(const bhray_config* cfg, const bhray::DevOptions& opt, bhray_dev*
     // ray queues and own output buffers of every frame, sized for the partition (grown by dev_set_partition when it changes)
     { int rc_ = ensure_frame_buffers(c, false); if (rc_) { g_create_error = c->err; dev_destroy(c); return rc_; } }
     if (cfg->flags & (BHRAY_F_TIMING | BHRAY_F_TIMING_SPARSE)) {
-        c->events.assign((size_t)BHRAY_TIMING_RING * (nl * 3 + 4), nullptr);
+        c->events.assign((size_t)BHRAY_TIMING_RING * events_per_batch(nl), nullptr);
         for (auto& e : c->events) CHK(hipEventCreate(&e));
         CHK(hipMalloc(&c->d_span, (size_t)BHRAY_TIMING_RING * SPAN_MAX * 2 * sizeof(unsigned long long)));
         CHK(hipMemset(c->d_span, 0, (size_t)BHRAY_TIMING_RING * SPAN_MAX * 2 * sizeof(unsigned long long)));
@@ -1032,26 +1049,51 @@ int dev_set_partition(bhray_dev* c, uint32_t partition, uint32_t stripe_rows, co
 // launch, in the slot's pinned staging) and the launch sequence, one method per ladder mode; launch_batch enqueues it.
 // ------------------------------------------------------------------------------------------
 namespace {
-struct Launch { int kind; const FrameLaunch* d; int blocks; bool count; std::vector<int> ev_before, ev_after; int build = -1; bool fixup = false; int levels = 1; FrameLaunch* h = nullptr; int fb = -1; };   // fb: a ladder trace launch's id in bhray_level_grid_info (launch_batch sizes its grid by queue length); kind 0 classify, 1 trace; timing events recorded around it; build: -1 the ctx's trace build, 0 latency, 1 dense
+enum class LaunchKind { classify, trace, predict };
+enum class TraceBuild { ctx, latency, dense };            // the build a trace launch asks for: the ctx's trace build (choose_build), or one named
+TraceBuild trace_build_of(int v) { return v < 0 ? TraceBuild::ctx : (v ? TraceBuild::dense : TraceBuild::latency); }   // (BHRAY_COARSE_BUILD's -1 / 0 / 1)
+// a ladder trace launch's id in bhray_level_grid_info (bhray_diag.h; size_grids sizes its grid by queue length)
+constexpr int GRID_ID_NONE = -1, GRID_ID_MERGED = 0, GRID_ID_SUPERSET = BHRAY_MAX_LEVELS + 1;   // MERGED: the speculative levels' launch (and the temporal mode's predicted one)
+constexpr int grid_id_level(uint32_t l) { return 1 + (int)l; }
+static_assert(GRID_ID_SUPERSET + 1 == BHRAY_LEVEL_GRID_LAUNCHES, "launch ids of bhray_level_grid_info");
+
+struct LaunchArgs { FrameLaunch* h; const FrameLaunch* d; };     // the nb argument entries of a launch: in the pinned staging, and their device address
+struct Launch {
+    LaunchKind kind; LaunchArgs args; int blocks;
+    bool count = false;                // classify, trace: the counting kernels
+    bool fixup = false;                // classify: CLASSIFY_FIXUP's kernels
+    int levels = 1;                    // predict: levels (blockIdx.z)
+    int grid_id = GRID_ID_NONE;        // trace
+    TraceVariant variant{};            // trace: the build that runs (resolved)
+    int ev_before[2] = {-1, -1}, ev_after[2] = {-1, -1};       // timing events recorded around it (ev_*; -1: none)
+    Launch& before(int e) { ev_before[0] = e; return *this; }
+    Launch& after(int e0, int e1 = -1) { ev_after[0] = e0; ev_after[1] = e1; return *this; }
+};
 
 struct BatchPlan {
     bhray_dev* c;
     Slot& S;
     const uint32_t nb, nl;             // frames staged, ladder levels
-    const bool count;                  // BHRAY_F_COUNTERS
-    const int literal;                 // the integrator's evaluation (launch_trace's `eval`)
-    const bool origin;                 // every frame of the batch has the hole at +0, +0, +0 (launch_trace's `origin`)
+    const TraceVariant ctx;            // the ctx's trace build for this batch, as asked for (choose_build)
     const int grid;                    // persistent trace blocks of the ctx's trace build
+    const bool timing;                 // this batch carries timing events, in entry `ring` of the ring
+    const size_t ring;
     hipStream_t st;
     size_t args_used;
+    const bool count = ctx.count;      // BHRAY_F_COUNTERS
+    bool overflow = false;             // a launch found no room in the argument block (no entry was written)
+    uint32_t own_trace = 0;            // bit l: level l has a trace launch of its own (dev_get_timing)
     std::vector<Launch> seq;
     uint32_t first_normal = 0;         // first level that still needs its own classify + trace pair
 
     // argument block of the next launch: nb FrameLaunch entries on the host, and their device address
-    void next_launch(FrameLaunch*& h, const FrameLaunch*& d) {
-        h = (FrameLaunch*)(S.h_args + args_used); d = (const FrameLaunch*)(S.d_args + args_used);
-        args_used += (size_t)nb * sizeof(FrameLaunch);
-        memset(h, 0, (size_t)nb * sizeof(FrameLaunch));
+    LaunchArgs next_launch() {
+        const size_t bytes = (size_t)nb * sizeof(FrameLaunch);
+        if (overflow || args_used + bytes > S.args_cap) { overflow = true; return {nullptr, nullptr}; }
+        LaunchArgs a{(FrameLaunch*)(S.h_args + args_used), (const FrameLaunch*)(S.d_args + args_used)};
+        args_used += bytes;
+        memset(a.h, 0, bytes);
+        return a;
     }
     void level_params(const FrameRes& R, uint32_t l, LevelParams& L) const {
         const Level& Lv = c->levels[l];
@@ -1080,52 +1122,62 @@ struct BatchPlan {
         const int tiles_x = (span + 7) / 8, tiles_y = ((int)Lv.rows.size() + 7) / 8;
         return ((tiles_x + BHRAY_CLASSIFY_BX - 1) / BHRAY_CLASSIFY_BX) * ((tiles_y + BHRAY_CLASSIFY_BY - 1) / BHRAY_CLASSIFY_BY);
     }
+    // counting builds: where the iterations of level l's rows are summed (FrameLaunch::row_work, SpecLevel::row_work)
+    unsigned long long* row_work(const FrameRes& R, uint32_t l) const { return (count && R.d_row_work) ? R.d_row_work + c->row_work_off[l] : nullptr; }
+    // level l as one of the levels of a merged trace launch: geometry and destination as its own launch would have them
+    SpecLevel spec_level(const FrameRes& R, uint32_t l, uint32_t* stamp = nullptr) const {
+        LevelParams Lp; level_params(R, l, Lp);
+        SpecLevel sl{};
+        sl.w = Lp.w; sl.h = Lp.h; sl.out = Lp.out; sl.out_pitch = Lp.out_pitch; sl.out_x0 = Lp.out_x0; sl.rowmap = Lp.rowmap; sl.stamp = stamp;
+        sl.row_work = row_work(R, l);
+        return sl;
+    }
+    // the next launch's argument entries: for each staged frame k, entry k holds level l's parameters and what fill(entry, frame) adds
+    template <class Fill>
+    LaunchArgs args_for(uint32_t l, Fill&& fill) {
+        const LaunchArgs a = next_launch();
+        if (a.h) for (uint32_t k = 0; k < nb; k++) { level_params(S.fr[k], l, a.h[k].L); fill(a.h[k], S.fr[k]); }
+        return a;
+    }
+    // what a trace launch that asks for `b` asks for
+    TraceVariant asked(TraceBuild b) const { TraceVariant v = ctx; if (b != TraceBuild::ctx) v.dense = (b == TraceBuild::dense); return v; }
+    int full_device_grid(TraceBuild b) const { return c->num_cus * trace_blocks_per_cu(asked(b)); }
+    Launch& classify(LaunchArgs a, uint32_t l, bool counted, bool fixup = false) {
+        seq.push_back({LaunchKind::classify, a, classify_blocks(l), counted, fixup});
+        return seq.back();
+    }
+    // level: the level whose trace interval ends behind the launch; -1: the temporal mode's predicted launch
+    Launch& trace(LaunchArgs a, int blocks, int grid_id, int level, TraceBuild b = TraceBuild::ctx) {
+        seq.push_back({LaunchKind::trace, a, blocks, count});
+        Launch& Ln = seq.back();
+        Ln.grid_id = grid_id; Ln.variant = trace_resolve(asked(b));
+        if (level >= 0) own_trace |= 1u << level;
+        return Ln.after(level >= 0 ? ev_level_traced((uint32_t)level) : ev_predicted_end(nl));
+    }
 
     // speculative_levels = ns: every needed pixel of levels 0..ns-1 traced in ONE launch, then classified
-    int speculative(uint32_t ns) {
+    void speculative(uint32_t ns) {
         // (1) every needed pixel of levels 0..ns-1 into ONE level-tagged queue, (2) one trace launch over it,
         // (3) classify levels 1..ns-1 against the traced images.  Queue control words of level 0 serve the merged queue.
         for (uint32_t l = 0; l < ns; l++) {
-            FrameLaunch* h; const FrameLaunch* d; next_launch(h, d);
-            for (uint32_t k = 0; k < nb; k++) {
-                const FrameRes& R = S.fr[k];
-                level_params(R, l, h[k].L);
-                h[k].L.pw = 1; h[k].L.ph = 1; h[k].L.prev = nullptr; h[k].L.tag = (int)l;    // "base case": every pixel is traced
-                h[k].queue = R.spec_queue; h[k].qctl = R.d_qctl; h[k].counters = nullptr;
-            }
-            seq.push_back({0, d, classify_blocks(l), false, {}, {}});
-            if (l == 0) seq.back().ev_before = {0};
-            if (l == ns - 1) seq.back().ev_after = {1};
+            Launch& Ln = classify(args_for(l, [&](FrameLaunch& F, const FrameRes& R) {
+                F.L.pw = 1; F.L.ph = 1; F.L.prev = nullptr; F.L.tag = (int)l;    // "base case": every pixel is traced
+                F.queue = R.spec_queue; F.qctl = R.d_qctl; F.counters = nullptr;
+            }), l, false);
+            if (l == 0) Ln.before(ev_level_begin(0));
+            if (l == ns - 1) Ln.after(ev_level_classified(0));
         }
-        {
-            FrameLaunch* h; const FrameLaunch* d; next_launch(h, d);
-            for (uint32_t k = 0; k < nb; k++) {
-                const FrameRes& R = S.fr[k];
-                level_params(R, 0, h[k].L);
-                h[k].SL.n = (int)ns;
-                for (uint32_t l = 0; l < ns; l++) {
-                    const Level& Lv = c->levels[l];
-                    h[k].SL.l[l].w = Lv.w; h[k].SL.l[l].h = Lv.h; h[k].SL.l[l].out = (l == 0) ? R.level_out[0] : R.spec_out[l]; h[k].SL.l[l].out_pitch = Lv.w;
-                    h[k].SL.l[l].row_work = (count && R.d_row_work) ? R.d_row_work + c->row_work_off[l] : nullptr;
-                }
-                h[k].queue = R.spec_queue; h[k].qctl = R.d_qctl; h[k].counters = count ? R.d_counters : nullptr;
-            }
-            seq.push_back({1, d, grid, count, {}, {2}});
-            seq.back().fb = 0;
-            if (ns < nl) seq.back().build = c->coarse_build;
-        }
-        for (uint32_t l = 1; l < ns; l++) {
-            FrameLaunch* h; const FrameLaunch* d; next_launch(h, d);
-            for (uint32_t k = 0; k < nb; k++) {
-                const FrameRes& R = S.fr[k];
-                level_params(R, l, h[k].L);
-                h[k].L.spec = R.spec_out[l];
-                h[k].queue = nullptr; h[k].qctl = R.d_qctl + 2 * l; h[k].counters = count ? R.d_counters + l : nullptr;
-            }
-            seq.push_back({0, d, classify_blocks(l), count, {(int)(3 * l)}, {(int)(3 * l + 1), (int)(3 * l + 2)}});   // no trace launch of its own
-        }
+        trace(args_for(0, [&](FrameLaunch& F, const FrameRes& R) {
+            F.SL.n = (int)ns;
+            for (uint32_t l = 0; l < ns; l++) { F.SL.l[l] = spec_level(R, l); if (l > 0) F.SL.l[l].out = R.spec_out[l]; }
+            F.queue = R.spec_queue; F.qctl = R.d_qctl; F.counters = count ? R.d_counters : nullptr;
+        }), grid, GRID_ID_MERGED, 0, ns < nl ? trace_build_of(c->coarse_build) : TraceBuild::ctx);   // (ns < nl always: dev_create)
+        for (uint32_t l = 1; l < ns; l++)
+            classify(args_for(l, [&](FrameLaunch& F, const FrameRes& R) {
+                F.L.spec = R.spec_out[l];
+                F.queue = nullptr; F.qctl = R.d_qctl + 2 * l; F.counters = count ? R.d_counters + l : nullptr;
+            }), l, count).before(ev_level_begin(l)).after(ev_level_classified(l), ev_level_traced(l));   // no trace launch of its own
         first_normal = ns;
-        return BHRAY_OK;
     }
 
     // BHRAY_F_TEMPORAL: the previous frame's traced set in ONE launch, then the ladder fixes up what that prediction missed
@@ -1145,83 +1197,60 @@ struct BatchPlan {
             }
         }
         // (0) the prediction: per level, the previous frame's traced set dilated by temporal_radius pixels -> one level-tagged queue
-        const FrameLaunch* pred_first = nullptr; int pred_blocks = 0;
+        LaunchArgs pred_first{nullptr, nullptr}; int pred_blocks = 0;
         for (uint32_t l = 0; l < nl; l++) {
-            FrameLaunch* h; const FrameLaunch* d; next_launch(h, d);
-            for (uint32_t k = 0; k < nb; k++) {
-                const FrameRes& R = S.fr[k];
-                level_params(R, l, h[k].L);
-                h[k].L.tag = (int)l;
-                h[k].queue = R.pred_queue; h[k].qctl = R.pred_ctl; h[k].need = R.need[l]; h[k].radius = (int)(l + 1 == nl ? c->temporal_radius : c->temporal_radius_coarse);
-            }
-            for (uint32_t k = 0; k < nb; k++) h[k].blocks = classify_blocks(l);
-            if (l == 0) { pred_first = d; pred_blocks = 0; }
-            if (classify_blocks(l) > pred_blocks) pred_blocks = classify_blocks(l);
+            const LaunchArgs a = args_for(l, [&](FrameLaunch& F, const FrameRes& R) {
+                F.L.tag = (int)l;
+                F.queue = R.pred_queue; F.qctl = R.pred_ctl; F.need = R.need[l]; F.radius = (int)(l + 1 == nl ? c->temporal_radius : c->temporal_radius_coarse);
+                F.blocks = classify_blocks(l);
+            });
+            if (l == 0) pred_first = a;
+            pred_blocks = std::max(pred_blocks, classify_blocks(l));
         }
-        seq.push_back({2, pred_first, pred_blocks, false, {(int)(3 * nl + 2)}, {}, -1, false, (int)nl});      // ONE launch, blockIdx.z = level (the entries are contiguous)
-        {
-            FrameLaunch* h; const FrameLaunch* d; next_launch(h, d);
-            for (uint32_t k = 0; k < nb; k++) {
-                const FrameRes& R = S.fr[k];
-                level_params(R, 0, h[k].L);
-                h[k].SL.n = (int)nl;
-                for (uint32_t l = 0; l < nl; l++) {
-                    LevelParams Lp; level_params(R, l, Lp);
-                    SpecLevel& sl = h[k].SL.l[l];
-                    sl.w = Lp.w; sl.h = Lp.h; sl.out = Lp.out; sl.out_pitch = Lp.out_pitch; sl.out_x0 = Lp.out_x0; sl.rowmap = Lp.rowmap; sl.stamp = R.stamp[l];
-                    sl.row_work = (count && R.d_row_work) ? R.d_row_work + c->row_work_off[l] : nullptr;
-                }
-                h[k].queue = R.pred_queue; h[k].qctl = R.pred_ctl; h[k].counters = count ? R.d_counters : nullptr;
-                h[k].stamp_value = R.stamp_value; h[k].probe_empty = 1;
-            }
-            // the predicted launch holds a whole frame's rays: the dense build (0.61 against 0.66 ms at 1080p); the fix-up launches are
-            // expected to be nearly empty: the latency build, which looks at the queue head before its first atomic.
-            // Grids: with ONE frame slot the device is this frame's - full-occupancy grids; with several slots the ctx's rule for every
-            // trace launch (2 persistent blocks per CU: `grid`) - a full-device persistent grid keeps the next batch's small kernels
-            // (its prediction, its fix-up classification) waiting until it has drained, and two batches then run one after the other
-            // (rank 3 of an 8-way 1080p partition, 20-frame blocks of a moving sequence: 0.0995 -> 0.0736 ms per frame, EXPERIMENTS R4.12)
-            seq.push_back({1, d, shared_device ? grid : c->num_cus * trace_blocks_per_cu(S.method, S.models, count, 1, literal, origin), count, {}, {(int)(3 * nl + 3)}, 1});
-            seq.back().fb = 0;
-        }
+        seq.push_back({LaunchKind::predict, pred_first, pred_blocks});      // ONE launch, blockIdx.z = level (the entries are contiguous)
+        seq.back().levels = (int)nl;
+        seq.back().before(ev_predicted_begin(nl));
+        // the predicted launch holds a whole frame's rays: the dense build (0.61 against 0.66 ms at 1080p); the fix-up launches are
+        // expected to be nearly empty: the latency build, which looks at the queue head before its first atomic.
+        // Grids: with ONE frame slot the device is this frame's - full-occupancy grids; with several slots the ctx's rule for every
+        // trace launch (2 persistent blocks per CU: `grid`) - a full-device persistent grid keeps the next batch's small kernels
+        // (its prediction, its fix-up classification) waiting until it has drained, and two batches then run one after the other
+        // (rank 3 of an 8-way 1080p partition, 20-frame blocks of a moving sequence: 0.0995 -> 0.0736 ms per frame, EXPERIMENTS R4.12)
+        trace(args_for(0, [&](FrameLaunch& F, const FrameRes& R) {
+            F.SL.n = (int)nl;
+            for (uint32_t l = 0; l < nl; l++) F.SL.l[l] = spec_level(R, l, R.stamp[l]);
+            F.queue = R.pred_queue; F.qctl = R.pred_ctl; F.counters = count ? R.d_counters : nullptr;
+            F.stamp_value = R.stamp_value; F.trace_flags = TRACE_PROBE_EMPTY;
+        }), shared_device ? grid : full_device_grid(TraceBuild::dense), GRID_ID_MERGED, -1, TraceBuild::dense);
         for (uint32_t l = 0; l < nl; l++) {
-            FrameLaunch* h; const FrameLaunch* d; next_launch(h, d);
-            for (uint32_t k = 0; k < nb; k++) {
-                const FrameRes& R = S.fr[k];
-                level_params(R, l, h[k].L);
-                h[k].L.pass = CLASSIFY_FIXUP; h[k].L.tag = (int)l;
-                h[k].queue = R.queue[l]; h[k].qctl = R.d_qctl + 2 * l; h[k].counters = count ? R.d_counters + l : nullptr;
-                h[k].need = R.need[l];
-                h[k].stamp = R.stamp[l]; h[k].stamp_value = R.stamp_value; h[k].probe_empty = 1;
-                h[k].row_work = (count && R.d_row_work) ? R.d_row_work + c->row_work_off[l] : nullptr;
-            }
-            seq.push_back({0, d, classify_blocks(l), count, {(int)(3 * l)}, {(int)(3 * l + 1)}, -1, true});
-            seq.push_back({1, d, shared_device ? grid : c->num_cus * trace_blocks_per_cu(S.method, S.models, count, 0, literal, origin), count, {}, {(int)(3 * l + 2)}, 0});
-            seq.back().fb = 1 + (int)l;
+            const LaunchArgs a = args_for(l, [&](FrameLaunch& F, const FrameRes& R) {
+                F.L.pass = CLASSIFY_FIXUP; F.L.tag = (int)l;
+                F.queue = R.queue[l]; F.qctl = R.d_qctl + 2 * l; F.counters = count ? R.d_counters + l : nullptr;
+                F.need = R.need[l];
+                F.stamp = R.stamp[l]; F.stamp_value = R.stamp_value; F.trace_flags = TRACE_PROBE_EMPTY;
+                F.row_work = row_work(R, l);
+            });
+            classify(a, l, count, true).before(ev_level_begin(l)).after(ev_level_classified(l));
+            trace(a, shared_device ? grid : full_device_grid(TraceBuild::latency), grid_id_level(l), (int)l, TraceBuild::latency);
         }
         first_normal = nl;
         return BHRAY_OK;
     }
 
     // the plain ladder: levels [first_normal, u0), one classify + one trace launch each
-    int levels(uint32_t u0) {
+    void levels(uint32_t u0) {
         for (uint32_t l = first_normal; l < u0; l++) {
-            FrameLaunch* h; const FrameLaunch* d; next_launch(h, d);
-            for (uint32_t k = 0; k < nb; k++) {
-                const FrameRes& R = S.fr[k];
-                level_params(R, l, h[k].L);
-                h[k].queue = R.queue[l]; h[k].qctl = R.d_qctl + 2 * l; h[k].counters = count ? R.d_counters + l : nullptr;
-                h[k].row_work = (count && R.d_row_work) ? R.d_row_work + c->row_work_off[l] : nullptr;
-            }
-            seq.push_back({0, d, classify_blocks(l), count, {(int)(3 * l)}, {(int)(3 * l + 1)}});
-            seq.push_back({1, d, grid, count, {}, {(int)(3 * l + 2)}});
-            seq.back().fb = 1 + (int)l;
-            if (l + 1 < nl) seq.back().build = c->coarse_build;
+            const LaunchArgs a = args_for(l, [&](FrameLaunch& F, const FrameRes& R) {
+                F.queue = R.queue[l]; F.qctl = R.d_qctl + 2 * l; F.counters = count ? R.d_counters + l : nullptr;
+                F.row_work = row_work(R, l);
+            });
+            classify(a, l, count).before(ev_level_begin(l)).after(ev_level_classified(l));
+            trace(a, grid, grid_id_level(l), (int)l, l + 1 < nl ? trace_build_of(c->coarse_build) : TraceBuild::ctx);
         }
-        return BHRAY_OK;
     }
 
     // superset_levels = nu: the last nu levels traced in ONE launch over a conservative superset
-    int superset(uint32_t nu, uint32_t u0) {
+    void superset(uint32_t nu, uint32_t u0) {
         // Superset speculation over the last nu levels: ONE trace launch instead of nu dependent ones.
         //  (1) tentative classification of levels u0..nl-1 in order: a pixel whose coarser inputs are known is classified exactly,
         //      a pixel with an input that is itself queued (PENDING) is queued conservatively -> one level-tagged queue;
@@ -1231,74 +1260,144 @@ struct BatchPlan {
         // Same pixels as the plain ladder; the extra rays are the conservatively queued pixels that turn out to interpolate.
         // Queue control words of level u0 serve the merged queue; the trace is timed as level u0's.
         for (uint32_t l = u0; l < nl; l++) {
-            FrameLaunch* h; const FrameLaunch* d; next_launch(h, d);
-            for (uint32_t k = 0; k < nb; k++) {
-                const FrameRes& R = S.fr[k];
-                level_params(R, l, h[k].L);
-                h[k].L.pass = CLASSIFY_TENTATIVE; h[k].L.tag = (int)(l - u0); h[k].L.no_store = (l == nl - 1) ? 1 : 0;
-                h[k].queue = R.super_queue; h[k].qctl = R.d_qctl + 2 * u0; h[k].counters = nullptr;
-            }
-            seq.push_back({0, d, classify_blocks(l), false, {}, {}});
-            if (l == u0) seq.back().ev_before = {(int)(3 * u0)};
-            if (l == nl - 1) seq.back().ev_after = {(int)(3 * u0 + 1)};
+            Launch& Ln = classify(args_for(l, [&](FrameLaunch& F, const FrameRes& R) {
+                F.L.pass = CLASSIFY_TENTATIVE; F.L.tag = (int)(l - u0); F.L.no_store = (l == nl - 1) ? 1 : 0;
+                F.queue = R.super_queue; F.qctl = R.d_qctl + 2 * u0; F.counters = nullptr;
+            }), l, false);
+            if (l == u0) Ln.before(ev_level_begin(u0));
+            if (l == nl - 1) Ln.after(ev_level_classified(u0));
         }
-        {
-            FrameLaunch* h; const FrameLaunch* d; next_launch(h, d);
-            for (uint32_t k = 0; k < nb; k++) {
-                const FrameRes& R = S.fr[k];
-                level_params(R, u0, h[k].L);
-                h[k].SL.n = (int)nu;
-                for (uint32_t l = u0; l < nl; l++) {
-                    LevelParams Lp; level_params(R, l, Lp);
-                    SpecLevel& sl = h[k].SL.l[l - u0];
-                    sl.w = Lp.w; sl.h = Lp.h; sl.out = Lp.out; sl.out_pitch = Lp.out_pitch; sl.out_x0 = Lp.out_x0; sl.rowmap = Lp.rowmap;
-                    sl.row_work = (count && R.d_row_work) ? R.d_row_work + c->row_work_off[l] : nullptr;
-                }
-                h[k].queue = R.super_queue; h[k].qctl = R.d_qctl + 2 * u0; h[k].counters = count ? R.d_counters + u0 : nullptr;
-            }
-            seq.push_back({1, d, grid, count, {}, {(int)(3 * u0 + 2)}});
-            seq.back().fb = BHRAY_MAX_LEVELS + 1;
-        }
+        trace(args_for(u0, [&](FrameLaunch& F, const FrameRes& R) {
+            F.SL.n = (int)nu;
+            for (uint32_t l = u0; l < nl; l++) F.SL.l[l - u0] = spec_level(R, l);
+            F.queue = R.super_queue; F.qctl = R.d_qctl + 2 * u0; F.counters = count ? R.d_counters + u0 : nullptr;
+        }), grid, GRID_ID_SUPERSET, (int)u0);
         for (uint32_t l = u0; l < nl; l++) {
-            FrameLaunch* h; const FrameLaunch* d; next_launch(h, d);
-            for (uint32_t k = 0; k < nb; k++) {
-                const FrameRes& R = S.fr[k];
-                level_params(R, l, h[k].L);
-                h[k].L.pass = CLASSIFY_KEEP;
-                h[k].queue = nullptr; h[k].qctl = R.d_qctl + 2 * l; h[k].counters = count ? R.d_counters + l : nullptr;
+            Launch& Ln = classify(args_for(l, [&](FrameLaunch& F, const FrameRes& R) {
+                F.L.pass = CLASSIFY_KEEP;
+                F.queue = nullptr; F.qctl = R.d_qctl + 2 * l; F.counters = count ? R.d_counters + l : nullptr;
+            }), l, count);
+            if (l > u0) Ln.before(ev_level_begin(l)).after(ev_level_classified(l), ev_level_traced(l));      // (level u0's: inside its trace interval)
+        }
+    }
+
+    // step 3: the launches of the ctx's ladder mode, and their argument entries
+    int build() {
+        const uint32_t ns = c->cfg.speculative_levels;
+        const bool temporal_mode = (c->cfg.flags & BHRAY_F_TEMPORAL) != 0;
+        const uint32_t nu = temporal_mode ? 0 : c->cfg.superset_levels;
+        const uint32_t u0 = nu ? nl - nu : nl;                     // first level of the superset group
+        if (!c->levels[nl - 1].rows.empty()) {                     // a partition without rows has nothing to launch (then no level has rows)
+            if (ns) speculative(ns);
+            if (temporal_mode) { int rc = temporal(); if (rc) return rc; }
+            levels(u0);
+            if (nu) superset(nu, u0);
+        }
+        return overflow ? fail(c, BHRAY_E_STATE, "internal: argument block overflow") : BHRAY_OK;
+    }
+
+    // step 4: what every trace launch carries besides its plan's arguments - execution span, work counters, scheduling flags
+    int decorate_traces() {
+        if (timing && c->d_span) {                 // execution spans of this batch's trace launches (entry 0 of each launch's FrameLaunch array)
+            int nt = 0;
+            for (const Launch& Ln : seq) {
+                if (Ln.kind != LaunchKind::trace || nt >= SPAN_MAX) continue;
+                Ln.args.h[0].span = c->d_span + (ring * SPAN_MAX + (size_t)nt) * 2;
+                nt++;
             }
-            if (l == u0) seq.push_back({0, d, classify_blocks(l), count, {}, {}});      // inside level u0's trace interval
-            else seq.push_back({0, d, classify_blocks(l), count, {(int)(3 * l)}, {(int)(3 * l + 1), (int)(3 * l + 2)}});
+            c->ring_spans[ring] = (uint8_t)nt;
+            HIPCHK(c, hipMemsetAsync(c->d_span + ring * SPAN_MAX * 2, 0, (size_t)SPAN_MAX * 2 * sizeof(unsigned long long), st));
+        } else {
+            c->ring_spans[ring] = 0;
+        }
+        for (const Launch& Ln : seq) {             // every trace launch adds the steps its waves issue for a frame to that frame's work counters
+            if (Ln.kind != LaunchKind::trace) continue;
+            FrameLaunch* hl = Ln.args.h;
+            for (uint32_t k = 0; k < nb; k++) hl[k].work = S.fr[k].d_work;
+            // a whole frame, one frame per launch: thin shares are dealt strided (bhray_kernels.hip, thin_stride; TRACE_THIN_STRIDED)
+            if (c->cfg.row_world <= 1 && nb == 1) hl[0].trace_flags |= TRACE_THIN_STRIDED;
+            // the quad march (bhray_quad.inc) for launches whose queue turns out short: how many waves per SIMD it may use (TRACE_QUAD_WPS_*; 0 = off)
+            // Measured (profiles/EXPERIMENTS.md R6.1): one wave per SIMD -21 % per launch (RK, a level-0-sized queue), two -10 %, three +10 %: a second wave on a
+            // SIMD slows both, and from the third on a scalar wave with four times the rays is faster.  The Euler step has too little 3-vector work to gain at two.
+            // Only for a host that renders one frame at a time (one frame per launch, at most two frame slots): beside other frames' waves on the same SIMDs
+            // the quad march's shorter iteration is gone and its four lanes per ray cost throughput - a rank of an 8-way partition, batches of 5 frames: +3.5 %
+            // per frame in the driver's blocks against -11-14 % one frame at a time (R6.1).  BHRAY_QUAD=n forces it for every latency-build launch.
+            // ... and wave priority by predicted ray length (TRACE_WAVE_PRIO; BHRAY_WAVE_PRIO in bhray_kernels.hip) for a host with ONE frame slot: it shortens a lone frame's launches (S = 2 1.16 -> 1.13 ms,
+            // S = 3 0.97 -> 0.95), but as soon as two frames overlap it costs - the drop-in shim with two frames in flight 0.816 -> 0.873 ms per frame, a saturated device 3.5 % (EXPERIMENTS.md R6.5)
+            if (c->wave_prio >= 0 ? c->wave_prio != 0 : (nb == 1 && c->slots.size() <= 1)) for (uint32_t k = 0; k < nb; k++) hl[k].trace_flags |= TRACE_WAVE_PRIO;
+            const int quad_wps = c->quad_wps >= 0 ? c->quad_wps : ((nb == 1 && c->slots.size() <= 2) ? (S.method == 0 ? 1 : 2) : 0);
+            for (uint32_t k = 0; k < nb; k++) hl[k].trace_flags |= (quad_wps & TRACE_QUAD_WPS_MASK) << TRACE_QUAD_WPS_SHIFT;
         }
         return BHRAY_OK;
     }
-};
-}  // namespace
 
-// Enqueues every launch of the batch staged in the current slot: one argument block (FrameParams + per-launch FrameLaunch
-// arrays) copied to the device, then the same launch sequence a single frame needs, each launch covering all staged frames.
-namespace {
-int launch_batch(bhray_dev* c) {
-    Slot& S = c->slots[(size_t)(c->batch_counter % c->slots.size())];
-    const uint32_t nb = S.pending;
-    if (nb == 0) return BHRAY_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const uint32_t nl = c->cfg.levels;
-    // BHRAY_F_TIMING_SPARSE: events around the launches of every 4th batch only (every recorded event is a packet in the stream's
-    // queue: 12 per frame cost a saturated device 1.6 %)
-    const bool sparse = (c->cfg.flags & BHRAY_F_TIMING_SPARSE) != 0;
-    const bool count = (c->cfg.flags & BHRAY_F_COUNTERS) != 0;
-    const bool timing = (c->cfg.flags & (BHRAY_F_TIMING | BHRAY_F_TIMING_SPARSE)) != 0 && (!sparse || (c->batch_counter & 3u) == 0);
-    if ((c->cfg.flags & (BHRAY_F_TIMING | BHRAY_F_TIMING_SPARSE)) != 0 && !timing) {
-        const size_t ring0 = (size_t)(c->batch_counter % BHRAY_TIMING_RING);
-        c->ring_frames[ring0] = 0; c->sky_recorded[ring0] = 0;          // this batch carries no events
+    // step 5:
+    // Trace grids by queue length (DESIGN.md 4.3).  Every ladder trace launch reports the rays its queues held (FrameLaunch::qlen -> S.h_qlen, one word per slot
+    // position and launch); the next batch staged here gives the same launch enough blocks for that many rays plus a margin instead of the ctx's grid: a launch of the
+    // coarse levels finds a few hundred waves' worth of rays, and every further wave of a full grid takes a wave slot, loads its arguments and fails an atomic on the
+    // queue head only to leave.  Launches that RUN a dense build only (trace_resolve: a lensed-mesh launch, or a mesh launch of the literal / fma evaluations, asks for
+    // one and gets the latency build, which sizes its thin shares, strided dealing and quad march from gridDim), not the temporal mode's
+    // launches (their own rule, R4.10 / R4.12), not a counting ctx.  A word read here was written by the previous batch of this slot if that has run its trace launches
+    // already, by the one before it otherwise (dev_render waited for the previous batch's upload, which follows the older batch's kernels in the stream): either is
+    // an estimate, and a wrong estimate costs time only - persistent waves pull until the queues are exhausted, whatever the grid.  For the same reason the reset on
+    // a change of kernel variant below is best effort: the slot's previous batch, of the old variant, may still be in flight and report behind it.
+    void size_grids() {
+        const bool report = !count && !(c->cfg.flags & BHRAY_F_TEMPORAL);
+        if (S.qlen_method != S.method || S.qlen_models != S.models) {
+            for (size_t i = 0; i < (size_t)c->batch * BHRAY_LEVEL_GRID_LAUNCHES; i++) S.h_qlen[i] = QLEN_NONE;
+            S.qlen_method = S.method; S.qlen_models = S.models;
+        }
+        bhray_level_grid_info& G = S.grids;
+        memset(&G, 0, sizeof G);
+        for (int i = 0; i < BHRAY_LEVEL_GRID_LAUNCHES; i++) G.expected_rays[i] = BHRAY_LEVEL_GRID_NO_FEEDBACK;
+        G.enabled = (report && c->level_grid) ? 1u : 0u; G.frames = nb; G.ctx_grid = (uint32_t)grid; G.dense = trace_resolve(ctx).dense ? 1u : 0u;
+        for (Launch& Ln : seq) {
+            if (Ln.kind != LaunchKind::trace || Ln.grid_id < 0) continue;
+            const int unsized = Ln.blocks;
+            uint64_t expected = BHRAY_LEVEL_GRID_NO_FEEDBACK;
+            if (report) {
+                uint64_t sum = 0; bool all = true;
+                for (uint32_t k = 0; k < nb; k++) {
+                    uint32_t* w = S.h_qlen + (size_t)k * BHRAY_LEVEL_GRID_LAUNCHES + (size_t)Ln.grid_id;
+                    const uint32_t v = __atomic_load_n(w, __ATOMIC_RELAXED);
+                    if (v == QLEN_NONE) all = false; else sum += v;
+                    Ln.args.h[k].qlen = w;
+                }
+                if (all && c->level_grid && Ln.variant.dense) expected = sum;
+            }
+            if (expected != BHRAY_LEVEL_GRID_NO_FEEDBACK)
+                Ln.blocks = (int)bhray_trace_grid_for(expected, nb, (uint32_t)Ln.blocks, c->level_grid_gen, c->level_grid_margin, c->level_grid_floor);
+            G.expected_rays[Ln.grid_id] = expected; G.blocks[Ln.grid_id] = (uint32_t)Ln.blocks;
+            c->grid_launches++; c->grid_blocks += (uint64_t)Ln.blocks; if (Ln.blocks >= unsized) c->grid_ceiling_launches++;
+        }
     }
-    hipStream_t st = S.stream;
-    const uint32_t B = c->batch;
-    const FrameParams* dP = (const FrameParams*)S.d_args;
-    // Persistent trace grid: (resident blocks per CU) x CUs.  With several batches in flight each launch takes only
-    // half of the block slots: the kernels of the other batches fill the rest, and a wave of a half-size grid pulls
-    // more than one load of rays, so the refill keeps its lanes busy (+4 % at 16 slots).
+
+    // step 6: the argument block, then the launches in order
+    int enqueue() {
+        const FrameParams* dP = (const FrameParams*)S.d_args;
+        HIPCHK(c, launch_upload(S.h_args, S.d_args, (args_used + 15) / 16, S.d_qctl, (size_t)nb * BHRAY_QCTL_WORDS, st));   // + queue control reset
+        HIPCHK(c, hipEventRecord(S.uploaded, st));
+        if (count) HIPCHK(c, hipMemsetAsync(S.d_counters, 0, (size_t)nb * BHRAY_MAX_LEVELS * sizeof(Counters64), st));
+        if (count) for (uint32_t k = 0; k < nb; k++) if (S.fr[k].d_row_work) HIPCHK(c, hipMemsetAsync(S.fr[k].d_row_work, 0, c->row_work_off[nl] * sizeof(unsigned long long), st));
+        hipEvent_t* fev = timing ? batch_events(c, ring) : nullptr;
+        if (timing) { c->sky_recorded[ring] = 0; c->ring_frames[ring] = (uint8_t)nb; c->ring_own_trace[ring] = (uint8_t)own_trace; }
+        for (const Launch& Ln : seq) {
+            if (timing) for (int e : Ln.ev_before) if (e >= 0) HIPCHK(c, hipEventRecord(fev[e], st));
+            if (Ln.kind == LaunchKind::predict) HIPCHK(c, launch_predict(dP, Ln.args.d, (int)nb, Ln.levels, Ln.blocks, st));
+            else if (Ln.kind == LaunchKind::classify) HIPCHK(c, launch_classify(dP, Ln.args.d, (int)nb, Ln.blocks, Ln.count, Ln.fixup, st));
+            else {
+                HIPCHK(c, launch_trace(dP, Ln.args.d, (int)nb, Ln.variant, c->d_err, Ln.blocks, st));
+                if (Ln.variant.origin) c->origin_launches++; else c->general_launches++;
+            }
+            if (timing) for (int e : Ln.ev_after) if (e >= 0) HIPCHK(c, hipEventRecord(fev[e], st));
+        }
+        HIPCHK(c, hipEventRecord(S.done, st));
+        return BHRAY_OK;
+    }
+};
+
+// step 1: the trace build this batch's launches ask for, where the plan names no other
+TraceVariant choose_build(bhray_dev* c, const Slot& S, uint32_t nb) {
     // Register budget of the no-mesh trace kernel (bhray_kernels.hip): the dense build when the device is saturated with
     // rays - at least ~4 whole frames' worth in flight (slots x frames per batch / row partitions) - otherwise the latency
     // build (measured on MI355X: 1920x1080, 16 slots: 4830 vs 4160 Mrays/s; 1/8 row tile, 16 slots x 8 frames: 0.070 vs
@@ -1325,7 +1424,7 @@ int launch_batch(bhray_dev* c) {
     const double weight = std::max(1.0, (double)c->cfg.frame_w * (double)c->cfg.frame_h / (1920.0 * 1080.0)) / (double)c->cfg.row_world;   // 1920x1080 frames' worth per frame of this partition
     const bool dense = c->dense_override >= 0 ? c->dense_override != 0
                                               : ((double)nb * weight >= 2.5 || (double)(in_flight * (size_t)c->batch) * weight >= (double)(dyn > 0 ? dyn : 4));
-    const int literal = (c->cfg.flags & BHRAY_F_LITERAL) ? 1 : ((c->cfg.flags & BHRAY_F_EVAL_FMA) ? 2 : 0);   // the integrator's evaluation (launch_trace's `eval`)
+    const int literal = (c->cfg.flags & BHRAY_F_LITERAL) ? 1 : ((c->cfg.flags & BHRAY_F_EVAL_FMA) ? 2 : 0);   // the integrator's evaluation (TraceVariant::eval)
     // The hole at the scene's origin - the three position words of EVERY frame staged in this batch are zero bits (a -0 is not: x - (-0) is not x for x = -0) - selects the ORIGIN
     // builds of the trace kernels (bhray_kernels.hip: no position - bpos in the march) for every trace launch of the batch and for the occupancy query that sizes their grids.
     // Per batch, from the uniform words staged with each frame: a scene whose hole moves changes builds from one batch to the next, with the same pixels.
@@ -1335,127 +1434,46 @@ int launch_batch(bhray_dev* c) {
         memcpy(w, ((const FrameParams*)S.h_args)[k].bh, sizeof w);
         origin = (w[0] | w[1] | w[2]) == 0u;
     }
-    int bpc = trace_blocks_per_cu(S.method, S.models, count, dense, literal, origin);
+    return {S.method, S.models, (c->cfg.flags & BHRAY_F_COUNTERS) != 0, dense, literal, origin};
+}
+
+// step 2: the persistent blocks of a trace launch of that build
+int choose_grid(const bhray_dev* c, const TraceVariant& ctx) {
+    // Persistent trace grid: (resident blocks per CU) x CUs.  With several batches in flight each launch takes only
+    // half of the block slots: the kernels of the other batches fill the rest, and a wave of a half-size grid pulls
+    // more than one load of rays, so the refill keeps its lanes busy (+4 % at 16 slots).
+    int bpc = trace_blocks_per_cu(ctx);
     if (c->slots.size() > 1 && bpc > 1) bpc = bpc > 4 ? 2 : (bpc / 2 > 1 ? bpc / 2 : 1);     // measured: 2 blocks per CU is best at 8-16 slots
     if (c->bpc_override > 0) bpc = c->bpc_override;
     int grid = c->num_cus * bpc;
     // ... and one and a half for the Euler kernels (their steps are short: a block's share of a queue is used up sooner, and a smaller grid leaves the later launches'
     // blocks room beside it): 512 -> 384 blocks at 22 slots +1.5 % (20- and 400-frame blocks), with the mesh +2.4-3 %, a rank of 8 0 / +2 %; the RK kernels: nothing
     // (profiles/r05_ab_euler_grid.txt, EXPERIMENTS.md R5.9)
-    if (S.method == 0 && c->slots.size() >= 8 && bpc == 2 && c->bpc_override <= 0) grid = c->num_cus * 3 / 2;      // (measured at 22 slots only: from 8 slots on)
+    if (ctx.method == 0 && c->slots.size() >= 8 && bpc == 2 && c->bpc_override <= 0) grid = c->num_cus * 3 / 2;      // (measured at 22 slots only: from 8 slots on)
     if (c->grid_override > 0) grid = c->grid_override;
-    BatchPlan plan{c, S, nb, nl, count, literal, origin, grid, st, (size_t)B * sizeof(FrameParams)};
-    const uint32_t ns = c->cfg.speculative_levels;
-    const bool any_rows = !c->levels[nl - 1].rows.empty();    // a partition without rows has nothing to launch (then no level has rows)
-    const bool temporal = (c->cfg.flags & BHRAY_F_TEMPORAL) != 0;
-    const uint32_t nu = temporal ? 0 : c->cfg.superset_levels;
-    const uint32_t u0 = nu ? nl - nu : nl;                     // first level of the superset group
-    if (any_rows) {
-        int rc = BHRAY_OK;
-        {
-            if (ns) rc = plan.speculative(ns);
-            if (!rc && temporal) rc = plan.temporal();
-            if (!rc) rc = plan.levels(u0);
-            if (!rc && nu) rc = plan.superset(nu, u0);
-        }
-        if (rc) return rc;
-    }
-    std::vector<Launch>& seq = plan.seq;
-    const size_t args_used = plan.args_used;
-    if (args_used > S.args_cap) return fail(c, BHRAY_E_STATE, "internal: argument block overflow");
+    return grid;
+}
+
+// Enqueues every launch of the batch staged in the current slot: one argument block (FrameParams + per-launch FrameLaunch
+// arrays) copied to the device, then the same launch sequence a single frame needs, each launch covering all staged frames.
+int launch_batch(bhray_dev* c) {
+    Slot& S = c->slots[(size_t)(c->batch_counter % c->slots.size())];
+    const uint32_t nb = S.pending;
+    if (nb == 0) return BHRAY_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    // BHRAY_F_TIMING_SPARSE: events around the launches of every 4th batch only (every recorded event is a packet in the stream's
+    // queue: 12 per frame cost a saturated device 1.6 %)
+    const bool sparse = (c->cfg.flags & BHRAY_F_TIMING_SPARSE) != 0;
+    const bool timing = (c->cfg.flags & (BHRAY_F_TIMING | BHRAY_F_TIMING_SPARSE)) != 0 && (!sparse || (c->batch_counter & 3u) == 0);
     const size_t ring = (size_t)(c->batch_counter % BHRAY_TIMING_RING);
-    if (timing && c->d_span) {                 // execution spans of this batch's trace launches (entry 0 of each launch's FrameLaunch array)
-        int nt = 0;
-        for (const Launch& Ln : seq) {
-            if (Ln.kind != 1 || nt >= SPAN_MAX) continue;
-            FrameLaunch* h0 = (FrameLaunch*)(S.h_args + ((const uint8_t*)Ln.d - S.d_args));
-            h0->span = c->d_span + (ring * SPAN_MAX + (size_t)nt) * 2;
-            nt++;
-        }
-        c->ring_spans[ring] = (uint8_t)nt;
-        HIPCHK(c, hipMemsetAsync(c->d_span + ring * SPAN_MAX * 2, 0, (size_t)SPAN_MAX * 2 * sizeof(unsigned long long), st));
-    } else {
-        c->ring_spans[ring] = 0;
-    }
-    for (const Launch& Ln : seq) {             // every trace launch adds the steps its waves issue for a frame to that frame's work counters
-        if (Ln.kind != 1) continue;
-        FrameLaunch* hl = (FrameLaunch*)(S.h_args + ((const uint8_t*)Ln.d - S.d_args));
-        for (uint32_t k = 0; k < nb; k++) hl[k].work = S.fr[k].d_work;
-        // a whole frame, one frame per launch: thin shares are dealt strided (bhray_kernels.hip, thin_stride; bit 1 of probe_empty)
-        if (c->cfg.row_world <= 1 && nb == 1) hl[0].probe_empty |= 2;
-        // the quad march (bhray_quad.inc) for launches whose queue turns out short: how many waves per SIMD it may use (bits 2-4; 0 = off)
-        // Measured (profiles/EXPERIMENTS.md R6.1): one wave per SIMD -21 % per launch (RK, a level-0-sized queue), two -10 %, three +10 %: a second wave on a
-        // SIMD slows both, and from the third on a scalar wave with four times the rays is faster.  The Euler step has too little 3-vector work to gain at two.
-        // Only for a host that renders one frame at a time (one frame per launch, at most two frame slots): beside other frames' waves on the same SIMDs
-        // the quad march's shorter iteration is gone and its four lanes per ray cost throughput - a rank of an 8-way partition, batches of 5 frames: +3.5 %
-        // per frame in the driver's blocks against -11-14 % one frame at a time (R6.1).  BHRAY_QUAD=n forces it for every latency-build launch.
-        // ... and wave priority by predicted ray length (bit 5; BHRAY_WAVE_PRIO in bhray_kernels.hip) for a host with ONE frame slot: it shortens a lone frame's launches (S = 2 1.16 -> 1.13 ms,
-        // S = 3 0.97 -> 0.95), but as soon as two frames overlap it costs - the drop-in shim with two frames in flight 0.816 -> 0.873 ms per frame, a saturated device 3.5 % (EXPERIMENTS.md R6.5)
-        if (c->wave_prio >= 0 ? c->wave_prio != 0 : (nb == 1 && c->slots.size() <= 1)) for (uint32_t k = 0; k < nb; k++) hl[k].probe_empty |= 32;
-        const int quad_wps = c->quad_wps >= 0 ? c->quad_wps : ((nb == 1 && c->slots.size() <= 2) ? (S.method == 0 ? 1 : 2) : 0);
-        for (uint32_t k = 0; k < nb; k++) hl[k].probe_empty |= (quad_wps & 7) << 2;
-    }
-    // Trace grids by queue length (DESIGN.md 4.3).  Every ladder trace launch reports the rays its queues held (FrameLaunch::qlen -> S.h_qlen, one word per slot
-    // position and launch); the next batch staged here gives the same launch enough blocks for that many rays plus a margin instead of the ctx's grid: a launch of the
-    // coarse levels finds a few hundred waves' worth of rays, and every further wave of a full grid takes a wave slot, loads its arguments and fails an atomic on the
-    // queue head only to leave.  Launches that RUN a dense build only (trace_dense_build: a lensed-mesh launch, or a mesh launch of the literal / fma evaluations, asks for
-    // one and gets the latency build, which sizes its thin shares, strided dealing and quad march from gridDim), not the temporal mode's
-    // launches (their own rule, R4.10 / R4.12), not a counting ctx.  A word read here was written by the previous batch of this slot if that has run its trace launches
-    // already, by the one before it otherwise (dev_render waited for the previous batch's upload, which follows the older batch's kernels in the stream): either is
-    // an estimate, and a wrong estimate costs time only - persistent waves pull until the queues are exhausted, whatever the grid.  For the same reason the reset on
-    // a change of kernel variant below is best effort: the slot's previous batch, of the old variant, may still be in flight and report behind it.
-    {
-        const bool report = !count && !temporal;
-        if (S.qlen_method != S.method || S.qlen_models != S.models) {
-            for (size_t i = 0; i < (size_t)B * BHRAY_LEVEL_GRID_LAUNCHES; i++) S.h_qlen[i] = QLEN_NONE;
-            S.qlen_method = S.method; S.qlen_models = S.models;
-        }
-        bhray_level_grid_info& G = S.grids;
-        memset(&G, 0, sizeof G);
-        for (int i = 0; i < BHRAY_LEVEL_GRID_LAUNCHES; i++) G.expected_rays[i] = BHRAY_LEVEL_GRID_NO_FEEDBACK;
-        G.enabled = (report && c->level_grid) ? 1u : 0u; G.frames = nb; G.ctx_grid = (uint32_t)grid; G.dense = trace_dense_build(S.method, S.models, count, dense, literal) ? 1u : 0u;
-        for (Launch& Ln : seq) {
-            if (Ln.kind != 1 || Ln.fb < 0) continue;
-            const bool ln_dense = trace_dense_build(S.method, S.models, Ln.count, Ln.build < 0 ? dense : Ln.build != 0, literal);    // the build launch_trace will run
-            const int unsized = Ln.blocks;
-            uint64_t expected = BHRAY_LEVEL_GRID_NO_FEEDBACK;
-            if (report) {
-                FrameLaunch* fl = (FrameLaunch*)(S.h_args + ((const uint8_t*)Ln.d - S.d_args));
-                uint64_t sum = 0; bool all = true;
-                for (uint32_t k = 0; k < nb; k++) {
-                    uint32_t* w = S.h_qlen + (size_t)k * BHRAY_LEVEL_GRID_LAUNCHES + (size_t)Ln.fb;
-                    const uint32_t v = __atomic_load_n(w, __ATOMIC_RELAXED);
-                    if (v == QLEN_NONE) all = false; else sum += v;
-                    fl[k].qlen = w;
-                }
-                if (all && c->level_grid && ln_dense) expected = sum;
-            }
-            if (expected != BHRAY_LEVEL_GRID_NO_FEEDBACK)
-                Ln.blocks = (int)bhray_trace_grid_for(expected, nb, (uint32_t)Ln.blocks, c->level_grid_gen, c->level_grid_margin, c->level_grid_floor);
-            G.expected_rays[Ln.fb] = expected; G.blocks[Ln.fb] = (uint32_t)Ln.blocks;
-            c->grid_launches++; c->grid_blocks += (uint64_t)Ln.blocks; if (Ln.blocks >= unsized) c->grid_ceiling_launches++;
-        }
-    }
+    if ((c->cfg.flags & (BHRAY_F_TIMING | BHRAY_F_TIMING_SPARSE)) != 0 && !timing) { c->ring_frames[ring] = 0; c->sky_recorded[ring] = 0; }   // this batch carries no events
+    const TraceVariant ctx = choose_build(c, S, nb);
+    BatchPlan plan{c, S, nb, c->cfg.levels, ctx, choose_grid(c, ctx), timing, ring, S.stream, (size_t)c->batch * sizeof(FrameParams)};
+    { int rc = plan.build(); if (rc) return rc; }
+    { int rc = plan.decorate_traces(); if (rc) return rc; }
+    plan.size_grids();
     S.launched_frames = nb;
-    // enqueue
-    HIPCHK(c, launch_upload(S.h_args, S.d_args, (args_used + 15) / 16, S.d_qctl, (size_t)nb * BHRAY_QCTL_WORDS, st));   // + queue control reset
-    HIPCHK(c, hipEventRecord(S.uploaded, st));
-    if (count) HIPCHK(c, hipMemsetAsync(S.d_counters, 0, (size_t)nb * BHRAY_MAX_LEVELS * sizeof(Counters64), st));
-    if (count) for (uint32_t k = 0; k < nb; k++) if (S.fr[k].d_row_work) HIPCHK(c, hipMemsetAsync(S.fr[k].d_row_work, 0, c->row_work_off[nl] * sizeof(unsigned long long), st));
-    hipEvent_t* fev = timing ? &c->events[ring * (nl * 3 + 4)] : nullptr;
-    if (timing) { c->sky_recorded[ring] = 0; c->ring_frames[ring] = (uint8_t)nb; }
-    for (const Launch& Ln : seq) {
-        if (timing) for (int e : Ln.ev_before) HIPCHK(c, hipEventRecord(fev[e], st));
-        if (Ln.kind == 2) HIPCHK(c, launch_predict(dP, Ln.d, (int)nb, Ln.levels, Ln.blocks, st));
-        else if (Ln.kind == 0) HIPCHK(c, launch_classify(dP, Ln.d, (int)nb, Ln.blocks, Ln.count, Ln.fixup, st));
-        else {
-            const bool ln_dense = Ln.build < 0 ? dense : Ln.build != 0;
-            HIPCHK(c, launch_trace(dP, Ln.d, (int)nb, S.method, S.models, Ln.count, ln_dense, literal, origin, c->d_err, Ln.blocks, st));
-            if (origin && trace_origin_build(S.method, S.models, Ln.count, ln_dense, literal)) c->origin_launches++; else c->general_launches++;
-        }
-        if (timing) for (int e : Ln.ev_after) HIPCHK(c, hipEventRecord(fev[e], st));
-    }
-    HIPCHK(c, hipEventRecord(S.done, st));
+    { int rc = plan.enqueue(); if (rc) return rc; }
     S.used = true;
     S.batch_id = c->batch_counter;
     S.pending = 0;
@@ -1688,11 +1706,11 @@ int dev_resolve_sky(bhray_dev* c) {
     TexDev sky; sky.rgba = c->tex[BHRAY_TEX_SKY]; sky.w = c->tex_w[BHRAY_TEX_SKY]; sky.h = c->tex_h[BHRAY_TEX_SKY];
     const bool timing = (c->cfg.flags & BHRAY_F_TIMING) != 0;
     const size_t ring = (size_t)(S.batch_id % BHRAY_TIMING_RING);
-    hipEvent_t* ev = timing ? &c->events[ring * (c->cfg.levels * 3 + 4) + c->cfg.levels * 3] : nullptr;
-    if (timing) HIPCHK(c, hipEventRecord(ev[0], S.stream));
+    hipEvent_t* ev = timing ? batch_events(c, ring) : nullptr;
+    if (timing) HIPCHK(c, hipEventRecord(ev[ev_sky_begin(c->cfg.levels)], S.stream));
     HIPCHK(c, launch_sky(sky, R.out, R.sky_out, npix, S.stream));
     R.sky_frame_id = R.frame_id;
-    if (timing) { HIPCHK(c, hipEventRecord(ev[1], S.stream)); c->sky_recorded[ring] = 1; }
+    if (timing) { HIPCHK(c, hipEventRecord(ev[ev_sky_end(c->cfg.levels)], S.stream)); c->sky_recorded[ring] = 1; }
     HIPCHK(c, hipEventRecord(S.done, S.stream));
     return BHRAY_OK;
 }
@@ -1986,28 +2004,26 @@ int dev_get_timing(bhray_dev* c, bhray_timing* out) {
     if (c->batch_counter - begin > BHRAY_TIMING_RING) begin = c->batch_counter - BHRAY_TIMING_RING;
     for (uint64_t f = begin; f < c->batch_counter; f++) {
         const size_t ring = (size_t)(f % BHRAY_TIMING_RING);
-        hipEvent_t* ev = &c->events[ring * (nl * 3 + 4)];
+        hipEvent_t* ev = batch_events(c, ring);
         if (!c->ring_frames[ring]) continue;                           // a batch without events (BHRAY_F_TIMING_SPARSE)
         if (c->sky_recorded[ring]) {
-            float t = 0; HIPCHK(c, hipEventElapsedTime(&t, ev[3 * nl], ev[3 * nl + 1])); out->sky_ms += t; out->sky_launches++;
+            float t = 0; HIPCHK(c, hipEventElapsedTime(&t, ev[ev_sky_begin(nl)], ev[ev_sky_end(nl)])); out->sky_ms += t; out->sky_launches++;
         }
         hipEvent_t first = nullptr, last = nullptr;
         for (uint32_t l = 0; l < nl; l++) {
             if (c->levels[l].rows.empty()) continue;
             float a = 0, b = 0;
-            HIPCHK(c, hipEventElapsedTime(&a, ev[3 * l], ev[3 * l + 1]));
-            HIPCHK(c, hipEventElapsedTime(&b, ev[3 * l + 1], ev[3 * l + 2]));
-            const bool spec_classified = (c->cfg.speculative_levels && l >= 1 && l < c->cfg.speculative_levels) ||
-                                         (c->cfg.superset_levels && l > nl - c->cfg.superset_levels);               // no trace launch of its own
+            HIPCHK(c, hipEventElapsedTime(&a, ev[ev_level_begin(l)], ev[ev_level_classified(l)]));
+            HIPCHK(c, hipEventElapsedTime(&b, ev[ev_level_classified(l)], ev[ev_level_traced(l)]));
             out->classify_ms += a; out->level_classify_ms[l] += a; out->classify_launches++;
-            if (!spec_classified) { out->trace_ms += b; out->level_trace_ms[l] += b; out->trace_launches++; }
-            if (!first) first = ev[3 * l];
-            last = ev[3 * l + 2];
+            if (c->ring_own_trace[ring] >> l & 1) { out->trace_ms += b; out->level_trace_ms[l] += b; out->trace_launches++; }   // (the speculative and superset modes classify some levels only)
+            if (!first) first = ev[ev_level_begin(l)];
+            last = ev[ev_level_traced(l)];
         }
         if ((c->cfg.flags & BHRAY_F_TEMPORAL) && first) {      // prediction + predicted trace launch: the bulk of a temporal-mode frame
-            float t = 0; HIPCHK(c, hipEventElapsedTime(&t, ev[3 * nl + 2], ev[3 * nl + 3]));
+            float t = 0; HIPCHK(c, hipEventElapsedTime(&t, ev[ev_predicted_begin(nl)], ev[ev_predicted_end(nl)]));
             out->predicted_trace_ms += t; out->predicted_launches++;
-            first = ev[3 * nl + 2];
+            first = ev[ev_predicted_begin(nl)];
         }
         if (first && last) { float t = 0; HIPCHK(c, hipEventElapsedTime(&t, first, last)); out->total_ms += t; }
         out->frames += c->ring_frames[ring];

@@ -118,7 +118,7 @@ struct FrameLaunch {
     int radius;            // predict_kernel: dilation of the previous frame's traced set, in pixels of this level
     const uint32_t* stamp; // this level's stamp image (classify); nullptr outside temporal mode
     uint32_t stamp_value;  // stamp of the current frame
-    int probe_empty;       // trace, bit 0: this launch is expected to find its queue (nearly) used up - look before the first atomic; bit 1: thin shares are dealt strided (a whole frame, one frame per launch); bits 2-4: waves per SIMD the quad march may use (bhray_quad.inc); bit 5: waves set their issue priority by their rays' predicted length
+    int trace_flags;       // trace: TRACE_* bits below (scheduling only: no pixel depends on them)
     int blocks;            // predict (one launch, all levels): this level's own block count
     unsigned long long* span; // trace, entry 0 of a timed launch: [0] max(~first block start) [1] max(last block end), device wall clock; nullptr: untimed
     unsigned long long* work; // trace, entry 0 of a launch: work[blockIdx & (BHRAY_WORK_WORDS - 1)] += integrator steps this wave ISSUED for the frames of the batch
@@ -127,6 +127,11 @@ struct FrameLaunch {
     uint32_t* qlen;           // trace: *qlen = qctl[0], the rays this frame's queue held for this launch, in pinned host memory: what the host sizes the NEXT launch of this
                               // slot position and ladder launch from (bhray_trace_grid_for; launch_batch).  One plain store by block 0; nullptr: not reported
 };
+// FrameLaunch::trace_flags
+enum : int { TRACE_PROBE_EMPTY = 1,        // this launch is expected to find its queue (nearly) used up - look before the first atomic
+             TRACE_THIN_STRIDED = 2,       // thin shares are dealt strided (a whole frame, one frame per launch)
+             TRACE_QUAD_WPS_SHIFT = 2, TRACE_QUAD_WPS_MASK = 7,   // (flags >> shift) & mask: waves per SIMD the quad march may use (bhray_quad.inc); 0 = never
+             TRACE_WAVE_PRIO = 32 };       // waves set their issue priority by their rays' predicted length
 #define BHRAY_WORK_WORDS 16      // counters per frame (the waves of a launch spread over them: one word would serialise 2 048 atomics at every launch's end)
 #define BHRAY_QCTL_WORDS (2 * BHRAY_MAX_LEVELS + 2 * BHRAY_WORK_WORDS)   // 32-bit words of a frame's control block: queue counts / heads, then the work counters (64-bit)
 
@@ -139,14 +144,46 @@ struct FrameLaunch {
 #endif
 // launchers (bhray_kernels.hip); Pb / Fb are device arrays of nb entries
 hipError_t launch_classify(const FrameParams* Pb, const FrameLaunch* Fb, int nb, int blocks, bool count, bool fixup, hipStream_t s);
-// origin: every frame of the batch has the hole at +0, +0, +0 - the ORIGIN build of the variant where it has one (trace_origin_build), the general build otherwise
-// models / has_models: 0 no usable visible model (the no-mesh kernels), 1 models tested in flat space only (the shader's behaviour), 2 also on every step inside the
-// relativity sphere (bhray_set_mesh_lensing: the lensed-mesh kernels)
-hipError_t launch_trace(const FrameParams* Pb, const FrameLaunch* Fb, int nb, int method, int models, bool count, bool dense, int eval, bool origin, int* err_flag,
-                        int grid_blocks, hipStream_t s);
-int trace_blocks_per_cu(int method, int has_models, int count, int dense, int eval, int origin);   // eval: 0 contract, 1 BHRAY_F_LITERAL, 2 BHRAY_F_EVAL_FMA
-bool trace_dense_build(int method, int models, bool count, bool dense, int eval);    // does a launch of this variant that asks for the dense build get one? (no: the latency build of the same variant)
-bool trace_origin_build(int method, int models, bool count, bool dense, int eval);   // does a launch of this variant with `origin` set get an ORIGIN build?
+// The build of trace_kernel a launch asks for.  models: 0 no usable visible model (the no-mesh kernels), 1 models tested in flat space only (the shader's behaviour), 2 also on
+// every step inside the relativity sphere (bhray_set_mesh_lensing: the lensed-mesh kernels); dense: the build for a saturated device (no: the latency build);
+// eval: 0 the numerics contract, 1 BHRAY_F_LITERAL, 2 BHRAY_F_EVAL_FMA; origin: every frame of the batch has the hole at +0, +0, +0.
+struct TraceVariant { int method; int models; bool count; bool dense; int eval; bool origin; };
+constexpr bool operator==(const TraceVariant& a, const TraceVariant& b) {
+    return a.method == b.method && a.models == b.models && a.count == b.count && a.dense == b.dense && a.eval == b.eval && a.origin == b.origin;
+}
+#ifndef BHRAY_UNIFIED
+#define BHRAY_UNIFIED 1          // (both described in bhray_kernels.hip; the defaults are needed here for trace_resolve, which is inline: EVERY translation unit that includes this
+#endif                           // header must be built with the same -D as bhray_kernels.hip - the Makefile's EXTRA reaches the .hip rule, and only .hip files include it)
+#ifndef BHRAY_ORIGIN_KERNEL
+#define BHRAY_ORIGIN_KERNEL 1
+#endif
+// The build that runs when `asked` is asked for - the only place that knows the fallbacks.  Every build of a variant computes the same pixels, bit for bit, so a
+// fallback costs time only.  What is instantiated is exactly the set of variants that resolve to themselves (bhray_kernels.hip: trace_kernel_ptr).
+constexpr TraceVariant trace_resolve(TraceVariant v) {
+    if (v.models == 2 && v.eval == 0) { v.dense = false; v.origin = false; return v; }   // lensed meshes: the latency general build, counting or not
+    if (v.models == 2) v.models = 1;                                          // no lensed kernel under another evaluation (refused at bhray_set_mesh_lensing): flat-space models
+    if (v.count || (v.eval != 0 && v.models != 0)) v.dense = false;           // dense builds exist where throughput is reported (trace_variant_exists, bhray_kernels.hip)
+    if (!(BHRAY_ORIGIN_KERNEL != 0 && BHRAY_UNIFIED != 0 && v.eval == 0 && v.models == 0 && !v.count)) v.origin = false;   // ORIGIN builds: the no-mesh, non-counting contract kernels
+    return v;
+}
+// (method, models, count, dense, eval, origin)
+static_assert(trace_resolve({1, 0, true,  true,  0, false}) == TraceVariant{1, 0, true,  false, 0, false}, "trace_resolve");   // a dense counting request: latency
+static_assert(trace_resolve({1, 1, false, true,  1, false}) == TraceVariant{1, 1, false, false, 1, false}, "trace_resolve");   // a dense mesh request under the literal / fma evaluations: latency
+static_assert(trace_resolve({0, 1, false, true,  2, false}) == TraceVariant{0, 1, false, false, 2, false}, "trace_resolve");
+static_assert(trace_resolve({1, 1, false, true,  0, false}) == TraceVariant{1, 1, false, true,  0, false}, "trace_resolve");   // ... under the contract: dense
+static_assert(trace_resolve({1, 2, false, true,  0, true }) == TraceVariant{1, 2, false, false, 0, false}, "trace_resolve");   // lensed with dense and origin: latency and general, still lensed
+static_assert(trace_resolve({0, 2, true,  true,  0, true }) == TraceVariant{0, 2, true,  false, 0, false}, "trace_resolve");
+static_assert(trace_resolve({1, 2, false, false, 1, false}) == TraceVariant{1, 1, false, false, 1, false}, "trace_resolve");   // lensed under another evaluation: flat-space models
+static_assert(trace_resolve({1, 0, false, true,  0, true }) == TraceVariant{1, 0, false, true,  0, BHRAY_ORIGIN_KERNEL != 0 && BHRAY_UNIFIED != 0}, "trace_resolve");   // origin survives for (contract, no mesh, no count), dense ...
+static_assert(trace_resolve({0, 0, false, false, 0, true }) == TraceVariant{0, 0, false, false, 0, BHRAY_ORIGIN_KERNEL != 0 && BHRAY_UNIFIED != 0}, "trace_resolve");   // ... and latency, where the ORIGIN builds are built at all
+static_assert(trace_resolve({1, 1, false, true,  0, true }) == TraceVariant{1, 1, false, true,  0, false}, "trace_resolve");   // origin is dropped for mesh,
+static_assert(trace_resolve({1, 0, true,  false, 0, true }) == TraceVariant{1, 0, true,  false, 0, false}, "trace_resolve");   // for count
+static_assert(trace_resolve({1, 0, false, true,  1, true }) == TraceVariant{1, 0, false, true,  1, false}, "trace_resolve");   // and for another evaluation
+static_assert(trace_resolve({1, 0, false, true,  2, false}) == TraceVariant{1, 0, false, true,  2, false}, "trace_resolve");   // an already-resolved variant resolves to itself
+static_assert(trace_resolve(trace_resolve(TraceVariant{0, 2, true, true, 2, true})) == trace_resolve(TraceVariant{0, 2, true, true, 2, true}), "trace_resolve is idempotent");
+// launch_trace and trace_blocks_per_cu resolve `asked` themselves
+hipError_t launch_trace(const FrameParams* Pb, const FrameLaunch* Fb, int nb, TraceVariant asked, int* err_flag, int grid_blocks, hipStream_t s);
+int trace_blocks_per_cu(TraceVariant asked);
 // copies n16 16-byte words from pinned host memory to device memory with a kernel (stays on the compute queue: a DMA copy
 // between the launches of a stream costs a cross-engine handshake each time)
 // and zeroes `nzero` 32-bit words at `zero` (the queue control words of the batch) in the same launch

@@ -21,6 +21,7 @@
 // powf(.,1.3) (device libm, 1-2 ulp, not amplified).
 #include <hip/hip_fp16.h>
 #include <type_traits>
+#include <utility>
 
 #include "bhray_internal.h"
 #include "bhray_math.h"
@@ -1147,7 +1148,7 @@ __device__ __forceinline__ bool lens_near_mesh(const FrameParams& P, F3 pos, F3 
                                  // lasts as long as its longest ray, and beside three other waves on its SIMD that ray steps at 1.0 us per iteration instead of 0.72.  One frame at a
                                  // time: RK -3 % (S = 2: 1.16 -> 1.13 ms) / -2 % (S = 3: 0.97 -> 0.95; -10 % with timing events in the stream), Euler -2 %; the dense builds at saturation LOSE 3.5 % (the arbiter serves the preferred
                                  // wave's dependent chain where another wave had an instruction ready), and so does the drop-in shim with two frames in flight (+7 %): bit 1 stays off and the
-                                 // host enables bit 0's launches (FrameLaunch::probe_empty bit 5) for a ctx with ONE frame slot only.  profiles/EXPERIMENTS.md R6.5
+                                 // host enables bit 0's launches (TRACE_WAVE_PRIO in FrameLaunch::trace_flags) for a ctx with ONE frame slot only.  profiles/EXPERIMENTS.md R6.5
 #endif
 // predicted length class of a ray from its impact parameter b (b^2 = |(cam - hole) x dir|^2, horizon radius 1: the photon sphere's critical value is 27/4; rays just outside it wind
 // round the hole and are the longest of a frame, rays far outside cross the sphere on a chord): class 3 for BHRAY_PRIO_3_LO < b^2 < BHRAY_PRIO_3_HI, 2 / 1 for the wider bands
@@ -1294,9 +1295,9 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
     // A queue that is (nearly) used up when this wave arrives is seen with a plain load, before any atomic: 4 096 waves hitting one
     // word with failing atomics cost ~50 us per launch (11-13 ns each) - what an empty queue (a fix-up launch of the temporal mode)
     // used to take.  Only here (a load in front of every refill doubles the refill's round trips: -6 % throughput, measured) and only
-    // in the latency build and in launches the host expects to be nearly empty (probe_empty): in the dense build even the untaken
+    // in the latency build and in launches the host expects to be nearly empty (TRACE_PROBE_EMPTY): in the dense build even the untaken
     // branch costs a saturated device 2 % (measured: 4 930 -> 4 835 Mrays/s).
-    if (!DENSE && (F.probe_empty & 1) && __hip_atomic_load(qhead, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= qcount) continue;
+    if (!DENSE && (F.trace_flags & TRACE_PROBE_EMPTY) && __hip_atomic_load(qhead, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= qcount) continue;
     // Latency build, a queue with fewer rays than one wave per SIMD has lanes (coarse ladder levels, fix-up launches): the rays are dealt
     // out evenly over the first BHRAY_THIN_WAVES waves (one per SIMD: the first blocks of a grid land on different CUs) - wave w takes
     // entries [w * share, (w + 1) * share) once, without an atomic - instead of 64 to each of the first waves.  (Over ALL waves of the
@@ -1307,7 +1308,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
     // A batch (nb > 1): the blocks whose OWN frame this is (blockIdx % nb == fb: every block starts with its own frame) deal the frame's
     // rays out among themselves the same way, and the blocks that come by later to help (fi > 0) leave such a frame alone - it has no
     // queue head to pull from.  (A rank of an 8-way partition renders its coarse levels in launches of ten frames x a few hundred rays.)
-    // A WHOLE frame, one frame per launch (the host says so: bit 1 of probe_empty): a share of fewer than BHRAY_THIN_STRIDED_BELOW rays is taken STRIDED - wave w takes
+    // A WHOLE frame, one frame per launch (the host says so: TRACE_THIN_STRIDED): a share of fewer than BHRAY_THIN_STRIDED_BELOW rays is taken STRIDED - wave w takes
     // entries w, w + waves, w + 2 waves, ... - so that every wave holds an even sample of the frame instead of neighbouring pixels: no wave is left with nothing but the photon
     // ring's rays.  One frame at a time, levels 0+1 of 1920x1080: RK 0.285 -> 0.247 ms, Euler 0.194 -> 0.162, with the mesh 0.66 -> 0.57 (the frame 1.21 -> 1.18, 0.805 -> 0.762 ms).
     // Not for a rank of a partition (the sky slab of an 8-way partition: level 2 0.187 -> 0.205) nor for batches (0.077 -> 0.081 ms per frame): neighbouring rays finish
@@ -1319,7 +1320,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
             const uint32_t waves = total < (uint32_t)BHRAY_THIN_WAVES ? total : (uint32_t)BHRAY_THIN_WAVES;
             const uint32_t share = (qcount + waves - 1) / waves;
             if (share < 64u) thin_share = share > 0u ? share : 1u;
-            if ((F.probe_empty & 2) && share < (uint32_t)BHRAY_THIN_STRIDED_BELOW) thin_stride = waves;
+            if ((F.trace_flags & TRACE_THIN_STRIDED) && share < (uint32_t)BHRAY_THIN_STRIDED_BELOW) thin_stride = waves;
         }
     } else if (!DENSE && BHRAY_THIN_WAVES > 0 && (nb == 1 || gridDim.x >= 4u * (uint32_t)nb)) {   // (every frame of a batch needs blocks of its own)
         uint32_t own_blocks = gridDim.x;
@@ -1330,16 +1331,16 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
         if (waves > 0u) {
             const uint32_t share = (qcount + waves - 1) / waves;
             if (share < 64u) thin_share = share > 0u ? share : 1u;
-            if ((F.probe_empty & 2) && share < (uint32_t)BHRAY_THIN_STRIDED_BELOW) thin_stride = waves;
+            if ((F.trace_flags & TRACE_THIN_STRIDED) && share < (uint32_t)BHRAY_THIN_STRIDED_BELOW) thin_stride = waves;
         }
         if (thin_share != 0u && fi != 0) continue;
     }
     const HotParams H = load_hot<MODELS, ORIGIN>(P);
-    // The quad march (bhray_quad.inc): a queue that fits 16 rays per wave on the waves the host allows it (bits 2-4 of probe_empty: waves per
+    // The quad march (bhray_quad.inc): a queue that fits 16 rays per wave on the waves the host allows it (TRACE_QUAD_WPS_* of trace_flags: waves per
     // SIMD; 0 = off) is marched with one ray per QUAD of lanes - x, y, z on three lanes - instead of one per lane: fewer instructions per
     // iteration of the launch's longest ray, the same operations per ray.  Dealt out once like a scalar thin share; whole rounds of one wave per SIMD.
     if constexpr (!DENSE && !MODELS && !COUNT && EVAL == 0) {
-        const uint32_t q_wps = ((uint32_t)F.probe_empty >> 2) & 7u;
+        const uint32_t q_wps = ((uint32_t)F.trace_flags >> TRACE_QUAD_WPS_SHIFT) & (uint32_t)TRACE_QUAD_WPS_MASK;
         if (q_wps != 0u && BHRAY_THIN_WAVES > 0 && (nb == 1 || gridDim.x >= 4u * (uint32_t)nb)) {
             uint32_t own_blocks = gridDim.x, my_block = blockIdx.x;
             if (nb > 1) { own_blocks = (gridDim.x - (uint32_t)fb + (uint32_t)nb - 1u) / (uint32_t)nb; my_block = blockIdx.x / (uint32_t)nb; }
@@ -1353,7 +1354,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                 const uint32_t w = my_block * (BHRAY_TRACE_THREADS / 64) + (threadIdx.x >> 6);
                 if (w < waves && qcount != 0u) {
                     const uint32_t share = (qcount + waves - 1u) / waves;          // <= 16
-                    const bool strided = (F.probe_empty & 2) != 0;                 // a whole frame, one frame per launch: entries w, w + waves, ... (see the thin shares below)
+                    const bool strided = (F.trace_flags & TRACE_THIN_STRIDED) != 0;                 // a whole frame, one frame per launch: entries w, w + waves, ... (see the thin shares below)
                     quad_march<METHOD>(P, F, H, qcount, strided ? w : w * share, share, strided ? waves : 0u, work_steps);
                 }
                 continue;
@@ -1437,13 +1438,13 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                     it = 0; HIT_SET(0);
                     mode = P.relativity0 ? M_REL : M_FLAT;
                     if (COUNT) cnt[3]++;
-                    if (WAVE_PRIO && (F.probe_empty & 32)) {   // scheduling only: plain arithmetic, no pixel depends on it
+                    if (WAVE_PRIO && (F.trace_flags & TRACE_WAVE_PRIO)) {   // scheduling only: plain arithmetic, no pixel depends on it
                         const F3 cb = cross(qrel, rdir);
                         const float b2 = dot(cb, cb);
                         cold.set_urg((b2 > BHRAY_PRIO_3_LO && b2 < BHRAY_PRIO_3_HI) ? 3 : ((b2 > BHRAY_PRIO_2_LO && b2 < BHRAY_PRIO_2_HI) ? 2 : (b2 < BHRAY_PRIO_1_HI ? 1 : 0)));
                     }
                 }
-                if (WAVE_PRIO && (F.probe_empty & 32)) {       // the wave's priority: its longest ray's class (until the next refill)
+                if (WAVE_PRIO && (F.trace_flags & TRACE_WAVE_PRIO)) {       // the wave's priority: its longest ray's class (until the next refill)
                     const int u = mode != M_EMPTY ? cold.urg() : -1;
                     if (__any(u == 3)) __builtin_amdgcn_s_setprio(3);
                     else if (__any(u == 2)) __builtin_amdgcn_s_setprio(2);
@@ -1980,7 +1981,7 @@ hipError_t launch_classify(const FrameParams* Pb, const FrameLaunch* Fb, int nb,
     return hipGetLastError();
 }
 
-// Which builds of trace_kernel<METHOD, MODELS, COUNT, DENSE, EVAL, ORIGIN, LENSED> exist (12 x 2 integrators general builds + 2 x 2 ORIGIN builds + 2 x 2 lensed-mesh builds - trace_lensed_ptr -
+// Which builds of trace_kernel<METHOD, MODELS, COUNT, DENSE, EVAL, ORIGIN, LENSED> exist (16 x 2 integrators general builds + 2 x 2 ORIGIN builds + 2 x 2 lensed-mesh builds
 // = 40 instantiations; 36 in round 11, 32 in round 9, 48 in round 5, 72 in round 3).
 // eval: 0 the numerics contract, 1 BHRAY_F_LITERAL, 2 BHRAY_F_EVAL_FMA.  Every variant has a build for lone launches (the latency build);
 // the build for a saturated device (dense) exists where throughput is reported: not for counting kernels (BHRAY_F_COUNTERS is a diagnosis
@@ -1989,82 +1990,58 @@ hipError_t launch_classify(const FrameParams* Pb, const FrameLaunch* Fb, int nb,
 constexpr bool trace_variant_exists(int eval, bool models, bool dense, bool count) {
     return !(count && dense) && !(eval != 0 && models && dense);
 }
-// ... and which of them also have an ORIGIN build - the hole's position the constant +0 vector, the unified pairs without position - bpos (bhray_march.inc) - for launches whose
-// frames all have the hole at the scene's origin: the no-mesh, non-counting contract kernels (RK and Euler, latency and dense: four).  None where there is no origin text to hold
-// (-DBHRAY_UNIFIED=0) and none in the stand-in for the kernels before them (-DBHRAY_ORIGIN_KERNEL=0).  A launch whose variant has none gets the general build: the same pixels.
-constexpr bool trace_origin_variant_exists(int eval, bool models, bool dense, bool count) {
-    return BHRAY_ORIGIN_KERNEL != 0 && BHRAY_UNIFIED != 0 && eval == 0 && !models && !count && trace_variant_exists(eval, models, dense, count);
+// Which of them also have an ORIGIN build - the hole's position the constant +0 vector, the unified pairs without position - bpos (bhray_march.inc) - for launches whose frames
+// all have the hole at the scene's origin: the no-mesh, non-counting contract kernels (RK and Euler, latency and dense: four; none with -DBHRAY_UNIFIED=0, where there is no
+// origin text to hold, or -DBHRAY_ORIGIN_KERNEL=0), which kernels the lensed meshes get (trace_kernel's LENSED; `models` == 2: the contract's evaluation, both integrators, the
+// latency build, counting or not) and what a launch gets that asks for a build that does not exist: trace_resolve (bhray_internal.h).  The builds instantiated are the variants
+// that resolve to themselves.  The loop order is the order the kernels stand in the code object (lensed first, then per integrator the evaluations 1, 2, 0, mesh / counting /
+// ORIGIN / dense before their opposites): kept, so the object does not change.
+struct TraceBuilds { int n; TraceVariant v[40]; };
+constexpr TraceBuilds trace_builds() {
+    TraceBuilds t{};
+    for (int lensed = 1; lensed >= 0; lensed--) for (int method = 0; method < 2; method++) for (int e = 1; e <= 3; e++) for (int mesh = 1; mesh >= lensed; mesh--)
+        for (int count = 1; count >= 0; count--) for (int origin = 1; origin >= 0; origin--) for (int dense = 1; dense >= 0; dense--) {
+            const TraceVariant v{method, lensed ? 2 : mesh, count != 0, dense != 0, e % 3, origin != 0};
+            if (trace_resolve(v) == v) t.v[t.n++] = v;
+        }
+    return t;
 }
-template <int METHOD, bool MODELS, bool COUNT, bool DENSE, int EVAL, bool ORIGIN>
-static const void* trace_kernel_ptr_t() {
-    if constexpr (ORIGIN && !trace_origin_variant_exists(EVAL, MODELS, DENSE, COUNT)) return trace_kernel_ptr_t<METHOD, MODELS, COUNT, DENSE, EVAL, false>();
-    else if constexpr (trace_variant_exists(EVAL, MODELS, DENSE, COUNT)) return (const void*)trace_kernel<METHOD, MODELS, COUNT, DENSE, EVAL, ORIGIN>;
-    else return trace_kernel_ptr_t<METHOD, MODELS, COUNT, false, EVAL, ORIGIN>();
-}
-template <int METHOD, int EVAL, bool ORIGIN>
-static const void* trace_kernel_ptr_meo(bool models, bool count, bool dense) {
-    if (models) {
-        if (dense) return count ? trace_kernel_ptr_t<METHOD, true, true, true, EVAL, ORIGIN>() : trace_kernel_ptr_t<METHOD, true, false, true, EVAL, ORIGIN>();
-        return count ? trace_kernel_ptr_t<METHOD, true, true, false, EVAL, ORIGIN>() : trace_kernel_ptr_t<METHOD, true, false, false, EVAL, ORIGIN>();
+constexpr TraceBuilds TRACE_BUILDS = trace_builds();
+static_assert(TRACE_BUILDS.n == 36 + (BHRAY_ORIGIN_KERNEL != 0 && BHRAY_UNIFIED != 0 ? 4 : 0), "instantiations of trace_kernel");
+constexpr bool trace_variant_exists_agrees() {     // trace_variant_exists is trace_resolve's rule for the dense builds
+    for (int i = 0; i < 24; i++) {
+        const TraceVariant v{0, i & 1, (i & 2) != 0, (i & 4) != 0, i >> 3, false};
+        if ((trace_resolve(v) == v) != trace_variant_exists(v.eval, v.models != 0, v.dense, v.count)) return false;
     }
-    if (dense) return count ? trace_kernel_ptr_t<METHOD, false, true, true, EVAL, ORIGIN>() : trace_kernel_ptr_t<METHOD, false, false, true, EVAL, ORIGIN>();
-    return count ? trace_kernel_ptr_t<METHOD, false, true, false, EVAL, ORIGIN>() : trace_kernel_ptr_t<METHOD, false, false, false, EVAL, ORIGIN>();
+    return true;
 }
-template <int METHOD, int EVAL>
-static const void* trace_kernel_ptr_me(bool models, bool count, bool dense, bool origin) {
-    return origin ? trace_kernel_ptr_meo<METHOD, EVAL, true>(models, count, dense) : trace_kernel_ptr_meo<METHOD, EVAL, false>(models, count, dense);
+static_assert(trace_variant_exists_agrees(), "trace_variant_exists / trace_resolve");
+template <int I>
+static const void* trace_kernel_at() {
+    constexpr TraceVariant V = TRACE_BUILDS.v[I];
+    return (const void*)trace_kernel<V.method, V.models != 0, V.count, V.dense, V.eval, V.origin, V.models == 2>;
 }
-// The lensed-mesh kernels (trace_kernel's LENSED; `models` == 2): the contract's evaluation, both integrators, the latency build, counting or not - four instantiations.  A request
-// for the dense build or the ORIGIN build gets these (the same pixels, as with every build that does not exist); another evaluation has no lensed kernel and is refused at
-// bhray_set_mesh_lensing - asked for here all the same it gets the variant that tests models in flat space only.
-static const void* trace_lensed_ptr(int method, bool count) {
-    if (method == 0) return count ? (const void*)trace_kernel<0, true, true, false, 0, false, true> : (const void*)trace_kernel<0, true, false, false, 0, false, true>;
-    return count ? (const void*)trace_kernel<1, true, true, false, 0, false, true> : (const void*)trace_kernel<1, true, false, false, 0, false, true>;
+template <int... I>
+static const void* trace_kernel_lookup(const TraceVariant& resolved, std::integer_sequence<int, I...>) {
+    static const void* const table[] = {trace_kernel_at<I>()...};
+    for (int i = 0; i < TRACE_BUILDS.n; i++) if (TRACE_BUILDS.v[i] == resolved) return table[i];
+    return nullptr;                                // not a resolved variant: the launch fails (hipErrorInvalidDeviceFunction)
 }
-static const void* trace_kernel_ptr(int method, int models_mode, bool count, bool dense, int eval, bool origin) {
-    if (models_mode == 2 && eval == 0) return trace_lensed_ptr(method, count);       // (dense, origin: no such builds)
-    const bool models = models_mode != 0;
-    if (method == 0) {
-        if (eval == 1) return trace_kernel_ptr_me<0, 1>(models, count, dense, origin);
-        if (eval == 2) return trace_kernel_ptr_me<0, 2>(models, count, dense, origin);
-        return trace_kernel_ptr_me<0, 0>(models, count, dense, origin);
-    }
-    if (eval == 1) return trace_kernel_ptr_me<1, 1>(models, count, dense, origin);
-    if (eval == 2) return trace_kernel_ptr_me<1, 2>(models, count, dense, origin);
-    return trace_kernel_ptr_me<1, 0>(models, count, dense, origin);
-}
+static const void* trace_kernel_ptr(const TraceVariant& resolved) { return trace_kernel_lookup(resolved, std::make_integer_sequence<int, TRACE_BUILDS.n>{}); }
 static size_t trace_dyn_lds(bool models) { return models ? (size_t)BHRAY_BVH_LDS_STACK * BHRAY_TRACE_THREADS * 8 : 0; }   // trace_ray_model's traversal ring
 
-// `origin`: every frame of the batch has the hole at +0, +0, +0 (the host's test of the uniform words: bhray_api.hip) - the ORIGIN build where the variant has one
-bool trace_origin_build(int method, int models_mode, bool count, bool dense, int eval) {
-    (void)method;
-    if (models_mode == 2 && eval == 0) return false;
-    const bool models = models_mode != 0;
-    if (!trace_variant_exists(eval, models, dense, count)) dense = false;
-    return trace_origin_variant_exists(eval, models, dense, count);
-}
-
-// `dense`: the dense build is asked for - and is it what trace_kernel_ptr hands out?  Not for the lensed-mesh kernels, a counting launch, or the mesh variant under
-// BHRAY_F_LITERAL / BHRAY_F_EVAL_FMA: those get the latency build, whose thin shares are sized from gridDim (the host sizes only real dense builds by queue length).
-bool trace_dense_build(int method, int models_mode, bool count, bool dense, int eval) {
-    (void)method;
-    if (models_mode == 2 && eval == 0) return false;
-    return dense && trace_variant_exists(eval, models_mode != 0, true, count);
-}
-
-hipError_t launch_trace(const FrameParams* Pb, const FrameLaunch* Fb, int nb, int method, int models, bool count, bool dense, int eval, bool origin, int* err_flag,
-                        int grid_blocks, hipStream_t s) {
+hipError_t launch_trace(const FrameParams* Pb, const FrameLaunch* Fb, int nb, TraceVariant asked, int* err_flag, int grid_blocks, hipStream_t s) {
     if (nb <= 0) return hipSuccess;
     (void)hipGetLastError();
     void* args[] = {(void*)&Pb, (void*)&Fb, (void*)&nb, (void*)&err_flag};
-    return hipLaunchKernel(trace_kernel_ptr(method, models, count, dense, eval, origin), dim3((grid_blocks * 256 + BHRAY_TRACE_THREADS - 1) / BHRAY_TRACE_THREADS),
-                           dim3(BHRAY_TRACE_THREADS), args, trace_dyn_lds(models != 0), s);
+    return hipLaunchKernel(trace_kernel_ptr(trace_resolve(asked)), dim3((grid_blocks * 256 + BHRAY_TRACE_THREADS - 1) / BHRAY_TRACE_THREADS),
+                           dim3(BHRAY_TRACE_THREADS), args, trace_dyn_lds(asked.models != 0), s);
 }
 
-int trace_blocks_per_cu(int method, int has_models, int count, int dense, int eval, int origin) {
+int trace_blocks_per_cu(TraceVariant asked) {
     int n = 0;
-    const void* f = trace_kernel_ptr(method, has_models, count != 0, dense != 0, eval, origin != 0);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, BHRAY_TRACE_THREADS, trace_dyn_lds(has_models != 0)) != hipSuccess || n < 1) n = 2;
+    const void* f = trace_kernel_ptr(trace_resolve(asked));
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, BHRAY_TRACE_THREADS, trace_dyn_lds(asked.models != 0)) != hipSuccess || n < 1) n = 2;
     n = n * BHRAY_TRACE_THREADS / 256;            // in units of 256 threads (the grid is sized in those)
     return n < 1 ? 1 : n;
 }

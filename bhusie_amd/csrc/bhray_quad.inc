@@ -14,7 +14,7 @@
 //
 // Where.  The latency build of the no-mesh kernel under the numerics contract (EVAL == 0, not counting), for a frame whose queue fits
 // 16 rays per wave on at most BHRAY_QUAD_MAX_WPS waves per SIMD; the rays are dealt out once, without an atomic, like the scalar thin
-// shares (trace_kernel).  The host allows it per launch (bits 2-4 of FrameLaunch::probe_empty = waves per SIMD it may use; 0 = never).
+// shares (trace_kernel).  The host allows it per launch (TRACE_QUAD_WPS_* of FrameLaunch::trace_flags = waves per SIMD it may use; 0 = never).
 #ifndef BHRAY_QUAD_MAX_WPS
 #define BHRAY_QUAD_MAX_WPS 4
 #endif
