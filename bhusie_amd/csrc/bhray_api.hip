@@ -126,6 +126,10 @@ struct ModelStore {
     BvhResult* d_result = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};     // before the copies, between copies and build, behind the build
     bhray_model_build_info info{};
+    // the affine pose of DESIGN.md §14: the rest arrays (allocated by the slot's first dev_set_model_pose) and the pose in force; points / normals are then
+    // what launch_bvh_pose makes of them
+    float4* rest_points = nullptr; float4* rest_normals = nullptr;
+    bool posed = false; float pose[12] = {0};
 };
 
 }  // namespace
@@ -320,6 +324,8 @@ void free_model(ModelStore& m) {
     if (m.lookup) (void)hipFree(m.lookup);
     if (m.leaf) (void)hipFree(m.leaf);
     if (m.d_result) (void)hipFree(m.d_result);
+    if (m.rest_points) (void)hipFree(m.rest_points);
+    if (m.rest_normals) (void)hipFree(m.rest_normals);
     bvh_build_destroy(m.build);
     for (hipEvent_t e : m.ev) if (e) (void)hipEventDestroy(e);
     m = ModelStore();
@@ -912,19 +918,63 @@ int dev_upload_model_build(bhray_dev* c, uint32_t mi, const bhray_model_desc* d)
     return BHRAY_OK;
 }
 
-int dev_update_model_vertices(bhray_dev* c, uint32_t mi, const float* points, int32_t point_count, const float* normals, int32_t normal_count) {
+namespace {
+// bhray_update_model_vertices (kind = hipMemcpyHostToDevice) and bhray_update_model_vertices_device (hipMemcpyDefault, behind `after`).  On a posed slot the new
+// arrays are the new REST arrays and the pose in force is applied again; on any other slot they are what the build reads.
+int update_vertices(bhray_dev* c, uint32_t mi, const void* points, int32_t point_count, const void* normals, int32_t normal_count, hipMemcpyKind kind, hipEvent_t after, const char* name) {
     if (!c) return BHRAY_E_INVALID;
     if (mi >= BHRAY_MAX_MODELS) return fail(c, BHRAY_E_INVALID, "bad model arguments");
     ModelStore& m = c->models[mi];
-    if (!m.loaded || !m.build) return fail(c, BHRAY_E_STATE, "bhray_update_model_vertices: slot %u was not built by bhray_upload_model_build", mi);
+    if (!m.loaded || !m.build) return fail(c, BHRAY_E_STATE, "%s: slot %u was not built by bhray_upload_model_build", name, mi);
     if ((points && point_count != m.point_count) || (normals && normal_count != m.normal_count))
-        return fail(c, BHRAY_E_INVALID, "bhray_update_model_vertices: the slot holds %d points and %d normals", m.point_count, m.normal_count);
+        return fail(c, BHRAY_E_INVALID, "%s: the slot holds %d points and %d normals", name, m.point_count, m.normal_count);
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = launch_batch(c); if (rc) return rc; }          // staged frames show the old geometry
     HIPCHK(c, sync_all(c));                                   // and the frames in flight read the buffers that are rewritten here
+    if (after) HIPCHK(c, hipStreamWaitEvent(c->slots[0].stream, after, 0));
     return build_on_device(c, m, [&](hipStream_t st) {
-        if (points) HIPCHK(c, hipMemcpyAsync(m.points, points, (size_t)m.point_count * 16, hipMemcpyHostToDevice, st));
-        if (normals) HIPCHK(c, hipMemcpyAsync(m.normals, normals, (size_t)m.normal_count * 16, hipMemcpyHostToDevice, st));
+        if (points) HIPCHK(c, hipMemcpyAsync(m.posed ? m.rest_points : m.points, points, (size_t)m.point_count * 16, kind, st));
+        if (normals) HIPCHK(c, hipMemcpyAsync(m.posed ? m.rest_normals : m.normals, normals, (size_t)m.normal_count * 16, kind, st));
+        if (m.posed) HIPCHK(c, launch_bvh_pose(m.rest_points, m.rest_normals, m.points, m.normals, m.point_count, m.normal_count, m.pose, st));
+        return (int)BHRAY_OK;
+    });
+}
+}  // namespace
+
+int dev_update_model_vertices(bhray_dev* c, uint32_t mi, const float* points, int32_t point_count, const float* normals, int32_t normal_count) {
+    return update_vertices(c, mi, points, point_count, normals, normal_count, hipMemcpyHostToDevice, nullptr, "bhray_update_model_vertices");
+}
+
+int dev_update_model_vertices_device(bhray_dev* c, uint32_t mi, const void* d_points, int32_t point_count, const void* d_normals, int32_t normal_count, hipEvent_t after) {
+    return update_vertices(c, mi, d_points, point_count, d_normals, normal_count, hipMemcpyDefault, after, "bhray_update_model_vertices_device");
+}
+
+// DESIGN.md §14.  The pose is absolute: always rest arrays -> points / normals.  NULL: the rest arrays back, byte for byte.
+int dev_set_model_pose(bhray_dev* c, uint32_t mi, const float* pose) {
+    if (!c) return BHRAY_E_INVALID;
+    if (mi >= BHRAY_MAX_MODELS) return fail(c, BHRAY_E_INVALID, "bad model arguments");
+    ModelStore& m = c->models[mi];
+    if (!m.loaded || !m.build) return fail(c, BHRAY_E_STATE, "bhray_set_model_pose: slot %u was not built by bhray_upload_model_build", mi);
+    if (pose) for (int i = 0; i < 12; i++) if (!std::isfinite(pose[i])) return fail(c, BHRAY_E_INVALID, "bhray_set_model_pose: pose entry %d is not finite", i);
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = launch_batch(c); if (rc) return rc; }          // staged frames show the old geometry
+    HIPCHK(c, sync_all(c));
+    hipStream_t s = c->slots[0].stream;
+    const size_t pb = (size_t)std::max(m.point_count, 1) * 16, nb = (size_t)std::max(m.normal_count, 1) * 16;
+    if (pose && !m.posed) {                                   // what the slot holds now is its rest geometry
+        if (!m.rest_points) HIPCHK(c, hipMalloc(&m.rest_points, pb));
+        if (!m.rest_normals) HIPCHK(c, hipMalloc(&m.rest_normals, nb));
+        HIPCHK(c, hipMemcpyAsync(m.rest_points, m.points, (size_t)m.point_count * 16, hipMemcpyDeviceToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(m.rest_normals, m.normals, (size_t)m.normal_count * 16, hipMemcpyDeviceToDevice, s));
+    }
+    const bool restore = !pose && m.posed;
+    if (pose) { memcpy(m.pose, pose, sizeof m.pose); m.posed = true; } else m.posed = false;
+    return build_on_device(c, m, [&](hipStream_t st) {
+        if (m.posed) HIPCHK(c, launch_bvh_pose(m.rest_points, m.rest_normals, m.points, m.normals, m.point_count, m.normal_count, m.pose, st));
+        else if (restore) {
+            HIPCHK(c, hipMemcpyAsync(m.points, m.rest_points, (size_t)m.point_count * 16, hipMemcpyDeviceToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(m.normals, m.rest_normals, (size_t)m.normal_count * 16, hipMemcpyDeviceToDevice, st));
+        }
         return (int)BHRAY_OK;
     });
 }
@@ -951,6 +1001,21 @@ int dev_read_model_bvh(bhray_dev* c, uint32_t mi, bhray_node* nodes, uint32_t no
     HIPCHK(c, hipSetDevice(c->device));
     if (nn > 0) HIPCHK(c, hipMemcpy(nodes, m.nodes, (size_t)nn * 32, hipMemcpyDeviceToHost));
     if (nt > 0) HIPCHK(c, hipMemcpy(lookup, m.lookup, (size_t)nt * 4, hipMemcpyDeviceToHost));
+    return BHRAY_OK;
+}
+
+int dev_read_model_vertices(bhray_dev* c, uint32_t mi, float* points, uint32_t point_cap, float* normals, uint32_t normal_cap, uint32_t* point_count, uint32_t* normal_count) {
+    if (!c) return BHRAY_E_INVALID;
+    if (mi >= BHRAY_MAX_MODELS) return fail(c, BHRAY_E_INVALID, "bad model arguments");
+    const ModelStore& m = c->models[mi];
+    if (!m.loaded) return fail(c, BHRAY_E_STATE, "model slot %u is empty", mi);
+    const uint32_t np = m.triangle_count > 0 ? (uint32_t)m.point_count : 0u, nn = m.triangle_count > 0 ? (uint32_t)m.normal_count : 0u;   // a slot of 0 triangles holds no arrays
+    if (point_count) *point_count = np;
+    if (normal_count) *normal_count = nn;
+    if ((points && np > point_cap) || (normals && nn > normal_cap)) return fail(c, BHRAY_E_INVALID, "bhray_read_model_vertices: the slot holds %u points and %u normals", np, nn);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (points && np > 0) HIPCHK(c, hipMemcpy(points, m.points, (size_t)np * 16, hipMemcpyDeviceToHost));
+    if (normals && nn > 0) HIPCHK(c, hipMemcpy(normals, m.normals, (size_t)nn * 16, hipMemcpyDeviceToHost));
     return BHRAY_OK;
 }
 

@@ -9,6 +9,7 @@
 //   wave waits for another, min / max are exact: the bytes do not depend on scheduling, device or run.
 //   -> the 96-byte leaf records -> 64 bytes of result (counts, depth, the root-children union for ModelDev::root_cull).
 // The per-element steps are bhray_bvh_core.h (plain C++ that a host program can run as well).
+// launch_bvh_pose writes a slot's points and normals from its rest arrays and a 3x4 affine pose; the build above then runs on the result.
 #include <cstring>
 
 #include <hip/hip_runtime.h>
@@ -132,7 +133,39 @@ __global__ void bvh_result_kernel(const BvhF4* nodes, const int32_t* level, cons
     *out = r;
 }
 
+// The affine pose of a device-built slot: vertex v < P is rest point v, the others are rest normals.  One float4 in, one float4 out per
+// thread (lane i at base + 16 i: one 1 KiB access per wave); the 12 pose floats are a kernel argument, wave-uniform, in SGPRs.  One rounded binary32
+// operation at a time in the order written (-ffp-contract=off): row r of a point is ((m[4r] x + m[4r+1] y) + m[4r+2] z) + m[4r+3], a normal gets the
+// linear part only, w is copied.  The wave that holds the last point and the first normal is the only one whose lanes differ in `point`.
+struct BvhPose { float m[12]; };
+__global__ __launch_bounds__(BLOCK) void bvh_pose_kernel(const float4* rest_points, const float4* rest_normals, float4* points, float4* normals, int P, int N, BvhPose pose) {
+    const int v = blockIdx.x * BLOCK + threadIdx.x;
+    if (v >= P + N) return;
+    const bool point = v < P;
+    const float4 in = *(point ? rest_points + v : rest_normals + (v - P));
+    float4* const dst = point ? points + v : normals + (v - P);      // one address, so one 16-byte store
+    float4 out;
+    float r[3];
+    for (int a = 0; a < 3; a++) {
+        const float lin = ((pose.m[4 * a] * in.x + pose.m[4 * a + 1] * in.y) + pose.m[4 * a + 2] * in.z);
+        r[a] = point ? lin + pose.m[4 * a + 3] : lin;
+    }
+    out.x = r[0]; out.y = r[1]; out.z = r[2]; out.w = in.w;
+    *dst = out;
+}
+
 }  // namespace
+
+hipError_t launch_bvh_pose(const float4* rest_points, const float4* rest_normals, float4* points, float4* normals, int point_count, int normal_count,
+                           const float pose[12], hipStream_t s) {
+    if (point_count < 0 || normal_count < 0 || point_count > BHRAY_MAX_MODEL_VERTICES || normal_count > BHRAY_MAX_MODEL_VERTICES) return hipErrorInvalidValue;
+    const int n = point_count + normal_count;                      // at most 2^20
+    if (n == 0) return hipSuccess;
+    BvhPose p;
+    memcpy(p.m, pose, sizeof p.m);
+    hipLaunchKernelGGL(bvh_pose_kernel, dim3(blocks_for(n)), dim3(BLOCK), 0, s, rest_points, rest_normals, points, normals, point_count, normal_count, p);
+    return hipGetLastError();
+}
 
 void bvh_build_destroy(BvhBuild* b) {
     if (!b) return;

@@ -58,6 +58,10 @@ int  dev_upload_model_uniform(bhray_dev* c, uint32_t model_index, const void* by
 int  dev_upload_model(bhray_dev* c, uint32_t model_index, const bhray_model_desc* desc);
 int  dev_upload_model_build(bhray_dev* c, uint32_t model_index, const bhray_model_desc* desc);    // tree built on the device (bhray_bvh.hip)
 int  dev_update_model_vertices(bhray_dev* c, uint32_t model_index, const float* points, int32_t point_count, const float* normals, int32_t normal_count);
+// the arrays in device memory (any device); copied on the build stream behind `after` (may be NULL: nothing to wait for)
+int  dev_update_model_vertices_device(bhray_dev* c, uint32_t model_index, const void* d_points, int32_t point_count, const void* d_normals, int32_t normal_count, hipEvent_t after);
+int  dev_set_model_pose(bhray_dev* c, uint32_t model_index, const float* pose_3x4);   // affine pose of a device-built slot; NULL: the rest arrays
+int  dev_read_model_vertices(bhray_dev* c, uint32_t model_index, float* points, uint32_t point_cap, float* normals, uint32_t normal_cap, uint32_t* point_count, uint32_t* normal_count);
 int  dev_get_model_build_info(bhray_dev* c, uint32_t model_index, bhray_model_build_info* out);
 int  dev_read_model_bvh(bhray_dev* c, uint32_t model_index, bhray_node* nodes, uint32_t node_cap, int32_t* lookup, uint32_t lookup_cap, uint32_t* node_count, uint32_t* triangle_count);
 int  dev_set_model_transform(bhray_dev* c, uint32_t model_index, const float position[3], int32_t visible);

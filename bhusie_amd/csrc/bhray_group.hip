@@ -1475,6 +1475,40 @@ int bhray_update_model_vertices(bhray_ctx* c, uint32_t mi, const float* points, 
     for (Part& p : c->parts) if (p.dev) DEV(c, p.dev, dev_update_model_vertices(p.dev, mi, points, point_count, normals, normal_count));
     return BHRAY_OK;
 }
+// the arrays lie in device memory: every engine copies them on its build stream, behind what `s` (NULL: the legacy stream, as bhray_wait_stream) holds now
+int bhray_update_model_vertices_device(bhray_ctx* c, uint32_t mi, const void* d_points, int32_t point_count, const void* d_normals, int32_t normal_count, void* s) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    if (c->gather) { int rc = group_sync(c); if (rc) return rc; }
+    int dev = -1;
+    for (Part& p : c->parts) if (p.dev) { dev = p.device; break; }
+    if (dev < 0) return gfail(c, BHRAY_E_STATE, "no local partition");
+    if (s) { int sd = -1; if (hipStreamGetDevice((hipStream_t)s, &sd) == hipSuccess && sd >= 0) dev = sd; }
+    GHIP(c, hipSetDevice(dev));
+    hipEvent_t ev = nullptr;
+    GHIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, (hipStream_t)s);
+    int rc = e == hipSuccess ? BHRAY_OK : gfail(c, BHRAY_E_HIP, "hipEventRecord: %s", hipGetErrorString(e));
+    for (Part& p : c->parts) if (p.dev && rc == BHRAY_OK) { rc = dev_update_model_vertices_device(p.dev, mi, d_points, point_count, d_normals, normal_count, ev); if (rc) rc = dfail(c, p.dev, rc); }
+    (void)hipSetDevice(dev);
+    (void)hipEventDestroy(ev);                                // every engine has synchronised its build stream: nothing waits for it any more
+    return rc;
+}
+// every local partition's device poses and rebuilds its own copy
+int bhray_set_model_pose(bhray_ctx* c, uint32_t mi, const float pose[12]) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    if (c->gather) { int rc = group_sync(c); if (rc) return rc; }
+    for (Part& p : c->parts) if (p.dev) DEV(c, p.dev, dev_set_model_pose(p.dev, mi, pose));
+    return BHRAY_OK;
+}
+int bhray_read_model_vertices(bhray_ctx* c, uint32_t mi, float* points, uint32_t point_cap, float* normals, uint32_t normal_cap, uint32_t* point_count, uint32_t* normal_count) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    if (c->gather) { int rc = group_sync(c); if (rc) return rc; }
+    for (Part& p : c->parts) if (p.dev) { DEV(c, p.dev, dev_read_model_vertices(p.dev, mi, points, point_cap, normals, normal_cap, point_count, normal_count)); return BHRAY_OK; }
+    return gfail(c, BHRAY_E_STATE, "no local partition");
+}
 int bhray_get_model_build_info(bhray_ctx* c, uint32_t mi, bhray_model_build_info* out) {
     if (!c) return BHRAY_E_INVALID;
     ENTER(c);

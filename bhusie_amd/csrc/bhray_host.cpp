@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <new>
 #include <string>
 #include <utility>
@@ -182,6 +183,34 @@ void bhray_black_hole_uniform_update(bhray_black_hole_uniform* u, const bhray_bl
     const float m[12] = {right.x, right.y, right.z, 0.0f, up.x, up.y, up.z, 0.0f, fwd.x, fwd.y, fwd.z, 0.0f};
     memcpy(u->rotation_matrix, m, sizeof m);
     u->normal[0] = up.x; u->normal[1] = up.y; u->normal[2] = up.z;
+}
+
+// The 3x4 pose of bhray_set_model_pose from the reference's Model fields: the quaternion of BlackHoleUniform::update above (same text), its
+// "Quaternion * Vector3" applied to the three axes (the columns of R, not normalised), A = R * scale, t = pivot - A pivot.
+int bhray_pose_from_euler(const float rotation[3], const float pivot[3], float scale, float pose_3x4_out[12]) {
+    if (!rotation || !pivot || !pose_3x4_out) return BHRAY_E_INVALID;
+    for (int i = 0; i < 3; i++) if (!std::isfinite(rotation[i]) || !std::isfinite(pivot[i])) return BHRAY_E_INVALID;
+    if (!std::isfinite(scale)) return BHRAY_E_INVALID;
+    const float half = 0.5f;
+    const float sx = sinf(rotation[0] * half), cx = cosf(rotation[0] * half);
+    const float sy = sinf(rotation[1] * half), cy = cosf(rotation[1] * half);
+    const float sz = sinf(rotation[2] * half), cz = cosf(rotation[2] * half);
+    const float qs = ((-sx * sy) * sz) + ((cx * cy) * cz);
+    const V3 qv = v3(((sx * cy) * cz) + ((sy * sz) * cx), ((-sx * sz) * cy) + ((sy * cx) * cz), ((sx * sy) * cz) + ((sz * cx) * cy));
+    const V3 axes[3] = {v3(1.0f, 0.0f, 0.0f), v3(0.0f, 1.0f, 0.0f), v3(0.0f, 0.0f, 1.0f)};
+    float A[3][3];
+    for (int col = 0; col < 3; col++) {
+        const V3 vec = axes[col];
+        const V3 tmp = cross(qv, vec) + vec * qs;
+        const V3 r = cross(qv, tmp) * 2.0f + vec;
+        A[0][col] = r.x * scale; A[1][col] = r.y * scale; A[2][col] = r.z * scale;
+    }
+    for (int r = 0; r < 3; r++) {
+        const float ap = ((A[r][0] * pivot[0] + A[r][1] * pivot[1]) + A[r][2] * pivot[2]);
+        pose_3x4_out[4 * r] = A[r][0]; pose_3x4_out[4 * r + 1] = A[r][1]; pose_3x4_out[4 * r + 2] = A[r][2];
+        pose_3x4_out[4 * r + 3] = pivot[r] - ap;
+    }
+    return BHRAY_OK;
 }
 
 int bhray_model_new(bhray_model** out) {

@@ -223,5 +223,9 @@ hipError_t launch_bvh_validate(BvhBuild* b, const int32_t* triangles, int point_
 // nodes: room for 2 T - 1 nodes; lookup: T; leaf: 6 T float4.  Enqueues only.
 hipError_t launch_bvh_build(BvhBuild* b, const float4* points, const float4* normals, const int32_t* triangles, float4* nodes, int32_t* lookup, float4* leaf,
                             BvhResult* d_result, hipStream_t s);
+// The affine pose of DESIGN.md §14: points[i] = A rest_points[i] + t, normals[i] = A rest_normals[i] (w copied), pose = row-major 3x4 (A | t).  One launch over
+// point_count + normal_count vertices; the counts are independent and either may be 0.  Enqueues only.
+hipError_t launch_bvh_pose(const float4* rest_points, const float4* rest_normals, float4* points, float4* normals, int point_count, int normal_count,
+                           const float pose[12], hipStream_t s);
 
 }  // namespace bhray

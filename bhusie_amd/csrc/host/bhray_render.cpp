@@ -1,7 +1,8 @@
 // bhray_render — minimal C++ host program over renderer.hpp: renders one frame of the reference's default scene
 // (camera (0,0,-19), hole at the origin, disk 2..10, R = 20; camera.rs:10-16, blackhole.rs:16-28) and writes the HDR frame
 // as raw little-endian f32 RGBA (row 0 = top).  Usage:
-//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--lensed-mesh] [--devices 0,1,2,...]
+//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...]
+// --pose: every --obj mesh is turned by the Euler rotation (RX, RY, RZ) about its own origin on the GPU (bhray_pose_from_euler + bhray_set_model_pose); needs --bvh device.
 // --lensed-mesh: the meshes are tested on every step inside the relativity sphere too (bhray_set_mesh_lensing): a mesh inside the sphere is visible.
 // --bvh device: every mesh's tree is built on the GPU (bhray_upload_model_build) instead of by the reference's host builder (the default).
 // --obj: repeatable; the i-th mesh goes to model slot i (Renderer::add_model), at the position its OBJ loader gives it.
@@ -137,9 +138,10 @@ int main(int argc, char** argv) {
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
         return 0;
     }
-    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--lensed-mesh] [--devices 0,1,...]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...]\n", argv[0]); return 2; }
     uint32_t bw = 72, bh = 41, levels = 4, disk = 256;
-    bool rk = false, bvh_device = false, lensed = false;
+    bool rk = false, bvh_device = false, lensed = false, posed = false;
+    float rotation[3] = {0.0f, 0.0f, 0.0f};
     std::vector<const char*> objs;
     std::vector<int> devices;
     for (int i = 2; i < argc; i++) {
@@ -149,10 +151,12 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--disk-size") && i + 1 < argc) disk = (uint32_t)std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--obj") && i + 1 < argc) objs.push_back(argv[++i]);
         else if (!std::strcmp(argv[i], "--bvh") && i + 1 < argc && (!std::strcmp(argv[i + 1], "device") || !std::strcmp(argv[i + 1], "reference"))) bvh_device = !std::strcmp(argv[++i], "device");
+        else if (!std::strcmp(argv[i], "--pose") && i + 3 < argc) { posed = true; for (int a = 0; a < 3; a++) rotation[a] = (float)std::atof(argv[++i]); }
         else if (!std::strcmp(argv[i], "--lensed-mesh")) lensed = true;
         else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) { for (const char* p = argv[++i]; *p; ) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p) p++; } }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
+    if (posed && !bvh_device) { std::fprintf(stderr, "--pose needs --bvh device (a pose is applied to a tree built on the GPU)\n"); return 2; }
     try {
         std::unique_ptr<bhusie::Renderer> rp(devices.empty() ? new bhusie::Renderer({bw, bh}, 3, levels) : new bhusie::Renderer({bw, bh}, 3, levels, devices));
         bhusie::Renderer& r = *rp;
@@ -164,6 +168,12 @@ int main(int argc, char** argv) {
         r.ray_pipeline().set_texture(BHRAY_TEX_SKY, grey, 1, 1);
         std::vector<bhusie::Model> models;
         for (const char* obj : objs) { models.emplace_back(obj); r.add_model(models.back(), bvh_device); }
+        if (posed) {
+            const float pivot[3] = {0.0f, 0.0f, 0.0f};
+            float pose[12];
+            bhusie::check(bhray_pose_from_euler(rotation, pivot, 1.0f, pose));
+            for (uint32_t i = 0; i < (uint32_t)models.size(); i++) r.ray_pipeline().set_model_pose(i, pose);
+        }
         r.ray_details.integration_method = rk ? 1 : 0;
         r.mesh_lensing = lensed;
         r.render(0.0f);

@@ -161,6 +161,8 @@ public:
     void update_model_vertices(uint32_t index, const float* points, int32_t point_count, const float* normals, int32_t normal_count) {
         check(bhray_update_model_vertices(ctx_, index, points, point_count, normals, normal_count), ctx_);
     }
+    // affine pose of a device-built slot, applied on the GPU (row-major 3x4, bhray_pose_from_euler makes one; nullptr: the rest geometry)
+    void set_model_pose(uint32_t index, const float* pose_3x4) { check(bhray_set_model_pose(ctx_, index, pose_3x4), ctx_); }
     void set_model_transform(uint32_t index, const float position[3], int32_t visible) { check(bhray_set_model_transform(ctx_, index, position, visible), ctx_); }
     void set_mesh_lensing(bool on) { check(bhray_set_mesh_lensing(ctx_, on ? 1 : 0), ctx_); }   // lensed meshes: from the next pass on
     void set_materials(const void* material_uniforms_128) { check(bhray_set_materials(ctx_, material_uniforms_128, 128), ctx_); }   // mod.rs:389 (ignored by the shader)

@@ -200,6 +200,9 @@ SYMBOLS = {
     "bhray_upload_model": (C.c_int, [vp, u32, P(BhrayModelDesc)]),
     "bhray_upload_model_build": (C.c_int, [vp, u32, P(BhrayModelDesc)]),
     "bhray_update_model_vertices": (C.c_int, [vp, u32, vp, i32, vp, i32]),
+    "bhray_update_model_vertices_device": (C.c_int, [vp, u32, vp, i32, vp, i32, vp]),
+    "bhray_set_model_pose": (C.c_int, [vp, u32, P(C.c_float)]),
+    "bhray_pose_from_euler": (C.c_int, [P(C.c_float), P(C.c_float), C.c_float, P(C.c_float)]),
     "bhray_set_model_transform": (C.c_int, [vp, u32, P(C.c_float), i32]),
     "bhray_set_uniforms": (C.c_int, [vp, vp, vp, vp]),
     "bhray_set_mesh_lensing": (C.c_int, [vp, i32]),
@@ -265,6 +268,7 @@ DIAG_SYMBOLS = {
     "bhray_get_gather_info": (C.c_int, [vp, P(BhrayGatherInfo)]),
     "bhray_get_model_build_info": (C.c_int, [vp, u32, P(BhrayModelBuildInfo)]),
     "bhray_read_model_bvh": (C.c_int, [vp, u32, vp, u32, vp, u32, P(u32), P(u32)]),
+    "bhray_read_model_vertices": (C.c_int, [vp, u32, vp, u32, vp, u32, P(u32), P(u32)]),
 }
 
 

@@ -45,6 +45,14 @@ def bloom_sizes(frame_w: int, frame_h: int):
     return [(int(a), int(b)) for a, b in zip(w, h)]
 
 
+def pose_from_euler(rotation, pivot=(0.0, 0.0, 0.0), scale=1.0) -> np.ndarray:
+    """The (3, 4) float32 pose [A | t] of RayPass.set_model_pose for a rotation (Euler angles, BlackHole's convention) about `pivot` with a uniform
+    scale: A = R * scale, t = pivot - A pivot (bhray_pose_from_euler: host arithmetic)."""
+    out = (C.c_float * 12)()
+    check(lib().bhray_pose_from_euler((C.c_float * 3)(*[float(x) for x in rotation]), (C.c_float * 3)(*[float(x) for x in pivot]), float(scale), out))
+    return np.array(out, dtype=np.float32).reshape(3, 4)
+
+
 def comm_unique_id() -> bytes:
     """A fresh RCCL communicator id (one process per GPU: call on ONE rank, hand the bytes to every rank's RayPass)."""
     buf = (C.c_uint8 * 128)()
@@ -196,6 +204,33 @@ class RayPass:
             assert a is None or (a.ndim == 2 and a.shape[1] == 4)
         check(self._L.bhray_update_model_vertices(self._h, index, p.ctypes.data if p is not None else None, len(p) if p is not None else 0,
                                                   n.ctypes.data if n is not None else None, len(n) if n is not None else 0), self._h, self._L)
+
+    def update_model_vertices_device(self, d_points, d_normals, point_count, normal_count, stream=None, index=0):
+        """update_model_vertices with the arrays in device memory: d_points / d_normals are device pointers (int; None keeps that array) to point_count /
+        normal_count float4s; the copies are ordered behind everything enqueued so far on hipStream_t `stream` (None: the legacy stream).  The call
+        synchronises, so the source may be overwritten once it returns (bhray_update_model_vertices_device)."""
+        check(self._L.bhray_update_model_vertices_device(self._h, index, C.c_void_p(d_points) if d_points else None, int(point_count) if d_points else 0,
+                                                         C.c_void_p(d_normals) if d_normals else None, int(normal_count) if d_normals else 0,
+                                                         C.c_void_p(stream) if stream else None), self._h, self._L)
+
+    def set_model_pose(self, pose, index=0):
+        """Affine pose of a slot built by upload_model_build, applied to its rest geometry on the GPU; the tree is rebuilt there (bhray_set_model_pose,
+        DESIGN.md §14).  pose: 12 floats, row-major 3x4 [A | t] (pose_from_euler makes one), always relative to the rest arrays; None: back to them."""
+        if pose is None:
+            m = None
+        else:
+            a = np.ascontiguousarray(pose, dtype=np.float32).reshape(-1)
+            assert a.size == 12
+            m = (C.c_float * 12)(*[float(x) for x in a])
+        check(self._L.bhray_set_model_pose(self._h, index, m), self._h, self._L)
+
+    def read_model_vertices(self, index=0) -> dict:
+        """dict(points, normals): the (n, 4) float32 arrays the kernels read for slot `index` now - posed, if a pose is in force (bhray_read_model_vertices)"""
+        np_, nn = C.c_uint32(), C.c_uint32()
+        check(self._L.bhray_read_model_vertices(self._h, index, None, 0, None, 0, C.byref(np_), C.byref(nn)), self._h, self._L)      # the counts
+        points, normals = np.zeros((np_.value, 4), dtype=np.float32), np.zeros((nn.value, 4), dtype=np.float32)
+        check(self._L.bhray_read_model_vertices(self._h, index, points.ctypes.data, np_.value, normals.ctypes.data, nn.value, C.byref(np_), C.byref(nn)), self._h, self._L)
+        return dict(points=points, normals=normals)
 
     def read_model_bvh(self, index=0) -> dict:
         """dict(nodes, bvh_lookup) - the shape of Model.arrays() - of the tree slot `index` holds on the device, in the device's numbering."""
@@ -492,6 +527,7 @@ class Renderer:
         self.ray_details = RayDetails()                      # mod.rs:116-121
         self.ray_pass = RayPass(cfg if cfg is not None else ladder_from_base((72, 41), 3, 4), device=device, **kw)
         self.models: list[Model] = []                        # scene.models: slot i of the ctx holds models[i]
+        self._device_built: list[bool] = []                  # ... and whether its tree was built on the GPU (add_model(build="device"))
         self.mesh_lensing = False                            # lensed meshes (RayPass.set_mesh_lensing): applied before each render
         self._lensing_applied = False                        # what the ctx was last told (its default: off)
 
@@ -503,9 +539,9 @@ class Renderer:
         """Model slot 0 (replaced if it is there)."""
         self.ray_pass.upload_model(model, 0)
         if self.models:
-            self.models[0] = model
+            self.models[0], self._device_built[0] = model, False
         else:
-            self.models.append(model)
+            self.models.append(model); self._device_built.append(False)
         self.ray_details.model_count = len(self.models)      # mod.rs:384 (scene.models.size())
 
     def add_model(self, model: Model, build: str = "host") -> int:
@@ -520,9 +556,18 @@ class Renderer:
             self.ray_pass.upload_model_build(model, index)
         else:
             self.ray_pass.upload_model(model, index)
-        self.models.append(model)
+        self.models.append(model); self._device_built.append(build == "device")
         self.ray_details.model_count = len(self.models)      # mod.rs:384 (scene.models.size())
         return index
+
+    def set_model_rotation(self, index: int, rotation, pivot=(0.0, 0.0, 0.0), scale: float = 1.0):
+        """What the reference's Model.rotation promises and never does: model `index` (added with build="device") turned by the Euler angles `rotation`
+        about `pivot` (model space), scaled by `scale` - on the GPU, from its rest geometry (pose_from_euler + RayPass.set_model_pose)."""
+        if not 0 <= index < len(self.models):
+            raise ValueError(f"set_model_rotation: no model {index}")
+        if not self._device_built[index]:
+            raise ValueError(f"set_model_rotation: model {index} was built on the host; add it with build='device'")
+        self.ray_pass.set_model_pose(pose_from_euler(rotation, pivot, scale), index)
 
     def render(self, dt: float = 0.0):
         self.ray_details.time += dt                          # mod.rs:382

@@ -121,7 +121,8 @@ typedef struct bhray_model_header {     /* first 48 bytes of ModelUniform (Rust 
     float    position[3];
     int32_t  visible;
     float    rotation[3];               /* uploaded, never applied by the shader (ray.wgsl:56); a host that wants a rotated or
-                                           deforming model sends the moved vertices through bhray_update_model_vertices */
+                                           deforming model sends the moved vertices through bhray_update_model_vertices, or
+                                           turns a device-built slot with bhray_pose_from_euler + bhray_set_model_pose */
     uint32_t pad3;
     int32_t  point_count;
     int32_t  normal_count;
@@ -379,6 +380,42 @@ int bhray_upload_model_build(bhray_ctx* ctx, uint32_t model_index, const bhray_m
  * BHRAY_E_STATE for a slot that was not built on the device, BHRAY_E_INVALID when a count differs. */
 int bhray_update_model_vertices(bhray_ctx* ctx, uint32_t model_index, const float* points, int32_t point_count,
                                 const float* normals, int32_t normal_count);
+/* As bhray_update_model_vertices with the arrays in DEVICE memory (a simulation or skinning pass on the same GPU): same
+ * slot rules, count checks and NULL-keeps rule.  The copies are hipMemcpyAsync(.., hipMemcpyDefault) on the build stream,
+ * placed behind an event recorded on hip_stream (NULL: the legacy stream, as bhray_wait_stream), so they see everything
+ * enqueued there so far.  On a ctx of several devices every engine copies from the same source (the runtime does the
+ * peer copy).  The call synchronises as the host variant does: the source may be overwritten once it returns.        */
+int bhray_update_model_vertices_device(bhray_ctx* ctx, uint32_t model_index, const void* d_points, int32_t point_count,
+                                       const void* d_normals, int32_t normal_count, void* hip_stream);
+/* Affine pose of a slot built by bhray_upload_model_build, applied on the device: 48 bytes of host
+ * traffic move a mesh, the tree is rebuilt by the builder of §12 from the posed arrays.
+ * pose_3x4: 12 floats, row-major: m[4r+0..2] = row r of the linear part A, m[4r+3] = t[r].  NULL = back to the rest arrays.
+ *  - BHRAY_E_STATE for an empty or host-built slot, BHRAY_E_INVALID for model_index >= BHRAY_MAX_MODELS and for a pose
+ *    entry that is not finite (checked on the host before anything is enqueued: the slot keeps what it held).
+ *  - The pose is ABSOLUTE: always applied to the slot's rest arrays, never to the result of an earlier pose.  The first
+ *    pose call of a slot allocates the rest buffers and fills them, device to device, with the points and normals the
+ *    slot holds; a slot that is never posed allocates nothing; the rest buffers are freed with the slot.  NULL copies
+ *    the rest arrays back byte for byte and rebuilds.
+ *  - binary32, one rounded operation at a time in the order written (no fused multiply-add): a rest point (x, y, z, w)
+ *    becomes x' = ((m[0]*x + m[1]*y) + m[2]*z) + m[3], y' and z' likewise with rows 1 and 2, w' = the bits of w.  A rest
+ *    normal gets the same sums without the last addition (A n: no translation, no renormalisation), w copied.  There is
+ *    no fast path for the identity: it is evaluated like any other pose, so a point's -0 coordinate becomes +0.
+ *  - Under a non-rigid A the normal is NOT the inverse-transpose normal; it only colours the hit (ray.wgsl:834-836).
+ *  - The preconditions of §12 (finite coordinates, extents below 2^127) apply to the POSED arrays and are the caller's
+ *    responsibility, as for uploaded arrays.
+ *  - Synchronisation is that of bhray_update_model_vertices: staged frames are launched first and keep the old
+ *    geometry, the frames in flight are waited for, then the pose kernel and the build run.  In
+ *    bhray_model_build_info the pose launch takes the place of the copies: upload_ms is then the pose kernel's time.
+ *  - bhray_set_model_transform's position stays the shader's offset, applied on top of the posed geometry.
+ *  - On a posed slot bhray_update_model_vertices and bhray_update_model_vertices_device write the new arrays into the
+ *    REST buffers and apply the pose in force again; on an unposed slot they behave as before.
+ *  - One process per GPU: every rank calls it alike.                                                                  */
+int bhray_set_model_pose(bhray_ctx* ctx, uint32_t model_index, const float pose_3x4[12]);
+/* Host helper, no device: the pose of a rotation (Euler angles, the convention of bhray_black_hole_uniform_update: the
+ * same quaternion, applied to the three axes as the columns of R) about `pivot` with a uniform `scale`: A = R * scale,
+ * t = pivot - A pivot.  What maps the reference's Model.rotation (never applied there) to bhray_set_model_pose.
+ * BHRAY_E_INVALID for a NULL argument or an input that is not finite.                                                  */
+int bhray_pose_from_euler(const float rotation[3], const float pivot[3], float scale, float pose_3x4_out[12]);
 /* Per-frame model state without re-uploading 48 MB (the reference re-uploads, mod.rs:391).  */
 int bhray_set_model_transform(bhray_ctx* ctx, uint32_t model_index, const float position[3], int32_t visible);
 

@@ -154,13 +154,19 @@ int bhray_read_level(bhray_ctx* ctx, uint32_t level, float* dst_rgba32f, size_t 
  * filled, the rest 0.  An empty slot: BHRAY_E_STATE.                                                                  */
 typedef struct bhray_model_build_info {
     uint32_t built_on_device, triangles, nodes, leaves, max_leaf, max_depth;
-    float    upload_ms, build_ms;   /* HIP events around the copies / the build kernels of the last build */
+    float    upload_ms, build_ms;   /* HIP events around the copies / the build kernels of the last build; after
+                                       bhray_set_model_pose the pose kernel stands where the copies stood (upload_ms is its time) */
 } bhray_model_build_info;
 int bhray_get_model_build_info(bhray_ctx* ctx, uint32_t model_index, bhray_model_build_info* out);
 /* The tree a slot holds on the device (any slot, host-built ones too; first local partition): node_count nodes in
  * the device's numbering and triangle_count lookup entries.  Caps too small: BHRAY_E_INVALID, counts still written. */
 int bhray_read_model_bvh(bhray_ctx* ctx, uint32_t model_index, bhray_node* nodes, uint32_t node_cap, int32_t* lookup,
                          uint32_t lookup_cap, uint32_t* node_count, uint32_t* triangle_count);
+/* The points / normals a slot's kernels read now (posed, if a pose is in force: DESIGN.md §14; first local partition), 4 floats
+ * each.  Either pointer may be NULL (that array is not read).  Caps too small: BHRAY_E_INVALID, counts still written.
+ * A slot of 0 triangles holds no arrays: both counts are 0.                                                            */
+int bhray_read_model_vertices(bhray_ctx* ctx, uint32_t model_index, float* points, uint32_t point_cap, float* normals, uint32_t normal_cap,
+                              uint32_t* point_count, uint32_t* normal_count);
 
 /* ------------------------------------------------------------------------------------------
  * Gather statistics (multi-GPU)

@@ -9,7 +9,9 @@
  trace    ms per frame of configs[2] (1918x1081 ladder, adaptive RK) in a 20-frame block (22 frame slots, 2 speculative levels; median
           of 5 blocks after 2) and one frame at a time (median of 12 after 3) with the reference tree, the SAH tree and the device tree.
  animate  frames per second of the loop update vertices -> render -> resolve_sky -> sync at 1918x1081, device path against the same loop
-          through the host builder (model rebuilt with bhray_model_build_bvh and uploaded again every frame)."""
+          through the host builder (model rebuilt with bhray_model_build_bvh and uploaded again every frame).
+ pose     the same for a mesh posed on the device: wall clock of bhray_set_model_pose with its upload_ms (the pose kernel) and
+          build_ms, median of 20 after 3, and frames per second of the loop set pose -> render -> resolve_sky -> sync, beside the host-update loop."""
 import json
 import os
 import statistics
@@ -128,6 +130,26 @@ def main():
         rp.upload_model_build(model)
         r["animation_fps_device"] = round(1e3 / med_ms(animate_device, 20, 3), 2)
         r["animation_fps_host"] = round(1e3 / med_ms(animate_host, 3, 1), 3)
+        # -- the posed animation: 48 bytes per frame instead of the moved arrays
+        rp.upload_model_build(model)
+        turn = [0]
+        pv = {"upload_ms": [], "build_ms": []}
+
+        def pose():
+            turn[0] += 1
+            rp.set_model_pose(B.pose_from_euler((0.0, 0.01 * turn[0], 0.0)))
+
+        def pose_and_note():
+            pose()
+            i = rp.model_build_info()
+            pv["upload_ms"].append(i["upload_ms"]); pv["build_ms"].append(i["build_ms"])
+
+        def animate_pose():
+            pose(); show()
+        r["set_model_pose_ms"] = med_ms(pose_and_note, 20, 3)
+        r["pose_event_upload_ms"] = round(statistics.median(pv["upload_ms"][3:]), 4)
+        r["pose_event_build_ms"] = round(statistics.median(pv["build_ms"][3:]), 4)
+        r["animation_fps_pose"] = round(1e3 / med_ms(animate_pose, 20, 3), 2)
         rp.close()
         # -- what the tree costs to trace
         model.build_bvh()
