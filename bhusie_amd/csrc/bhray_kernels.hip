@@ -26,14 +26,61 @@
 #include "bhray_internal.h"
 #include "bhray_math.h"
 
+#ifndef BHRAY_PHASE_SEQ
+#define BHRAY_PHASE_SEQ 7        // The trace wave's phases between two batches of steps (refill, disk shading, flat passes, epilogue) and the hit tests on the step's rare path with the short
+                                 // correctly rounded sequences of N8 where the shader's text has 1/x, sqrt(x) or a texel's byte / 255 - rcp_rn, sqrt_rn, unorm8_rn and the `_ph` twins below -
+                                 // instead of the compiler's IEEE lowering: the same bits on every input (bhray_selftest), 7-11 vector instructions less per use, in code a whole wave executes
+                                 // for the few lanes that need it.  General quotients a / b stay the IEEE lowering.  Per build, as BHRAY_ERR_SKIP's bits: bit 0 the dense no-mesh builds (the
+                                 // flagship's), bit 1 the latency no-mesh builds (and their quad march), bit 2 the dense mesh builds, bit 3 the latency mesh builds, lensed ones included (off:
+                                 // their scratch grows by 4-24 bytes per lane with the sequences' range tests - profiles/r15_trace_resource_usage.txt).  0 (`make phases0`: libbhray_phases0.so,
+                                 // what tests/test_gpu_phase_seq.py and the A/B of profiles/EXPERIMENTS.md R15.1 compare with): the trace kernels' text before, function by function.
+#endif
+
+#ifndef BHRAY_POW13
+#define BHRAY_POW13 0            // the disk's optical depth pow(30 * density, 1.3) as bh_pow_1p3 (bhray_math.h: the specialised form, carried in binary64, within 0.500000 ulp of the real power -
+                                 // tests/test_pow13_cpu.py) instead of the device library's general powf (1-2 ulp): the one place where colour pixels' bits change; direction pixels and classes
+                                 // do not.  Bits per build as BHRAY_PHASE_SEQ's; never the counting kernels.  OFF in what ships: the binary64 pairs cost the dense no-mesh builds their bucket
+                                 // (80 VGPRs and 52-92 bytes of scratch per lane instead of 0) and every mesh build 100-128 bytes more scratch (profiles/r15_trace_resource_usage.txt); only the
+                                 // latency no-mesh builds hold it (<= 128 VGPRs, 0 bytes), and one library must not colour a frame differently on one slot and on 22.  `make pow13`
+                                 // (-DBHRAY_POW13=2 -> libbhray_pow13.so) builds those for tests/test_gpu_phase_seq.py, which holds the device's form to the colour bar.
+#endif
+
 namespace bhray {
+
+constexpr bool pow13_build(bool models, bool dense) { return (BHRAY_POW13 & (models ? (dense ? 4 : 8) : (dense ? 1 : 2))) != 0; }
+constexpr bool POW13_QUAD = pow13_build(false, false);
+constexpr bool phase_seq_build(bool models, bool dense) { return (BHRAY_PHASE_SEQ & (models ? (dense ? 4 : 8) : (dense ? 1 : 2))) != 0; }
+constexpr bool PHASE_SEQ_QUAD = phase_seq_build(false, false);          // the quad march (bhray_quad.inc) is a part of the latency no-mesh builds: it names this at its calls
+
+// The `_ph` twins of bhray_math.h's sqrtf / 1.0f / x / length / distance / fdistance / normalize / div_s for the device-only code of the phases, SEQ per build (defined behind
+// rcp_rn / sqrt_rn below; bhray_math.h's own forms stay what the host code and the CPU restatements use, and are what SEQ = false evaluates).
+template <bool SEQ> __device__ __forceinline__ float sqrt_ph(float x);                       // == sqrtf(x)
+template <bool SEQ> __device__ __forceinline__ float rcp_ph(float x);                        // == 1.0f / x
+template <bool SEQ> __device__ __forceinline__ float length_ph(F3 a);                        // == length(a)
+template <bool SEQ> __device__ __forceinline__ float distance_ph(F3 a, F3 b);                // == distance(a, b)
+template <bool SEQ> __device__ __forceinline__ float fdistance_ph(F3 a, F3 b);               // == fdistance(a, b)
+template <bool SEQ> __device__ __forceinline__ F3 div_s_ph(F3 a, float s);                   // == div_s(a, s)
+template <bool SEQ> __device__ __forceinline__ F3 normalize_ph(F3 a);                        // == normalize(a)
+__device__ __forceinline__ void dist_rsqrt_rn(float d2, float& dist, float& rs);             // dist = sqrtf(d2), rs = 1.0f / sqrtf(dist)
+__device__ __forceinline__ void two_over_rn(float a, float b, float& ra, float& rb);         // ra = 2.0f / a, rb = 2.0f / b
+
+// A texel's byte as unorm: == x / 255.0f for the 256 values a byte takes (every one of them checked on the device by bhray_selftest and against exact rational arithmetic by
+// tests/test_phase_seq_cpu.py): the product with RN(1/255) and one fused residual correction (Markstein) - 3 instructions for the IEEE lowering's 10, sixteen times per bilinear sample.
+__device__ __forceinline__ float unorm8_rn(float x) {
+    const float r = 0x1.010102p-8f;                                     // RN(1 / 255)
+    const float q0 = x * r;
+    return __builtin_fmaf(__builtin_fmaf(-255.0f, q0, x), r, q0);
+}
+template <bool SEQ> __device__ __forceinline__ float unorm8(float x) { if constexpr (SEQ) return unorm8_rn(x); else return x / 255.0f; }
 
 // ------------------------------------------------------------------------------------------
 // textures: RGBA8 unorm, bilinear, clamp-to-edge (texture.rs:32,61-69; textureSampleLevel 0)
+// (SEQ: the bytes through unorm8_rn - the trace kernels' samples, per build; the sky pass keeps the division)
 // ------------------------------------------------------------------------------------------
+template <bool SEQ>
 __device__ __forceinline__ float4 texel(const TexDev& t, int x, int y) {
     const uchar4 p = *reinterpret_cast<const uchar4*>(t.rgba + 4 * ((size_t)y * (size_t)t.w + (size_t)x));
-    return make_float4((float)p.x / 255.0f, (float)p.y / 255.0f, (float)p.z / 255.0f, (float)p.w / 255.0f);
+    return make_float4(unorm8<SEQ>((float)p.x), unorm8<SEQ>((float)p.y), unorm8<SEQ>((float)p.z), unorm8<SEQ>((float)p.w));
 }
 __device__ __forceinline__ float unit_coord(float u, int n, int& i0, int& i1) {
     float x = u * (float)n - 0.5f;
@@ -46,11 +93,12 @@ __device__ __forceinline__ float unit_coord(float u, int n, int& i0, int& i1) {
     i0 = a; i1 = b;
     return x - fl;
 }
+template <bool SEQ>
 __device__ __forceinline__ float4 sample_bilinear(const TexDev& t, float u, float v) {
     int x0, x1, y0, y1;
     float fx = unit_coord(u, t.w, x0, x1);
     float fy = unit_coord(v, t.h, y0, y1);
-    float4 a = texel(t, x0, y0), b = texel(t, x1, y0), c = texel(t, x0, y1), d = texel(t, x1, y1);
+    float4 a = texel<SEQ>(t, x0, y0), b = texel<SEQ>(t, x1, y0), c = texel<SEQ>(t, x0, y1), d = texel<SEQ>(t, x1, y1);
     float4 r;
     r.x = mix_(mix_(a.x, b.x, fx), mix_(c.x, d.x, fx), fy);
     r.y = mix_(mix_(a.y, b.y, fx), mix_(c.y, d.y, fx), fy);
@@ -73,9 +121,10 @@ __device__ __forceinline__ BilinearTaps fetch_bilinear(const TexDev& t, float u,
     r.d = *reinterpret_cast<const uchar4*>(t.rgba + 4 * ((size_t)y1 * (size_t)t.w + (size_t)x1));
     return r;
 }
-__device__ __forceinline__ float4 unorm4(uchar4 p) { return make_float4((float)p.x / 255.0f, (float)p.y / 255.0f, (float)p.z / 255.0f, (float)p.w / 255.0f); }
+template <bool SEQ> __device__ __forceinline__ float4 unorm4(uchar4 p) { return make_float4(unorm8<SEQ>((float)p.x), unorm8<SEQ>((float)p.y), unorm8<SEQ>((float)p.z), unorm8<SEQ>((float)p.w)); }
+template <bool SEQ>
 __device__ __forceinline__ float4 blend_bilinear(const BilinearTaps& t) {
-    const float4 a = unorm4(t.a), b = unorm4(t.b), c = unorm4(t.c), d = unorm4(t.d);
+    const float4 a = unorm4<SEQ>(t.a), b = unorm4<SEQ>(t.b), c = unorm4<SEQ>(t.c), d = unorm4<SEQ>(t.d);
     float4 r;
     r.x = mix_(mix_(a.x, b.x, t.fx), mix_(c.x, d.x, t.fx), t.fy);
     r.y = mix_(mix_(a.y, b.y, t.fx), mix_(c.y, d.y, t.fx), t.fy);
@@ -95,6 +144,7 @@ struct Hit {            // RenderState (ray.wgsl:92-98) without the members noth
 };
 
 // hit_sphere, ray.wgsl:725-766.  Returns hit and t (the normal is never consumed on this path).
+template <bool SEQ>
 __device__ __forceinline__ bool hit_sphere(F3 pos, F3 dir, float radius, F3 center, float t_min, float t_max, float& t_out) {
     F3 oc = pos - center;
     float a = dot(dir, dir);
@@ -102,7 +152,7 @@ __device__ __forceinline__ bool hit_sphere(F3 pos, F3 dir, float radius, F3 cent
     float c = dot(oc, oc) - radius * radius;
     float disc = b * b - 4.0f * a * c;
     if (disc > 0.0f) {
-        float sq = sqrtf(disc);
+        float sq = sqrt_ph<SEQ>(disc);
         float t1 = (-b - sq) / (2.0f * a);
         float t2 = (-b + sq) / (2.0f * a);
         float tc = t_max;
@@ -114,6 +164,7 @@ __device__ __forceinline__ bool hit_sphere(F3 pos, F3 dir, float radius, F3 cent
 }
 
 // hit_torus2d, ray.wgsl:668-701.
+template <bool SEQ>
 __device__ __forceinline__ bool hit_torus2d(F3 pos, F3 dir, float inner, float outer, F3 tpos, F3 normal,
                                             float t_min, float t_max, float& t_out) {
     float denom = dot(normal, dir);
@@ -121,7 +172,7 @@ __device__ __forceinline__ bool hit_torus2d(F3 pos, F3 dir, float inner, float o
     float t = dot(dist, normal) / denom;
     if (t < t_max && t > t_min) {
         F3 ip = pos + dir * t;
-        float dc = distance(tpos, ip);
+        float dc = distance_ph<SEQ>(tpos, ip);
         if (dc >= inner && dc <= outer) { t_out = t; return true; }
     }
     return false;
@@ -164,20 +215,26 @@ __device__ __forceinline__ HotParams load_hot(const FrameParams& P) {
 }
 
 // Disk shading, ray.wgsl:612-663 (the part of hit_black_hole after the disk won).
-template <bool COUNT>
+template <bool COUNT, bool SEQ, bool POW13>
 __device__ __forceinline__ void shade_disk(const HotParams& P, F3 pos, F3 dir, float t, float total_distance, Hit& rs,
                                         unsigned long long* cnt) {
     F3 bpos = P.bh;
     F3 ip = pos + dir * t;
-    float dist = distance(bpos, ip);
-    float density = 1.0f - length(div_s(ip, P.outer));
+    // SEQ: the distance and the reciprocal of its root behind ONE range test (dist_rsqrt_rn); the else arms of this function are the text before, word for word
+    float dist, inv_sqrt_dist = 0.0f;
+    if constexpr (SEQ) { const F3 bi = bpos - ip; dist_rsqrt_rn(dot(bi, bi), dist, inv_sqrt_dist); }
+    else dist = distance(bpos, ip);
+    float density = 1.0f - length_ph<SEQ>(div_s_ph<SEQ>(ip, P.outer));
     {
         float e0 = P.inner, e1 = P.inner + 1.0f;
         float s = clamp_((dist - e0) / (e1 - e0), 0.0f, 1.0f);
         density *= s * s * (3.0f - 2.0f * s);
     }
-    density *= 1.0f / sqrtf(dist);
-    float od = powf(30.0f * density, 1.3f);
+    if constexpr (SEQ) density *= inv_sqrt_dist;
+    else density *= 1.0f / sqrtf(dist);
+    float od;
+    if constexpr (POW13) od = bh_pow_1p3(30.0f * density);
+    else od = powf(30.0f * density, 1.3f);
     rs.opacity = clamp_(od * 0.2f, 0.0f, 1.0f);
     rs.color = f3(od, od, od);
     if (COUNT) cnt[8]++;
@@ -185,7 +242,7 @@ __device__ __forceinline__ void shade_disk(const HotParams& P, F3 pos, F3 dir, f
     BilinearTaps tap_disk, tap_temp;
     if (P.show_tex != 0) {
         float r = (dist - P.inner) / (P.outer - P.inner);
-        F3 rel = div_s(ip - bpos, P.outer);
+        F3 rel = div_s_ph<SEQ>(ip - bpos, P.outer);
         F3 c0 = f3(P.M[0], P.M[1], P.M[2]), c1 = f3(P.M[3], P.M[4], P.M[5]), c2 = f3(P.M[6], P.M[7], P.M[8]);
         F3 rot = (c0 * rel.x + c1 * rel.y) + c2 * rel.z;
         float angle = -bh_atan2(rot.z, rot.x);
@@ -197,20 +254,27 @@ __device__ __forceinline__ void shade_disk(const HotParams& P, F3 pos, F3 dir, f
     if (P.show_shift != 0) {
         float temp_max = 100000.0f, temp_min = 10000.0f, temp = 15000.0f;
         float y = 1.0f - (temp - temp_min) / (temp_max - temp_min);
-        F3 sv = cross(normalize(ip), normalize(f3(0.0f, -1.0f, 0.0f))) * 0.6f;
+        F3 sv = cross(normalize_ph<SEQ>(ip), normalize(f3(0.0f, -1.0f, 0.0f))) * 0.6f;      // (the second operand is a constant: folded)
         float velocity = dot(dir, sv);
-        float doppler = sqrtf((1.0f - velocity) / (1.0f + velocity));
-        float grav = sqrtf((1.0f - 2.0f / dist) / (1.0f - 2.0f / total_distance));
+        float doppler = sqrt_ph<SEQ>((1.0f - velocity) / (1.0f + velocity));
+        float grav;
+        if constexpr (SEQ) {
+            float two_dist, two_total;
+            two_over_rn(dist, total_distance, two_dist, two_total);
+            grav = sqrt_ph<true>((1.0f - two_dist) / (1.0f - two_total));
+        } else {
+            grav = sqrtf((1.0f - 2.0f / dist) / (1.0f - 2.0f / total_distance));
+        }
         float sh = clamp_(grav * doppler, 0.0f, 1.0f);
         tap_temp = fetch_bilinear(P.temp, sh * sh, y);
     }
     if (P.show_tex != 0) {
-        const float4 dc = blend_bilinear(tap_disk);
+        const float4 dc = blend_bilinear<SEQ>(tap_disk);
         rs.opacity *= clamp_(0.7f + dc.w * 0.5f, 0.0f, 1.0f);
         rs.color = rs.color * (f3(dc.x, dc.y, dc.z) * dc.w);
     }
     if (P.show_shift != 0) {
-        const float4 sc = blend_bilinear(tap_temp);
+        const float4 sc = blend_bilinear<SEQ>(tap_temp);
         rs.color = rs.color * f3(sc.x, sc.y, sc.z);
     }
 }
@@ -267,12 +331,13 @@ __device__ __forceinline__ void black_hole_culls_rel(const HotParams& H, float n
         near_disk = (pos_dist <= H.outer + reach) & (fabsf(numer) <= (1.01f * t_max) * H.bn_len + 1e-4f * H.bn_len);
     }
 }
+template <bool SEQ>
 __device__ __forceinline__ bool hit_black_hole_geom(const HotParams& H, F3 pos, F3 dir, bool near_horizon, bool near_disk, float t_min, float t_max, Hit& rs, float& td_out) {
     const F3 bpos = H.bh;
     float ts = t_max, td = t_max;
     bool hs = false, hd = false;
-    if (near_horizon) hs = hit_sphere(pos, dir, 1.0f, bpos, t_min, t_max, ts);
-    if (near_disk) hd = hit_torus2d(pos, dir, H.inner, H.outer, bpos, H.bn, t_min, t_max, td);
+    if (near_horizon) hs = hit_sphere<SEQ>(pos, dir, 1.0f, bpos, t_min, t_max, ts);
+    if (near_disk) hd = hit_torus2d<SEQ>(pos, dir, H.inner, H.outer, bpos, H.bn, t_min, t_max, td);
     rs.hit = hs; rs.t = hs ? ts : t_max; rs.color = f3(0.0f, 0.0f, 0.0f); rs.opacity = hs ? 1.0f : 0.0f;
     td_out = td;
     return hd && td < rs.t;
@@ -604,6 +669,37 @@ __device__ __forceinline__ float pow_m001_step(float x) {
     return x == u2f(0x7f800000u) ? 0.0f : q;
 }
 __device__ __forceinline__ float fdistance_rn(F3 a, F3 b) { const F3 v = a - b; return sqrt_rn(fdot(v, v)); }   // == fdistance(a, b)
+
+// The phases' twins (BHRAY_PHASE_SEQ; declared at the head of the file).  SEQ: the expression of bhray_math.h the twin names with rcp_rn / sqrt_rn in place of `1.0f / x` /
+// `sqrtf(x)` - the same value on every input, so the frames are the same bytes (tests/test_gpu_phase_seq.py against libbhray_phases0.so).  Where two sequences follow each other
+// on dependent operands ONE wave-uniform range test covers both, as in fnormalize_rn: the root of a radicand in [2^-95, 2^95] lies in [2^-47.5, 2^47.5], inside the range of the
+// root and of the reciprocal that follow; and 2 * RN(1/x) == RN(2/x) for 2^-125 <= x < 2^126 (RN(1/x) is a normal number of (2^-126, 2^125]: doubling it is exact and cannot
+// overflow, and rounding commutes with an exact scaling by two).  The composed forms have legs of their own in bhray_selftest.
+template <bool SEQ> __device__ __forceinline__ float sqrt_ph(float x) { if constexpr (SEQ) return sqrt_rn(x); else return sqrtf(x); }
+template <bool SEQ> __device__ __forceinline__ float rcp_ph(float x) { if constexpr (SEQ) return rcp_rn(x); else return 1.0f / x; }
+template <bool SEQ> __device__ __forceinline__ float length_ph(F3 a) { if constexpr (SEQ) return sqrt_rn(dot(a, a)); else return length(a); }
+template <bool SEQ> __device__ __forceinline__ float distance_ph(F3 a, F3 b) { if constexpr (SEQ) { const F3 v = a - b; return sqrt_rn(dot(v, v)); } else return distance(a, b); }
+template <bool SEQ> __device__ __forceinline__ float fdistance_ph(F3 a, F3 b) { if constexpr (SEQ) return fdistance_rn(a, b); else return fdistance(a, b); }
+template <bool SEQ> __device__ __forceinline__ F3 div_s_ph(F3 a, float s) { if constexpr (SEQ) return a * rcp_rn(s); else return div_s(a, s); }
+template <bool SEQ> __device__ __forceinline__ F3 normalize_ph(F3 a) {                // SEQ: one test for the root and the reciprocal
+    if constexpr (SEQ) {
+        const float d = dot(a, a);
+        float r = rcp_newton(sqrt_corrected(d));
+        if (__builtin_expect(__ballot(!sqrt_in_range(d)) != 0ull, 0)) r = 1.0f / sqrtf(d);
+        return a * r;
+    } else {
+        return normalize(a);
+    }
+}
+__device__ __forceinline__ void dist_rsqrt_rn(float d2, float& dist, float& rs) {      // one test for the root, the root's root and its reciprocal
+    dist = sqrt_corrected(d2);
+    rs = rcp_newton(sqrt_corrected(dist));
+    if (__builtin_expect(__ballot(!sqrt_in_range(d2)) != 0ull, 0)) { dist = sqrtf(d2); rs = 1.0f / sqrtf(dist); }
+}
+__device__ __forceinline__ void two_over_rn(float a, float b, float& ra, float& rb) {  // one test for two independent reciprocals
+    ra = 2.0f * rcp_newton(a); rb = 2.0f * rcp_newton(b);
+    if (__builtin_expect(__ballot(!rcp_in_range(a) | !rcp_in_range(b)) != 0ull, 0)) { ra = 2.0f / a; rb = 2.0f / b; }
+}
 
 __device__ __forceinline__ float pow5(float d) { return ((d * d) * (d * d)) * d; }
 
@@ -1262,6 +1358,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
     // the RK step's error estimate behind a wave-uniform bound (next_ray_rk_t): 0 the full text, 1 skipped where the bound holds, 2 the full text and the bound's counters
     constexpr int ERR_SKIP = (METHOD != 1 || EVAL != 0 || BHRAY_ERR_SKIP == 0) ? 0 : COUNT ? 2
                            : (MODELS ? (BHRAY_ERR_SKIP & 4) != 0 : DENSE ? (BHRAY_ERR_SKIP & 1) != 0 : (BHRAY_ERR_SKIP & 2) != 0) ? 1 : 0;
+    constexpr bool PH = phase_seq_build(MODELS, DENSE);          // the phases' short exact sequences (BHRAY_PHASE_SEQ) in this build
     constexpr bool COLD_LDS = (DENSE && !MODELS) || (MODELS && BHRAY_MESH_COLD_LDS != 0);
     constexpr bool MESH_DENSE = MODELS && DENSE;                                              // the mesh variant's build for a saturated device
     constexpr bool MESH_PARK = MESH_DENSE && !COLD_LDS;   // its traversal in a region of its own (see the flat phase)
@@ -1425,11 +1522,11 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                     }
                     // create_ray, ray.wgsl:269-285 (right/up/fwd_ff hoisted to the host, bit-identical)
                     const int sm = (lw - 1) < (lh - 1) ? (lw - 1) : (lh - 1);
-                    const float increment = 1.0f / (float)sm;
+                    const float increment = rcp_ph<PH>((float)sm);
                     const float posx = (2.0f * ((float)px - (float)(lw - 1) * 0.5f)) * increment;
                     const float posy = (2.0f * ((float)py - (float)(lh - 1) * 0.5f)) * increment;
                     const F3 cam = ld3(P.cam);               // uniform: scalar loads here, not three VGPRs held across the step loop
-                    const F3 rdir = normalize((ld3(P.right) * posx + ld3(P.up) * posy) + ld3(P.fwd_ff));
+                    const F3 rdir = normalize_ph<PH>((ld3(P.right) * posx + ld3(P.up) * posy) + ld3(P.fwd_ff));
                     cold.set_rdir(rdir);
                     cpos = cam; cdir = rdir; ppos = cam; pdir = rdir;
                     rkpos = cam; rkdir = rdir; rkh = P.step_size;
@@ -1500,7 +1597,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                         mode = flat ? M_FLAT : M_REL;
                         if (rs.hit) {                                             // a mesh, or the horizon (colour 0): ray.wgsl:571-576
                             cpos = cpos + pdir * rs.t;
-                            cpos_dist = fdistance(cpos, bpos);
+                            cpos_dist = fdistance_ph<PH>(cpos, bpos);
                             if (METHOD == 0) { dist_c = cpos_dist; qrel = cpos - bpos; }
                             const F3 cc = f3(clamp_(rs.color.x, 0.0f, 1.0f), clamp_(rs.color.y, 0.0f, 1.0f), clamp_(rs.color.z, 0.0f, 1.0f));
                             cold.set_color(cold.color() + cc * (amount * rs.opacity));
@@ -1517,9 +1614,9 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
             if (mode >= M_SHADE_REL) {
                 const float pend_t = cold.pend_t();
                 Hit crs; crs.hit = true; crs.t = pend_t; crs.color = f3(0.0f, 0.0f, 0.0f); crs.opacity = 0.0f;
-                shade_disk<COUNT>(H, ppos, pdir, pend_t, H.ray_distance, crs, cnt);
+                shade_disk<COUNT, PH, pow13_build(MODELS, DENSE) && !COUNT>(H, ppos, pdir, pend_t, H.ray_distance, crs, cnt);
                 cpos = cpos + pdir * crs.t;
-                cpos_dist = fdistance(cpos, bpos);
+                cpos_dist = fdistance_ph<PH>(cpos, bpos);
                 if (METHOD == 0) { dist_c = cpos_dist; qrel = cpos - bpos; }
                 const F3 cc = f3(clamp_(crs.color.x, 0.0f, 1.0f), clamp_(crs.color.y, 0.0f, 1.0f), clamp_(crs.color.z, 0.0f, 1.0f));
                 cold.set_color(cold.color() + cc * (amount * crs.opacity));
@@ -1669,16 +1766,16 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                     // (the radius through an opaque copy: R*R is loop-invariant, and hoisted out of the frame loop it costs the dense build a
                     // VGPR it does not have - it was the kernel's one spill, 8 bytes of scratch per lane)
                     float Rflat = H.R; asm volatile("" : "+v"(Rflat));
-                    const bool hs = hit_sphere(ppos, pdir, Rflat, bpos, t_min, t_max, ths);
+                    const bool hs = hit_sphere<PH>(ppos, pdir, Rflat, bpos, t_min, t_max, ths);
                     if (!hs && !rs.hit) {
                         mode = M_FINISH;                                   // break (no increment)
                     } else {
                         bool chit = false; Hit crs = rs;
-                        if (hs && ths < rs.t) { cpos = cpos + cdir * ths; mode = M_REL; cpos_dist = fdistance(cpos, bpos); if (METHOD == 0) { dist_c = cpos_dist; qrel = cpos - bpos; } }
+                        if (hs && ths < rs.t) { cpos = cpos + cdir * ths; mode = M_REL; cpos_dist = fdistance_ph<PH>(cpos, bpos); if (METHOD == 0) { dist_c = cpos_dist; qrel = cpos - bpos; } }
                         else { chit = rs.hit; }
                         if (chit) {
                             cpos = cpos + pdir * crs.t;
-                            cpos_dist = fdistance(cpos, bpos);
+                            cpos_dist = fdistance_ph<PH>(cpos, bpos);
                             if (METHOD == 0) { dist_c = cpos_dist; qrel = cpos - bpos; }
                             const F3 cc = f3(clamp_(crs.color.x, 0.0f, 1.0f), clamp_(crs.color.y, 0.0f, 1.0f), clamp_(crs.color.z, 0.0f, 1.0f));
                             cold.set_color(cold.color() + cc * (amount * crs.opacity));
@@ -1717,13 +1814,13 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                     if (amount > 0.001f) {
                         if (COUNT) cnt[9]++;
                         // cartesian_to_spherical(dir.xzy), ray.wgsl:255-261, 585-586
-                        const float theta = bh_atan2(sqrtf(cdir.x * cdir.x + cdir.z * cdir.z), cdir.y);
+                        const float theta = bh_atan2(sqrt_ph<PH>(cdir.x * cdir.x + cdir.z * cdir.z), cdir.y);
                         const float phi = bh_atan2(cdir.z, cdir.x);
                         const float PI_F = 3.1415926f;
                         float u = (phi + 2.6f * PI_F) / (2.0f * PI_F);
                         float v = (PI_F - theta) / PI_F;
                         u = u - truncf(u); v = v - truncf(v);
-                        const float4 sc = sample_bilinear(P.sky, u, v);
+                        const float4 sc = sample_bilinear<PH>(P.sky, u, v);
                         const F3 miss = f3((sc.x * sc.x) * (sc.x * sc.x), (sc.y * sc.y) * (sc.y * sc.y), (sc.z * sc.z) * (sc.z * sc.z));
                         color = color + miss * amount;
                     }
@@ -1825,7 +1922,7 @@ __global__ __launch_bounds__(256) void sky_kernel(const TexDev sky, const float4
         float u = (phi + 2.6f * PI_F) / (2.0f * PI_F);
         float v = (PI_F - theta) / PI_F;
         u = u - truncf(u); v = v - truncf(v);
-        const float4 sc = sample_bilinear(sky, u, v);
+        const float4 sc = sample_bilinear<false>(sky, u, v);
         p = make_float4((sc.x * sc.x) * (sc.x * sc.x), (sc.y * sc.y) * (sc.y * sc.y), (sc.z * sc.z) * (sc.z * sc.z), 1.0f);
     }
     // rgba16float target (sky.wgsl:1): round to nearest even
@@ -1875,6 +1972,34 @@ __global__ __launch_bounds__(256) void selftest_kernel(unsigned long long* __res
             if (f2u(want) != f2u(got)) nr++;
             const float cd = fabsf(x), cl = fabsf(y);                          // distances: no sign; `closest` is never a NaN
             if (!(cl != cl)) { const float w2 = cd < cl ? cd : cl, g2 = closest_min(cd, cl); if (f2u(w2) != f2u(g2)) nr++; }
+        }
+    }
+    // The phases' composed sequences (BHRAY_PHASE_SEQ) against the text they replace, bit for bit: every byte through unorm8_rn (counted with 1/x), and dist_rsqrt_rn /
+    // two_over_rn / normalize_ph (counted with sqrt) on 2^20 operands - bit patterns spread over all exponents and both signs, and the special values -
+    // with 64 consecutive patterns per wave, so that waves inside the ranges run the short forms and the others the IEEE lowering.
+    {
+        const unsigned long long gid = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+        if (gid < 256ull) { const float x = (float)(int)gid; if (f2u(unorm8_rn(x)) != f2u(x / 255.0f)) nr++; }
+        if (gid < (1ull << 20)) {
+            const uint32_t sp[16] = {0x7fc00000u, 0xffc00001u, 0x7f800000u, 0xff800000u, 0x00000000u, 0x80000000u, 0x00000001u, 0x007fffffu,
+                                     0x00800000u, 0x01000000u, 0x7e7fffffu, 0x7e800000u, 0x0fffffffu, 0x10000000u, 0x6f000000u, 0x6f000001u};      // NaNs, infinities, zeros, denormals, the ranges' ends
+            // the upper 12 bits walk sign and exponent wave by wave (64 lanes share them), the lower 20 are hashed mantissa bits
+            const uint32_t hi = (uint32_t)(gid >> 6) & 0xfffu, h = (uint32_t)gid * 2654435761u;
+            const uint32_t ua = gid < 16ull ? sp[gid] : ((hi << 20) | (h >> 12));
+            const uint32_t ub = (gid & 64ull) ? ((uint32_t)(h * 2246822519u) >> 2) + 0x20000000u : ua ^ 0x00012345u;      // a second operand: mostly in range / next to the first
+            const float a = u2f(ua), b = u2f(ub);
+            float d1, r1, d0, r0;
+            dist_rsqrt_rn(a, d1, r1);
+            d0 = sqrtf(a); r0 = 1.0f / sqrtf(d0);
+            if ((f2u(d1) != f2u(d0) && !(d1 != d1 && d0 != d0)) || (f2u(r1) != f2u(r0) && !(r1 != r1 && r0 != r0))) ns++;
+            float ta, tb;
+            two_over_rn(a, b, ta, tb);
+            const float wa = 2.0f / a, wb = 2.0f / b;
+            if ((f2u(ta) != f2u(wa) && !(ta != ta && wa != wa)) || (f2u(tb) != f2u(wb) && !(tb != tb && wb != wb))) nr++;
+            const F3 v = f3(a, b, u2f(ua ^ 0x00400000u));
+            const F3 n1 = normalize_ph<true>(v), n0 = normalize(v);
+            if ((f2u(n1.x) != f2u(n0.x) && !(n1.x != n1.x && n0.x != n0.x)) || (f2u(n1.y) != f2u(n0.y) && !(n1.y != n1.y && n0.y != n0.y)) ||
+                (f2u(n1.z) != f2u(n0.z) && !(n1.z != n1.z && n0.z != n0.z))) ns++;
         }
     }
     if (nr) atomicAdd(&bad[0], nr);

@@ -78,6 +78,54 @@ BH_HD float bh_pow_m001(float x) {          // x^(-0.001), ray.wgsl:459
     return q;
 }
 
+// x^1.3 for the disk's optical depth (ray.wgsl:623), behaving as powf(x, 1.3f): NaN for finite x < 0 and NaN, +0 for +-0, +inf for +-inf.  The exponent is the binary32 constant
+// 1.3f, as the shader's literal is.  Exponent split, log polynomial, product, exp polynomial - carried in binary64, because the result has to come within the host libm's
+// powf of the real power (0.5014 ulp measured: a correctly rounded value for practical purposes), and a binary32 form would need every term of both series as a hi / lo pair.
+// ln m = 2 atanh(s), s = (m - 1) / (m + 1), m in (0.7071, 1.4143): |s| < 0.1716, the series cut after s^15 (next term 2^-45 of the sum); the quotient as a binary32
+// reciprocal refined by one Newton step in binary64 (2^-46).  2^f, |f| <= 1/2, as exp(f ln 2) by its Taylor polynomial of degree 11 (remainder 2^-47).  One rounding to
+// binary32 at the end, through the conversion - which also delivers overflow as +inf and the denormal results correctly rounded.  tests/test_pow13_cpu.py measures it.
+BH_HD float bh_pow_1p3(float x) {
+    if (x == u2f(0xff800000u)) return u2f(0x7f800000u);                     // powf(-inf, 1.3f) = +inf
+    if (!(x == x) || x < 0.0f) return u2f(0x7fc00000u);
+    if (x == 0.0f) return 0.0f;
+    if (x == u2f(0x7f800000u)) return x;
+    uint32_t u = f2u(x);
+    int e = (int)(u >> 23) - 127;
+    if ((u >> 23) == 0) { x = x * 8388608.0f; u = f2u(x); e = (int)(u >> 23) - 127 - 23; }
+    float mf = u2f((u & 0x007fffffu) | 0x3f800000u);
+    if (mf > 1.41421354f) { mf = mf * 0.5f; e = e + 1; }
+    const double m = (double)mf, den = m + 1.0;
+    double r = (double)(1.0f / (mf + 1.0f));
+    r = fma(fma(-den, r, 1.0), r, r);
+    const double s = (m - 1.0) * r, s2 = s * s;
+    double p = 1.0 / 15.0;
+    p = fma(p, s2, 1.0 / 13.0);
+    p = fma(p, s2, 1.0 / 11.0);
+    p = fma(p, s2, 1.0 / 9.0);
+    p = fma(p, s2, 1.0 / 7.0);
+    p = fma(p, s2, 1.0 / 5.0);
+    p = fma(p, s2, 1.0 / 3.0);
+    p = fma(p, s2, 1.0);
+    const double log2m = ((2.0 * s) * p) * 1.4426950408889634;            // ln m * log2(e)
+    const double t = (double)1.3f * ((double)e + log2m);                   // log2 of the result
+    const double kd = (double)(int)(t + (t < 0.0 ? -0.5 : 0.5));
+    const double z = (t - kd) * 0.6931471805599453;                        // |z| <= ln(2) / 2
+    double q = 1.0 / 39916800.0;
+    q = fma(q, z, 1.0 / 3628800.0);
+    q = fma(q, z, 1.0 / 362880.0);
+    q = fma(q, z, 1.0 / 40320.0);
+    q = fma(q, z, 1.0 / 5040.0);
+    q = fma(q, z, 1.0 / 720.0);
+    q = fma(q, z, 1.0 / 120.0);
+    q = fma(q, z, 1.0 / 24.0);
+    q = fma(q, z, 1.0 / 6.0);
+    q = fma(q, z, 0.5);
+    q = fma(q, z, 1.0);
+    q = fma(q, z, 1.0);
+    const double scale = __builtin_bit_cast(double, (uint64_t)((int)kd + 1023) << 52);      // 2^k, |k| < 260
+    return (float)(q * scale);
+}
+
 BH_HD float bh_asin_kernel(float z) {
     float z2 = z * z;
     float p = 4.2163199048e-2f;

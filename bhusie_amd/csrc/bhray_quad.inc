@@ -139,9 +139,9 @@ __device__ __forceinline__ void quad_march(const FrameParams& P, const FrameLaun
         if (__any(mode >= M_SHADE_REL)) {
             if (mode >= M_SHADE_REL) {
                 Hit crs; crs.hit = true; crs.t = pend_t; crs.color = f3(0.0f, 0.0f, 0.0f); crs.opacity = 0.0f;
-                shade_disk<false>(H, qgather(ppos), qgather(pdir), pend_t, H.ray_distance, crs, nullptr);
+                shade_disk<false, PHASE_SEQ_QUAD, POW13_QUAD>(H, qgather(ppos), qgather(pdir), pend_t, H.ray_distance, crs, nullptr);
                 cpos = cpos + pdir * crs.t;
-                cpos_dist = fdistance(qgather(cpos), bpos);
+                cpos_dist = fdistance_ph<PHASE_SEQ_QUAD>(qgather(cpos), bpos);
                 if (METHOD == 0) { dist_c = cpos_dist; qrel = cpos - bh_c; }
                 const float cc = clamp_(qpick(crs.color, c), 0.0f, 1.0f);
                 col = col + cc * (amount * crs.opacity);
@@ -158,12 +158,12 @@ __device__ __forceinline__ void quad_march(const FrameParams& P, const FrameLaun
                     mode = M_FINISH;
                 } else {
                     float ths = t_max;
-                    const bool hs = hit_sphere(qgather(ppos), qgather(pdir), H.R, bpos, t_min, t_max, ths);
+                    const bool hs = hit_sphere<PHASE_SEQ_QUAD>(qgather(ppos), qgather(pdir), H.R, bpos, t_min, t_max, ths);
                     if (!hs) {
                         mode = M_FINISH;                                   // break (no increment)
                     } else {                                               // (the sphere is always nearer than "no mesh hit": ths < t_max)
                         cpos = cpos + cdir * ths; mode = M_REL;
-                        cpos_dist = fdistance(qgather(cpos), bpos);
+                        cpos_dist = fdistance_ph<PHASE_SEQ_QUAD>(qgather(cpos), bpos);
                         if (METHOD == 0) { dist_c = cpos_dist; qrel = cpos - bh_c; }
                         if (amount < 0.005f) mode = M_FINISH; else it++;
                     }
@@ -184,7 +184,7 @@ __device__ __forceinline__ void quad_march(const FrameParams& P, const FrameLaun
                         float u = (phi + 2.6f * PI_F) / (2.0f * PI_F);
                         float v = (PI_F - theta) / PI_F;
                         u = u - truncf(u); v = v - truncf(v);
-                        const float4 sc = sample_bilinear(P.sky, u, v);
+                        const float4 sc = sample_bilinear<PHASE_SEQ_QUAD>(P.sky, u, v);
                         const F3 miss = f3((sc.x * sc.x) * (sc.x * sc.x), (sc.y * sc.y) * (sc.y * sc.y), (sc.z * sc.z) * (sc.z * sc.z));
                         color = color + miss * amount;
                     }

@@ -31,7 +31,7 @@
                 it++;
                 if (near_horizon || near_disk || cd > H.R) {
                     Hit crs; float td;
-                    const bool disk = hit_black_hole_geom(H, qgather(ppos), qgather(pdir), near_horizon, near_disk, t_min, seg, crs, td);
+                    const bool disk = hit_black_hole_geom<PHASE_SEQ_QUAD>(H, qgather(ppos), qgather(pdir), near_horizon, near_disk, t_min, seg, crs, td);
                     if (cd > H.R) {
                         mode = M_FLAT;
                         const float fw = H.R * H.feather;
@@ -47,7 +47,7 @@
                     } else {
                         if (crs.hit) {                                   // horizon: colour 0, opacity 1
                             cpos = cpos + pdir * crs.t;
-                            cpos_dist = fdistance(qgather(cpos), bpos);
+                            cpos_dist = fdistance_ph<PHASE_SEQ_QUAD>(qgather(cpos), bpos);
                             if (METHOD == 0) { dist_c = cpos_dist; qrel = cpos - bh_c; }
                             const float cc = clamp_(qpick(crs.color, c), 0.0f, 1.0f);
                             col = col + cc * (amount * crs.opacity);

@@ -56,7 +56,7 @@
                     it++;                                          // the plain march; the rare paths that do not count the step take it back
                     if (near_horizon || near_disk || cd > H.R || near_mesh) {
                     Hit crs; float td;
-                    const bool disk = hit_black_hole_geom(H, ppos, pdir, near_horizon, near_disk, t_min, seg, crs, td);
+                    const bool disk = hit_black_hole_geom<PH>(H, ppos, pdir, near_horizon, near_disk, t_min, seg, crs, td);
                     if (cd > H.R) {
                         mode = M_FLAT;
                         const float fw = H.R * H.feather;
@@ -85,7 +85,7 @@
                     } else {
                     if (crs.hit && !lens_paused) {               // horizon: colour 0, opacity 1
                         cpos = cpos + pdir * crs.t;
-                        cpos_dist = fdistance(cpos, bpos);
+                        cpos_dist = fdistance_ph<PH>(cpos, bpos);
                         if (METHOD == 0) { dist_c = cpos_dist; qrel = cpos - bpos; }
                         const F3 cc = f3(clamp_(crs.color.x, 0.0f, 1.0f), clamp_(crs.color.y, 0.0f, 1.0f), clamp_(crs.color.z, 0.0f, 1.0f));
                         cold.set_color(cold.color() + cc * (amount * crs.opacity));
@@ -145,7 +145,7 @@
                     if constexpr (LENSED) near_mesh = lens_near_mesh(P, ppos, pdir, seg);
                     if (near_horizon || near_disk || cd > H.R || near_mesh) {
                     Hit crs; float td;
-                    const bool disk = hit_black_hole_geom(H, ppos, pdir, near_horizon, near_disk, t_min, seg, crs, td);
+                    const bool disk = hit_black_hole_geom<PH>(H, ppos, pdir, near_horizon, near_disk, t_min, seg, crs, td);
                     if (cd > H.R) {
                         mode = M_FLAT;
                         const float fw = H.R * H.feather;
@@ -174,7 +174,7 @@
                     }
                     if (crs.hit && !lens_paused) {               // horizon: colour 0, opacity 1
                         cpos = cpos + pdir * crs.t;
-                        cpos_dist = fdistance(cpos, bpos);
+                        cpos_dist = fdistance_ph<PH>(cpos, bpos);
                         if (METHOD == 0) { dist_c = cpos_dist; qrel = cpos - bpos; }
                         const F3 cc = f3(clamp_(crs.color.x, 0.0f, 1.0f), clamp_(crs.color.y, 0.0f, 1.0f), clamp_(crs.color.z, 0.0f, 1.0f));
                         cold.set_color(cold.color() + cc * (amount * crs.opacity));

@@ -79,7 +79,7 @@
                             }
                         }
                         Hit crs; float td;
-                        const bool disk = hit_black_hole_geom(H, U_PIN, udir, near_horizon, near_disk, t_min, seg, crs, td);
+                        const bool disk = hit_black_hole_geom<PH>(H, U_PIN, udir, near_horizon, near_disk, t_min, seg, crs, td);
                         F3 ncpos = U_POUT, ncdir = udir;                    // what cpos / cdir become for a lane that leaves
                         float ncd = cd;
                         if (cd > H.R) {
@@ -97,7 +97,7 @@
                         } else {
                             if (crs.hit) {                                  // horizon: colour 0, opacity 1
                                 ncpos = ncpos + udir * crs.t;
-                                ncd = fdistance(ncpos, bpos);
+                                ncd = fdistance_ph<PH>(ncpos, bpos);
                                 if (METHOD == 0) { dist_c = ncd; if (!BHRAY_U_ORIGIN) qrel = ncpos - bpos; }
                                 const F3 cc = f3(clamp_(crs.color.x, 0.0f, 1.0f), clamp_(crs.color.y, 0.0f, 1.0f), clamp_(crs.color.z, 0.0f, 1.0f));
                                 cold.set_color(cold.color() + cc * (amount * crs.opacity));
