@@ -1,0 +1,152 @@
+"""Ray generators for RayPass.trace_rays / Renderer.render_rays (bhray_trace_rays): pure NumPy, binary32 arithmetic.
+
+Each returns an (h * w, 8) float32 array of ray records - origin, pad, direction, pad (layouts.BhrayRay) - row 0 the top row, x fastest, as a frame's pixels.
+
+pinhole_rays    the shader's create_ray (ray.wgsl:269-285), operation by operation: the rays of a `levels = 1` frame, bit for bit
+equirect_rays   a 360 x 180 degree panorama: the centre column looks along `forward`
+fisheye_rays    an equidistant fisheye of opening angle `fov` about `forward`; pixels outside the image circle get a zero direction (not traced: alpha -1)
+
+All three use create_ray's basis: plane_up = (0, -1, 0), right = normalize(cross(forward, plane_up)), up = normalize(cross(forward, right)) - `up` is the direction in
+which the image's rows increase.  Directions are unit as a binary32 normalise leaves them (v * (1 / sqrt(dot(v, v)))), which is what the trace kernels expect.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+F = np.float32
+_PI = F(3.14159274)
+
+
+def _dot(a, b):                                       # N1: (x*x + y*y) + z*z, one rounding per operation
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def _cross(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1],
+                     a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1).astype(F)
+
+
+def _normalize(a):                                    # N2: v * (1 / length(v))
+    r = F(1.0) / np.sqrt(_dot(a, a), dtype=F)
+    return (a * np.asarray(r, dtype=F)[..., None]).astype(F)
+
+
+def _sincos(xin, kind):
+    """bh_sincos<kind> of bhray_math.h for one binary32 value (kind 0: sin, 1: cos), operation by operation"""
+    xin = F(xin)
+    x = F(abs(xin))
+    sign = bool(np.signbit(xin)) if kind == 0 else False
+    if not x <= F(3.0e9):
+        return F(np.nan)
+    j = int(x * F(1.27323954)) & 0xFFFFFFFF
+    j = j + (j & 1)
+    y = F(j)
+    x = F(F(F(x - F(y * F(0.78515625))) - F(y * F(2.4187564849853515625e-4))) - F(y * F(3.77489497744594108e-8)))
+    j &= 7
+    if j > 3:
+        sign = not sign
+        j -= 4
+    if kind == 1 and j > 1:
+        sign = not sign
+    z = F(x * x)
+    mid = j in (1, 2)
+    use_cos = mid if kind == 0 else not mid
+    if use_cos:
+        p = F(2.443315711809948e-5)
+        p = F(F(p * z) - F(1.388731625493765e-3))
+        p = F(F(p * z) + F(4.166664568298827e-2))
+        r = F(F(F(F(p * z) * z) - F(F(0.5) * z)) + F(1.0))
+    else:
+        p = F(-1.9515295891e-4)
+        p = F(F(p * z) + F(8.3321608736e-3))
+        p = F(F(p * z) - F(1.6666654611e-1))
+        r = F(F(F(p * z) * x) + x)
+    return F(-r) if sign else r
+
+
+def _tan(x):                                          # bh_tan: ray.wgsl:279 under N4
+    return F(_sincos(x, 0) / _sincos(x, 1))
+
+
+def _basis(forward):
+    fwd = np.asarray(forward, dtype=F).reshape(3)
+    right = _normalize(_cross(fwd, np.array([0.0, -1.0, 0.0], dtype=F)))
+    up = _normalize(_cross(fwd, right))
+    return fwd, right, up
+
+
+def _records(position, dirs):
+    n = dirs.shape[0]
+    out = np.zeros((n, 8), dtype=F)
+    out[:, 0:3] = np.asarray(position, dtype=F).reshape(3)
+    out[:, 4:7] = dirs
+    return out
+
+
+def _camera_fields(camera):
+    """(position, forward, fov) as binary32 from a scene.Camera (through its uniform: the bytes the ctx gets) or from the 32 uniform bytes themselves"""
+    b = camera if isinstance(camera, (bytes, bytearray)) else camera.uniform()
+    u = np.frombuffer(bytes(b), dtype=F)
+    assert u.size == 8, "a CameraUniform is 32 bytes"
+    return u[0:3].copy(), u[4:7].copy(), F(u[7])
+
+
+def pinhole_rays(camera, w: int, h: int) -> np.ndarray:
+    """create_ray for every pixel of a w x h level (ray.wgsl:269-285)."""
+    w, h = int(w), int(h)
+    assert w >= 2 and h >= 2, "create_ray divides by min(w, h) - 1"
+    pos, forward, fov = _camera_fields(camera)
+    fwd, right, up = _basis(forward)
+    sm = min(w - 1, h - 1)
+    increment = F(1.0) / F(sm)
+    px = np.arange(w, dtype=F)[None, :]
+    py = np.arange(h, dtype=F)[:, None]
+    posx = (F(2.0) * (px - F(F(w - 1) * F(0.5)))) * increment
+    posy = (F(2.0) * (py - F(F(h - 1) * F(0.5)))) * increment
+    posx = np.broadcast_to(posx, (h, w)).astype(F)
+    posy = np.broadcast_to(posy, (h, w)).astype(F)
+    fov_factor = F(F(1.0) / _tan(F(fov / F(2.0))))
+    fwd_ff = (fwd * fov_factor).astype(F)
+    v = ((right[None, None, :] * posx[..., None]).astype(F) + (up[None, None, :] * posy[..., None]).astype(F)).astype(F) + fwd_ff[None, None, :]
+    return _records(pos, _normalize(v.astype(F)).reshape(h * w, 3))
+
+
+def equirect_rays(position, forward, w: int, h: int) -> np.ndarray:
+    """360 x 180 degrees, pixel centres: column i at longitude (i - (w - 1) / 2) * 2 pi / w from `forward` towards `right`, row j at latitude
+    (j - (h - 1) / 2) * pi / h towards `up` (the image's downward direction, as in create_ray: row 0 is the top)."""
+    w, h = int(w), int(h)
+    assert w >= 1 and h >= 1
+    fwd, right, up = _basis(forward)
+    fwd = _normalize(fwd)
+    lon = (np.arange(w, dtype=F) - F(F(w - 1) * F(0.5))) * F(F(2.0) * _PI / F(w))
+    lat = (np.arange(h, dtype=F) - F(F(h - 1) * F(0.5))) * F(_PI / F(h))
+    cl, sl = np.cos(lon, dtype=F)[None, :], np.sin(lon, dtype=F)[None, :]
+    cp, sp = np.cos(lat, dtype=F)[:, None], np.sin(lat, dtype=F)[:, None]
+    a = (cp * cl).astype(F)[..., None]
+    b = (cp * sl).astype(F)[..., None]
+    c = np.broadcast_to(sp, (h, w)).astype(F)[..., None]
+    v = ((fwd * a).astype(F) + (right * b).astype(F)).astype(F) + (up * c).astype(F)
+    return _records(position, _normalize(v.astype(F)).reshape(h * w, 3))
+
+
+def fisheye_rays(position, forward, w: int, h: int, fov: float) -> np.ndarray:
+    """Equidistant fisheye: a pixel at distance r from the image centre - in units of the image circle's radius min(w - 1, h - 1) / 2 - looks fov / 2 * r away from
+    `forward`, in the image direction it lies in.  r > 1: outside the circle, direction zero."""
+    w, h = int(w), int(h)
+    assert w >= 2 and h >= 2
+    fwd, right, up = _basis(forward)
+    fwd = _normalize(fwd)
+    radius = F(F(min(w - 1, h - 1)) * F(0.5))
+    x = np.broadcast_to(((np.arange(w, dtype=F) - F(F(w - 1) * F(0.5))) / radius)[None, :], (h, w)).astype(F)
+    y = np.broadcast_to(((np.arange(h, dtype=F) - F(F(h - 1) * F(0.5))) / radius)[:, None], (h, w)).astype(F)
+    r = np.sqrt((x * x + y * y).astype(F), dtype=F)
+    inside = r <= F(1.0)
+    theta = (r * F(F(fov) * F(0.5))).astype(F)
+    safe = np.where(r > F(0.0), r, F(1.0)).astype(F)
+    cphi, sphi = (x / safe).astype(F), (y / safe).astype(F)           # r == 0: the centre, sin(theta) = 0 - the image direction does not matter
+    st, ct = np.sin(theta, dtype=F), np.cos(theta, dtype=F)
+    v = ((fwd * ct[..., None]).astype(F) + (right * (st * cphi).astype(F)[..., None]).astype(F)).astype(F) + (up * (st * sphi).astype(F)[..., None]).astype(F)
+    d = _normalize(v.astype(F))
+    d = np.where(inside[..., None], d, F(0.0)).astype(F)
+    return _records(position, d.reshape(h * w, 3))

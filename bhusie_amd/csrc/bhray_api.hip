@@ -195,6 +195,15 @@ struct bhray_dev {
     uint64_t grid_launches = 0, grid_blocks = 0, grid_ceiling_launches = 0;   // ladder trace launches enqueued, their blocks, those with the ctx's grid (dev_get_level_grids)
     uint64_t origin_launches = 0, general_launches = 0;      // trace launches enqueued with an ORIGIN build / with any other (dev_get_trace_builds)
     bool rendered = false;
+    // ray batches (dev_trace_rays / dev_trace_rays_device): a stream of their own, created by the first batch - a ctx that only renders frames keeps the
+    // streams it had -, the events that order a batch against the caller's stream, the argument block of one launch (FrameParams, FrameLaunch and the two queue control
+    // words: pinned, and its device copy) and the host variant's grow-only staging (pinned in / out, device in / out)
+    hipStream_t q_stream = nullptr;
+    hipEvent_t q_begin = nullptr, q_done = nullptr, q_uploaded = nullptr;
+    uint8_t* q_hargs = nullptr; uint8_t* q_dargs = nullptr;
+    bool q_used = false;                   // a batch has been enqueued (q_uploaded has been recorded; the engine's error word may be a batch's)
+    float4* q_hin = nullptr; float4* q_hout = nullptr; float4* q_din = nullptr; float4* q_dout = nullptr;
+    size_t q_cap = 0;                      // rays the staging holds
     // asynchronous hand-off (dev_read_hdr_async)
     hipEvent_t read_ev[BHRAY_READ_RING] = {nullptr};     // ticket t -> read_ev[t % BHRAY_READ_RING]
     uint64_t read_tickets = 0;
@@ -308,11 +317,13 @@ void derive_frame(const bhray_dev* c, FrameParams& P) {
 
 int launch_batch(bhray_dev* c);
 
+// everything the engine has enqueued: the frames in flight and the outstanding ray batches (both read the scene memory the callers of this rewrite)
 hipError_t sync_all(bhray_dev* c) {
     for (Slot& S : c->slots) {
         hipError_t e = hipStreamSynchronize(S.stream);
         if (e != hipSuccess) return e;
     }
+    if (c->q_stream) return hipStreamSynchronize(c->q_stream);
     return hipSuccess;
 }
 
@@ -403,6 +414,15 @@ void dev_destroy(bhray_dev* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     for (Slot& S : c->slots) if (S.stream) (void)hipStreamSynchronize(S.stream);
+    if (c->q_stream) (void)hipStreamSynchronize(c->q_stream);
+    if (c->q_hargs) (void)hipHostFree(c->q_hargs);
+    if (c->q_dargs) (void)hipFree(c->q_dargs);
+    if (c->q_hin) (void)hipHostFree(c->q_hin);
+    if (c->q_hout) (void)hipHostFree(c->q_hout);
+    if (c->q_din) (void)hipFree(c->q_din);
+    if (c->q_dout) (void)hipFree(c->q_dout);
+    for (hipEvent_t e : {c->q_begin, c->q_done, c->q_uploaded}) if (e) (void)hipEventDestroy(e);
+    if (c->q_stream) (void)hipStreamDestroy(c->q_stream);
     for (Slot& S : c->slots) {
         for (FrameRes& R : S.fr) {
             for (auto p : R.level_out) if (p) (void)hipFree(p);
@@ -1084,6 +1104,122 @@ int dev_set_uniforms(bhray_dev* c, const void* cam32, const void* bh132, const v
     return BHRAY_OK;
 }
 
+// ---- ray batches (include/bhray.h: bhray_trace_rays) ------------------------------------------------------------
+namespace {
+constexpr size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+constexpr size_t Q_OFF_LAUNCH = align16(sizeof(FrameParams)), Q_OFF_CTL = Q_OFF_LAUNCH + align16(sizeof(FrameLaunch)), Q_ARGS_BYTES = Q_OFF_CTL + 16;
+
+// why this engine traces no ray batch now (the refused states), or BHRAY_OK
+int rays_refused(bhray_dev* c, const char* name) {
+    if (!c->have_uniforms) return fail(c, BHRAY_E_STATE, "%s: bhray_set_uniforms has not been called", name);
+    if (c->cfg.flags & (BHRAY_F_LITERAL | BHRAY_F_EVAL_FMA)) return fail(c, BHRAY_E_STATE, "%s: no ray-list kernel for BHRAY_F_LITERAL / BHRAY_F_EVAL_FMA", name);
+    if (c->mesh_lensing) return fail(c, BHRAY_E_STATE, "%s: ray batches under mesh lensing are not built", name);
+    return BHRAY_OK;
+}
+
+int ensure_query(bhray_dev* c) {
+    if (!c->q_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->q_stream, hipStreamNonBlocking));
+    for (hipEvent_t* e : {&c->q_begin, &c->q_done, &c->q_uploaded}) if (!*e) HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    if (!c->q_hargs) HIPCHK(c, hipHostMalloc(&c->q_hargs, Q_ARGS_BYTES));
+    if (!c->q_dargs) HIPCHK(c, hipMalloc(&c->q_dargs, Q_ARGS_BYTES));
+    return BHRAY_OK;
+}
+
+// One launch on the query stream: n rays at d_rays -> n results at d_out, under the engine's current uniforms, textures and models.  Enqueues only.
+int enqueue_rays(bhray_dev* c, const float4* d_rays, uint32_t n, float4* d_out) {
+    // the pinned block of the batch before must have reached the device before it is rewritten (its device copy is read in stream order)
+    if (c->q_used && hipEventQuery(c->q_uploaded) != hipSuccess) HIPCHK(c, hipEventSynchronize(c->q_uploaded));
+    FrameParams& P = *(FrameParams*)c->q_hargs;
+    derive_frame(c, P);                                           // exactly a frame's; the ray-list kernels read none of the camera members
+    FrameLaunch& F = *(FrameLaunch*)(c->q_hargs + Q_OFF_LAUNCH);
+    memset(&F, 0, sizeof F);
+    F.L.w = (int)n; F.L.h = 1;
+    F.L.prev = d_rays; F.L.out = d_out;                           // the records and the results (TraceVariant::rays)
+    F.qctl = (uint32_t*)(c->q_dargs + Q_OFF_CTL);                 // [0] = n, [1] = 0: uploaded with the block, so the launch needs no reset of its own
+    uint32_t* ctl = (uint32_t*)(c->q_hargs + Q_OFF_CTL);
+    ctl[0] = n; ctl[1] = 0; ctl[2] = 0; ctl[3] = 0;
+    const TraceVariant v{P.method, P.model_count > 0 ? 1 : 0, false, false, 0, false, true};
+    int ctx_grid = c->num_cus * trace_blocks_per_cu(v);
+    if (c->grid_override > 0) ctx_grid = c->grid_override;
+    const int grid = (int)bhray_trace_grid_for(n, 1, (uint32_t)ctx_grid, c->level_grid_gen, 0, c->level_grid_floor);      // n is exact: no margin
+    HIPCHK(c, launch_upload(c->q_hargs, c->q_dargs, Q_ARGS_BYTES / 16, nullptr, 0, c->q_stream));
+    HIPCHK(c, hipEventRecord(c->q_uploaded, c->q_stream));
+    c->q_used = true;
+    HIPCHK(c, launch_trace((const FrameParams*)c->q_dargs, (const FrameLaunch*)(c->q_dargs + Q_OFF_LAUNCH), 1, v, c->d_err, grid, c->q_stream));
+    return BHRAY_OK;
+}
+}  // namespace
+
+// out: n x RGBA32F (may be NULL when sky16 is not); sky16: NULL, or n x RGBA16F - sky.wgsl over the results (launch_sky, the pass of dev_resolve_sky)
+int dev_trace_rays(bhray_dev* c, const bhray_ray* rays, uint32_t n, float* out, uint16_t* sky16) {
+    if (!c) return BHRAY_E_INVALID;
+    if (n > BHRAY_MAX_RAYS_PER_CALL || (n != 0 && (!rays || (!out && !sky16)))) return fail(c, BHRAY_E_INVALID, "bhray_trace_rays: bad arguments");
+    { int rc = rays_refused(c, "bhray_trace_rays"); if (rc) return rc; }
+    if (n == 0) return BHRAY_OK;
+    for (uint32_t i = 0; i < n; i++) {                            // before anything is enqueued
+        const float* o = rays[i].origin; const float* d = rays[i].direction;
+        const bool finite = std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]) && std::isfinite(d[0]) && std::isfinite(d[1]) && std::isfinite(d[2]);
+        if (!finite || (d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f))
+            return fail(c, BHRAY_E_INVALID, "bhray_trace_rays: ray %u has a non-finite component or a zero direction", i);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = launch_batch(c); if (rc) return rc; }              // the staged frames first: they keep the uniforms they were staged with
+    { int rc = ensure_query(c); if (rc) return rc; }
+    if (n > c->q_cap) {                                           // grow-only staging
+        HIPCHK(c, hipStreamSynchronize(c->q_stream));
+        if (c->q_hin) (void)hipHostFree(c->q_hin);
+        if (c->q_hout) (void)hipHostFree(c->q_hout);
+        if (c->q_din) (void)hipFree(c->q_din);
+        if (c->q_dout) (void)hipFree(c->q_dout);
+        c->q_hin = c->q_hout = c->q_din = c->q_dout = nullptr; c->q_cap = 0;
+        const size_t cap = std::max<size_t>(n, 4096);
+        HIPCHK(c, hipHostMalloc(&c->q_hin, cap * sizeof(bhray_ray)));
+        HIPCHK(c, hipHostMalloc(&c->q_hout, cap * sizeof(float4)));
+        HIPCHK(c, hipMalloc(&c->q_din, cap * sizeof(bhray_ray)));
+        HIPCHK(c, hipMalloc(&c->q_dout, cap * sizeof(float4)));
+        c->q_cap = cap;
+    } else {
+        HIPCHK(c, hipStreamSynchronize(c->q_stream));           // (a copy of an earlier call that failed half-way may still read the staging)
+    }
+    memcpy(c->q_hin, rays, (size_t)n * sizeof(bhray_ray));
+    HIPCHK(c, hipMemcpyAsync(c->q_din, c->q_hin, (size_t)n * sizeof(bhray_ray), hipMemcpyHostToDevice, c->q_stream));
+    { int rc = enqueue_rays(c, c->q_din, n, c->q_dout); if (rc) return rc; }
+    HIPCHK(c, hipMemcpyAsync(c->q_hout, c->q_dout, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, c->q_stream));
+    if (sky16) {                                                  // the records are used up: their device buffer (32 bytes per ray) takes the image (8), their pinned one its copy
+        TexDev sky; sky.rgba = c->tex[BHRAY_TEX_SKY]; sky.w = c->tex_w[BHRAY_TEX_SKY]; sky.h = c->tex_h[BHRAY_TEX_SKY];
+        HIPCHK(c, launch_sky(sky, c->q_dout, (uint2*)c->q_din, n, c->q_stream));
+        HIPCHK(c, hipMemcpyAsync(c->q_hin, c->q_din, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, c->q_stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->q_stream));
+    {   // the kernels' error word, as dev_sync reads it for the frames
+        int e = 0;
+        HIPCHK(c, hipMemcpy(&e, c->d_err, sizeof e, hipMemcpyDeviceToHost));
+        if (e != 0) {
+            HIPCHK(c, hipMemset(c->d_err, 0, sizeof(int)));
+            return fail(c, e, "kernel reported: %s", bhray_strerror(e));
+        }
+    }
+    if (out) memcpy(out, c->q_hout, (size_t)n * sizeof(float4));
+    if (sky16) memcpy(sky16, c->q_hin, (size_t)n * sizeof(uint2));
+    return BHRAY_OK;
+}
+
+int dev_trace_rays_device(bhray_dev* c, const void* d_rays, uint32_t n, void* d_out, hipStream_t s) {
+    if (!c) return BHRAY_E_INVALID;
+    if (n > BHRAY_MAX_RAYS_PER_CALL || (n != 0 && (!d_rays || !d_out))) return fail(c, BHRAY_E_INVALID, "bhray_trace_rays_device: bad arguments");
+    if (((uintptr_t)d_rays | (uintptr_t)d_out) & 15u) return fail(c, BHRAY_E_INVALID, "bhray_trace_rays_device: the arrays must be 16-byte aligned");
+    { int rc = rays_refused(c, "bhray_trace_rays_device"); if (rc) return rc; }
+    if (n == 0) return BHRAY_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = ensure_query(c); if (rc) return rc; }
+    HIPCHK(c, hipEventRecord(c->q_begin, s));                     // the batch starts behind what `s` holds now ...
+    HIPCHK(c, hipStreamWaitEvent(c->q_stream, c->q_begin, 0));
+    { int rc = enqueue_rays(c, (const float4*)d_rays, n, (float4*)d_out); if (rc) return rc; }
+    HIPCHK(c, hipEventRecord(c->q_done, c->q_stream));            // ... and what `s` gets from now on starts behind the batch
+    HIPCHK(c, hipStreamWaitEvent(s, c->q_done, 0));
+    return BHRAY_OK;
+}
+
 // Another row partition for this engine (bhray_set_partition): same frame, same ladder, other rows.  Everything enqueued so far is
 // waited for; the row tables are rewritten in place, the per-frame queues and output buffers grow if the new rows need more.  The level
 // images, textures, models and uniforms stay.  The temporal mode's per-pixel history stays too (rows that are new to this partition
@@ -1622,7 +1758,7 @@ int dev_sync(bhray_dev* c) {
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = launch_batch(c); if (rc) return rc; }
     HIPCHK(c, sync_all(c));
-    if (c->rendered) {
+    if (c->rendered || c->q_used) {
         int e = 0;
         HIPCHK(c, hipMemcpy(&e, c->d_err, sizeof e, hipMemcpyDeviceToHost));
         if (e != 0) {

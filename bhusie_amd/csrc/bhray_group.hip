@@ -1547,6 +1547,35 @@ int bhray_set_mesh_lensing(bhray_ctx* c, int32_t on) {
     for (Part& p : c->parts) if (p.dev) DEV(c, p.dev, dev_set_mesh_lensing(p.dev, on));
     return BHRAY_OK;
 }
+// Ray batches: one engine, its own query stream.  A ctx that splits the frame over several partitions is refused (out of scope: whose rays?).
+static int rays_entry(bhray_ctx* c, const char* name) {
+    if (c->cfg.device_count >= 2 || !c->single) return gfail(c, BHRAY_E_STATE, "%s: not on a ctx that renders a frame with several partitions (device_count >= 2, or a gather)", name);
+    return BHRAY_OK;
+}
+int bhray_trace_rays(bhray_ctx* c, const bhray_ray* rays, uint32_t n, float* out) {
+    if (!c) return BHRAY_E_INVALID;
+    if (n > BHRAY_MAX_RAYS_PER_CALL || (n != 0 && (!rays || !out))) return gfail(c, BHRAY_E_INVALID, "bhray_trace_rays: bad arguments");
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_trace_rays"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_trace_rays(c->parts[0].dev, rays, n, out, nullptr));
+    return BHRAY_OK;
+}
+int bhray_trace_rays_sky(bhray_ctx* c, const bhray_ray* rays, uint32_t n, float* out, uint16_t* sky16) {
+    if (!c) return BHRAY_E_INVALID;
+    if (n > BHRAY_MAX_RAYS_PER_CALL || (n != 0 && (!rays || !sky16))) return gfail(c, BHRAY_E_INVALID, "bhray_trace_rays_sky: bad arguments");
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_trace_rays_sky"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_trace_rays(c->parts[0].dev, rays, n, out, sky16));
+    return BHRAY_OK;
+}
+int bhray_trace_rays_device(bhray_ctx* c, const void* d_rays, uint32_t n, void* d_out, void* s) {
+    if (!c) return BHRAY_E_INVALID;
+    if (n > BHRAY_MAX_RAYS_PER_CALL || (n != 0 && (!d_rays || !d_out))) return gfail(c, BHRAY_E_INVALID, "bhray_trace_rays_device: bad arguments");
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_trace_rays_device"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_trace_rays_device(c->parts[0].dev, d_rays, n, d_out, (hipStream_t)s));
+    return BHRAY_OK;
+}
 int bhray_set_uniforms(bhray_ctx* c, const void* cam32, const void* bh132, const void* det32) {
     if (!c) return BHRAY_E_INVALID;
     if (c->gather && cam32 && bh132) track_hole_row(c, cam32, bh132);

@@ -1330,7 +1330,13 @@ namespace bhray {
 #ifndef BHRAY_TRACE_KERNEL_ATTR
 #define BHRAY_TRACE_KERNEL_ATTR      // (experiments: e.g. __attribute__((amdgpu_num_sgpr(88))))
 #endif
-template <int METHOD, bool MODELS, bool COUNT, bool DENSE, int EVAL = 0, bool ORIGIN = false, bool LENSED = false>
+// RAYS (bhray_trace_rays): the launch traces a caller's ray list instead of a queue of pixels.  Entry idx of the launch IS ray idx: the refill loads the
+// record (bhray_ray: origin, direction - two float4, L.prev) instead of decoding a pixel and running create_ray, forms the per-ray twins of the frame uniforms that depend
+// on where a ray starts (ray_distance, ray_distance_f, relativity0, the initial closest approach: FrameParams' operation sequences, per ray), and the epilogue stores to
+// L.out[idx].  A record with a non-finite component or an all-zero direction is answered (0, 0, 0, -1) at load and never takes a lane.  Kernels of their own, as LENSED:
+// every other instantiation is the text it was.  Everything behind the refill - march, phases, traversal - is the shipped text: no step or phase reads the camera
+// (the audit: DESIGN.md §15).  Out of these kernels by constexpr: the quad march, wave priority, the strided thin shares (a frame's scheduling, measured on frames).
+template <int METHOD, bool MODELS, bool COUNT, bool DENSE, int EVAL = 0, bool ORIGIN = false, bool LENSED = false, bool RAYS = false>
 __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS ? (DENSE ? BHRAY_TRACE_WAVES_MESH_DENSE : BHRAY_TRACE_WAVES_MESH) : (DENSE ? BHRAY_TRACE_WAVES_DENSE : BHRAY_TRACE_WAVES)) void trace_kernel(const FrameParams* __restrict__ Pb, const FrameLaunch* __restrict__ Fb, const int nb, int* __restrict__ err_flag) {
     const int lane = threadIdx.x & 63;
     int err = 0;
@@ -1353,6 +1359,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
     constexpr int REL_BATCH = (METHOD == 0 && DENSE && !MODELS) ? BHRAY_REL_BATCH_EULER_DENSE : BHRAY_REL_BATCH;
     constexpr int REFILL_MIN = (METHOD == 0 && DENSE && !MODELS) ? BHRAY_REFILL_MIN_EULER_DENSE : BHRAY_REFILL_MIN;
     static_assert(!LENSED || (MODELS && !DENSE && EVAL == 0 && !ORIGIN), "the lensed-mesh kernels: mesh variant, latency build, the contract's evaluation, general hole position");
+    static_assert(!RAYS || (!COUNT && !DENSE && EVAL == 0 && !ORIGIN && !LENSED), "the ray-list kernels: latency build, the contract's evaluation, general hole position, no counting, flat-space models");
     constexpr bool UNIFIED = BHRAY_UNIFIED != 0 && EVAL == 0 && (!MODELS || BHRAY_UNIFIED_MESH != 0) && !COUNT && !LENSED;           // the unified march (bhray_step_u.inc) in the contract kernels that do not count (the lensed-mesh kernels: the general step, whose ppos / pdir a paused lane keeps)
     constexpr bool ONE_TEST = UNIFIED && !MODELS && (((BHRAY_ONE_TEST & 1) != 0 && !DENSE) || ((BHRAY_ONE_TEST & 2) != 0 && DENSE));
     // the RK step's error estimate behind a wave-uniform bound (next_ray_rk_t): 0 the full text, 1 skipped where the bound holds, 2 the full text and the bound's counters
@@ -1366,7 +1373,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
     constexpr bool BVH_WW = MESH_DENSE;                   // ... and the while-while traversal
     constexpr bool ROTATE = BHRAY_PHASE_ORDER != 0;                        // the march behind the refill (per build: a build that measures slower keeps the earlier order here)
     constexpr bool FLAT2 = ROTATE && UNIFIED && !MODELS && METHOD == 1;    // ... and an exit finished in one visit: general step + second flat pass behind the flat phase
-    constexpr bool WAVE_PRIO = ((BHRAY_WAVE_PRIO & 1) != 0 && !DENSE && !MODELS) || ((BHRAY_WAVE_PRIO & 2) != 0 && DENSE);   // (the mesh variant's lone launches wait for their traversals: nothing, measured)
+    constexpr bool WAVE_PRIO = !RAYS && (((BHRAY_WAVE_PRIO & 1) != 0 && !DENSE && !MODELS) || ((BHRAY_WAVE_PRIO & 2) != 0 && DENSE));   // (the mesh variant's lone launches wait for their traversals: nothing, measured)
     __shared__ float cold_lds[COLD_LDS ? (8 + BHRAY_HIT_LDS + (WAVE_PRIO ? 1 : 0)) * BHRAY_TRACE_THREADS : 1];
     // Integrator steps this wave issues for the frames of the batch -> Fb[0].work at the kernel's end.  Wave-uniform: a scalar register.
     // Counted in whole batches of steps, where the step loop is entered (a batch cut short by its last ray counts in full), and for the
@@ -1417,7 +1424,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
             const uint32_t waves = total < (uint32_t)BHRAY_THIN_WAVES ? total : (uint32_t)BHRAY_THIN_WAVES;
             const uint32_t share = (qcount + waves - 1) / waves;
             if (share < 64u) thin_share = share > 0u ? share : 1u;
-            if ((F.trace_flags & TRACE_THIN_STRIDED) && share < (uint32_t)BHRAY_THIN_STRIDED_BELOW) thin_stride = waves;
+            if (!RAYS && (F.trace_flags & TRACE_THIN_STRIDED) && share < (uint32_t)BHRAY_THIN_STRIDED_BELOW) thin_stride = waves;
         }
     } else if (!DENSE && BHRAY_THIN_WAVES > 0 && (nb == 1 || gridDim.x >= 4u * (uint32_t)nb)) {   // (every frame of a batch needs blocks of its own)
         uint32_t own_blocks = gridDim.x;
@@ -1428,7 +1435,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
         if (waves > 0u) {
             const uint32_t share = (qcount + waves - 1) / waves;
             if (share < 64u) thin_share = share > 0u ? share : 1u;
-            if ((F.trace_flags & TRACE_THIN_STRIDED) && share < (uint32_t)BHRAY_THIN_STRIDED_BELOW) thin_stride = waves;
+            if (!RAYS && (F.trace_flags & TRACE_THIN_STRIDED) && share < (uint32_t)BHRAY_THIN_STRIDED_BELOW) thin_stride = waves;
         }
         if (thin_share != 0u && fi != 0) continue;
     }
@@ -1436,7 +1443,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
     // The quad march (bhray_quad.inc): a queue that fits 16 rays per wave on the waves the host allows it (TRACE_QUAD_WPS_* of trace_flags: waves per
     // SIMD; 0 = off) is marched with one ray per QUAD of lanes - x, y, z on three lanes - instead of one per lane: fewer instructions per
     // iteration of the launch's longest ray, the same operations per ray.  Dealt out once like a scalar thin share; whole rounds of one wave per SIMD.
-    if constexpr (!DENSE && !MODELS && !COUNT && EVAL == 0) {
+    if constexpr (!DENSE && !MODELS && !COUNT && EVAL == 0 && !RAYS) {
         const uint32_t q_wps = ((uint32_t)F.trace_flags >> TRACE_QUAD_WPS_SHIFT) & (uint32_t)TRACE_QUAD_WPS_MASK;
         if (q_wps != 0u && BHRAY_THIN_WAVES > 0 && (nb == 1 || gridDim.x >= 4u * (uint32_t)nb)) {
             uint32_t own_blocks = gridDim.x, my_block = blockIdx.x;
@@ -1508,6 +1515,30 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                 const uint32_t rank = lanes_below(need);
                 uint32_t idx = base + rank;
                 if (!DENSE && thin_stride != 0u) idx = base + rank * thin_stride;
+                if constexpr (RAYS) {
+                if (mode == M_EMPTY && rank < n && idx < qcount) {
+                    // the record: two 16-byte loads of a 32-byte aligned pair (bhray_ray; one 64-byte line per two rays); the pad words are not looked at
+                    const float4* __restrict__ rec = L.prev + 2 * (size_t)idx;
+                    const float4 ro = rec[0], rd = rec[1];
+                    const F3 org = f3(ro.x, ro.y, ro.z), rdir = f3(rd.x, rd.y, rd.z);
+                    const bool finite = (fabsf(org.x) < INFINITY) & (fabsf(org.y) < INFINITY) & (fabsf(org.z) < INFINITY) &
+                                        (fabsf(rdir.x) < INFINITY) & (fabsf(rdir.y) < INFINITY) & (fabsf(rdir.z) < INFINITY);       // a NaN fails its compare
+                    const bool usable = finite & ((rdir.x != 0.0f) | (rdir.y != 0.0f) | (rdir.z != 0.0f));
+                    if (!usable) {
+                        L.out[idx] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);       // not traced: the lane stays empty (the wave's exit test below knows)
+                    } else {
+                        cold.set_pix(idx);
+                        cold.set_rdir(rdir);
+                        cpos = org; cdir = rdir; ppos = org; pdir = rdir;
+                        rkpos = org; rkdir = rdir; rkh = P.step_size;
+                        // the frame uniforms that depend on the ray's origin, per ray: derive_frame's operation sequences (bhray_api.hip: distance, fdistance, the compare)
+                        cold.set_color(f3(0, 0, 0)); amount = 1.0f; closest = distance_ph<PH>(org, bpos);
+                        dist_c = fdistance_ph<PH>(org, bpos); cpos_dist = dist_c; qrel = org - bpos;
+                        it = 0; HIT_SET(0);
+                        mode = closest < H.R ? M_REL : M_FLAT;
+                    }
+                }
+                } else {
                 if (mode == M_EMPTY && (DENSE || rank < n) && idx < qcount) {
                     const uint32_t pix = queue[idx];
                     cold.set_pix(pix);
@@ -1541,6 +1572,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                         cold.set_urg((b2 > BHRAY_PRIO_3_LO && b2 < BHRAY_PRIO_3_HI) ? 3 : ((b2 > BHRAY_PRIO_2_LO && b2 < BHRAY_PRIO_2_HI) ? 2 : (b2 < BHRAY_PRIO_1_HI ? 1 : 0)));
                     }
                 }
+                }
                 if (WAVE_PRIO && (F.trace_flags & TRACE_WAVE_PRIO)) {       // the wave's priority: its longest ray's class (until the next refill)
                     const int u = mode != M_EMPTY ? cold.urg() : -1;
                     if (__any(u == 3)) __builtin_amdgcn_s_setprio(3);
@@ -1549,7 +1581,10 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                     else __builtin_amdgcn_s_setprio(0);
                 }
             }
-            if (!__any(mode != M_EMPTY)) break;
+            if (!__any(mode != M_EMPTY)) {
+                if constexpr (RAYS) { if (!exhausted) continue; }       // (a refill that met unusable records only took no lane: the list is not used up yet - the next round refills)
+                break;
+            }
         }
 #if BHRAY_PHASE_ORDER
         // (BHRAY_PHASE_ORDER: the march here, so that the lanes the epilogue frees at the round's end meet the refill before the next batch, not behind it)
@@ -1614,7 +1649,10 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
             if (mode >= M_SHADE_REL) {
                 const float pend_t = cold.pend_t();
                 Hit crs; crs.hit = true; crs.t = pend_t; crs.color = f3(0.0f, 0.0f, 0.0f); crs.opacity = 0.0f;
-                shade_disk<COUNT, PH, pow13_build(MODELS, DENSE) && !COUNT>(H, ppos, pdir, pend_t, H.ray_distance, crs, cnt);
+                // RAYS: the ray's own distance (ray.wgsl:511) from its record again - the lane holds its index - instead of a register carried across the step loop
+                float ray_distance = H.ray_distance;
+                if constexpr (RAYS) { const float4 ro = L.prev[2 * (size_t)cold.pix()]; ray_distance = distance_ph<PH>(f3(ro.x, ro.y, ro.z), bpos); }
+                shade_disk<COUNT, PH, pow13_build(MODELS, DENSE) && !COUNT>(H, ppos, pdir, pend_t, ray_distance, crs, cnt);
                 cpos = cpos + pdir * crs.t;
                 cpos_dist = fdistance_ph<PH>(cpos, bpos);
                 if (METHOD == 0) { dist_c = cpos_dist; qrel = cpos - bpos; }
@@ -1828,7 +1866,9 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                 } else {
                     o = make_float4(cdir.x, cdir.y, cdir.z, 0.0f);
                 }
-                {
+                if constexpr (RAYS) {
+                    L.out[pix] = o;                                        // result idx of the list: no rowmap, pitch or stamp
+                } else {
                     const int ox = (int)(pix & 0x7fffu), oy = (int)((pix >> 15) & 0x7fffu);
                     if (SL.n > 0) {
                         const int lv = (int)(pix >> 30);
@@ -2107,7 +2147,7 @@ hipError_t launch_classify(const FrameParams* Pb, const FrameLaunch* Fb, int nb,
 }
 
 // Which builds of trace_kernel<METHOD, MODELS, COUNT, DENSE, EVAL, ORIGIN, LENSED> exist (16 x 2 integrators general builds + 2 x 2 ORIGIN builds + 2 x 2 lensed-mesh builds
-// = 40 instantiations; 36 in round 11, 32 in round 9, 48 in round 5, 72 in round 3).
+// + 2 x 2 ray-list builds = 44 instantiations; 40 before the ray lists, 36 in round 11, 32 in round 9, 48 in round 5, 72 in round 3).
 // eval: 0 the numerics contract, 1 BHRAY_F_LITERAL, 2 BHRAY_F_EVAL_FMA.  Every variant has a build for lone launches (the latency build);
 // the build for a saturated device (dense) exists where throughput is reported: not for counting kernels (BHRAY_F_COUNTERS is a diagnosis
 // mode: the same counts whichever build marches) and, of the two measurement-only evaluations, not for the mesh variant.  A launch that
@@ -2121,7 +2161,7 @@ constexpr bool trace_variant_exists(int eval, bool models, bool dense, bool coun
 // latency build, counting or not) and what a launch gets that asks for a build that does not exist: trace_resolve (bhray_internal.h).  The builds instantiated are the variants
 // that resolve to themselves.  The loop order is the order the kernels stand in the code object (lensed first, then per integrator the evaluations 1, 2, 0, mesh / counting /
 // ORIGIN / dense before their opposites): kept, so the object does not change.
-struct TraceBuilds { int n; TraceVariant v[40]; };
+struct TraceBuilds { int n; TraceVariant v[44]; };
 constexpr TraceBuilds trace_builds() {
     TraceBuilds t{};
     for (int lensed = 1; lensed >= 0; lensed--) for (int method = 0; method < 2; method++) for (int e = 1; e <= 3; e++) for (int mesh = 1; mesh >= lensed; mesh--)
@@ -2129,10 +2169,15 @@ constexpr TraceBuilds trace_builds() {
             const TraceVariant v{method, lensed ? 2 : mesh, count != 0, dense != 0, e % 3, origin != 0};
             if (trace_resolve(v) == v) t.v[t.n++] = v;
         }
+    // the ray-list kernels (trace_kernel's RAYS): both integrators x {no models, flat-space models}; behind everything else, so the others keep their places
+    for (int method = 0; method < 2; method++) for (int mesh = 1; mesh >= 0; mesh--) {
+        const TraceVariant v{method, mesh, false, false, 0, false, true};
+        if (trace_resolve(v) == v) t.v[t.n++] = v;
+    }
     return t;
 }
 constexpr TraceBuilds TRACE_BUILDS = trace_builds();
-static_assert(TRACE_BUILDS.n == 36 + (BHRAY_ORIGIN_KERNEL != 0 && BHRAY_UNIFIED != 0 ? 4 : 0), "instantiations of trace_kernel");
+static_assert(TRACE_BUILDS.n == 36 + (BHRAY_ORIGIN_KERNEL != 0 && BHRAY_UNIFIED != 0 ? 4 : 0) + 4, "instantiations of trace_kernel (the last four: the ray-list kernels)");
 constexpr bool trace_variant_exists_agrees() {     // trace_variant_exists is trace_resolve's rule for the dense builds
     for (int i = 0; i < 24; i++) {
         const TraceVariant v{0, i & 1, (i & 2) != 0, (i & 4) != 0, i >> 3, false};
@@ -2144,7 +2189,7 @@ static_assert(trace_variant_exists_agrees(), "trace_variant_exists / trace_resol
 template <int I>
 static const void* trace_kernel_at() {
     constexpr TraceVariant V = TRACE_BUILDS.v[I];
-    return (const void*)trace_kernel<V.method, V.models != 0, V.count, V.dense, V.eval, V.origin, V.models == 2>;
+    return (const void*)trace_kernel<V.method, V.models != 0, V.count, V.dense, V.eval, V.origin, V.models == 2, V.rays>;
 }
 template <int... I>
 static const void* trace_kernel_lookup(const TraceVariant& resolved, std::integer_sequence<int, I...>) {

@@ -59,6 +59,11 @@ OFF(bhray_fxaa_details, subpixel_quality, 12);
 SZ(bhray_mix_details, 4);
 OFF(bhray_mix_details, mix_ratio, 0);
 
+// a ray of bhray_trace_rays: two 16-byte halves (the kernel loads it as two float4)
+SZ(bhray_ray, 32);
+OFF(bhray_ray, origin, 0); OFF(bhray_ray, pad0, 12); OFF(bhray_ray, direction, 16); OFF(bhray_ray, pad1, 28);
+static_assert(BHRAY_MAX_RAYS_PER_CALL == (1u << 26), "BHRAY_MAX_RAYS_PER_CALL");
+
 // not reference layouts, but ABI the bindings restate (bhusie_amd/layouts.py)
 static_assert(sizeof(bhray_counters) == 104, "bhray_counters");
 static_assert(BHRAY_COMM_ID_BYTES == 128, "ncclUniqueId");

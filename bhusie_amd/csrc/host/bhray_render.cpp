@@ -1,7 +1,9 @@
 // bhray_render — minimal C++ host program over renderer.hpp: renders one frame of the reference's default scene
 // (camera (0,0,-19), hole at the origin, disk 2..10, R = 20; camera.rs:10-16, blackhole.rs:16-28) and writes the HDR frame
 // as raw little-endian f32 RGBA (row 0 = top).  Usage:
-//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...]
+//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H]
+// --panorama W H: instead of the pinhole frame, a 360 x 180 degree panorama of W x H pixels from the camera's position, its centre column looking along the camera's forward
+// (bhusie::equirect_rays through Renderer::render_rays: bhray_trace_rays); written the same way.  Not with --lensed-mesh or --devices.
 // --pose: every --obj mesh is turned by the Euler rotation (RX, RY, RZ) about its own origin on the GPU (bhray_pose_from_euler + bhray_set_model_pose); needs --bvh device.
 // --lensed-mesh: the meshes are tested on every step inside the relativity sphere too (bhray_set_mesh_lensing): a mesh inside the sphere is visible.
 // --bvh device: every mesh's tree is built on the GPU (bhray_upload_model_build) instead of by the reference's host builder (the default).
@@ -138,8 +140,8 @@ int main(int argc, char** argv) {
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
         return 0;
     }
-    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...]\n", argv[0]); return 2; }
-    uint32_t bw = 72, bh = 41, levels = 4, disk = 256;
+    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H]\n", argv[0]); return 2; }
+    uint32_t bw = 72, bh = 41, levels = 4, disk = 256, pano_w = 0, pano_h = 0;
     bool rk = false, bvh_device = false, lensed = false, posed = false;
     float rotation[3] = {0.0f, 0.0f, 0.0f};
     std::vector<const char*> objs;
@@ -153,6 +155,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--bvh") && i + 1 < argc && (!std::strcmp(argv[i + 1], "device") || !std::strcmp(argv[i + 1], "reference"))) bvh_device = !std::strcmp(argv[++i], "device");
         else if (!std::strcmp(argv[i], "--pose") && i + 3 < argc) { posed = true; for (int a = 0; a < 3; a++) rotation[a] = (float)std::atof(argv[++i]); }
         else if (!std::strcmp(argv[i], "--lensed-mesh")) lensed = true;
+        else if (!std::strcmp(argv[i], "--panorama") && i + 2 < argc) { pano_w = (uint32_t)std::atoi(argv[++i]); pano_h = (uint32_t)std::atoi(argv[++i]); if (pano_w < 1 || pano_h < 1) { std::fprintf(stderr, "--panorama needs W >= 1 and H >= 1\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) { for (const char* p = argv[++i]; *p; ) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p) p++; } }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
@@ -176,9 +179,15 @@ int main(int argc, char** argv) {
         }
         r.ray_details.integration_method = rk ? 1 : 0;
         r.mesh_lensing = lensed;
-        r.render(0.0f);
-        const std::vector<float> out = r.ray_pipeline().output();
+        std::vector<float> out;
         auto res = r.ray_pipeline().resolution();
+        if (pano_w) {
+            out = r.render_rays(bhusie::equirect_rays(r.camera.position, r.camera.forward, pano_w, pano_h));
+            res = {pano_w, pano_h};
+        } else {
+            r.render(0.0f);
+            out = r.ray_pipeline().output();
+        }
         FILE* f = std::fopen(argv[1], "wb");
         if (!f) { std::perror(argv[1]); return 1; }
         std::fwrite(out.data(), sizeof(float), out.size(), f);

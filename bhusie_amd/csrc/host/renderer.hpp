@@ -9,6 +9,7 @@
 //   Renderer              src/renderer/mod.rs:58-207, 370-420            {new, render} restricted to the ray pass
 // Header-only; link with -lbhray.  Errors become std::runtime_error (the reference panics).
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
@@ -178,6 +179,12 @@ public:
         check(bhray_read_hdr(ctx_, out.data(), (size_t)cfg_.frame_w * 16), ctx_);
         return out;
     }
+    // ray batches (bhray_trace_rays): what trace_ray returns for each ray under the current uniforms, textures and models - 4 f32 per ray
+    std::vector<float> trace_rays(const std::vector<bhray_ray>& rays) {
+        std::vector<float> out(rays.size() * 4);
+        check(bhray_trace_rays(ctx_, rays.data(), (uint32_t)rays.size(), out.data()), ctx_);
+        return out;
+    }
     bhray_ctx* ctx() { return ctx_; }
 private:
     bhray_config cfg_;
@@ -189,6 +196,36 @@ private:
     std::vector<uint64_t> tickets_;
     std::vector<bool> pending_;
 };
+
+// A 360 x 180 degree panorama's rays (bhusie_amd/cameras.py: equirect_rays): pixel centres, column i at longitude (i - (w - 1) / 2) * 2 pi / w from `forward` towards
+// `right`, row j at latitude (j - (h - 1) / 2) * pi / h towards `up`, in create_ray's basis (plane_up = (0, -1, 0): ray.wgsl:275-277); binary32 throughout, directions
+// normalised as the kernels expect (v * (1 / sqrt(dot(v, v)))).
+inline std::vector<bhray_ray> equirect_rays(const float position[3], const float forward[3], uint32_t w, uint32_t h) {
+    auto cross = [](const float a[3], const float b[3], float o[3]) { o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0]; };
+    auto normalize = [](float v[3]) { const float r = 1.0f / std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); v[0] *= r; v[1] *= r; v[2] *= r; };
+    const float plane_up[3] = {0.0f, -1.0f, 0.0f};
+    float fwd[3] = {forward[0], forward[1], forward[2]}, right[3], up[3];
+    cross(fwd, plane_up, right); normalize(right);
+    cross(fwd, right, up); normalize(up);
+    normalize(fwd);
+    const float pi = 3.14159274f;
+    std::vector<bhray_ray> rays((size_t)w * h);
+    for (uint32_t j = 0; j < h; j++) {
+        const float lat = ((float)j - (float)(h - 1) * 0.5f) * (pi / (float)h);
+        const float cp = std::cos(lat), sp = std::sin(lat);
+        for (uint32_t i = 0; i < w; i++) {
+            const float lon = ((float)i - (float)(w - 1) * 0.5f) * (2.0f * pi / (float)w);
+            const float a = cp * std::cos(lon), b = cp * std::sin(lon);
+            bhray_ray& r = rays[(size_t)j * w + i];
+            float d[3];
+            for (int k = 0; k < 3; k++) d[k] = (fwd[k] * a + right[k] * b) + up[k] * sp;
+            normalize(d);
+            for (int k = 0; k < 3; k++) { r.origin[k] = position[k]; r.direction[k] = d[k]; }
+            r.pad0 = 0.0f; r.pad1 = 0.0f;
+        }
+    }
+    return rays;
+}
 
 // Renderer::{new, render} restricted to the ray pass.
 class Renderer {
@@ -233,6 +270,12 @@ public:
         apply_lensing();
         ray_pipeline_.pass_handoff();
         return ray_pipeline_.finish();
+    }
+    // an image through caller-supplied rays (w * h of them, row 0 the top) under this renderer's black hole, details, textures and models: RGBA32F as output()
+    std::vector<float> render_rays(const std::vector<bhray_ray>& rays) {
+        ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);
+        apply_lensing();
+        return ray_pipeline_.trace_rays(rays);
     }
 private:
     void apply_lensing() { if (mesh_lensing != lensing_applied_) { ray_pipeline_.set_mesh_lensing(mesh_lensing); lensing_applied_ = mesh_lensing; } }

@@ -20,6 +20,7 @@ F_EVAL_FMA = 32
 F_GATHER_SKY = 128
 TEX_TEMP_LUT, TEX_DISK, TEX_SKY = 0, 1, 2
 FXAA_MAX_ITERATIONS = 1024
+MAX_RAYS_PER_CALL = 1 << 26          # BHRAY_MAX_RAYS_PER_CALL
 
 
 class BhrayError(RuntimeError):
@@ -67,6 +68,10 @@ class BhrayFxaaDetails(C.Structure):       # fxaa_pipline.rs:76-83 (FXAADetailsU
 
 class BhrayMixDetails(C.Structure):         # mix_pipeline.rs:5-7 (MixDetails)
     _fields_ = [("mix_ratio", C.c_float)]
+
+
+class BhrayRay(C.Structure):                # bhray_ray: one ray of bhray_trace_rays, two 16-byte halves
+    _fields_ = [("origin", C.c_float * 3), ("pad0", C.c_float), ("direction", C.c_float * 3), ("pad1", C.c_float)]
 
 
 class BhrayModelDesc(C.Structure):
@@ -136,6 +141,7 @@ class BhrayModelBuildInfo(C.Structure):
 
 assert C.sizeof(BhrayDetails) == 32 and C.sizeof(BhrayCameraUniform) == 32 and C.sizeof(BhrayBlackHoleUniform) == 132
 assert C.sizeof(BhrayNode) == 32 and C.sizeof(BhrayTriangle) == 24
+assert C.sizeof(BhrayRay) == 32 and BhrayRay.direction.offset == 16
 
 LEVEL_GRID_LAUNCHES = MAX_LEVELS + 2
 LEVEL_GRID_NO_FEEDBACK = 2 ** 64 - 1
@@ -206,6 +212,9 @@ SYMBOLS = {
     "bhray_set_model_transform": (C.c_int, [vp, u32, P(C.c_float), i32]),
     "bhray_set_uniforms": (C.c_int, [vp, vp, vp, vp]),
     "bhray_set_mesh_lensing": (C.c_int, [vp, i32]),
+    "bhray_trace_rays": (C.c_int, [vp, P(BhrayRay), u32, P(C.c_float)]),
+    "bhray_trace_rays_device": (C.c_int, [vp, vp, u32, vp, vp]),
+    "bhray_trace_rays_sky": (C.c_int, [vp, P(BhrayRay), u32, P(C.c_float), vp]),
     "bhray_render": (C.c_int, [vp]),
     "bhray_flush": (C.c_int, [vp]),
     "bhray_sync": (C.c_int, [vp]),

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import lib
-from .layouts import (BhrayFxaaDetails, BhrayMixDetails, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters,
+from .layouts import (BhrayFxaaDetails, BhrayMixDetails, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters, BhrayRay,
                       BhrayGatherInfo, BhrayModelBuildInfo, BhrayModelDesc, BhrayRebalanceInfo, BhrayTiming, check)
 from .model import NODE_DTYPE, Model
 from .scene import BlackHole, Camera, RayDetails
@@ -308,6 +308,40 @@ class RayPass:
         relativity sphere.  Off by default; BhrayError (BHRAY_E_STATE) for on on a literal / eval_fma ctx."""
         check(self._L.bhray_set_mesh_lensing(self._h, 1 if on else 0), self._h, self._L)
 
+    # -- ray batches (bhray_trace_rays, DESIGN.md §15)
+    @staticmethod
+    def _ray_records(rays) -> np.ndarray:
+        """(n, 6) origin + direction or (n, 8) records -> contiguous (n, 8) float32 (layouts.BhrayRay)"""
+        r = np.asarray(rays, dtype=np.float32)
+        if r.ndim != 2 or r.shape[1] not in (6, 8):
+            raise ValueError(f"trace_rays: rays must be (n, 6) or (n, 8) float32, got {r.shape}")
+        if r.shape[1] == 8:
+            return np.ascontiguousarray(r)
+        out = np.zeros((r.shape[0], 8), dtype=np.float32)
+        out[:, 0:3] = r[:, 0:3]; out[:, 4:7] = r[:, 3:6]
+        return out
+
+    def trace_rays(self, rays, sky: bool = False):
+        """What the shader's trace_ray returns for each ray under the ctx's current uniforms, textures and models: (n, 4) float32, (colour, 1) or
+        (escape direction, 0).  A non-finite component or an all-zero direction: BhrayError (BHRAY_E_INVALID).  sky=True: also the RGBA16F image of the
+        sky pass over the results, returned as a pair (bhray_trace_rays_sky)."""
+        rec = self._ray_records(rays)
+        n = rec.shape[0]
+        out = np.zeros((n, 4), dtype=np.float32)
+        rp = rec.ctypes.data_as(C.POINTER(BhrayRay)) if n else None
+        op = out.ctypes.data_as(C.POINTER(C.c_float)) if n else None
+        if not sky:
+            check(self._L.bhray_trace_rays(self._h, rp, n, op), self._h, self._L)
+            return out
+        out16 = np.zeros((n, 4), dtype=np.float16)
+        check(self._L.bhray_trace_rays_sky(self._h, rp, n, op, out16.ctypes.data if n else None), self._h, self._L)
+        return out, out16
+
+    def trace_rays_device(self, d_rays: int, n: int, d_out: int, stream: int | None = None):
+        """The device form: n records at device address d_rays -> n RGBA32F results at d_out, enqueued behind what `stream` (a hipStream_t; None: the legacy
+        stream) holds now; work enqueued on `stream` afterwards sees the results.  An unusable ray's result is (0, 0, 0, -1) (bhray_trace_rays_device)."""
+        check(self._L.bhray_trace_rays_device(self._h, C.c_void_p(d_rays), int(n), C.c_void_p(d_out), C.c_void_p(stream) if stream else None), self._h, self._L)
+
     # -- per frame
     def set_uniforms(self, camera: bytes, black_hole: bytes, details: bytes):
         assert len(camera) == 32 and len(black_hole) == 132 and len(details) == 32
@@ -579,6 +613,28 @@ class Renderer:
 
     def read_hdr(self):
         return self.ray_pass.read_hdr()
+
+    def render_rays(self, rays, shape, resolve_sky: bool = False):
+        """An image seen through caller-supplied rays (bhusie_amd.cameras: pinhole_rays, equirect_rays, fisheye_rays, or any (h * w, 6 | 8) array) under this
+        renderer's black hole, details, textures and models: (h, w, 4) float32 - (colour, 1) or (escape direction, 0), as read_hdr.  A ray with a zero
+        direction or a non-finite component (a fisheye's pixels outside its circle) is not traced: (0, 0, 0, -1).  resolve_sky=True: the RGBA16F image of the
+        sky pass over it instead (RayPass.resolve_sky's semantics; the untraced pixels pass through: black, alpha -1)."""
+        h, w = int(shape[0]), int(shape[1])
+        rec = RayPass._ray_records(rays)
+        if rec.shape[0] != h * w:
+            raise ValueError(f"render_rays: {rec.shape[0]} rays for a {w}x{h} image")
+        self.ray_pass.set_uniforms(self.camera.uniform(), self.black_hole.uniform(), self.ray_details.uniform())
+        if bool(self.mesh_lensing) != self._lensing_applied:
+            self.ray_pass.set_mesh_lensing(self.mesh_lensing)
+            self._lensing_applied = bool(self.mesh_lensing)
+        six = rec[:, [0, 1, 2, 4, 5, 6]]
+        usable = np.isfinite(six).all(axis=1) & (rec[:, 4:7] != 0.0).any(axis=1)
+        img = np.zeros((h * w, 4), dtype=np.float16 if resolve_sky else np.float32)
+        img[:, 3] = -1.0
+        if usable.any():
+            got = self.ray_pass.trace_rays(rec[usable], sky=resolve_sky)
+            img[usable] = got[1] if resolve_sky else got
+        return img.reshape(h, w, 4)
 
     def save_image(self, path):
         """The reference's Save Image (mod.rs:473-482): the display pass's RGBA8 image of the last frame, written with alpha 255

@@ -439,6 +439,44 @@ int bhray_set_uniforms(bhray_ctx* ctx, const void* camera_uniform_32,
  * rank calls it alike.  bhray_rebalance's wave-step measure does not see the traversal work of lensed frames.       */
 int bhray_set_mesh_lensing(bhray_ctx* ctx, int32_t on);
 
+/* Ray batches (not in the reference, whose shader only traces the rays create_ray makes of its pinhole
+ * camera - but its trace_ray(ray) takes any ray): trace a caller's list of rays - a panorama, a stereo pair, jittered
+ * samples, the view of an observer who is not the camera.
+ * Result i (four f32) is what the shader's trace_ray returns for ray i under the ctx's CURRENT state: the black hole
+ * and details of the last bhray_set_uniforms, the resident textures, models 0 .. model_count-1 with their transforms:
+ * (colour, 1) or (escape direction, 0), as a frame's pixel before the sky pass.  The camera block of the uniforms is
+ * not read: what a frame takes from the camera's position - the ray's distance from the hole (ray.wgsl:511), whether it
+ * starts inside the relativity sphere (488) and its first closest approach - is formed per ray, with the operation
+ * sequences the frames use, so create_ray's rays (bhusie_amd/cameras.py: pinhole_rays) give a levels = 1 frame, bit
+ * for bit.
+ * Directions are used as given: unit length, as a binary32 normalise produces it, is the caller's business (the step's
+ * culls and segment lengths assume it).  The pad words are not read.  A ray with a non-finite component or an
+ * all-zero direction is not traced: bhray_trace_rays refuses the whole call with BHRAY_E_INVALID before anything is
+ * enqueued (out untouched); bhray_trace_rays_device cannot look, so the kernel tests at load and that ray's result is
+ * (0, 0, 0, -1).
+ * n == 0: BHRAY_OK, nothing happens.  n > BHRAY_MAX_RAYS_PER_CALL, a NULL ctx or a NULL array: BHRAY_E_INVALID.
+ * BHRAY_E_STATE: before the first bhray_set_uniforms; on a ctx created with BHRAY_F_LITERAL or BHRAY_F_EVAL_FMA (no
+ * such kernels exist: the rule of bhray_set_mesh_lensing); while mesh lensing is on; on a ctx with device_count >= 2.
+ * A BHRAY_F_COUNTERS ctx runs the kernels that do not count: its counters do not move.
+ * bhray_trace_rays launches the staged frames first (they keep the uniforms they were staged with), copies the rays
+ * in, traces, copies the results out and returns when `out_rgba32f` is complete.
+ * bhray_trace_rays_device only enqueues: the batch runs on a stream the ctx owns for queries, starts behind an event
+ * recorded on hip_stream (NULL: the legacy stream, as bhray_wait_stream) and, before the call returns, hip_stream is
+ * made to wait for the batch's end - work enqueued on hip_stream afterwards sees the results.  d_rays (n records,
+ * 16-byte aligned) and d_out_rgba32f (n x 16 bytes) belong to the ctx's device and stay valid until then.
+ * Frames in flight are not waited for (the scene is only read), and frames before and after a batch keep their bits.
+ * Every call that waits for the frames in flight before it rewrites scene memory - the texture and model uploads, the
+ * vertex updates, bhray_set_model_pose, bhray_destroy - waits for the outstanding ray batches too, and so does
+ * bhray_sync, which reports a batch's device fault as it reports a frame's.                                          */
+typedef struct bhray_ray { float origin[3]; float pad0; float direction[3]; float pad1; } bhray_ray;   /* 32 bytes */
+#define BHRAY_MAX_RAYS_PER_CALL (1u << 26)
+int bhray_trace_rays(bhray_ctx* ctx, const bhray_ray* rays, uint32_t n, float* out_rgba32f);
+int bhray_trace_rays_device(bhray_ctx* ctx, const void* d_rays, uint32_t n, void* d_out_rgba32f, void* hip_stream);
+/* bhray_trace_rays followed by the sky pass over its results (the kernel of bhray_resolve_sky, with its semantics: alpha == 0
+ * results become sky^4 with alpha 1, every other result - an unusable ray's (0, 0, 0, -1) cannot occur here - passes through;
+ * n x 4 binary16, round-to-nearest-even).  out_rgba32f may be NULL.  Everything else as bhray_trace_rays.                 */
+int bhray_trace_rays_sky(bhray_ctx* ctx, const bhray_ray* rays, uint32_t n, float* out_rgba32f, uint16_t* out_rgba16f);
+
 /* Dispatch — replaces `for rp in ray_pipelines { rp.pass() }` (mod.rs:415-417,
  * ray_pipeline.rs:301-309).  Asynchronous on the ctx stream; levels ordered.                 */
 int bhray_render(bhray_ctx* ctx);
