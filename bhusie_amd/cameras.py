@@ -92,8 +92,9 @@ def _camera_fields(camera):
     return u[0:3].copy(), u[4:7].copy(), F(u[7])
 
 
-def pinhole_rays(camera, w: int, h: int) -> np.ndarray:
-    """create_ray for every pixel of a w x h level (ray.wgsl:269-285)."""
+def pinhole_rays(camera, w: int, h: int, pixel=None) -> np.ndarray:
+    """create_ray for every pixel of a w x h level (ray.wgsl:269-285).  pixel=(x, y): that one pixel's ray only, as a (1, 8) array - the same
+    arithmetic, so the same bits as row y * w + x of the whole level (Renderer.pick)."""
     w, h = int(w), int(h)
     assert w >= 2 and h >= 2, "create_ray divides by min(w, h) - 1"
     pos, forward, fov = _camera_fields(camera)
@@ -102,8 +103,14 @@ def pinhole_rays(camera, w: int, h: int) -> np.ndarray:
     increment = F(1.0) / F(sm)
     px = np.arange(w, dtype=F)[None, :]
     py = np.arange(h, dtype=F)[:, None]
-    posx = (F(2.0) * (px - F(F(w - 1) * F(0.5)))) * increment
-    posy = (F(2.0) * (py - F(F(h - 1) * F(0.5)))) * increment
+    lw, lh = w, h
+    if pixel is not None:
+        x, y = int(pixel[0]), int(pixel[1])
+        assert 0 <= x < w and 0 <= y < h, "pinhole_rays: the pixel lies outside the level"
+        px, py = px[:, x:x + 1], py[y:y + 1, :]
+        w, h = 1, 1
+    posx = (F(2.0) * (px - F(F(lw - 1) * F(0.5)))) * increment
+    posy = (F(2.0) * (py - F(F(lh - 1) * F(0.5)))) * increment
     posx = np.broadcast_to(posx, (h, w)).astype(F)
     posy = np.broadcast_to(posy, (h, w)).astype(F)
     fov_factor = F(F(1.0) / _tan(F(fov / F(2.0))))

@@ -204,6 +204,8 @@ struct bhray_dev {
     bool q_used = false;                   // a batch has been enqueued (q_uploaded has been recorded; the engine's error word may be a batch's)
     float4* q_hin = nullptr; float4* q_hout = nullptr; float4* q_din = nullptr; float4* q_dout = nullptr;
     size_t q_cap = 0;                      // rays the staging holds
+    bhray_ray_record* q_hrec = nullptr; bhray_ray_record* q_drec = nullptr;      // the records' staging (bhray_trace_rays_records): grow-only, allocated by the first records batch
+    size_t q_rec_cap = 0;
     // asynchronous hand-off (dev_read_hdr_async)
     hipEvent_t read_ev[BHRAY_READ_RING] = {nullptr};     // ticket t -> read_ev[t % BHRAY_READ_RING]
     uint64_t read_tickets = 0;
@@ -421,6 +423,8 @@ void dev_destroy(bhray_dev* c) {
     if (c->q_hout) (void)hipHostFree(c->q_hout);
     if (c->q_din) (void)hipFree(c->q_din);
     if (c->q_dout) (void)hipFree(c->q_dout);
+    if (c->q_hrec) (void)hipHostFree(c->q_hrec);
+    if (c->q_drec) (void)hipFree(c->q_drec);
     for (hipEvent_t e : {c->q_begin, c->q_done, c->q_uploaded}) if (e) (void)hipEventDestroy(e);
     if (c->q_stream) (void)hipStreamDestroy(c->q_stream);
     for (Slot& S : c->slots) {
@@ -1126,7 +1130,8 @@ int ensure_query(bhray_dev* c) {
 }
 
 // One launch on the query stream: n rays at d_rays -> n results at d_out, under the engine's current uniforms, textures and models.  Enqueues only.
-int enqueue_rays(bhray_dev* c, const float4* d_rays, uint32_t n, float4* d_out) {
+// d_records: nullptr, or n bhray_ray_record (16-byte aligned) - the record kernels (TraceVariant::records).
+int enqueue_rays(bhray_dev* c, const float4* d_rays, uint32_t n, float4* d_out, void* d_records = nullptr) {
     // the pinned block of the batch before must have reached the device before it is rewritten (its device copy is read in stream order)
     if (c->q_used && hipEventQuery(c->q_uploaded) != hipSuccess) HIPCHK(c, hipEventSynchronize(c->q_uploaded));
     FrameParams& P = *(FrameParams*)c->q_hargs;
@@ -1138,7 +1143,8 @@ int enqueue_rays(bhray_dev* c, const float4* d_rays, uint32_t n, float4* d_out) 
     F.qctl = (uint32_t*)(c->q_dargs + Q_OFF_CTL);                 // [0] = n, [1] = 0: uploaded with the block, so the launch needs no reset of its own
     uint32_t* ctl = (uint32_t*)(c->q_hargs + Q_OFF_CTL);
     ctl[0] = n; ctl[1] = 0; ctl[2] = 0; ctl[3] = 0;
-    const TraceVariant v{P.method, P.model_count > 0 ? 1 : 0, false, false, 0, false, true};
+    F.row_work = (unsigned long long*)d_records;                  // the records (TraceVariant::records): the member a ray-list launch does not use otherwise
+    const TraceVariant v{P.method, P.model_count > 0 ? 1 : 0, false, false, 0, false, true, d_records != nullptr};
     int ctx_grid = c->num_cus * trace_blocks_per_cu(v);
     if (c->grid_override > 0) ctx_grid = c->grid_override;
     const int grid = (int)bhray_trace_grid_for(n, 1, (uint32_t)ctx_grid, c->level_grid_gen, 0, c->level_grid_floor);      // n is exact: no margin
@@ -1151,9 +1157,10 @@ int enqueue_rays(bhray_dev* c, const float4* d_rays, uint32_t n, float4* d_out) 
 }  // namespace
 
 // out: n x RGBA32F (may be NULL when sky16 is not); sky16: NULL, or n x RGBA16F - sky.wgsl over the results (launch_sky, the pass of dev_resolve_sky)
-int dev_trace_rays(bhray_dev* c, const bhray_ray* rays, uint32_t n, float* out, uint16_t* sky16) {
+// records: NULL, or n records (bhray_trace_rays_records: then `out` may be NULL too)
+int dev_trace_rays(bhray_dev* c, const bhray_ray* rays, uint32_t n, float* out, uint16_t* sky16, bhray_ray_record* records) {
     if (!c) return BHRAY_E_INVALID;
-    if (n > BHRAY_MAX_RAYS_PER_CALL || (n != 0 && (!rays || (!out && !sky16)))) return fail(c, BHRAY_E_INVALID, "bhray_trace_rays: bad arguments");
+    if (n > BHRAY_MAX_RAYS_PER_CALL || (n != 0 && (!rays || (!out && !sky16 && !records)))) return fail(c, BHRAY_E_INVALID, "bhray_trace_rays: bad arguments");
     { int rc = rays_refused(c, "bhray_trace_rays"); if (rc) return rc; }
     if (n == 0) return BHRAY_OK;
     for (uint32_t i = 0; i < n; i++) {                            // before anything is enqueued
@@ -1181,10 +1188,20 @@ int dev_trace_rays(bhray_dev* c, const bhray_ray* rays, uint32_t n, float* out, 
     } else {
         HIPCHK(c, hipStreamSynchronize(c->q_stream));           // (a copy of an earlier call that failed half-way may still read the staging)
     }
+    if (records && n > c->q_rec_cap) {                            // the same for the records (the stream is idle here)
+        if (c->q_hrec) (void)hipHostFree(c->q_hrec);
+        if (c->q_drec) (void)hipFree(c->q_drec);
+        c->q_hrec = c->q_drec = nullptr; c->q_rec_cap = 0;
+        const size_t cap = std::max<size_t>(n, 4096);
+        HIPCHK(c, hipHostMalloc(&c->q_hrec, cap * sizeof(bhray_ray_record)));
+        HIPCHK(c, hipMalloc(&c->q_drec, cap * sizeof(bhray_ray_record)));
+        c->q_rec_cap = cap;
+    }
     memcpy(c->q_hin, rays, (size_t)n * sizeof(bhray_ray));
     HIPCHK(c, hipMemcpyAsync(c->q_din, c->q_hin, (size_t)n * sizeof(bhray_ray), hipMemcpyHostToDevice, c->q_stream));
-    { int rc = enqueue_rays(c, c->q_din, n, c->q_dout); if (rc) return rc; }
+    { int rc = enqueue_rays(c, c->q_din, n, c->q_dout, records ? c->q_drec : nullptr); if (rc) return rc; }
     HIPCHK(c, hipMemcpyAsync(c->q_hout, c->q_dout, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, c->q_stream));
+    if (records) HIPCHK(c, hipMemcpyAsync(c->q_hrec, c->q_drec, (size_t)n * sizeof(bhray_ray_record), hipMemcpyDeviceToHost, c->q_stream));
     if (sky16) {                                                  // the records are used up: their device buffer (32 bytes per ray) takes the image (8), their pinned one its copy
         TexDev sky; sky.rgba = c->tex[BHRAY_TEX_SKY]; sky.w = c->tex_w[BHRAY_TEX_SKY]; sky.h = c->tex_h[BHRAY_TEX_SKY];
         HIPCHK(c, launch_sky(sky, c->q_dout, (uint2*)c->q_din, n, c->q_stream));
@@ -1200,21 +1217,23 @@ int dev_trace_rays(bhray_dev* c, const bhray_ray* rays, uint32_t n, float* out, 
         }
     }
     if (out) memcpy(out, c->q_hout, (size_t)n * sizeof(float4));
+    if (records) memcpy(records, c->q_hrec, (size_t)n * sizeof(bhray_ray_record));
     if (sky16) memcpy(sky16, c->q_hin, (size_t)n * sizeof(uint2));
     return BHRAY_OK;
 }
 
-int dev_trace_rays_device(bhray_dev* c, const void* d_rays, uint32_t n, void* d_out, hipStream_t s) {
+// d_records: NULL (bhray_trace_rays_device), or n records, 16-byte aligned (bhray_trace_rays_records_device, whose entry refuses a NULL)
+int dev_trace_rays_device(bhray_dev* c, const void* d_rays, uint32_t n, void* d_out, void* d_records, hipStream_t s) {
     if (!c) return BHRAY_E_INVALID;
     if (n > BHRAY_MAX_RAYS_PER_CALL || (n != 0 && (!d_rays || !d_out))) return fail(c, BHRAY_E_INVALID, "bhray_trace_rays_device: bad arguments");
-    if (((uintptr_t)d_rays | (uintptr_t)d_out) & 15u) return fail(c, BHRAY_E_INVALID, "bhray_trace_rays_device: the arrays must be 16-byte aligned");
+    if (((uintptr_t)d_rays | (uintptr_t)d_out | (uintptr_t)d_records) & 15u) return fail(c, BHRAY_E_INVALID, "bhray_trace_rays_device: the arrays must be 16-byte aligned");
     { int rc = rays_refused(c, "bhray_trace_rays_device"); if (rc) return rc; }
     if (n == 0) return BHRAY_OK;
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = ensure_query(c); if (rc) return rc; }
     HIPCHK(c, hipEventRecord(c->q_begin, s));                     // the batch starts behind what `s` holds now ...
     HIPCHK(c, hipStreamWaitEvent(c->q_stream, c->q_begin, 0));
-    { int rc = enqueue_rays(c, (const float4*)d_rays, n, (float4*)d_out); if (rc) return rc; }
+    { int rc = enqueue_rays(c, (const float4*)d_rays, n, (float4*)d_out, d_records); if (rc) return rc; }
     HIPCHK(c, hipEventRecord(c->q_done, c->q_stream));            // ... and what `s` gets from now on starts behind the batch
     HIPCHK(c, hipStreamWaitEvent(s, c->q_done, 0));
     return BHRAY_OK;

@@ -1573,7 +1573,24 @@ int bhray_trace_rays_device(bhray_ctx* c, const void* d_rays, uint32_t n, void* 
     if (n > BHRAY_MAX_RAYS_PER_CALL || (n != 0 && (!d_rays || !d_out))) return gfail(c, BHRAY_E_INVALID, "bhray_trace_rays_device: bad arguments");
     ENTER(c);
     { int rc = rays_entry(c, "bhray_trace_rays_device"); if (rc) return rc; }
-    DEV(c, c->parts[0].dev, dev_trace_rays_device(c->parts[0].dev, d_rays, n, d_out, (hipStream_t)s));
+    DEV(c, c->parts[0].dev, dev_trace_rays_device(c->parts[0].dev, d_rays, n, d_out, nullptr, (hipStream_t)s));
+    return BHRAY_OK;
+}
+// Ray records: the same entry rules; one engine.
+int bhray_trace_rays_records(bhray_ctx* c, const bhray_ray* rays, uint32_t n, float* out, bhray_ray_record* records) {
+    if (!c) return BHRAY_E_INVALID;
+    if (n > BHRAY_MAX_RAYS_PER_CALL || (n != 0 && (!rays || !records))) return gfail(c, BHRAY_E_INVALID, "bhray_trace_rays_records: bad arguments");
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_trace_rays_records"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_trace_rays(c->parts[0].dev, rays, n, out, nullptr, records));
+    return BHRAY_OK;
+}
+int bhray_trace_rays_records_device(bhray_ctx* c, const void* d_rays, uint32_t n, void* d_out, void* d_records, void* s) {
+    if (!c) return BHRAY_E_INVALID;
+    if (n > BHRAY_MAX_RAYS_PER_CALL || (n != 0 && (!d_rays || !d_out || !d_records))) return gfail(c, BHRAY_E_INVALID, "bhray_trace_rays_records_device: bad arguments");
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_trace_rays_records_device"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_trace_rays_device(c->parts[0].dev, d_rays, n, d_out, d_records, (hipStream_t)s));
     return BHRAY_OK;
 }
 int bhray_set_uniforms(bhray_ctx* c, const void* cam32, const void* bh132, const void* det32) {

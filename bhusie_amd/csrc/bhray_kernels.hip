@@ -427,9 +427,10 @@ struct BvhLds { int2* stack; };     // stack: this lane's column (entry k at sta
 // that moment, as the reference decides it) and is recorded in `pend` - so the nodes are visited in the same order, with the same
 // pruning, and equal-t ties between triangles resolve as in the reference.  Node pairs re-read on the way down are not counted.
 // A tree deeper than 64 levels raises BHRAY_E_BVH_DEPTH (D2).
-template <bool COUNT, bool WW>
+// SLOT (the record kernels): *slot_out = the bvh_lookup slot (contents + i) of the triangle that won, written where the hit is taken; untouched without a hit.
+template <bool COUNT, bool WW, bool SLOT = false>
 __device__ BHRAY_MODEL_INLINE void trace_ray_model(const ModelDev& M, const BvhLds lds, F3 pos, F3 dir, float t_min, float t_max,
-                                             Hit& closest, F3& normal_out, unsigned long long* cnt, int* err) {
+                                             Hit& closest, F3& normal_out, unsigned long long* cnt, int* err, int* slot_out = nullptr) {
     static_assert(BHRAY_BVH_LDS_STACK >= 2 && BHRAY_BVH_STACK <= 64, "short stack / trail sizes");
     constexpr int D = BHRAY_BVH_LDS_STACK;
     F3 mpos = ld3(M.pos);
@@ -507,7 +508,7 @@ __device__ BHRAY_MODEL_INLINE void trace_ray_model(const ModelDev& M, const BvhL
                 if (hit_triangle(pos, dir, t_min, t_max, f3(A.x, A.y, A.z) + mpos, f3(B.x, B.y, B.z) + mpos,
                                  f3(Cc.x, Cc.y, Cc.z) + mpos, f3(N1.x, N1.y, N1.z), f3(N2.x, N2.y, N2.z),
                                  f3(N3.x, N3.y, N3.z), t, col, nrm)) {
-                    if (t < closest.t) { closest.hit = true; closest.t = t; closest.color = col; closest.opacity = 1.0f; normal_out = nrm; }
+                    if (t < closest.t) { closest.hit = true; closest.t = t; closest.color = col; closest.opacity = 1.0f; normal_out = nrm; if constexpr (SLOT) *slot_out = contents + i; }
                 }
             }
             do_pop();
@@ -559,7 +560,7 @@ __device__ BHRAY_MODEL_INLINE void trace_ray_model(const ModelDev& M, const BvhL
                 if (hit_triangle(pos, dir, t_min, t_max, f3(A.x, A.y, A.z) + mpos, f3(B.x, B.y, B.z) + mpos,
                                  f3(Cc.x, Cc.y, Cc.z) + mpos, f3(N1.x, N1.y, N1.z), f3(N2.x, N2.y, N2.z),
                                  f3(N3.x, N3.y, N3.z), t, col, nrm)) {
-                    if (t < closest.t) { closest.hit = true; closest.t = t; closest.color = col; closest.opacity = 1.0f; normal_out = nrm; }
+                    if (t < closest.t) { closest.hit = true; closest.t = t; closest.color = col; closest.opacity = 1.0f; normal_out = nrm; if constexpr (SLOT) *slot_out = contents + i; }
                 }
             }
             pop = true;
@@ -1270,6 +1271,14 @@ __device__ __forceinline__ bool lens_near_mesh(const FrameParams& P, F3 pos, F3 
 #define BHRAY_HIT_LDS 1         // dense build: "a hit happened" in the cold LDS state rather than an SGPR pair merged at every join of the step loop (+0.3 %, A/B in two sessions: profiles/EXPERIMENTS.md R3.9)
 #endif
 
+// The record kernels (trace_kernel's RECORDS): words 0-4 of record idx - curr.position right behind the ray's first accepted hit, what it hit, the triangle - where
+// that hit arises: one 16-byte and one 4-byte store.  Words 5-7 are the epilogue's.
+__device__ __forceinline__ void record_first_hit(float4* __restrict__ records, uint32_t idx, F3 pos, uint32_t hit, int triangle) {
+    float4* rec = records + 2 * (size_t)idx;
+    rec[0] = make_float4(pos.x, pos.y, pos.z, __uint_as_float(hit));
+    *reinterpret_cast<int*>(rec + 1) = triangle;
+}
+
 // Cold per-lane ray state: values the integrator step loop reads or writes only on its rare paths (sphere exit, an actual hit)
 // or not at all (the pixel id) — 8 words per lane.  The dense build (6 waves per SIMD = 80 VGPRs) keeps them in LDS, one word
 // per lane per plane (lane-consecutive addresses: conflict-free ds_read/ds_write_b32), which takes them out of the register
@@ -1327,6 +1336,10 @@ extern "C" __attribute__((visibility("default"))) int bhray_debug_wave_log(unsig
 }
 namespace bhray {
 #endif
+#ifndef BHRAY_TRACE_WAVES_RECORDS_EULER
+#define BHRAY_TRACE_WAVES_RECORDS_EULER 5     // the Euler no-mesh record kernel is budgeted for the 5 waves per SIMD its ray-list twin reaches unasked (88 VGPRs under the latency build's
+                                              // budget of 4): with the record stores on the rare paths the allocator otherwise settles at 103 VGPRs and 4 waves
+#endif
 #ifndef BHRAY_TRACE_KERNEL_ATTR
 #define BHRAY_TRACE_KERNEL_ATTR      // (experiments: e.g. __attribute__((amdgpu_num_sgpr(88))))
 #endif
@@ -1336,8 +1349,13 @@ namespace bhray {
 // L.out[idx].  A record with a non-finite component or an all-zero direction is answered (0, 0, 0, -1) at load and never takes a lane.  Kernels of their own, as LENSED:
 // every other instantiation is the text it was.  Everything behind the refill - march, phases, traversal - is the shipped text: no step or phase reads the camera
 // (the audit: DESIGN.md §15).  Out of these kernels by constexpr: the quad march, wave priority, the strided thin shares (a frame's scheduling, measured on frames).
-template <int METHOD, bool MODELS, bool COUNT, bool DENSE, int EVAL = 0, bool ORIGIN = false, bool LENSED = false, bool RAYS = false>
-__global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS ? (DENSE ? BHRAY_TRACE_WAVES_MESH_DENSE : BHRAY_TRACE_WAVES_MESH) : (DENSE ? BHRAY_TRACE_WAVES_DENSE : BHRAY_TRACE_WAVES)) void trace_kernel(const FrameParams* __restrict__ Pb, const FrameLaunch* __restrict__ Fb, const int nb, int* __restrict__ err_flag) {
+// RECORDS (bhray_trace_rays_records; implies RAYS): besides result idx the launch writes record idx (bhray_ray_record, 32 bytes = two float4) to the array
+// FrameLaunch::row_work points at - a member only the counting builds read, and a ray-list launch never counts.  Nothing new is live across the step loop: words 0-4
+// (position, hit, triangle) are stored where the ray's first hit arises (the places that run HIT_SET(1), while the flag is still clear; the lane holds its index in the
+// cold state), words 5-7 (iterations, closest, transmittance) in the epilogue from `it`, `closest`, `amount`, which also stores words 0-4 for a ray that never hit.
+// Kernels of their own again: every other instantiation is the text it was.
+template <int METHOD, bool MODELS, bool COUNT, bool DENSE, int EVAL = 0, bool ORIGIN = false, bool LENSED = false, bool RAYS = false, bool RECORDS = false>
+__global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS ? (DENSE ? BHRAY_TRACE_WAVES_MESH_DENSE : BHRAY_TRACE_WAVES_MESH) : (DENSE ? BHRAY_TRACE_WAVES_DENSE : (RECORDS && METHOD == 0) ? BHRAY_TRACE_WAVES_RECORDS_EULER : BHRAY_TRACE_WAVES)) void trace_kernel(const FrameParams* __restrict__ Pb, const FrameLaunch* __restrict__ Fb, const int nb, int* __restrict__ err_flag) {
     const int lane = threadIdx.x & 63;
     int err = 0;
     // Execution span of this launch (timed batches only: Fb[0].span != nullptr): first block's start and last block's end on the
@@ -1360,6 +1378,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
     constexpr int REFILL_MIN = (METHOD == 0 && DENSE && !MODELS) ? BHRAY_REFILL_MIN_EULER_DENSE : BHRAY_REFILL_MIN;
     static_assert(!LENSED || (MODELS && !DENSE && EVAL == 0 && !ORIGIN), "the lensed-mesh kernels: mesh variant, latency build, the contract's evaluation, general hole position");
     static_assert(!RAYS || (!COUNT && !DENSE && EVAL == 0 && !ORIGIN && !LENSED), "the ray-list kernels: latency build, the contract's evaluation, general hole position, no counting, flat-space models");
+    static_assert(!RECORDS || RAYS, "the record kernels are ray-list kernels");
     constexpr bool UNIFIED = BHRAY_UNIFIED != 0 && EVAL == 0 && (!MODELS || BHRAY_UNIFIED_MESH != 0) && !COUNT && !LENSED;           // the unified march (bhray_step_u.inc) in the contract kernels that do not count (the lensed-mesh kernels: the general step, whose ppos / pdir a paused lane keeps)
     constexpr bool ONE_TEST = UNIFIED && !MODELS && (((BHRAY_ONE_TEST & 1) != 0 && !DENSE) || ((BHRAY_ONE_TEST & 2) != 0 && DENSE));
     // the RK step's error estimate behind a wave-uniform bound (next_ray_rk_t): 0 the full text, 1 skipped where the bound holds, 2 the full text and the bound's counters
@@ -1395,6 +1414,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
     const uint32_t* __restrict__ queue = F.queue;
     uint32_t* __restrict__ qhead = F.qctl + 1;
     Counters64* __restrict__ counters = F.counters;
+    [[maybe_unused]] float4* __restrict__ records = RECORDS ? reinterpret_cast<float4*>(F.row_work) : nullptr;      // (RECORDS: row_work holds the n records; see the template's comment)
     const uint32_t qcount = F.qctl[0];
     // A queue that is (nearly) used up when this wave arrives is seen with a plain load, before any atomic: 4 096 waves hitting one
     // word with failing atomics cost ~50 us per launch (11-13 ns each) - what an empty queue (a fix-up launch of the temporal mode)
@@ -1526,6 +1546,10 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                     const bool usable = finite & ((rdir.x != 0.0f) | (rdir.y != 0.0f) | (rdir.z != 0.0f));
                     if (!usable) {
                         L.out[idx] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);       // not traced: the lane stays empty (the wave's exit test below knows)
+                        if constexpr (RECORDS) {                                  // BHRAY_HIT_UNUSABLE, triangle -1, every other word zero
+                            records[2 * (size_t)idx] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float((uint32_t)BHRAY_HIT_UNUSABLE));
+                            records[2 * (size_t)idx + 1] = make_float4(__int_as_float(-1), 0.0f, 0.0f, 0.0f);
+                        }
                     } else {
                         cold.set_pix(idx);
                         cold.set_rdir(rdir);
@@ -1659,6 +1683,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                 const F3 cc = f3(clamp_(crs.color.x, 0.0f, 1.0f), clamp_(crs.color.y, 0.0f, 1.0f), clamp_(crs.color.z, 0.0f, 1.0f));
                 cold.set_color(cold.color() + cc * (amount * crs.opacity));
                 amount *= 1.0f - crs.opacity;
+                if constexpr (RECORDS) { if (!HIT_GET()) record_first_hit(records, cold.pix(), cpos, (uint32_t)BHRAY_HIT_DISK, -1); }
                 HIT_SET(1);
                 if (amount < 0.005f) mode = M_FINISH;
                 else { it++; mode = (mode == M_SHADE_FLAT) ? M_FLAT : M_REL; }
@@ -1765,6 +1790,8 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                 } else {
                     if (COUNT) cnt[5]++;
                     Hit rs; rs.hit = false; rs.t = t_max; rs.color = f3(0, 0, 0); rs.opacity = 0.0f;
+                    [[maybe_unused]] int win_model = 0, win_slot = 0;       // RECORDS: the model that holds the nearest hit and the winning triangle's bvh_lookup slot in it
+                    static_assert(!RECORDS || !MESH_PARK, "the record kernels are latency builds: the traversal runs here, not in the parked region");
                     if (MESH_PARK) {      // the traversal has run in its own region above
                         if (mesh_r.hit && mesh_r.t < rs.t) {
                             rs = mesh_r;
@@ -1791,8 +1818,10 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                                         if (COUNT && skip) cnt[6]++;
                                     }
                                 }
-                                if (!skip) trace_ray_model<COUNT, BVH_WW>(P.models[mi], bvh_lds, cpos, cdir, t_min, t_max, r, nrm, cnt, &err);
+                                [[maybe_unused]] int slot = 0;
+                                if (!skip) trace_ray_model<COUNT, BVH_WW, RECORDS>(P.models[mi], bvh_lds, cpos, cdir, t_min, t_max, r, nrm, cnt, &err, &slot);
                                 if (r.hit && r.t < rs.t) {
+                                    if constexpr (RECORDS) { win_model = mi; win_slot = slot; }
                                     rs = r;
                                     const F3 light = normalize(f3(0.2f, 0.2f, -1.0f));
                                     rs.color = rs.color * dot(nrm, light);
@@ -1818,6 +1847,9 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                             const F3 cc = f3(clamp_(crs.color.x, 0.0f, 1.0f), clamp_(crs.color.y, 0.0f, 1.0f), clamp_(crs.color.z, 0.0f, 1.0f));
                             cold.set_color(cold.color() + cc * (amount * crs.opacity));
                             amount *= 1.0f - crs.opacity;
+                            if constexpr (RECORDS) {      // a mesh: the triangle through the model's bvh_lookup (device-resident for host-built and device-built trees), once, here
+                                if (!HIT_GET()) record_first_hit(records, cold.pix(), cpos, (uint32_t)BHRAY_HIT_MESH | ((uint32_t)win_model << 8), P.models[win_model].lookup[win_slot]);
+                            }
                             HIT_SET(1);
                         }
                         if (amount < 0.005f) mode = M_FINISH; else it++;
@@ -1868,6 +1900,17 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                 }
                 if constexpr (RAYS) {
                     L.out[pix] = o;                                        // result idx of the list: no rowmap, pitch or stamp
+                    if constexpr (RECORDS) {
+                        // trace_ray's i, closest_to_bh and color_amount where its loop ended (the audit: DESIGN.md §16); a ray that never hit: curr.position there, NONE, -1
+                        float4* rec = records + 2 * (size_t)pix;
+                        if (HIT_GET()) {
+                            float* w = reinterpret_cast<float*>(rec + 1);
+                            w[1] = __int_as_float(it); w[2] = closest; w[3] = amount;
+                        } else {
+                            rec[0] = make_float4(cpos.x, cpos.y, cpos.z, __uint_as_float((uint32_t)BHRAY_HIT_NONE));
+                            rec[1] = make_float4(__int_as_float(-1), __int_as_float(it), closest, amount);
+                        }
+                    }
                 } else {
                     const int ox = (int)(pix & 0x7fffu), oy = (int)((pix >> 15) & 0x7fffu);
                     if (SL.n > 0) {
@@ -2147,7 +2190,7 @@ hipError_t launch_classify(const FrameParams* Pb, const FrameLaunch* Fb, int nb,
 }
 
 // Which builds of trace_kernel<METHOD, MODELS, COUNT, DENSE, EVAL, ORIGIN, LENSED> exist (16 x 2 integrators general builds + 2 x 2 ORIGIN builds + 2 x 2 lensed-mesh builds
-// + 2 x 2 ray-list builds = 44 instantiations; 40 before the ray lists, 36 in round 11, 32 in round 9, 48 in round 5, 72 in round 3).
+// + 2 x 2 ray-list builds + 2 x 2 record builds = 48 instantiations; 44 before the records, 40 before the ray lists, 36 in round 11, 32 in round 9, 48 in round 5, 72 in round 3).
 // eval: 0 the numerics contract, 1 BHRAY_F_LITERAL, 2 BHRAY_F_EVAL_FMA.  Every variant has a build for lone launches (the latency build);
 // the build for a saturated device (dense) exists where throughput is reported: not for counting kernels (BHRAY_F_COUNTERS is a diagnosis
 // mode: the same counts whichever build marches) and, of the two measurement-only evaluations, not for the mesh variant.  A launch that
@@ -2161,7 +2204,7 @@ constexpr bool trace_variant_exists(int eval, bool models, bool dense, bool coun
 // latency build, counting or not) and what a launch gets that asks for a build that does not exist: trace_resolve (bhray_internal.h).  The builds instantiated are the variants
 // that resolve to themselves.  The loop order is the order the kernels stand in the code object (lensed first, then per integrator the evaluations 1, 2, 0, mesh / counting /
 // ORIGIN / dense before their opposites): kept, so the object does not change.
-struct TraceBuilds { int n; TraceVariant v[44]; };
+struct TraceBuilds { int n; TraceVariant v[48]; };
 constexpr TraceBuilds trace_builds() {
     TraceBuilds t{};
     for (int lensed = 1; lensed >= 0; lensed--) for (int method = 0; method < 2; method++) for (int e = 1; e <= 3; e++) for (int mesh = 1; mesh >= lensed; mesh--)
@@ -2174,10 +2217,15 @@ constexpr TraceBuilds trace_builds() {
         const TraceVariant v{method, mesh, false, false, 0, false, true};
         if (trace_resolve(v) == v) t.v[t.n++] = v;
     }
+    // the record kernels (trace_kernel's RECORDS): the same four again, behind them
+    for (int method = 0; method < 2; method++) for (int mesh = 1; mesh >= 0; mesh--) {
+        const TraceVariant v{method, mesh, false, false, 0, false, true, true};
+        if (trace_resolve(v) == v) t.v[t.n++] = v;
+    }
     return t;
 }
 constexpr TraceBuilds TRACE_BUILDS = trace_builds();
-static_assert(TRACE_BUILDS.n == 36 + (BHRAY_ORIGIN_KERNEL != 0 && BHRAY_UNIFIED != 0 ? 4 : 0) + 4, "instantiations of trace_kernel (the last four: the ray-list kernels)");
+static_assert(TRACE_BUILDS.n == 36 + (BHRAY_ORIGIN_KERNEL != 0 && BHRAY_UNIFIED != 0 ? 4 : 0) + 4 + 4, "instantiations of trace_kernel (the last eight: the ray-list kernels, then the record kernels)");
 constexpr bool trace_variant_exists_agrees() {     // trace_variant_exists is trace_resolve's rule for the dense builds
     for (int i = 0; i < 24; i++) {
         const TraceVariant v{0, i & 1, (i & 2) != 0, (i & 4) != 0, i >> 3, false};
@@ -2189,7 +2237,7 @@ static_assert(trace_variant_exists_agrees(), "trace_variant_exists / trace_resol
 template <int I>
 static const void* trace_kernel_at() {
     constexpr TraceVariant V = TRACE_BUILDS.v[I];
-    return (const void*)trace_kernel<V.method, V.models != 0, V.count, V.dense, V.eval, V.origin, V.models == 2, V.rays>;
+    return (const void*)trace_kernel<V.method, V.models != 0, V.count, V.dense, V.eval, V.origin, V.models == 2, V.rays, V.records>;
 }
 template <int... I>
 static const void* trace_kernel_lookup(const TraceVariant& resolved, std::integer_sequence<int, I...>) {

@@ -63,6 +63,11 @@ OFF(bhray_mix_details, mix_ratio, 0);
 SZ(bhray_ray, 32);
 OFF(bhray_ray, origin, 0); OFF(bhray_ray, pad0, 12); OFF(bhray_ray, direction, 16); OFF(bhray_ray, pad1, 28);
 static_assert(BHRAY_MAX_RAYS_PER_CALL == (1u << 26), "BHRAY_MAX_RAYS_PER_CALL");
+// a record of bhray_trace_rays_records: two 16-byte halves (the kernel stores words 0-3 as one float4, word 4 alone, words 5-7 in the epilogue)
+SZ(bhray_ray_record, 32);
+OFF(bhray_ray_record, position, 0); OFF(bhray_ray_record, hit, 12); OFF(bhray_ray_record, triangle, 16); OFF(bhray_ray_record, iterations, 20);
+OFF(bhray_ray_record, closest, 24); OFF(bhray_ray_record, transmittance, 28);
+static_assert(BHRAY_HIT_NONE == 0 && BHRAY_HIT_HORIZON == 1 && BHRAY_HIT_DISK == 2 && BHRAY_HIT_MESH == 3 && BHRAY_HIT_UNUSABLE == 255, "BHRAY_HIT_*");
 
 // not reference layouts, but ABI the bindings restate (bhusie_amd/layouts.py)
 static_assert(sizeof(bhray_counters) == 104, "bhray_counters");

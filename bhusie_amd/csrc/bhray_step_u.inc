@@ -102,6 +102,7 @@
                                 const F3 cc = f3(clamp_(crs.color.x, 0.0f, 1.0f), clamp_(crs.color.y, 0.0f, 1.0f), clamp_(crs.color.z, 0.0f, 1.0f));
                                 cold.set_color(cold.color() + cc * (amount * crs.opacity));
                                 amount *= 1.0f - crs.opacity;
+                                if constexpr (RECORDS) { if (!HIT_GET()) record_first_hit(records, cold.pix(), ncpos, (uint32_t)BHRAY_HIT_HORIZON, -1); }
                                 HIT_SET(1);
                             }
                             if (amount < 0.005f) { mode = M_FINISH; it--; }

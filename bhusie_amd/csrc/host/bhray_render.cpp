@@ -1,7 +1,10 @@
 // bhray_render — minimal C++ host program over renderer.hpp: renders one frame of the reference's default scene
 // (camera (0,0,-19), hole at the origin, disk 2..10, R = 20; camera.rs:10-16, blackhole.rs:16-28) and writes the HDR frame
 // as raw little-endian f32 RGBA (row 0 = top).  Usage:
-//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H]
+//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--pick X Y]
+// --pick X Y: after the frame, one line with the record of its pixel (X, Y) - that pixel's pinhole ray through bhray_trace_rays_records (Renderer::pick):
+//   pick X Y hit=none|horizon|disk|mesh model=M triangle=T position=PX PY PZ iterations=I closest=C transmittance=A
+// Not with --lensed-mesh, --devices or --panorama.
 // --panorama W H: instead of the pinhole frame, a 360 x 180 degree panorama of W x H pixels from the camera's position, its centre column looking along the camera's forward
 // (bhusie::equirect_rays through Renderer::render_rays: bhray_trace_rays); written the same way.  Not with --lensed-mesh or --devices.
 // --pose: every --obj mesh is turned by the Euler rotation (RX, RY, RZ) about its own origin on the GPU (bhray_pose_from_euler + bhray_set_model_pose); needs --bvh device.
@@ -140,8 +143,9 @@ int main(int argc, char** argv) {
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
         return 0;
     }
-    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--pick X Y]\n", argv[0]); return 2; }
     uint32_t bw = 72, bh = 41, levels = 4, disk = 256, pano_w = 0, pano_h = 0;
+    long pick_x = -1, pick_y = -1;
     bool rk = false, bvh_device = false, lensed = false, posed = false;
     float rotation[3] = {0.0f, 0.0f, 0.0f};
     std::vector<const char*> objs;
@@ -156,9 +160,11 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--pose") && i + 3 < argc) { posed = true; for (int a = 0; a < 3; a++) rotation[a] = (float)std::atof(argv[++i]); }
         else if (!std::strcmp(argv[i], "--lensed-mesh")) lensed = true;
         else if (!std::strcmp(argv[i], "--panorama") && i + 2 < argc) { pano_w = (uint32_t)std::atoi(argv[++i]); pano_h = (uint32_t)std::atoi(argv[++i]); if (pano_w < 1 || pano_h < 1) { std::fprintf(stderr, "--panorama needs W >= 1 and H >= 1\n"); return 2; } }
+        else if (!std::strcmp(argv[i], "--pick") && i + 2 < argc) { pick_x = std::atol(argv[++i]); pick_y = std::atol(argv[++i]); if (pick_x < 0 || pick_y < 0) { std::fprintf(stderr, "--pick needs X >= 0 and Y >= 0\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) { for (const char* p = argv[++i]; *p; ) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p) p++; } }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
+    if (pick_x >= 0 && pano_w) { std::fprintf(stderr, "--pick names a pixel of the pinhole frame: not with --panorama\n"); return 2; }
     if (posed && !bvh_device) { std::fprintf(stderr, "--pose needs --bvh device (a pose is applied to a tree built on the GPU)\n"); return 2; }
     try {
         std::unique_ptr<bhusie::Renderer> rp(devices.empty() ? new bhusie::Renderer({bw, bh}, 3, levels) : new bhusie::Renderer({bw, bh}, 3, levels, devices));
@@ -193,6 +199,13 @@ int main(int argc, char** argv) {
         std::fwrite(out.data(), sizeof(float), out.size(), f);
         std::fclose(f);
         std::printf("%ux%u\n", res.first, res.second);
+        if (pick_x >= 0) {
+            const bhray_ray_record p = r.pick((uint32_t)pick_x, (uint32_t)pick_y);
+            const uint32_t kind = p.hit & 0xffu;
+            const char* name = kind == BHRAY_HIT_NONE ? "none" : kind == BHRAY_HIT_HORIZON ? "horizon" : kind == BHRAY_HIT_DISK ? "disk" : kind == BHRAY_HIT_MESH ? "mesh" : "unusable";
+            std::printf("pick %ld %ld hit=%s model=%d triangle=%d position=%.9g %.9g %.9g iterations=%u closest=%.9g transmittance=%.9g\n", pick_x, pick_y, name,
+                        kind == BHRAY_HIT_MESH ? (int)((p.hit >> 8) & 0xffu) : -1, (int)p.triangle, p.position[0], p.position[1], p.position[2], p.iterations, p.closest, p.transmittance);
+        }
     } catch (const std::exception& e) {
         std::fprintf(stderr, "%s\n", e.what());
         return 1;

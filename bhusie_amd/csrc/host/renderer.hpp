@@ -185,6 +185,14 @@ public:
         check(bhray_trace_rays(ctx_, rays.data(), (uint32_t)rays.size(), out.data()), ctx_);
         return out;
     }
+    // ray records (bhray_trace_rays_records): trace_rays, and per ray its first hit, the model and triangle, where, the iterations, the closest approach and
+    // the light left; `results` (4 f32 per ray) is filled when it is not null
+    std::vector<bhray_ray_record> trace_rays_records(const std::vector<bhray_ray>& rays, std::vector<float>* results = nullptr) {
+        std::vector<bhray_ray_record> records(rays.size());
+        if (results) results->assign(rays.size() * 4, 0.0f);
+        check(bhray_trace_rays_records(ctx_, rays.data(), (uint32_t)rays.size(), results ? results->data() : nullptr, records.data()), ctx_);
+        return records;
+    }
     bhray_ctx* ctx() { return ctx_; }
 private:
     bhray_config cfg_;
@@ -225,6 +233,60 @@ inline std::vector<bhray_ray> equirect_rays(const float position[3], const float
         }
     }
     return rays;
+}
+
+// create_ray (ray.wgsl:269-285) for pixel (x, y) of a w x h level, as bhusie_amd/cameras.py: pinhole_rays forms it - binary32, operation by operation, tan(fov / 2) as the
+// library's portable sine over cosine (bhray_math.h: bh_sincos, restated here because this header sees the C ABI only).  Build without floating-point contraction.
+namespace detail {
+inline float sincos_portable(float xin, int kind) {          // kind 0: sin, 1: cos
+    float x = std::fabs(xin);
+    bool sign = kind == 0 ? std::signbit(xin) : false;
+    if (!(x <= 3.0e9f)) return std::nanf("");
+    uint32_t j = (uint32_t)(x * 1.27323954f);
+    j = j + (j & 1u);
+    const float y = (float)j;
+    x = ((x - y * 0.78515625f) - y * 2.4187564849853515625e-4f) - y * 3.77489497744594108e-8f;
+    j = j & 7u;
+    if (j > 3u) { sign = !sign; j = j - 4u; }
+    if (kind == 1 && j > 1u) sign = !sign;
+    const float z = x * x;
+    const bool mid = (j == 1u || j == 2u);
+    const bool use_cos = kind == 0 ? mid : !mid;
+    float r;
+    if (use_cos) {
+        float p = 2.443315711809948e-5f;
+        p = p * z - 1.388731625493765e-3f;
+        p = p * z + 4.166664568298827e-2f;
+        r = ((p * z) * z - 0.5f * z) + 1.0f;
+    } else {
+        float p = -1.9515295891e-4f;
+        p = p * z + 8.3321608736e-3f;
+        p = p * z - 1.6666654611e-1f;
+        r = (p * z) * x + x;
+    }
+    return sign ? -r : r;
+}
+}  // namespace detail
+inline bhray_ray pinhole_ray(const float position[3], const float forward[3], float fov, uint32_t w, uint32_t h, uint32_t x, uint32_t y) {
+    auto cross = [](const float a[3], const float b[3], float o[3]) { o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0]; };
+    auto normalize = [](float v[3]) { const float r = 1.0f / std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); v[0] *= r; v[1] *= r; v[2] *= r; };
+    const float plane_up[3] = {0.0f, -1.0f, 0.0f};
+    float right[3], up[3];
+    cross(forward, plane_up, right); normalize(right);
+    cross(forward, right, up); normalize(up);
+    const uint32_t sm = (w - 1) < (h - 1) ? (w - 1) : (h - 1);
+    const float increment = 1.0f / (float)sm;
+    const float posx = (2.0f * ((float)x - (float)(w - 1) * 0.5f)) * increment;
+    const float posy = (2.0f * ((float)y - (float)(h - 1) * 0.5f)) * increment;
+    const float half = fov / 2.0f;
+    const float fov_factor = 1.0f / (detail::sincos_portable(half, 0) / detail::sincos_portable(half, 1));
+    bhray_ray r;
+    float d[3];
+    for (int k = 0; k < 3; k++) d[k] = (right[k] * posx + up[k] * posy) + forward[k] * fov_factor;
+    normalize(d);
+    for (int k = 0; k < 3; k++) { r.origin[k] = position[k]; r.direction[k] = d[k]; }
+    r.pad0 = 0.0f; r.pad1 = 0.0f;
+    return r;
 }
 
 // Renderer::{new, render} restricted to the ray pass.
@@ -276,6 +338,14 @@ public:
         ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);
         apply_lensing();
         return ray_pipeline_.trace_rays(rays);
+    }
+    // what is under frame pixel (x, y): the record of that pixel's pinhole ray under the current scene (hit & 0xff: BHRAY_HIT_*; (hit >> 8) & 0xff: the model slot of a mesh hit)
+    bhray_ray_record pick(uint32_t x, uint32_t y) {
+        const auto res = ray_pipeline_.resolution();
+        if (x >= res.first || y >= res.second) throw std::runtime_error("bhray: pick: the pixel lies outside the frame");
+        ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);
+        apply_lensing();
+        return ray_pipeline_.trace_rays_records({pinhole_ray(camera.position, camera.forward, camera.fov, res.first, res.second, x, y)})[0];
     }
 private:
     void apply_lensing() { if (mesh_lensing != lensing_applied_) { ray_pipeline_.set_mesh_lensing(mesh_lensing); lensing_applied_ = mesh_lensing; } }

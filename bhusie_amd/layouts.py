@@ -74,6 +74,14 @@ class BhrayRay(C.Structure):                # bhray_ray: one ray of bhray_trace_
     _fields_ = [("origin", C.c_float * 3), ("pad0", C.c_float), ("direction", C.c_float * 3), ("pad1", C.c_float)]
 
 
+class BhrayRayRecord(C.Structure):          # bhray_ray_record: what bhray_trace_rays_records knows about one ray, two 16-byte halves
+    _fields_ = [("position", C.c_float * 3), ("hit", C.c_uint32), ("triangle", C.c_int32), ("iterations", C.c_uint32),
+                ("closest", C.c_float), ("transmittance", C.c_float)]
+
+
+HIT_NONE, HIT_HORIZON, HIT_DISK, HIT_MESH, HIT_UNUSABLE = 0, 1, 2, 3, 255      # BHRAY_HIT_*: bits 0-7 of bhray_ray_record.hit (bits 8-15: the model slot of a MESH hit)
+
+
 class BhrayModelDesc(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("visible", C.c_int32),
                 ("points", C.c_void_p), ("normals", C.c_void_p), ("triangles", C.c_void_p),
@@ -142,6 +150,7 @@ class BhrayModelBuildInfo(C.Structure):
 assert C.sizeof(BhrayDetails) == 32 and C.sizeof(BhrayCameraUniform) == 32 and C.sizeof(BhrayBlackHoleUniform) == 132
 assert C.sizeof(BhrayNode) == 32 and C.sizeof(BhrayTriangle) == 24
 assert C.sizeof(BhrayRay) == 32 and BhrayRay.direction.offset == 16
+assert C.sizeof(BhrayRayRecord) == 32 and BhrayRayRecord.hit.offset == 12 and BhrayRayRecord.triangle.offset == 16 and BhrayRayRecord.transmittance.offset == 28
 
 LEVEL_GRID_LAUNCHES = MAX_LEVELS + 2
 LEVEL_GRID_NO_FEEDBACK = 2 ** 64 - 1
@@ -215,6 +224,8 @@ SYMBOLS = {
     "bhray_trace_rays": (C.c_int, [vp, P(BhrayRay), u32, P(C.c_float)]),
     "bhray_trace_rays_device": (C.c_int, [vp, vp, u32, vp, vp]),
     "bhray_trace_rays_sky": (C.c_int, [vp, P(BhrayRay), u32, P(C.c_float), vp]),
+    "bhray_trace_rays_records": (C.c_int, [vp, P(BhrayRay), u32, P(C.c_float), P(BhrayRayRecord)]),
+    "bhray_trace_rays_records_device": (C.c_int, [vp, vp, u32, vp, vp, vp]),
     "bhray_render": (C.c_int, [vp]),
     "bhray_flush": (C.c_int, [vp]),
     "bhray_sync": (C.c_int, [vp]),

@@ -13,10 +13,16 @@ import ctypes as C
 import numpy as np
 
 from ._lib import lib
-from .layouts import (BhrayFxaaDetails, BhrayMixDetails, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters, BhrayRay,
+from .layouts import (BhrayFxaaDetails, BhrayMixDetails, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters, BhrayRay, BhrayRayRecord, HIT_MESH, HIT_UNUSABLE,
                       BhrayGatherInfo, BhrayModelBuildInfo, BhrayModelDesc, BhrayRebalanceInfo, BhrayTiming, check)
 from .model import NODE_DTYPE, Model
 from .scene import BlackHole, Camera, RayDetails
+from .cameras import pinhole_rays
+
+# bhray_ray_record as a NumPy structured type (32 bytes: layouts.BhrayRayRecord)
+RAY_RECORD_DTYPE = np.dtype([("position", np.float32, 3), ("hit", np.uint32), ("triangle", np.int32), ("iterations", np.uint32),
+                             ("closest", np.float32), ("transmittance", np.float32)])
+assert RAY_RECORD_DTYPE.itemsize == C.sizeof(BhrayRayRecord) == 32
 
 
 def ladder_from_base(base=(72, 41), multiplier=3, levels=4) -> BhrayConfig:
@@ -342,6 +348,25 @@ class RayPass:
         stream) holds now; work enqueued on `stream` afterwards sees the results.  An unusable ray's result is (0, 0, 0, -1) (bhray_trace_rays_device)."""
         check(self._L.bhray_trace_rays_device(self._h, C.c_void_p(d_rays), int(n), C.c_void_p(d_out), C.c_void_p(stream) if stream else None), self._h, self._L)
 
+    # -- ray records (bhray_trace_rays_records, DESIGN.md §16)
+    def trace_rays_records(self, rays):
+        """trace_rays, and per ray what trace_ray knew when its loop ended: (results, records) - results as trace_rays, records a structured array
+        (RAY_RECORD_DTYPE over the 32 bytes of bhray_ray_record: position, hit, triangle, iterations, closest, transmittance)."""
+        rec = self._ray_records(rays)
+        n = rec.shape[0]
+        out = np.zeros((n, 4), dtype=np.float32)
+        records = np.zeros(n, dtype=RAY_RECORD_DTYPE)
+        check(self._L.bhray_trace_rays_records(self._h, rec.ctypes.data_as(C.POINTER(BhrayRay)) if n else None, n,
+                                               out.ctypes.data_as(C.POINTER(C.c_float)) if n else None,
+                                               records.ctypes.data_as(C.POINTER(BhrayRayRecord)) if n else None), self._h, self._L)
+        return out, records
+
+    def trace_rays_records_device(self, d_rays: int, n: int, d_out: int, d_records: int, stream: int | None = None):
+        """The device form (trace_rays_device's rules): also n records of 32 bytes at the 16-byte aligned device address d_records.  An unusable ray's
+        record is hit = HIT_UNUSABLE, triangle = -1, everything else zero (bhray_trace_rays_records_device)."""
+        check(self._L.bhray_trace_rays_records_device(self._h, C.c_void_p(d_rays), int(n), C.c_void_p(d_out), C.c_void_p(d_records),
+                                                      C.c_void_p(stream) if stream else None), self._h, self._L)
+
     # -- per frame
     def set_uniforms(self, camera: bytes, black_hole: bytes, details: bytes):
         assert len(camera) == 32 and len(black_hole) == 132 and len(details) == 32
@@ -635,6 +660,44 @@ class Renderer:
             got = self.ray_pass.trace_rays(rec[usable], sky=resolve_sky)
             img[usable] = got[1] if resolve_sky else got
         return img.reshape(h, w, 4)
+
+    def _apply_uniforms(self):
+        self.ray_pass.set_uniforms(self.camera.uniform(), self.black_hole.uniform(), self.ray_details.uniform())
+        if bool(self.mesh_lensing) != self._lensing_applied:
+            self.ray_pass.set_mesh_lensing(self.mesh_lensing)
+            self._lensing_applied = bool(self.mesh_lensing)
+
+    def render_records(self, rays, shape):
+        """The record layers of an image seen through caller-supplied rays (render_rays' rays and rules): an (h, w) structured array (RAY_RECORD_DTYPE) -
+        position, hit, triangle, iterations, closest, transmittance per pixel.  A ray that is not traced (zero direction, non-finite component):
+        hit = HIT_UNUSABLE, triangle = -1, everything else zero, as the device form answers it."""
+        h, w = int(shape[0]), int(shape[1])
+        rec = RayPass._ray_records(rays)
+        if rec.shape[0] != h * w:
+            raise ValueError(f"render_records: {rec.shape[0]} rays for a {w}x{h} image")
+        self._apply_uniforms()
+        six = rec[:, [0, 1, 2, 4, 5, 6]]
+        usable = np.isfinite(six).all(axis=1) & (rec[:, 4:7] != 0.0).any(axis=1)
+        layers = np.zeros(h * w, dtype=RAY_RECORD_DTYPE)
+        layers["hit"] = HIT_UNUSABLE
+        layers["triangle"] = -1
+        if usable.any():
+            layers[usable] = self.ray_pass.trace_rays_records(rec[usable])[1]
+        return layers.reshape(h, w)
+
+    def pick(self, x: int, y: int) -> dict:
+        """What is under frame pixel (x, y)?  Traces that pixel's pinhole ray (cameras.pinhole_rays' arithmetic for the one pixel: create_ray at the frame's
+        size) under the renderer's current scene and returns its record: {hit (HIT_*), model (the slot of a HIT_MESH hit, else None), triangle (index into
+        that model's triangles, else -1), position, iterations, closest, transmittance}."""
+        fw, fh = int(self.ray_pass.cfg.frame_w), int(self.ray_pass.cfg.frame_h)
+        if not (0 <= int(x) < fw and 0 <= int(y) < fh):
+            raise ValueError(f"pick: pixel ({x}, {y}) lies outside the {fw}x{fh} frame")
+        self._apply_uniforms()
+        r = self.ray_pass.trace_rays_records(pinhole_rays(self.camera, fw, fh, pixel=(int(x), int(y))))[1][0]
+        kind = int(r["hit"]) & 0xFF
+        return {"hit": kind, "model": (int(r["hit"]) >> 8) & 0xFF if kind == HIT_MESH else None, "triangle": int(r["triangle"]),
+                "position": tuple(float(v) for v in r["position"]), "iterations": int(r["iterations"]),
+                "closest": float(r["closest"]), "transmittance": float(r["transmittance"])}
 
     def save_image(self, path):
         """The reference's Save Image (mod.rs:473-482): the display pass's RGBA8 image of the last frame, written with alpha 255

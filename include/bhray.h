@@ -477,6 +477,38 @@ int bhray_trace_rays_device(bhray_ctx* ctx, const void* d_rays, uint32_t n, void
  * n x 4 binary16, round-to-nearest-even).  out_rgba32f may be NULL.  Everything else as bhray_trace_rays.                 */
 int bhray_trace_rays_sky(bhray_ctx* ctx, const bhray_ray* rays, uint32_t n, float* out_rgba32f, uint16_t* out_rgba16f);
 
+/* Ray records (not in the reference): bhray_trace_rays, and per ray what trace_ray knew when its loop
+ * ended - what the ray hit FIRST, where, how close it came to the hole, how many iterations it took and how much
+ * light it had left.  "First accepted hit" is the first time crs.hit is true in trace_ray's loop (ray.wgsl:570, where
+ * the shader sets hit = true): the horizon, the disk, or - in flat space, the only place the shader tests them - a
+ * mesh; a disk hit followed by the horizon records DISK.
+ *   position       curr.position right after that hit (ray.wgsl:571: curr + prev.direction * t); no hit: curr.position
+ *                  when the loop ended
+ *   hit            bits 0-7 BHRAY_HIT_*; bits 8-15 the model slot (MESH only, else 0); bits 16-31 zero
+ *   triangle       MESH: index into that model's `triangles` array as the caller uploaded it (through bvh_lookup; the
+ *                  same for a tree built by bhray_upload_model_build); else -1
+ *   iterations     trace_ray's i when its loop ended (the value the `i <= 5` test sees)
+ *   closest        closest_to_bh: the ray's initial distance, then the minimum over the integrator's steps
+ *   transmittance  color_amount when the loop ended
+ * Every rule of bhray_trace_rays / bhray_trace_rays_device holds unchanged - the refused states, the limits on n, the
+ * NULL rules (out_records / d_records must not be NULL for n != 0; out_rgba32f of the host form may be), the
+ * synchronisation, BHRAY_F_COUNTERS - and the results are bit for bit bhray_trace_rays' for the same rays.  d_records
+ * must be 16-byte aligned (BHRAY_E_INVALID).  The device form answers an unusable ray with hit = BHRAY_HIT_UNUSABLE,
+ * triangle = -1 and every other word zero, beside the result (0, 0, 0, -1).
+ * Not built: records under mesh lensing, on a ctx with device_count >= 2 (both BHRAY_E_STATE, as bhray_trace_rays), and
+ * for the pixels of a ladder frame (copied and interpolated pixels have no ray); the path length is not recorded.     */
+enum { BHRAY_HIT_NONE = 0, BHRAY_HIT_HORIZON = 1, BHRAY_HIT_DISK = 2, BHRAY_HIT_MESH = 3, BHRAY_HIT_UNUSABLE = 255 };
+typedef struct bhray_ray_record {
+    float    position[3];
+    uint32_t hit;
+    int32_t  triangle;
+    uint32_t iterations;
+    float    closest;
+    float    transmittance;
+} bhray_ray_record;          /* 32 bytes, two 16-byte halves */
+int bhray_trace_rays_records(bhray_ctx* ctx, const bhray_ray* rays, uint32_t n, float* out_rgba32f /* may be NULL */, bhray_ray_record* out_records);
+int bhray_trace_rays_records_device(bhray_ctx* ctx, const void* d_rays, uint32_t n, void* d_out_rgba32f, void* d_records, void* hip_stream);
+
 /* Dispatch — replaces `for rp in ray_pipelines { rp.pass() }` (mod.rs:415-417,
  * ray_pipeline.rs:301-309).  Asynchronous on the ctx stream; levels ordered.                 */
 int bhray_render(bhray_ctx* ctx);
