@@ -31,7 +31,6 @@ namespace {
 
 thread_local std::string g_create_error;
 
-#define BHRAY_READ_RING 64
 constexpr int SPAN_MAX = BHRAY_MAX_LEVELS + 2;      // trace launches per batch (per-level, + speculative / predicted)
 // Timing events of one batch (one entry of the ring bhray_dev::events), nl = ladder levels: three per level - before its classify, between classify and trace, behind its
 // trace (a level without a trace launch of its own records the last two together) -, two around the sky pass, two around the temporal mode's prediction + predicted trace
@@ -206,9 +205,7 @@ struct bhray_dev {
     size_t q_cap = 0;                      // rays the staging holds
     bhray_ray_record* q_hrec = nullptr; bhray_ray_record* q_drec = nullptr;      // the records' staging (bhray_trace_rays_records): grow-only, allocated by the first records batch
     size_t q_rec_cap = 0;
-    // asynchronous hand-off (dev_read_hdr_async)
-    hipEvent_t read_ev[BHRAY_READ_RING] = {nullptr};     // ticket t -> read_ev[t % BHRAY_READ_RING]
-    uint64_t read_tickets = 0;
+    bhray::ReadRing reads;                 // tickets of the asynchronous hand-off (dev_read_async)
     std::string err;
 };
 
@@ -462,7 +459,7 @@ void dev_destroy(bhray_dev* c) {
     for (auto& e : c->events) if (e) (void)hipEventDestroy(e);
     if (c->d_err) (void)hipFree(c->d_err);
     if (c->d_span) (void)hipFree(c->d_span);
-    for (auto& e : c->read_ev) if (e) (void)hipEventDestroy(e);
+    c->reads.destroy();
     delete c;
 }
 
@@ -1796,82 +1793,96 @@ int dev_local_row_index(const bhray_dev* c, uint32_t i, uint32_t* frame_row) {
     return BHRAY_OK;
 }
 
-int dev_read_hdr(bhray_dev* c, float* dst, size_t pitch) {
+// ---- the three images of the most recently staged frame (bhray::ImageKind) ---------------------------------------
+namespace {
+// the display pass (bhray_post.hip) and its image need the whole frame on this engine
+int display_whole_frame(bhray_dev* c) {
+    if (c->local_rows.size() != (size_t)c->cfg.frame_h)
+        return fail(c, BHRAY_E_STATE, "the display pass needs the whole frame: this ctx renders %zu of %u rows (BHRAY_GATHER_NONE)", c->local_rows.size(), c->cfg.frame_h);
+    if (display_scratch_bytes(c->cfg.frame_w, c->cfg.frame_h) == 0) return fail(c, BHRAY_E_INVALID, "the display pass needs a frame of at least 32 x 32 pixels");
+    return BHRAY_OK;
+}
+
+// "Resolved for this frame", written here and nowhere else: a slot position is reused, so an image belongs to the frame whose id it was stamped
+// with by its resolve pass, and an older frame's image is stale.  (The ray pass writes the hdr frame itself: nothing to resolve.)
+bool resolved(const FrameRes& R, ImageKind kind) {
+    if (kind == IMAGE_SKY) return R.sky_out && R.sky_frame_id == R.frame_id;
+    if (kind == IMAGE_DISPLAY) return R.disp_out && R.disp_frame_id == R.frame_id;
+    return true;
+}
+
+// Image `kind` of the most recently staged frame: its description, or the refusal.  The checks that every access form shares, in their one
+// order: a frame exists (need_frame - the hdr buffer exists from dev_create on, so a pointer to it and the blocking read never asked), this
+// engine holds the image, the image was resolved for THIS frame.
+// img->rows == 0: this partition owns no rows - nothing to copy and nothing to have resolved; img->stream is still the frame's stream.
+int last_image(bhray_dev* c, ImageKind kind, bool need_frame, FrameImage* img) {
+    *img = FrameImage{};
+    if (need_frame && !c->rendered) return fail(c, BHRAY_E_STATE, "nothing rendered yet");
+    Slot& S = c->slots[(size_t)c->last_slot];
+    const FrameRes& R = S.fr[(size_t)c->last_sub];
+    img->stream = S.stream;
+    if (kind == IMAGE_HDR) { img->src = R.out; img->render_target = true; }
+    if (kind == IMAGE_DISPLAY) { int rc = display_whole_frame(c); if (rc) return rc; }
+    else if (c->local_rows.empty()) return BHRAY_OK;
+    if (!resolved(R, kind)) return fail(c, BHRAY_E_STATE, "%s has not been called for this frame", kind == IMAGE_SKY ? "dev_resolve_sky" : "bhray_resolve_display");
+    if (kind == IMAGE_SKY) img->src = R.sky_out;
+    if (kind == IMAGE_DISPLAY) img->src = R.disp_out;
+    img->rows = c->local_rows.size();
+    img->row_bytes = (size_t)c->cfg.frame_w * (kind == IMAGE_HDR ? sizeof(float4) : kind == IMAGE_SKY ? sizeof(uint2) : sizeof(uint32_t));
+    return BHRAY_OK;
+}
+}  // namespace
+
+int dev_read(bhray_dev* c, ImageKind kind, void* dst, size_t pitch) {
     if (!c) return BHRAY_E_INVALID;
-    const size_t rowb = (size_t)c->cfg.frame_w * sizeof(float4);
-    if (c->local_rows.empty()) return dev_sync(c);              // this partition owns no rows: nothing to copy
-    if (!dst || pitch < rowb) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
-    int rc = dev_sync(c);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpy2D(dst, pitch, c->slots[(size_t)c->last_slot].fr[(size_t)c->last_sub].out, rowb, rowb, c->local_rows.size(), hipMemcpyDeviceToHost));
+    FrameImage img;
+    { int rc = last_image(c, kind, false, &img); if (rc) return rc; }
+    if (img.rows && !img.fits(dst, pitch)) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
+    { int rc = dev_sync(c); if (rc) return rc; }
+    if (img.rows) HIPCHK(c, img.copy_to(dst, pitch, false));
     return BHRAY_OK;
 }
 
 // Asynchronous hand-off of the most recently enqueued frame to host memory (a consumer on another device: the wgpu texture the
 // reference's SkyPipeline samples, ray_pipeline.rs:297-299, mod.rs:215).  The copy (SDMA: no CU time, 55.7 GB/s into pinned memory
-// on this box) is enqueued ON THE FRAME'S OWN SLOT STREAM, behind its kernels; the call returns at once and the other slots' frames
-// render while it runs.  (First version: dedicated copy streams ordered by events both ways - ROCm 7.2 then ran copies and kernels
-// strictly one after the other, 1.22 ms per 1080p frame; in stream order 0.62 ms, which is the link rate: profiles/EXPERIMENTS.md.)
+// on this box) is enqueued ON THE FRAME'S OWN SLOT STREAM, behind its kernels and resolve passes; the call returns at once and the other
+// slots' frames render while it runs.  (First version: dedicated copy streams ordered by events both ways - ROCm 7.2 then ran copies and
+// kernels strictly one after the other, 1.22 ms per 1080p frame; in stream order 0.62 ms, which is the link rate: profiles/EXPERIMENTS.md.)
 // `dst` should be pinned (bhray_host_alloc / hipHostRegister): a pageable destination makes the runtime stage the copy.
-int dev_read_hdr_async(bhray_dev* c, float* dst, size_t pitch, uint64_t* ticket) {
+// Every refusal - no frame, no resolve for this frame, an unusable destination - comes BEFORE anything is launched and before the ring is
+// touched: a misuse must not flush a partly filled batch on its way to the error, and consumes no ticket.  (The hdr and sky reads used to
+// refuse a bad destination behind the flush; the display read already did it this way.)
+int dev_read_async(bhray_dev* c, ImageKind kind, void* dst, size_t pitch, uint64_t* ticket) {
     if (!c || !ticket) return BHRAY_E_INVALID;
-    const size_t rowb = (size_t)c->cfg.frame_w * sizeof(float4);
-    if (!c->rendered) return fail(c, BHRAY_E_STATE, "nothing rendered yet");
+    FrameImage img;
+    { int rc = last_image(c, kind, true, &img); if (rc) return rc; }
+    if (img.rows && !img.fits(dst, pitch)) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
     HIPCHK(c, hipSetDevice(c->device));
-    { int rc = launch_batch(c); if (rc) return rc; }
-    const uint64_t t = c->read_tickets;
-    hipEvent_t& ev = c->read_ev[t % BHRAY_READ_RING];
-    if (!ev) HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    else if (t >= BHRAY_READ_RING) HIPCHK(c, hipEventSynchronize(ev));          // the ticket that held this event 64 copies ago
-    Slot& S = c->slots[(size_t)c->last_slot];
-    const size_t rows = c->local_rows.size();
-    if (rows) {
-        if (!dst || pitch < rowb) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
-        const uint8_t* src = (const uint8_t*)S.fr[(size_t)c->last_sub].out;
-        if (pitch == rowb) HIPCHK(c, hipMemcpyAsync(dst, src, rows * rowb, hipMemcpyDeviceToHost, S.stream));
-        else HIPCHK(c, hipMemcpy2DAsync(dst, pitch, src, rowb, rowb, rows, hipMemcpyDeviceToHost, S.stream));
-    }
-    HIPCHK(c, hipEventRecord(ev, S.stream));
-    HIPCHK(c, hipEventRecord(S.done, S.stream));           // whatever is ordered behind this slot's frame is ordered behind its copy too
-    *ticket = t;
-    c->read_tickets = t + 1;
+    { int rc = launch_batch(c); if (rc) return rc; }          // (a resolve launched the frame's batch: nothing is pending then)
+    hipEvent_t ev;
+    HIPCHK(c, c->reads.acquire(&ev));
+    if (img.rows) HIPCHK(c, img.copy_to(dst, pitch, true));
+    HIPCHK(c, hipEventRecord(ev, img.stream));
+    HIPCHK(c, hipEventRecord(c->slots[(size_t)c->last_slot].done, img.stream));   // whatever is ordered behind this slot's frame is ordered behind its copy too
+    *ticket = c->reads.commit();
     return BHRAY_OK;
 }
 
-// The same hand-off for the RGBA16F image of the sky pass (half the bytes): bhray_resolve_sky must have been called for the frame.
-int dev_read_sky_async(bhray_dev* c, uint16_t* dst, size_t pitch, uint64_t* ticket) {
-    if (!c || !ticket) return BHRAY_E_INVALID;
-    const size_t rowb = (size_t)c->cfg.frame_w * sizeof(uint2);
-    if (!c->rendered) return fail(c, BHRAY_E_STATE, "nothing rendered yet");
-    HIPCHK(c, hipSetDevice(c->device));
-    Slot& S = c->slots[(size_t)c->last_slot];
-    FrameRes& R = S.fr[(size_t)c->last_sub];
-    const size_t rows = c->local_rows.size();
-    // refused BEFORE anything is launched: a misuse (render without resolve_sky) must not flush a partly filled batch on its way to the error
-    if (rows && (!R.sky_out || R.sky_frame_id != R.frame_id)) return fail(c, BHRAY_E_STATE, "dev_resolve_sky has not been called for this frame");
-    { int rc = launch_batch(c); if (rc) return rc; }          // (dev_resolve_sky launched the frame's batch: nothing is pending unless a partition without rows skipped it)
-    const uint64_t t = c->read_tickets;
-    hipEvent_t& ev = c->read_ev[t % BHRAY_READ_RING];
-    if (!ev) HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    else if (t >= BHRAY_READ_RING) HIPCHK(c, hipEventSynchronize(ev));
-    if (rows) {
-        if (!dst || pitch < rowb) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
-        if (pitch == rowb) HIPCHK(c, hipMemcpyAsync(dst, R.sky_out, rows * rowb, hipMemcpyDeviceToHost, S.stream));
-        else HIPCHK(c, hipMemcpy2DAsync(dst, pitch, R.sky_out, rowb, rowb, rows, hipMemcpyDeviceToHost, S.stream));
-    }
-    HIPCHK(c, hipEventRecord(ev, S.stream));
-    HIPCHK(c, hipEventRecord(S.done, S.stream));
-    *ticket = t;
-    c->read_tickets = t + 1;
+int dev_device_ptr(bhray_dev* c, ImageKind kind, void** p, size_t* bytes) {
+    if (!c || !p) return BHRAY_E_INVALID;
+    *p = nullptr;
+    FrameImage img;
+    { int rc = last_image(c, kind, false, &img); if (rc) return rc; }
+    *p = (void*)img.src;
+    if (bytes) *bytes = img.rows * img.row_bytes;
     return BHRAY_OK;
 }
 
 int dev_wait_read(bhray_dev* c, uint64_t ticket) {
     if (!c) return BHRAY_E_INVALID;
-    if (ticket >= c->read_tickets) return fail(c, BHRAY_E_INVALID, "unknown read ticket");
-    if (c->read_tickets - ticket > BHRAY_READ_RING) return BHRAY_OK;              // its event was waited for when it was recycled
+    if (!c->reads.known(ticket)) return fail(c, BHRAY_E_INVALID, "unknown read ticket");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipEventSynchronize(c->read_ev[ticket % BHRAY_READ_RING]));
+    HIPCHK(c, c->reads.wait(ticket));
     return BHRAY_OK;
 }
 
@@ -1896,12 +1907,6 @@ int dev_read_level(bhray_dev* c, uint32_t level, float* dst, size_t pitch) {
         uint8_t* row = (uint8_t*)dst + (size_t)(c->cfg.crop_y + c->local_rows[i]) * pitch + (size_t)c->cfg.crop_x * sizeof(float4);
         memcpy(row, tmp.data() + i * frb, frb);
     }
-    return BHRAY_OK;
-}
-
-int dev_hdr_device_ptr(bhray_dev* c, void** p, size_t* bytes) {
-    if (!c || !p) return BHRAY_E_INVALID;
-    *p = c->slots[(size_t)c->last_slot].fr[(size_t)c->last_sub].out; if (bytes) *bytes = c->out_bytes;
     return BHRAY_OK;
 }
 
@@ -1935,46 +1940,14 @@ int dev_resolve_sky(bhray_dev* c) {
     return BHRAY_OK;
 }
 
-int dev_read_sky(bhray_dev* c, uint16_t* dst, size_t pitch) {
-    if (!c) return BHRAY_E_INVALID;
-    const size_t rowb = (size_t)c->cfg.frame_w * sizeof(uint2);
-    if (c->local_rows.empty()) return dev_sync(c);
-    if (!dst || pitch < rowb) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
-    FrameRes& S = c->slots[(size_t)c->last_slot].fr[(size_t)c->last_sub];
-    if (!S.sky_out || S.sky_frame_id != S.frame_id) return fail(c, BHRAY_E_STATE, "dev_resolve_sky has not been called for this frame");
-    int rc = dev_sync(c);
-    if (rc) return rc;
-    if (c->local_rows.empty()) return BHRAY_OK;
-    HIPCHK(c, hipMemcpy2D(dst, pitch, S.sky_out, rowb, rowb, c->local_rows.size(), hipMemcpyDeviceToHost));
-    return BHRAY_OK;
-}
-
-int dev_sky_device_ptr(bhray_dev* c, void** p, size_t* bytes) {
-    if (!c || !p) return BHRAY_E_INVALID;
-    *p = nullptr;
-    const FrameRes& R = c->slots[(size_t)c->last_slot].fr[(size_t)c->last_sub];
-    // the same rule as the reads: the image belongs to the frame it was resolved from (a slot position is reused: an older frame's image is stale)
-    if (!c->local_rows.empty() && (!R.sky_out || R.sky_frame_id != R.frame_id)) return fail(c, BHRAY_E_STATE, "dev_resolve_sky has not been called for this frame");
-    *p = R.sky_out;
-    if (bytes) *bytes = c->local_rows.size() * (size_t)c->cfg.frame_w * sizeof(uint2);
-    return BHRAY_OK;
-}
-
-// ---- display pass (bhray_post.hip): the sky image's rules, for the RGBA8 image --------------------------------
-static int display_whole_frame(bhray_dev* c) {
-    if (c->local_rows.size() != (size_t)c->cfg.frame_h)
-        return fail(c, BHRAY_E_STATE, "the display pass needs the whole frame: this ctx renders %zu of %u rows (BHRAY_GATHER_NONE)", c->local_rows.size(), c->cfg.frame_h);
-    if (display_scratch_bytes(c->cfg.frame_w, c->cfg.frame_h) == 0) return fail(c, BHRAY_E_INVALID, "the display pass needs a frame of at least 32 x 32 pixels");
-    return BHRAY_OK;
-}
-
+// the display pass (bhray_post.hip) behind the last frame and its sky image
 int dev_resolve_display(bhray_dev* c, const bhray_fxaa_details* fx, const bhray_mix_details* mx) {
     if (!c || !fx || !mx) return BHRAY_E_INVALID;
     if (!c->rendered) return fail(c, BHRAY_E_STATE, "nothing rendered yet");
     { int rc = display_whole_frame(c); if (rc) return rc; }
     Slot& S = c->slots[(size_t)c->last_slot];
     FrameRes& R = S.fr[(size_t)c->last_sub];
-    if (!R.sky_out || R.sky_frame_id != R.frame_id) { int rc = dev_resolve_sky(c); if (rc) return rc; }
+    if (!resolved(R, IMAGE_SKY)) { int rc = dev_resolve_sky(c); if (rc) return rc; }
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = launch_batch(c); if (rc) return rc; }
     const size_t npix = (size_t)c->cfg.frame_w * c->cfg.frame_h;
@@ -1983,54 +1956,6 @@ int dev_resolve_display(bhray_dev* c, const bhray_fxaa_details* fx, const bhray_
     HIPCHK(c, launch_display(R.sky_out, S.post_scratch, R.disp_out, c->cfg.frame_w, c->cfg.frame_h, *fx, *mx, S.stream));
     R.disp_frame_id = R.frame_id;
     HIPCHK(c, hipEventRecord(S.done, S.stream));
-    return BHRAY_OK;
-}
-
-int dev_read_display(bhray_dev* c, uint8_t* dst, size_t pitch) {
-    if (!c) return BHRAY_E_INVALID;
-    const size_t rowb = (size_t)c->cfg.frame_w * 4;
-    { int rc = display_whole_frame(c); if (rc) return rc; }
-    if (!dst || pitch < rowb) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
-    const FrameRes& R = c->slots[(size_t)c->last_slot].fr[(size_t)c->last_sub];
-    if (!c->rendered || !R.disp_out || R.disp_frame_id != R.frame_id) return fail(c, BHRAY_E_STATE, "bhray_resolve_display has not been called for this frame");
-    int rc = dev_sync(c);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpy2D(dst, pitch, R.disp_out, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost));
-    return BHRAY_OK;
-}
-
-int dev_read_display_async(bhray_dev* c, uint8_t* dst, size_t pitch, uint64_t* ticket) {
-    if (!c || !ticket) return BHRAY_E_INVALID;
-    const size_t rowb = (size_t)c->cfg.frame_w * 4;
-    if (!c->rendered) return fail(c, BHRAY_E_STATE, "nothing rendered yet");
-    { int rc = display_whole_frame(c); if (rc) return rc; }
-    if (!dst || pitch < rowb) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
-    HIPCHK(c, hipSetDevice(c->device));
-    Slot& S = c->slots[(size_t)c->last_slot];
-    FrameRes& R = S.fr[(size_t)c->last_sub];
-    if (!R.disp_out || R.disp_frame_id != R.frame_id) return fail(c, BHRAY_E_STATE, "bhray_resolve_display has not been called for this frame");
-    { int rc = launch_batch(c); if (rc) return rc; }
-    const uint64_t t = c->read_tickets;
-    hipEvent_t& ev = c->read_ev[t % BHRAY_READ_RING];
-    if (!ev) HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    else if (t >= BHRAY_READ_RING) HIPCHK(c, hipEventSynchronize(ev));
-    if (pitch == rowb) HIPCHK(c, hipMemcpyAsync(dst, R.disp_out, (size_t)c->cfg.frame_h * rowb, hipMemcpyDeviceToHost, S.stream));
-    else HIPCHK(c, hipMemcpy2DAsync(dst, pitch, R.disp_out, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost, S.stream));
-    HIPCHK(c, hipEventRecord(ev, S.stream));
-    HIPCHK(c, hipEventRecord(S.done, S.stream));
-    *ticket = t;
-    c->read_tickets = t + 1;
-    return BHRAY_OK;
-}
-
-int dev_display_device_ptr(bhray_dev* c, void** p, size_t* bytes) {
-    if (!c || !p) return BHRAY_E_INVALID;
-    *p = nullptr;
-    { int rc = display_whole_frame(c); if (rc) return rc; }
-    const FrameRes& R = c->slots[(size_t)c->last_slot].fr[(size_t)c->last_sub];
-    if (!c->rendered || !R.disp_out || R.disp_frame_id != R.frame_id) return fail(c, BHRAY_E_STATE, "bhray_resolve_display has not been called for this frame");
-    *p = R.disp_out;
-    if (bytes) *bytes = (size_t)c->cfg.frame_w * c->cfg.frame_h * 4;
     return BHRAY_OK;
 }
 

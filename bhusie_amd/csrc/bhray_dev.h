@@ -47,6 +47,51 @@ struct DevOptions {
     uint32_t max_streams = 0;    // > 0: at most this many HIP streams for the frame slots (the slots beyond share them) - several engines on ONE physical GPU
                                  // (functional tests of the multi-GPU path on a one-GPU box) must stay within the device's hardware queues TOGETHER
 };
+
+// The three images of the most recently staged frame that a ctx hands to its host, each by a blocking read, an asynchronous
+// read that returns a ticket, and a device pointer.
+enum ImageKind { IMAGE_HDR, IMAGE_SKY, IMAGE_DISPLAY };   // RGBA32F ray-pass frame, RGBA16F sky image, RGBA8 display image
+
+// What either layer's last_image() says about one of them: where it lies and on which stream it is produced.  rows == 0: nothing to copy
+// here (this partition owns no rows; the frame lives on another rank) - stream is then the stream a ticket's event is recorded on, or NULL.
+struct FrameImage {
+    const void* src = nullptr;
+    size_t row_bytes = 0, rows = 0;    // tightly packed rows
+    hipStream_t stream = nullptr;
+    bool render_target = false;        // the slot's next render writes into this very buffer: a copy enqueued on `stream` must be ordered ahead of it
+    bool fits(const void* dst, size_t pitch) const { return dst && pitch >= row_bytes; }
+    // device -> host, one copy for a tight pitch; enqueued on `stream`, or blocking (the caller has synchronised what produces the image)
+    hipError_t copy_to(void* dst, size_t pitch, bool async) const {
+        if (!async) return hipMemcpy2D(dst, pitch, src, row_bytes, row_bytes, rows, hipMemcpyDeviceToHost);
+        if (pitch == row_bytes) return hipMemcpyAsync(dst, src, rows * row_bytes, hipMemcpyDeviceToHost, stream);
+        return hipMemcpy2DAsync(dst, pitch, src, row_bytes, row_bytes, rows, hipMemcpyDeviceToHost, stream);
+    }
+};
+
+// Tickets of the asynchronous reads: ticket t owns ring position t % SIZE; the event there is recorded behind t's copy.
+struct ReadRing {
+    static constexpr uint64_t SIZE = 64;
+    hipEvent_t ev[SIZE] = {nullptr};
+    uint64_t next = 0;                 // tickets issued so far
+    // the event of the next ticket: created on first use, otherwise free once the ticket that held it SIZE copies ago has completed (waited for here).
+    // Takes no ticket: an error between here and commit() consumes none.
+    hipError_t acquire(hipEvent_t* out) {
+        hipEvent_t& e = ev[next % SIZE];
+        const hipError_t rc = !e ? hipEventCreateWithFlags(&e, hipEventDisableTiming) : (next >= SIZE ? hipEventSynchronize(e) : hipSuccess);
+        *out = e;
+        return rc;
+    }
+    // the ticket exists from here on.  Behind the record of acquire()'s event - or without either: a ticket that has nothing to wait for
+    // (a rank that does not hold the frame)
+    uint64_t commit() { return next++; }
+    bool known(uint64_t ticket) const { return ticket < next; }
+    // a known ticket: returns once its copy has completed (one more than SIZE old: its event was waited for when it was recycled; never recorded: at once)
+    hipError_t wait(uint64_t ticket) const {
+        if (next - ticket > SIZE || !ev[ticket % SIZE]) return hipSuccess;
+        return hipEventSynchronize(ev[ticket % SIZE]);
+    }
+    void destroy() { for (hipEvent_t& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } }
+};
 }  // namespace bhray
 
 const char* dev_last_error(const bhray_dev* c);            // c may be NULL: last create error of this thread
@@ -78,20 +123,15 @@ int  dev_flush(bhray_dev* c);
 int  dev_sync(bhray_dev* c);
 uint32_t dev_local_rows(const bhray_dev* c);
 int  dev_local_row_index(const bhray_dev* c, uint32_t i, uint32_t* frame_row);
-int  dev_read_hdr(bhray_dev* c, float* dst, size_t pitch);
-int  dev_read_hdr_async(bhray_dev* c, float* dst, size_t pitch, uint64_t* ticket);   // in stream order behind the last frame's kernels
-int  dev_read_sky_async(bhray_dev* c, uint16_t* dst, size_t pitch, uint64_t* ticket);
+// the three images of the most recently staged frame (bhray::ImageKind), each three ways; the sky and display images must have been resolved for that frame
+int  dev_read(bhray_dev* c, bhray::ImageKind kind, void* dst, size_t pitch);
+int  dev_read_async(bhray_dev* c, bhray::ImageKind kind, void* dst, size_t pitch, uint64_t* ticket);   // in stream order behind what produces the image
+int  dev_device_ptr(bhray_dev* c, bhray::ImageKind kind, void** p, size_t* bytes);
 int  dev_wait_read(bhray_dev* c, uint64_t ticket);
 int  dev_read_level(bhray_dev* c, uint32_t level, float* dst, size_t pitch);
-int  dev_hdr_device_ptr(bhray_dev* c, void** p, size_t* bytes);
 int  dev_bind_output(bhray_dev* c, void* p, size_t bytes);     // destination of the NEXT dev_render only
 int  dev_resolve_sky(bhray_dev* c);
-int  dev_read_sky(bhray_dev* c, uint16_t* dst, size_t pitch);
-int  dev_sky_device_ptr(bhray_dev* c, void** p, size_t* bytes);
 int  dev_resolve_display(bhray_dev* c, const bhray_fxaa_details* fxaa, const bhray_mix_details* mix);   // display pass (bhray_post.hip) behind the last frame
-int  dev_read_display(bhray_dev* c, uint8_t* dst, size_t pitch);
-int  dev_read_display_async(bhray_dev* c, uint8_t* dst, size_t pitch, uint64_t* ticket);
-int  dev_display_device_ptr(bhray_dev* c, void** p, size_t* bytes);
 int  dev_launch_display(bhray_dev* c, const void* sky, void* scratch, void* dst, const bhray_fxaa_details* fxaa, const bhray_mix_details* mix, hipStream_t stream);
 int  dev_wait_event(bhray_dev* c, hipEvent_t ev);             // the next render's launches start after ev (ev is owned by the caller)
 int  dev_next_stream(bhray_dev* c, void** s);

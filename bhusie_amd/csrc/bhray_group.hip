@@ -227,10 +227,10 @@ struct GroupSlot {                 // per batch slot (same index as the devices'
     hipEvent_t frame_done = nullptr;          // root: recorded behind the de-interleave
     float4* dst[BHRAY_MAX_FRAMES_PER_BATCH];  // root: destination of each frame of the batch staged here (own or caller-bound)
     uint2* sky[BHRAY_MAX_FRAMES_PER_BATCH];   // root: RGBA16F images of bhray_resolve_sky (allocated on first use)
-    uint64_t frame_no[BHRAY_MAX_FRAMES_PER_BATCH] = {};       // serial of the frame staged in each place (1-based), and of the frame its sky
-    uint64_t sky_frame_no[BHRAY_MAX_FRAMES_PER_BATCH] = {};   // image was resolved from: a sky image is current only while the two agree
+    uint64_t frame_id[BHRAY_MAX_FRAMES_PER_BATCH] = {};       // serial of the frame staged in each place (1-based), and of the frame its sky
+    uint64_t sky_frame_id[BHRAY_MAX_FRAMES_PER_BATCH] = {};   // image was resolved from: current only while the two agree (last_image; not with BHRAY_F_GATHER_SKY)
     uint32_t* disp[BHRAY_MAX_FRAMES_PER_BATCH] = {};          // root: RGBA8 images of bhray_resolve_display (allocated on first use) ...
-    uint64_t disp_frame_no[BHRAY_MAX_FRAMES_PER_BATCH] = {};  // ... and the frame each was resolved from (the sky image's rule)
+    uint64_t disp_frame_id[BHRAY_MAX_FRAMES_PER_BATCH] = {};  // ... and the frame each was resolved from (the sky image's rule)
     hipEvent_t tev[3] = {nullptr, nullptr, nullptr};   // timing: before receive, after receive, after de-interleave
     bool timed = false;
 };
@@ -305,8 +305,7 @@ struct bhray_ctx {
     bhray_fxaa_details post_fxaa{};        // display pass uniforms (bhray_set_post_uniforms), used by the next bhray_resolve_display
     bhray_mix_details post_mix{};
     uint2* post_scratch = nullptr;         // root of a gathering ctx: the display pass's bloom levels and tone-mapped image (all on the root's communication stream)
-    hipEvent_t read_ev[64] = {nullptr};
-    uint64_t read_tickets = 0;
+    bhray::ReadRing reads;                 // tickets of the asynchronous reads (group_read_async)
     std::vector<void*> external;           // bhray_import_external_fd: hipExternalMemory_t handles, by mapped pointer (pairs: ptr, handle)
     std::vector<int> external_fd;          // ... and the duplicated descriptor each import handed to the runtime, with what it referred to then
     std::vector<FdId> external_fd_id;
@@ -585,7 +584,6 @@ int group_gather(bhray_ctx* c, int si, uint32_t nb, const CommRank* only = nullp
             hipLaunchKernelGGL(unpack_kernel, dim3(c->table_rows, nb), dim3(256), 0, rr->stream, G.stagingp, fp, c->d_table, (int)W);
             GHIP(c, hipGetLastError());
         }
-        if (c->gather_sky) for (uint32_t k = 0; k < nb; k++) G.sky_frame_no[k] = G.frame_no[k];      // the sky image of every frame of the batch is current
         if (timing) { GHIP(c, hipEventRecord(G.tev[2], rr->stream)); G.timed = true; }
         GHIP(c, hipEventRecord(G.frame_done, rr->stream));
         // the root's next render into this slot writes its own rows into the frames the de-interleave is filling: keep them ordered
@@ -677,7 +675,7 @@ void group_free(bhray_ctx* c) {
         if (r.comm && R && !c->comms_aborted.load()) (void)R->CommDestroy(r.comm);
         if (r.stream) (void)hipStreamDestroy(r.stream);
     }
-    for (auto& e : c->read_ev) if (e) (void)hipEventDestroy(e);
+    c->reads.destroy();
     if (c->d_xchg && !c->ranks.empty()) { (void)hipSetDevice(c->ranks[0].device); (void)hipFree(c->d_xchg); }
     for (size_t i = 0; i + 1 < c->external.size(); i += 2) if (c->external[i + 1]) (void)hipDestroyExternalMemory((hipExternalMemory_t)c->external[i + 1]);
     for (size_t i = 0; i < c->external_fd.size(); i++) close_if_still_ours(c->external_fd[i], c->external_fd_id[i]);
@@ -695,7 +693,7 @@ int bind_partitions(bhray_ctx* c, int si, uint32_t sub, float4* bound, uint64_t 
         if (q == c->root) {
             float4* dst = bound ? bound : G.frames + (size_t)sub * frame_pixels(c);
             G.dst[sub] = dst;
-            G.frame_no[sub] = serial;
+            G.frame_id[sub] = serial;
             DEV(c, p.dev, dev_bind_output(p.dev, dst, frame_pixels(c) * sizeof(float4)));
         } else if (p.rows) {
             DEV(c, p.dev, dev_bind_output(p.dev, G.send[q] + (size_t)sub * p.rows * W, (size_t)p.rows * W * sizeof(float4)));
@@ -1704,29 +1702,108 @@ int bhray_local_row_index(const bhray_ctx* c, uint32_t i, uint32_t* frame_row) {
     return BHRAY_OK;
 }
 
+// ---- the three images of the most recently staged frame (bhray::ImageKind) ------------------------------------------
+// "Resolved for this frame" on the root, written here and nowhere else: a slot position is reused, so an image belongs to the frame whose
+// serial it was stamped with by its resolve pass, and an older frame's image is stale.  The gather produces the hdr frame itself and, with
+// BHRAY_F_GATHER_SKY, the sky image in its place: nothing to resolve, launching the batch makes them current.
+static bool resolved(const bhray_ctx* c, ImageKind kind) {
+    const GroupSlot& G = c->gslots[(size_t)c->last_slot];
+    const uint32_t k = c->last_sub;
+    if (kind == IMAGE_SKY) return G.sky[k] && (c->gather_sky || G.sky_frame_id[k] == G.frame_id[k]);
+    if (kind == IMAGE_DISPLAY) return G.disp[k] && G.disp_frame_id[k] == G.frame_id[k];
+    return true;
+}
+
+// Image `kind` of the most recently staged frame of a ctx that gathers: its description, or the refusal.  The checks every access form
+// shares, in their one order: a frame exists (need_frame), this ctx holds the image at all (BHRAY_F_GATHER_SKY assembles no RGBA32F
+// frame), the image was resolved for THIS frame.
+// img->rows == 0: the frame lives on another rank - nothing to copy here, no stream.
+static int last_image(bhray_ctx* c, ImageKind kind, bool need_frame, FrameImage* img) {
+    *img = FrameImage{};
+    if (need_frame && !c->rendered) return gfail(c, BHRAY_E_STATE, "nothing rendered yet");
+    if (kind == IMAGE_HDR && c->gather_sky) return gfail(c, BHRAY_E_STATE, "BHRAY_F_GATHER_SKY: the RGBA32F frame is not assembled (read the sky image)");
+    if (!c->root_local) return BHRAY_OK;
+    const GroupSlot& G = c->gslots[(size_t)c->last_slot];
+    const uint32_t k = c->last_sub;
+    if (!resolved(c, kind)) return gfail(c, BHRAY_E_STATE, "%s has not been called for this frame", kind == IMAGE_SKY ? "bhray_resolve_sky" : "bhray_resolve_display");
+    if (kind == IMAGE_HDR) {
+        img->src = G.dst[k]; img->row_bytes = (size_t)c->cfg.frame_w * sizeof(float4);
+        img->render_target = true;             // the root's next render into this slot writes its own rows straight into that frame
+    } else if (kind == IMAGE_SKY) {
+        img->src = G.sky[k]; img->row_bytes = (size_t)c->cfg.frame_w * sizeof(uint2);
+    } else {
+        img->src = G.disp[k]; img->row_bytes = (size_t)c->cfg.frame_w * sizeof(uint32_t);
+    }
+    img->rows = c->cfg.frame_h;
+    img->stream = rank_of(c, *root_part(c))->stream;      // the root's communication stream: the de-interleave and the resolve passes run on it
+    return BHRAY_OK;
+}
+
+static int group_read(bhray_ctx* c, ImageKind kind, void* dst, size_t pitch) {
+    FrameImage img;
+    // (of the blocking reads only the hdr one ever asked for a frame: the others find no resolved image, or - BHRAY_F_GATHER_SKY - deliver the image as created)
+    { int rc = last_image(c, kind, kind == IMAGE_HDR, &img); if (rc) return rc; }
+    if (img.rows && !img.fits(dst, pitch)) return gfail(c, BHRAY_E_INVALID, "bad destination / pitch");
+    { int rc = group_sync(c); if (rc) return rc; }
+    if (!img.rows) return BHRAY_OK;
+    GHIP(c, hipSetDevice(root_part(c)->device));
+    GHIP(c, img.copy_to(dst, pitch, false));
+    return BHRAY_OK;
+}
+
+// In stream order on the root's communication stream: behind the de-interleave and the resolve passes of this batch, ahead of the next
+// batch's receive.  (Cross-stream event ordering made ROCm 7.2 serialise copies and kernels: see dev_read_async.)  As there, every
+// refusal comes before the staged batch is launched and before the ring is touched, and consumes no ticket.
+static int group_read_async(bhray_ctx* c, ImageKind kind, void* dst, size_t pitch, uint64_t* ticket) {
+    FrameImage img;
+    { int rc = last_image(c, kind, true, &img); if (rc) return rc; }
+    if (img.rows && !img.fits(dst, pitch)) return gfail(c, BHRAY_E_INVALID, "bad destination / pitch");
+    { int rc = group_flush(c); if (rc) return rc; }                 // (the batch's gather produces the frame; behind a resolve nothing is pending)
+    if (!img.rows) { *ticket = c->reads.commit(); return BHRAY_OK; }      // nothing to copy here: a ticket without an event
+    Part& rp = *root_part(c);
+    GHIP(c, hipSetDevice(rp.device));
+    hipEvent_t ev;
+    GHIP(c, c->reads.acquire(&ev));
+    WATCH_CHECK(c);
+    GHIP(c, img.copy_to(dst, pitch, true));
+    GHIP(c, hipEventRecord(ev, img.stream));
+    *ticket = c->reads.commit();                                    // the ticket exists once its event does (an error above consumes none)
+    if (img.render_target) {
+        hipEvent_t done = c->gslots[(size_t)c->last_slot].frame_done;
+        GHIP(c, hipEventRecord(done, img.stream));
+        GHIP(c, hipStreamWaitEvent(dev_slot_stream(rp.dev, c->last_slot), done, 0));
+    }
+    return BHRAY_OK;
+}
+
+static int group_device_ptr(bhray_ctx* c, ImageKind kind, void** p, size_t* bytes) {
+    *p = nullptr;
+    FrameImage img;
+    { int rc = last_image(c, kind, false, &img); if (rc) return rc; }
+    *p = (void*)img.src;
+    if (bytes) *bytes = img.rows * img.row_bytes;
+    return BHRAY_OK;
+}
+
 int bhray_read_hdr(bhray_ctx* c, float* dst, size_t pitch) {
     if (!c) return BHRAY_E_INVALID;
     ENTER(c);
-    if (c->single) { DEV(c, c->parts[0].dev, dev_read_hdr(c->parts[0].dev, dst, pitch)); return BHRAY_OK; }
-    if (c->gather_sky) return gfail(c, BHRAY_E_STATE, "BHRAY_F_GATHER_SKY: the RGBA32F frame is not assembled (read the sky image)");
-    { int rc = group_sync(c); if (rc) return rc; }
-    if (!c->root_local) return BHRAY_OK;                        // the frame lives on another rank
-    if (!c->rendered) return gfail(c, BHRAY_E_STATE, "nothing rendered yet");
-    const size_t rowb = (size_t)c->cfg.frame_w * sizeof(float4);
-    if (!dst || pitch < rowb) return gfail(c, BHRAY_E_INVALID, "bad destination / pitch");
-    GHIP(c, hipSetDevice(root_part(c)->device));
-    GHIP(c, hipMemcpy2D(dst, pitch, c->gslots[(size_t)c->last_slot].dst[c->last_sub], rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost));
-    return BHRAY_OK;
+    if (c->single) { DEV(c, c->parts[0].dev, dev_read(c->parts[0].dev, IMAGE_HDR, dst, pitch)); return BHRAY_OK; }
+    return group_read(c, IMAGE_HDR, dst, pitch);
+}
+
+int bhray_read_hdr_async(bhray_ctx* c, float* dst, size_t pitch, uint64_t* ticket) {
+    if (!c || !ticket) return BHRAY_E_INVALID;
+    ENTER(c);
+    if (c->single) { DEV(c, c->parts[0].dev, dev_read_async(c->parts[0].dev, IMAGE_HDR, dst, pitch, ticket)); return BHRAY_OK; }
+    return group_read_async(c, IMAGE_HDR, dst, pitch, ticket);
 }
 
 int bhray_hdr_device_ptr(bhray_ctx* c, void** p, size_t* bytes) {
     if (!c || !p) return BHRAY_E_INVALID;
     ENTER(c);
-    if (c->single) { DEV(c, c->parts[0].dev, dev_hdr_device_ptr(c->parts[0].dev, p, bytes)); return BHRAY_OK; }
-    if (c->gather_sky) { *p = nullptr; return gfail(c, BHRAY_E_STATE, "BHRAY_F_GATHER_SKY: the RGBA32F frame is not assembled (read the sky image)"); }
-    *p = c->root_local ? (void*)c->gslots[(size_t)c->last_slot].dst[c->last_sub] : nullptr;
-    if (bytes) *bytes = c->root_local ? frame_pixels(c) * sizeof(float4) : 0;
-    return BHRAY_OK;
+    if (c->single) { DEV(c, c->parts[0].dev, dev_device_ptr(c->parts[0].dev, IMAGE_HDR, p, bytes)); return BHRAY_OK; }
+    return group_device_ptr(c, IMAGE_HDR, p, bytes);
 }
 
 int bhray_bind_output(bhray_ctx* c, void* p, size_t bytes) {
@@ -1734,7 +1811,7 @@ int bhray_bind_output(bhray_ctx* c, void* p, size_t bytes) {
     if (!p) { c->bound = nullptr; return BHRAY_OK; }
     if (c->gather_sky) return gfail(c, BHRAY_E_STATE, "BHRAY_F_GATHER_SKY: the RGBA32F frame is not assembled (read the sky image)");
     size_t need;
-    if (c->single) { void* q; DEV(c, c->parts[0].dev, dev_hdr_device_ptr(c->parts[0].dev, &q, &need)); }
+    if (c->single) { void* q; DEV(c, c->parts[0].dev, dev_device_ptr(c->parts[0].dev, IMAGE_HDR, &q, &need)); }
     else need = c->root_local ? frame_pixels(c) * sizeof(float4) : 0;
     if (bytes < need) return gfail(c, BHRAY_E_INVALID, "output binding needs %zu bytes", need);
     if (((uintptr_t)p & 15u) != 0) return gfail(c, BHRAY_E_INVALID, "output binding must be 16-byte aligned");
@@ -1742,69 +1819,13 @@ int bhray_bind_output(bhray_ctx* c, void* p, size_t bytes) {
     return BHRAY_OK;
 }
 
-// ---- asynchronous hand-off -------------------------------------------------------------------------
-int bhray_read_hdr_async(bhray_ctx* c, float* dst, size_t pitch, uint64_t* ticket) {
-    if (!c || !ticket) return BHRAY_E_INVALID;
-    ENTER(c);
-    if (c->single) { DEV(c, c->parts[0].dev, dev_read_hdr_async(c->parts[0].dev, dst, pitch, ticket)); return BHRAY_OK; }
-    if (c->gather_sky) return gfail(c, BHRAY_E_STATE, "BHRAY_F_GATHER_SKY: the RGBA32F frame is not assembled (read the sky image)");
-    if (!c->rendered) return gfail(c, BHRAY_E_STATE, "nothing rendered yet");
-    { int rc = group_flush(c); if (rc) return rc; }
-    const uint64_t t = c->read_tickets;
-    if (!c->root_local) { *ticket = t; c->read_tickets = t + 1; return BHRAY_OK; }   // the frame lives on another rank: nothing to copy here
-    const size_t rowb = (size_t)c->cfg.frame_w * sizeof(float4);
-    if (!dst || pitch < rowb) return gfail(c, BHRAY_E_INVALID, "bad destination / pitch");
-    Part& rp = *root_part(c);
-    CommRank* rr = rank_of(c, rp);
-    GHIP(c, hipSetDevice(rp.device));
-    hipEvent_t& ev = c->read_ev[t % 64];
-    if (!ev) GHIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    else if (t >= 64) { GHIP(c, hipEventSynchronize(ev)); WATCH_CHECK(c); }
-    GroupSlot& G = c->gslots[(size_t)c->last_slot];
-    // in stream order on the root's communication stream: behind the de-interleave (and the sky pass, if it was resolved) of this batch,
-    // ahead of the next batch's receive.  (Cross-stream event ordering made ROCm 7.2 serialise copies and kernels: see dev_read_hdr_async.)
-    if (pitch == rowb) GHIP(c, hipMemcpyAsync(dst, G.dst[c->last_sub], rowb * c->cfg.frame_h, hipMemcpyDeviceToHost, rr->stream));
-    else GHIP(c, hipMemcpy2DAsync(dst, pitch, G.dst[c->last_sub], rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost, rr->stream));
-    GHIP(c, hipEventRecord(ev, rr->stream));
-    *ticket = t; c->read_tickets = t + 1;                       // the ticket exists once its event does (an error above consumes none)
-    GHIP(c, hipEventRecord(G.frame_done, rr->stream));
-    GHIP(c, hipStreamWaitEvent(dev_slot_stream(rp.dev, c->last_slot), G.frame_done, 0));   // the root's next render into this slot writes its own rows into that frame
-    return BHRAY_OK;
-}
-
-int bhray_read_sky_async(bhray_ctx* c, uint16_t* dst, size_t pitch, uint64_t* ticket) {
-    if (!c || !ticket) return BHRAY_E_INVALID;
-    ENTER(c);
-    if (c->single) { DEV(c, c->parts[0].dev, dev_read_sky_async(c->parts[0].dev, dst, pitch, ticket)); return BHRAY_OK; }
-    if (!c->rendered) return gfail(c, BHRAY_E_STATE, "nothing rendered yet");
-    if (c->gather_sky) { int rc = group_flush(c); if (rc) return rc; }      // (the batch's gather produces the image)
-    const uint64_t t = c->read_tickets;
-    if (!c->root_local) { *ticket = t; c->read_tickets = t + 1; return BHRAY_OK; }
-    const size_t rowb = (size_t)c->cfg.frame_w * sizeof(uint2);
-    if (!dst || pitch < rowb) return gfail(c, BHRAY_E_INVALID, "bad destination / pitch");
-    const GroupSlot& GS = c->gslots[(size_t)c->last_slot];
-    uint2* src = GS.sky[c->last_sub];
-    if (!src || GS.sky_frame_no[c->last_sub] != GS.frame_no[c->last_sub]) return gfail(c, BHRAY_E_STATE, "bhray_resolve_sky has not been called for this frame");
-    Part& rp = *root_part(c);
-    CommRank* rr = rank_of(c, rp);
-    GHIP(c, hipSetDevice(rp.device));
-    hipEvent_t& ev = c->read_ev[t % 64];
-    if (!ev) GHIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    else if (t >= 64) { GHIP(c, hipEventSynchronize(ev)); WATCH_CHECK(c); }
-    if (pitch == rowb) GHIP(c, hipMemcpyAsync(dst, src, rowb * c->cfg.frame_h, hipMemcpyDeviceToHost, rr->stream));     // behind the sky pass, in stream order
-    else GHIP(c, hipMemcpy2DAsync(dst, pitch, src, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost, rr->stream));
-    GHIP(c, hipEventRecord(ev, rr->stream));
-    *ticket = t; c->read_tickets = t + 1;
-    return BHRAY_OK;
-}
-
+// ---- asynchronous hand-off: tickets ------------------------------------------------------------------
 int bhray_wait_read(bhray_ctx* c, uint64_t ticket) {
     if (!c) return BHRAY_E_INVALID;
     if (c->single) { DEV(c, c->parts[0].dev, dev_wait_read(c->parts[0].dev, ticket)); return BHRAY_OK; }
-    if (ticket >= c->read_tickets) return gfail(c, BHRAY_E_INVALID, "unknown read ticket");
-    if (!c->root_local || c->read_tickets - ticket > 64 || !c->read_ev[ticket % 64]) return BHRAY_OK;
-    GHIP(c, hipSetDevice(root_part(c)->device));
-    GHIP(c, hipEventSynchronize(c->read_ev[ticket % 64]));
+    if (!c->reads.known(ticket)) return gfail(c, BHRAY_E_INVALID, "unknown read ticket");
+    if (c->root_local) GHIP(c, hipSetDevice(root_part(c)->device));
+    GHIP(c, c->reads.wait(ticket));
     WATCH_CHECK(c);
     return BHRAY_OK;
 }
@@ -1927,7 +1948,7 @@ static int group_resolve_sky(bhray_ctx* c) {
     GHIP(c, hipSetDevice(rp.device));
     if (!G.sky[c->last_sub]) GHIP(c, hipMalloc(&G.sky[c->last_sub], frame_pixels(c) * sizeof(uint2)));
     DEV(c, rp.dev, dev_launch_sky(rp.dev, G.dst[c->last_sub], G.sky[c->last_sub], frame_pixels(c), rr->stream));   // behind the de-interleave
-    G.sky_frame_no[c->last_sub] = G.frame_no[c->last_sub];
+    G.sky_frame_id[c->last_sub] = G.frame_id[c->last_sub];
     GHIP(c, hipEventRecord(G.frame_done, rr->stream));
     // the root's next render into this slot writes its own rows straight into the frame the sky pass is reading (the wait that
     // group_gather enqueued captured the EARLIER record of frame_done, behind the de-interleave): order it behind this one
@@ -1945,31 +1966,22 @@ int bhray_resolve_sky(bhray_ctx* c) {
 int bhray_read_sky(bhray_ctx* c, uint16_t* dst, size_t pitch) {
     if (!c) return BHRAY_E_INVALID;
     ENTER(c);
-    if (c->single) { DEV(c, c->parts[0].dev, dev_read_sky(c->parts[0].dev, dst, pitch)); return BHRAY_OK; }
-    { int rc = group_sync(c); if (rc) return rc; }
-    if (!c->root_local) return BHRAY_OK;
-    const size_t rowb = (size_t)c->cfg.frame_w * sizeof(uint2);
-    if (!dst || pitch < rowb) return gfail(c, BHRAY_E_INVALID, "bad destination / pitch");
-    const GroupSlot& GS = c->gslots[(size_t)c->last_slot];
-    uint2* src = GS.sky[c->last_sub];
-    if (!src || GS.sky_frame_no[c->last_sub] != GS.frame_no[c->last_sub]) return gfail(c, BHRAY_E_STATE, "bhray_resolve_sky has not been called for this frame");
-    GHIP(c, hipSetDevice(root_part(c)->device));
-    GHIP(c, hipMemcpy2D(dst, pitch, src, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost));
-    return BHRAY_OK;
+    if (c->single) { DEV(c, c->parts[0].dev, dev_read(c->parts[0].dev, IMAGE_SKY, dst, pitch)); return BHRAY_OK; }
+    return group_read(c, IMAGE_SKY, dst, pitch);
+}
+
+int bhray_read_sky_async(bhray_ctx* c, uint16_t* dst, size_t pitch, uint64_t* ticket) {
+    if (!c || !ticket) return BHRAY_E_INVALID;
+    ENTER(c);
+    if (c->single) { DEV(c, c->parts[0].dev, dev_read_async(c->parts[0].dev, IMAGE_SKY, dst, pitch, ticket)); return BHRAY_OK; }
+    return group_read_async(c, IMAGE_SKY, dst, pitch, ticket);
 }
 
 int bhray_sky_device_ptr(bhray_ctx* c, void** p, size_t* bytes) {
     if (!c || !p) return BHRAY_E_INVALID;
-    if (c->single) { DEV(c, c->parts[0].dev, dev_sky_device_ptr(c->parts[0].dev, p, bytes)); return BHRAY_OK; }
     ENTER(c);
-    *p = nullptr;
-    if (c->root_local) {                 // the same rule as the reads: an image resolved from an earlier frame of this slot position is stale
-        const GroupSlot& GS = c->gslots[(size_t)c->last_slot];
-        if (!GS.sky[c->last_sub] || GS.sky_frame_no[c->last_sub] != GS.frame_no[c->last_sub]) return gfail(c, BHRAY_E_STATE, "bhray_resolve_sky has not been called for this frame");
-    }
-    *p = c->root_local ? (void*)c->gslots[(size_t)c->last_slot].sky[c->last_sub] : nullptr;
-    if (bytes) *bytes = c->root_local ? frame_pixels(c) * sizeof(uint2) : 0;
-    return BHRAY_OK;
+    if (c->single) { DEV(c, c->parts[0].dev, dev_device_ptr(c->parts[0].dev, IMAGE_SKY, p, bytes)); return BHRAY_OK; }
+    return group_device_ptr(c, IMAGE_SKY, p, bytes);
 }
 
 // ---- display pass (bhray_post.hip) ---------------------------------------------------------------------------
@@ -1982,13 +1994,6 @@ int bhray_set_post_uniforms(bhray_ctx* c, const void* fxaa16, const void* mix4) 
     return BHRAY_OK;
 }
 
-// the root's RGBA8 image of the most recently staged frame, if it was resolved for that frame
-static uint32_t* group_display(bhray_ctx* c) {
-    const GroupSlot& GS = c->gslots[(size_t)c->last_slot];
-    uint32_t* d = GS.disp[c->last_sub];
-    return (d && GS.disp_frame_no[c->last_sub] == GS.frame_no[c->last_sub]) ? d : nullptr;
-}
-
 int bhray_resolve_display(bhray_ctx* c) {
     if (!c) return BHRAY_E_INVALID;
     ENTER(c);
@@ -1998,7 +2003,7 @@ int bhray_resolve_display(bhray_ctx* c) {
     { int rc = group_flush(c); if (rc) return rc; }
     if (!c->root_local) return BHRAY_OK;                        // the frame lives on another rank
     GroupSlot& G = c->gslots[(size_t)c->last_slot];
-    if (!G.sky[c->last_sub] || G.sky_frame_no[c->last_sub] != G.frame_no[c->last_sub]) { int rc = group_resolve_sky(c); if (rc) return rc; }
+    if (!resolved(c, IMAGE_SKY)) { int rc = group_resolve_sky(c); if (rc) return rc; }
     Part& rp = *root_part(c);
     CommRank* rr = rank_of(c, rp);
     GHIP(c, hipSetDevice(rp.device));
@@ -2006,61 +2011,29 @@ int bhray_resolve_display(bhray_ctx* c) {
     if (!G.disp[c->last_sub]) GHIP(c, hipMalloc(&G.disp[c->last_sub], frame_pixels(c) * sizeof(uint32_t)));
     // behind the sky image on the root's communication stream (the gather's de-interleave, or bhray_resolve_sky's pass)
     DEV(c, rp.dev, dev_launch_display(rp.dev, G.sky[c->last_sub], c->post_scratch, G.disp[c->last_sub], &c->post_fxaa, &c->post_mix, rr->stream));
-    G.disp_frame_no[c->last_sub] = G.frame_no[c->last_sub];
+    G.disp_frame_id[c->last_sub] = G.frame_id[c->last_sub];
     return BHRAY_OK;
 }
 
 int bhray_read_display(bhray_ctx* c, uint8_t* dst, size_t pitch) {
     if (!c) return BHRAY_E_INVALID;
     ENTER(c);
-    if (c->single) { DEV(c, c->parts[0].dev, dev_read_display(c->parts[0].dev, dst, pitch)); return BHRAY_OK; }
-    { int rc = group_sync(c); if (rc) return rc; }
-    if (!c->root_local) return BHRAY_OK;
-    const size_t rowb = (size_t)c->cfg.frame_w * 4;
-    if (!dst || pitch < rowb) return gfail(c, BHRAY_E_INVALID, "bad destination / pitch");
-    uint32_t* src = c->rendered ? group_display(c) : nullptr;
-    if (!src) return gfail(c, BHRAY_E_STATE, "bhray_resolve_display has not been called for this frame");
-    GHIP(c, hipSetDevice(root_part(c)->device));
-    GHIP(c, hipMemcpy2D(dst, pitch, src, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost));
-    return BHRAY_OK;
+    if (c->single) { DEV(c, c->parts[0].dev, dev_read(c->parts[0].dev, IMAGE_DISPLAY, dst, pitch)); return BHRAY_OK; }
+    return group_read(c, IMAGE_DISPLAY, dst, pitch);
 }
 
 int bhray_read_display_async(bhray_ctx* c, uint8_t* dst, size_t pitch, uint64_t* ticket) {
     if (!c || !ticket) return BHRAY_E_INVALID;
     ENTER(c);
-    if (c->single) { DEV(c, c->parts[0].dev, dev_read_display_async(c->parts[0].dev, dst, pitch, ticket)); return BHRAY_OK; }
-    if (!c->rendered) return gfail(c, BHRAY_E_STATE, "nothing rendered yet");
-    const uint64_t t = c->read_tickets;
-    if (!c->root_local) { *ticket = t; c->read_tickets = t + 1; return BHRAY_OK; }
-    const size_t rowb = (size_t)c->cfg.frame_w * 4;
-    if (!dst || pitch < rowb) return gfail(c, BHRAY_E_INVALID, "bad destination / pitch");
-    uint32_t* src = group_display(c);
-    if (!src) return gfail(c, BHRAY_E_STATE, "bhray_resolve_display has not been called for this frame");
-    Part& rp = *root_part(c);
-    CommRank* rr = rank_of(c, rp);
-    GHIP(c, hipSetDevice(rp.device));
-    hipEvent_t& ev = c->read_ev[t % 64];
-    if (!ev) GHIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    else if (t >= 64) { GHIP(c, hipEventSynchronize(ev)); WATCH_CHECK(c); }
-    if (pitch == rowb) GHIP(c, hipMemcpyAsync(dst, src, rowb * c->cfg.frame_h, hipMemcpyDeviceToHost, rr->stream));     // behind the display pass, in stream order
-    else GHIP(c, hipMemcpy2DAsync(dst, pitch, src, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost, rr->stream));
-    GHIP(c, hipEventRecord(ev, rr->stream));
-    *ticket = t; c->read_tickets = t + 1;
-    return BHRAY_OK;
+    if (c->single) { DEV(c, c->parts[0].dev, dev_read_async(c->parts[0].dev, IMAGE_DISPLAY, dst, pitch, ticket)); return BHRAY_OK; }
+    return group_read_async(c, IMAGE_DISPLAY, dst, pitch, ticket);
 }
 
 int bhray_display_device_ptr(bhray_ctx* c, void** p, size_t* bytes) {
     if (!c || !p) return BHRAY_E_INVALID;
-    if (c->single) { DEV(c, c->parts[0].dev, dev_display_device_ptr(c->parts[0].dev, p, bytes)); return BHRAY_OK; }
     ENTER(c);
-    *p = nullptr;
-    if (c->root_local) {
-        uint32_t* d = c->rendered ? group_display(c) : nullptr;
-        if (!d) return gfail(c, BHRAY_E_STATE, "bhray_resolve_display has not been called for this frame");
-        *p = d;
-    }
-    if (bytes) *bytes = c->root_local ? frame_pixels(c) * 4 : 0;
-    return BHRAY_OK;
+    if (c->single) { DEV(c, c->parts[0].dev, dev_device_ptr(c->parts[0].dev, IMAGE_DISPLAY, p, bytes)); return BHRAY_OK; }
+    return group_device_ptr(c, IMAGE_DISPLAY, p, bytes);
 }
 
 // ---- measurement and verification: include/bhray_diag.h ----------------------------------------------
