@@ -17,7 +17,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 
 from ._lib import lib, LibraryMissing, LIB_PATH  # noqa: F401
 from .layouts import (BhrayConfig, BhrayCounters, BhrayTiming, BhrayDetails, BhrayCameraUniform,  # noqa: F401
-                      BhrayBlackHoleUniform, BhrayBlackHole, BhrayFxaaDetails, BhrayMixDetails, BhrayModelDesc, BhrayNode, BhrayRay, BhrayRayRecord, BhrayTriangle,
+                      BhrayBlackHoleUniform, BhrayBlackHole, BhrayFxaaDetails, BhrayMixDetails, BhrayModelDesc, BhrayNode, BhrayRay, BhrayRayRecord, BhrayPathPoint, PATH_POINT_DTYPE, BhrayTriangle,
                       HIT_NONE, HIT_HORIZON, HIT_DISK, HIT_MESH, HIT_UNUSABLE,
                       BhrayError, check)
 from .scene import Camera, BlackHole, RayDetails  # noqa: F401

@@ -205,6 +205,9 @@ struct bhray_dev {
     size_t q_cap = 0;                      // rays the staging holds
     bhray_ray_record* q_hrec = nullptr; bhray_ray_record* q_drec = nullptr;      // the records' staging (bhray_trace_rays_records): grow-only, allocated by the first records batch
     size_t q_rec_cap = 0;
+    bhray_path_point* q_hpts = nullptr; bhray_path_point* q_dpts = nullptr;      // the paths' staging (bhray_trace_rays_paths): grow-only, allocated by the first paths batch
+    uint32_t* q_hcnt = nullptr; uint32_t* q_dcnt = nullptr;
+    size_t q_pts_cap = 0, q_cnt_cap = 0;   // points / rays the staging holds
     bhray::ReadRing reads;                 // tickets of the asynchronous hand-off (dev_read_async)
     std::string err;
 };
@@ -422,6 +425,10 @@ void dev_destroy(bhray_dev* c) {
     if (c->q_dout) (void)hipFree(c->q_dout);
     if (c->q_hrec) (void)hipHostFree(c->q_hrec);
     if (c->q_drec) (void)hipFree(c->q_drec);
+    if (c->q_hpts) (void)hipHostFree(c->q_hpts);
+    if (c->q_dpts) (void)hipFree(c->q_dpts);
+    if (c->q_hcnt) (void)hipHostFree(c->q_hcnt);
+    if (c->q_dcnt) (void)hipFree(c->q_dcnt);
     for (hipEvent_t e : {c->q_begin, c->q_done, c->q_uploaded}) if (e) (void)hipEventDestroy(e);
     if (c->q_stream) (void)hipStreamDestroy(c->q_stream);
     for (Slot& S : c->slots) {
@@ -1128,7 +1135,9 @@ int ensure_query(bhray_dev* c) {
 
 // One launch on the query stream: n rays at d_rays -> n results at d_out, under the engine's current uniforms, textures and models.  Enqueues only.
 // d_records: nullptr, or n bhray_ray_record (16-byte aligned) - the record kernels (TraceVariant::records).
-int enqueue_rays(bhray_dev* c, const float4* d_rays, uint32_t n, float4* d_out, void* d_records = nullptr) {
+// paths: nullptr, or the path arguments (d_records is then not null) - the path kernels (TraceVariant::paths).
+struct PathArgs { void* d_points; void* d_counts; uint32_t stride_log2, max_points; };
+int enqueue_rays(bhray_dev* c, const float4* d_rays, uint32_t n, float4* d_out, void* d_records = nullptr, const PathArgs* paths = nullptr) {
     // the pinned block of the batch before must have reached the device before it is rewritten (its device copy is read in stream order)
     if (c->q_used && hipEventQuery(c->q_uploaded) != hipSuccess) HIPCHK(c, hipEventSynchronize(c->q_uploaded));
     FrameParams& P = *(FrameParams*)c->q_hargs;
@@ -1141,7 +1150,11 @@ int enqueue_rays(bhray_dev* c, const float4* d_rays, uint32_t n, float4* d_out, 
     uint32_t* ctl = (uint32_t*)(c->q_hargs + Q_OFF_CTL);
     ctl[0] = n; ctl[1] = 0; ctl[2] = 0; ctl[3] = 0;
     F.row_work = (unsigned long long*)d_records;                  // the records (TraceVariant::records): the member a ray-list launch does not use otherwise
-    const TraceVariant v{P.method, P.model_count > 0 ? 1 : 0, false, false, 0, false, true, d_records != nullptr};
+    if (paths) {                                                  // the paths (TraceVariant::paths): members of the classification and of temporal speculation, which no ray-list launch reads
+        F.need = (uint8_t*)paths->d_points; F.stamp = (const uint32_t*)paths->d_counts;
+        F.radius = (int)paths->stride_log2; F.stamp_value = paths->max_points;
+    }
+    const TraceVariant v{P.method, P.model_count > 0 ? 1 : 0, false, false, 0, false, true, d_records != nullptr, paths != nullptr};
     int ctx_grid = c->num_cus * trace_blocks_per_cu(v);
     if (c->grid_override > 0) ctx_grid = c->grid_override;
     const int grid = (int)bhray_trace_grid_for(n, 1, (uint32_t)ctx_grid, c->level_grid_gen, 0, c->level_grid_floor);      // n is exact: no margin
@@ -1155,9 +1168,12 @@ int enqueue_rays(bhray_dev* c, const float4* d_rays, uint32_t n, float4* d_out, 
 
 // out: n x RGBA32F (may be NULL when sky16 is not); sky16: NULL, or n x RGBA16F - sky.wgsl over the results (launch_sky, the pass of dev_resolve_sky)
 // records: NULL, or n records (bhray_trace_rays_records: then `out` may be NULL too)
-int dev_trace_rays(bhray_dev* c, const bhray_ray* rays, uint32_t n, float* out, uint16_t* sky16, bhray_ray_record* records) {
+// paths: NULL, or the path outputs (bhray_trace_rays_paths, whose entry has checked them: then `out` and `records` may be NULL) - n * max_points points, n counts
+int dev_trace_rays(bhray_dev* c, const bhray_ray* rays, uint32_t n, float* out, uint16_t* sky16, bhray_ray_record* records, const bhray_dev_paths* paths) {
     if (!c) return BHRAY_E_INVALID;
-    if (n > BHRAY_MAX_RAYS_PER_CALL || (n != 0 && (!rays || (!out && !sky16 && !records)))) return fail(c, BHRAY_E_INVALID, "bhray_trace_rays: bad arguments");
+    if (n > BHRAY_MAX_RAYS_PER_CALL || (n != 0 && (!rays || (!out && !sky16 && !records && !paths)))) return fail(c, BHRAY_E_INVALID, "bhray_trace_rays: bad arguments");
+    if (paths && (paths->max_points < 2u || paths->stride_log2 > BHRAY_MAX_PATH_STRIDE_LOG2 || (uint64_t)n * paths->max_points > BHRAY_MAX_PATH_POINTS_PER_CALL ||
+                  (n != 0 && (!paths->points || !paths->counts)))) return fail(c, BHRAY_E_INVALID, "bhray_trace_rays_paths: bad arguments");
     { int rc = rays_refused(c, "bhray_trace_rays"); if (rc) return rc; }
     if (n == 0) return BHRAY_OK;
     for (uint32_t i = 0; i < n; i++) {                            // before anything is enqueued
@@ -1185,7 +1201,27 @@ int dev_trace_rays(bhray_dev* c, const bhray_ray* rays, uint32_t n, float* out, 
     } else {
         HIPCHK(c, hipStreamSynchronize(c->q_stream));           // (a copy of an earlier call that failed half-way may still read the staging)
     }
-    if (records && n > c->q_rec_cap) {                            // the same for the records (the stream is idle here)
+    const bool want_rec = records || paths;                       // the path kernels are record kernels: their records are staged whether the caller takes them or not
+    const size_t npts = paths ? (size_t)n * paths->max_points : 0;
+    if (paths && npts > c->q_pts_cap) {                           // the same for the points and the counts (the stream is idle here)
+        if (c->q_hpts) (void)hipHostFree(c->q_hpts);
+        if (c->q_dpts) (void)hipFree(c->q_dpts);
+        c->q_hpts = c->q_dpts = nullptr; c->q_pts_cap = 0;
+        const size_t cap = std::max<size_t>(npts, 65536);
+        HIPCHK(c, hipHostMalloc(&c->q_hpts, cap * sizeof(bhray_path_point)));
+        HIPCHK(c, hipMalloc(&c->q_dpts, cap * sizeof(bhray_path_point)));
+        c->q_pts_cap = cap;
+    }
+    if (paths && n > c->q_cnt_cap) {
+        if (c->q_hcnt) (void)hipHostFree(c->q_hcnt);
+        if (c->q_dcnt) (void)hipFree(c->q_dcnt);
+        c->q_hcnt = c->q_dcnt = nullptr; c->q_cnt_cap = 0;
+        const size_t cap = std::max<size_t>(n, 4096);
+        HIPCHK(c, hipHostMalloc(&c->q_hcnt, cap * sizeof(uint32_t)));
+        HIPCHK(c, hipMalloc(&c->q_dcnt, cap * sizeof(uint32_t)));
+        c->q_cnt_cap = cap;
+    }
+    if (want_rec && n > c->q_rec_cap) {                           // the same for the records (the stream is idle here)
         if (c->q_hrec) (void)hipHostFree(c->q_hrec);
         if (c->q_drec) (void)hipFree(c->q_drec);
         c->q_hrec = c->q_drec = nullptr; c->q_rec_cap = 0;
@@ -1196,9 +1232,18 @@ int dev_trace_rays(bhray_dev* c, const bhray_ray* rays, uint32_t n, float* out, 
     }
     memcpy(c->q_hin, rays, (size_t)n * sizeof(bhray_ray));
     HIPCHK(c, hipMemcpyAsync(c->q_din, c->q_hin, (size_t)n * sizeof(bhray_ray), hipMemcpyHostToDevice, c->q_stream));
-    { int rc = enqueue_rays(c, c->q_din, n, c->q_dout, records ? c->q_drec : nullptr); if (rc) return rc; }
+    PathArgs pa{};
+    if (paths) {                                                  // slots the kernel does not write come back as zero bytes
+        pa = PathArgs{c->q_dpts, c->q_dcnt, paths->stride_log2, paths->max_points};
+        HIPCHK(c, hipMemsetAsync(c->q_dpts, 0, npts * sizeof(bhray_path_point), c->q_stream));
+    }
+    { int rc = enqueue_rays(c, c->q_din, n, c->q_dout, want_rec ? c->q_drec : nullptr, paths ? &pa : nullptr); if (rc) return rc; }
     HIPCHK(c, hipMemcpyAsync(c->q_hout, c->q_dout, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, c->q_stream));
     if (records) HIPCHK(c, hipMemcpyAsync(c->q_hrec, c->q_drec, (size_t)n * sizeof(bhray_ray_record), hipMemcpyDeviceToHost, c->q_stream));
+    if (paths) {
+        HIPCHK(c, hipMemcpyAsync(c->q_hpts, c->q_dpts, npts * sizeof(bhray_path_point), hipMemcpyDeviceToHost, c->q_stream));
+        HIPCHK(c, hipMemcpyAsync(c->q_hcnt, c->q_dcnt, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->q_stream));
+    }
     if (sky16) {                                                  // the records are used up: their device buffer (32 bytes per ray) takes the image (8), their pinned one its copy
         TexDev sky; sky.rgba = c->tex[BHRAY_TEX_SKY]; sky.w = c->tex_w[BHRAY_TEX_SKY]; sky.h = c->tex_h[BHRAY_TEX_SKY];
         HIPCHK(c, launch_sky(sky, c->q_dout, (uint2*)c->q_din, n, c->q_stream));
@@ -1215,22 +1260,29 @@ int dev_trace_rays(bhray_dev* c, const bhray_ray* rays, uint32_t n, float* out, 
     }
     if (out) memcpy(out, c->q_hout, (size_t)n * sizeof(float4));
     if (records) memcpy(records, c->q_hrec, (size_t)n * sizeof(bhray_ray_record));
+    if (paths) { memcpy(paths->points, c->q_hpts, npts * sizeof(bhray_path_point)); memcpy(paths->counts, c->q_hcnt, (size_t)n * sizeof(uint32_t)); }
     if (sky16) memcpy(sky16, c->q_hin, (size_t)n * sizeof(uint2));
     return BHRAY_OK;
 }
 
 // d_records: NULL (bhray_trace_rays_device), or n records, 16-byte aligned (bhray_trace_rays_records_device, whose entry refuses a NULL)
-int dev_trace_rays_device(bhray_dev* c, const void* d_rays, uint32_t n, void* d_out, void* d_records, hipStream_t s) {
+// paths: NULL, or the path outputs in device memory (bhray_trace_rays_paths_device: d_records is then not NULL) - points 16-byte aligned, counts 4-byte aligned
+int dev_trace_rays_device(bhray_dev* c, const void* d_rays, uint32_t n, void* d_out, void* d_records, hipStream_t s, const bhray_dev_paths* paths) {
     if (!c) return BHRAY_E_INVALID;
     if (n > BHRAY_MAX_RAYS_PER_CALL || (n != 0 && (!d_rays || !d_out))) return fail(c, BHRAY_E_INVALID, "bhray_trace_rays_device: bad arguments");
     if (((uintptr_t)d_rays | (uintptr_t)d_out | (uintptr_t)d_records) & 15u) return fail(c, BHRAY_E_INVALID, "bhray_trace_rays_device: the arrays must be 16-byte aligned");
+    if (paths && (paths->max_points < 2u || paths->stride_log2 > BHRAY_MAX_PATH_STRIDE_LOG2 || (uint64_t)n * paths->max_points > BHRAY_MAX_PATH_POINTS_PER_CALL ||
+                  (n != 0 && (!paths->points || !paths->counts || !d_records)) || ((uintptr_t)paths->points & 15u) || ((uintptr_t)paths->counts & 3u)))
+        return fail(c, BHRAY_E_INVALID, "bhray_trace_rays_paths_device: bad arguments");
     { int rc = rays_refused(c, "bhray_trace_rays_device"); if (rc) return rc; }
     if (n == 0) return BHRAY_OK;
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = ensure_query(c); if (rc) return rc; }
     HIPCHK(c, hipEventRecord(c->q_begin, s));                     // the batch starts behind what `s` holds now ...
     HIPCHK(c, hipStreamWaitEvent(c->q_stream, c->q_begin, 0));
-    { int rc = enqueue_rays(c, (const float4*)d_rays, n, (float4*)d_out, d_records); if (rc) return rc; }
+    PathArgs pa{};
+    if (paths) pa = PathArgs{paths->points, paths->counts, paths->stride_log2, paths->max_points};
+    { int rc = enqueue_rays(c, (const float4*)d_rays, n, (float4*)d_out, d_records, paths ? &pa : nullptr); if (rc) return rc; }
     HIPCHK(c, hipEventRecord(c->q_done, c->q_stream));            // ... and what `s` gets from now on starts behind the batch
     HIPCHK(c, hipStreamWaitEvent(s, c->q_done, 0));
     return BHRAY_OK;

@@ -113,8 +113,11 @@ int  dev_set_model_transform(bhray_dev* c, uint32_t model_index, const float pos
 int  dev_set_uniforms(bhray_dev* c, const void* cam32, const void* bh132, const void* det32);
 // ray batches: the host variant returns with `out` complete; the device variant enqueues on the engine's query stream, behind what `s` holds and ahead of what it gets
 // records / d_records: NULL, or a bhray_ray_record per ray beside the results (the record kernels)
-int  dev_trace_rays(bhray_dev* c, const bhray_ray* rays, uint32_t n, float* out_rgba32f, uint16_t* sky_rgba16f /* NULL: no sky pass over the results */, bhray_ray_record* records = nullptr);
-int  dev_trace_rays_device(bhray_dev* c, const void* d_rays, uint32_t n, void* d_out_rgba32f, void* d_records, hipStream_t s);
+// paths: NULL, or where the sampled paths go (the path kernels) - host memory for dev_trace_rays, device memory for dev_trace_rays_device
+struct bhray_dev_paths { uint32_t stride_log2, max_points; bhray_path_point* points /* n * max_points */; uint32_t* counts /* n */; };
+int  dev_trace_rays(bhray_dev* c, const bhray_ray* rays, uint32_t n, float* out_rgba32f, uint16_t* sky_rgba16f /* NULL: no sky pass over the results */, bhray_ray_record* records = nullptr,
+                    const bhray_dev_paths* paths = nullptr);
+int  dev_trace_rays_device(bhray_dev* c, const void* d_rays, uint32_t n, void* d_out_rgba32f, void* d_records, hipStream_t s, const bhray_dev_paths* paths = nullptr);
 int  dev_set_mesh_lensing(bhray_dev* c, int32_t on);       // from the next dev_render; BHRAY_E_STATE for on != 0 on a BHRAY_F_LITERAL / BHRAY_F_EVAL_FMA engine
 // another row partition (bhray_config.partition / stripe_rows / slab_row0 / row_rank / row_world) for the same frame; synchronises the engine
 int  dev_set_partition(bhray_dev* c, uint32_t partition, uint32_t stripe_rows, const uint32_t* slab_row0, uint32_t row_rank, uint32_t row_world);

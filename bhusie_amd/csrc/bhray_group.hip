@@ -1591,6 +1591,32 @@ int bhray_trace_rays_records_device(bhray_ctx* c, const void* d_rays, uint32_t n
     DEV(c, c->parts[0].dev, dev_trace_rays_device(c->parts[0].dev, d_rays, n, d_out, d_records, (hipStream_t)s));
     return BHRAY_OK;
 }
+// Ray paths: the same entry rules again; the argument errors before the state, so that they leave every output alone whatever the ctx is in.
+static bool paths_args_bad(uint32_t n, uint32_t stride_log2, uint32_t max_points) {
+    return n > BHRAY_MAX_RAYS_PER_CALL || max_points < 2u || stride_log2 > BHRAY_MAX_PATH_STRIDE_LOG2 || (uint64_t)n * max_points > BHRAY_MAX_PATH_POINTS_PER_CALL;
+}
+int bhray_trace_rays_paths(bhray_ctx* c, const bhray_ray* rays, uint32_t n, uint32_t stride_log2, uint32_t max_points, float* out, bhray_ray_record* records,
+                           bhray_path_point* points, uint32_t* counts) {
+    if (!c) return BHRAY_E_INVALID;
+    if (paths_args_bad(n, stride_log2, max_points) || (n != 0 && (!rays || !points || !counts))) return gfail(c, BHRAY_E_INVALID, "bhray_trace_rays_paths: bad arguments");
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_trace_rays_paths"); if (rc) return rc; }
+    const bhray_dev_paths p{stride_log2, max_points, points, counts};
+    DEV(c, c->parts[0].dev, dev_trace_rays(c->parts[0].dev, rays, n, out, nullptr, records, &p));
+    return BHRAY_OK;
+}
+int bhray_trace_rays_paths_device(bhray_ctx* c, const void* d_rays, uint32_t n, uint32_t stride_log2, uint32_t max_points, void* d_out, void* d_records,
+                                  void* d_points, void* d_counts, void* s) {
+    if (!c) return BHRAY_E_INVALID;
+    if (paths_args_bad(n, stride_log2, max_points) || (n != 0 && (!d_rays || !d_out || !d_records || !d_points || !d_counts)) ||
+        (((uintptr_t)d_points | (uintptr_t)d_records) & 15u) || ((uintptr_t)d_counts & 3u))
+        return gfail(c, BHRAY_E_INVALID, "bhray_trace_rays_paths_device: bad arguments");
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_trace_rays_paths_device"); if (rc) return rc; }
+    const bhray_dev_paths p{stride_log2, max_points, (bhray_path_point*)d_points, (uint32_t*)d_counts};
+    DEV(c, c->parts[0].dev, dev_trace_rays_device(c->parts[0].dev, d_rays, n, d_out, d_records, (hipStream_t)s, &p));
+    return BHRAY_OK;
+}
 int bhray_set_uniforms(bhray_ctx* c, const void* cam32, const void* bh132, const void* det32) {
     if (!c) return BHRAY_E_INVALID;
     if (c->gather && cam32 && bh132) track_hole_row(c, cam32, bh132);

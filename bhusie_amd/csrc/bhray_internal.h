@@ -151,9 +151,12 @@ hipError_t launch_classify(const FrameParams* Pb, const FrameLaunch* Fb, int nb,
 // FrameLaunch::L.prev holds the n records (bhray_ray: two float4 each), L.out the n results, qctl[0] = n; nothing else of L / SL / queue is read.
 // records (implies rays): the launch also writes a bhray_ray_record per ray (bhray_trace_rays_records, DESIGN.md §16: trace_kernel's RECORDS) to the array FrameLaunch::row_work
 // points at - the member only a counting launch reads, which a ray-list launch never is.
-struct TraceVariant { int method; int models; bool count; bool dense; int eval; bool origin; bool rays = false; bool records = false; };
+// paths (implies records): the launch also writes the sampled path of every ray (bhray_trace_rays_paths, DESIGN.md §17: trace_kernel's PATHS) - the points to the array
+// FrameLaunch::need points at, the counts to FrameLaunch::stamp, with stride_log2 in FrameLaunch::radius and max_points in FrameLaunch::stamp_value: members of the
+// classification and of temporal speculation, which a ray-list launch never reads.
+struct TraceVariant { int method; int models; bool count; bool dense; int eval; bool origin; bool rays = false; bool records = false; bool paths = false; };
 constexpr bool operator==(const TraceVariant& a, const TraceVariant& b) {
-    return a.method == b.method && a.models == b.models && a.count == b.count && a.dense == b.dense && a.eval == b.eval && a.origin == b.origin && a.rays == b.rays && a.records == b.records;
+    return a.method == b.method && a.models == b.models && a.count == b.count && a.dense == b.dense && a.eval == b.eval && a.origin == b.origin && a.rays == b.rays && a.records == b.records && a.paths == b.paths;
 }
 #ifndef BHRAY_UNIFIED
 #define BHRAY_UNIFIED 1          // (both described in bhray_kernels.hip; the defaults are needed here for trace_resolve, which is inline: EVERY translation unit that includes this
@@ -165,6 +168,7 @@ constexpr bool operator==(const TraceVariant& a, const TraceVariant& b) {
 // fallback costs time only.  What is instantiated is exactly the set of variants that resolve to themselves (bhray_kernels.hip: trace_kernel_ptr).
 constexpr TraceVariant trace_resolve(TraceVariant v) {
     // ray lists: the contract's evaluation only (the API refuses the others), latency build, general hole position, no counting; flat-space models (lensing is refused)
+    if (v.paths) v.records = true;                                            // the path kernels are record kernels
     if (v.records) v.rays = true;                                             // the record kernels are ray-list kernels
     if (v.rays) { v.models = v.models != 0 ? 1 : 0; v.count = false; v.dense = false; v.eval = 0; v.origin = false; return v; }
     if (v.models == 2 && v.eval == 0) { v.dense = false; v.origin = false; return v; }   // lensed meshes: the latency general build, counting or not
@@ -193,6 +197,9 @@ static_assert(!(trace_resolve({1, 0, false, false, 0, false, true}) == trace_res
 static_assert(trace_resolve({1, 2, true,  true,  0, true,  false, true}) == TraceVariant{1, 1, false, false, 0, false, true, true}, "trace_resolve");   // records imply a ray list, and resolve as one
 static_assert(!(trace_resolve({0, 0, false, false, 0, false, true, true}) == trace_resolve({0, 0, false, false, 0, false, true, false})), "trace_resolve: the record kernels are builds of their own");
 static_assert(trace_resolve({0, 1, false, false, 0, false, true, false}) == TraceVariant{0, 1, false, false, 0, false, true, false}, "trace_resolve");   // a ray list without records stays what it was
+static_assert(trace_resolve({1, 2, true,  true,  0, true,  false, false, true}) == TraceVariant{1, 1, false, false, 0, false, true, true, true}, "trace_resolve");   // paths imply records, and resolve as a ray list
+static_assert(!(trace_resolve({0, 0, false, false, 0, false, true, true, true}) == trace_resolve({0, 0, false, false, 0, false, true, true, false})), "trace_resolve: the path kernels are builds of their own");
+static_assert(trace_resolve({0, 1, false, false, 0, false, true, true, false}) == TraceVariant{0, 1, false, false, 0, false, true, true, false}, "trace_resolve");   // a records request without paths stays what it was
 static_assert(trace_resolve(trace_resolve(TraceVariant{0, 2, true, true, 2, true})) == trace_resolve(TraceVariant{0, 2, true, true, 2, true}), "trace_resolve is idempotent");
 // launch_trace and trace_blocks_per_cu resolve `asked` themselves
 hipError_t launch_trace(const FrameParams* Pb, const FrameLaunch* Fb, int nb, TraceVariant asked, int* err_flag, int grid_blocks, hipStream_t s);

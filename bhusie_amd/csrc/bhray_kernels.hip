@@ -1279,6 +1279,13 @@ __device__ __forceinline__ void record_first_hit(float4* __restrict__ records, u
     *reinterpret_cast<int*>(rec + 1) = triangle;
 }
 
+// The path kernels (trace_kernel's PATHS): point k of ray idx - (curr.position, i) - as one 16-byte store, where the step counter has taken the value i for
+// good, the ray goes on, i is a multiple of 2^s and the row has room.  s and max_points are launch uniforms; nothing but the guard's operands is live for it.
+__device__ __forceinline__ void path_sample(float4* __restrict__ points, uint32_t idx, uint32_t s, uint32_t max_points, F3 pos, int it) {
+    const uint32_t i = (uint32_t)it, k = i >> s;
+    if ((i & ((1u << s) - 1u)) == 0u && k < max_points) points[(size_t)idx * max_points + k] = make_float4(pos.x, pos.y, pos.z, __uint_as_float(i));
+}
+
 // Cold per-lane ray state: values the integrator step loop reads or writes only on its rare paths (sphere exit, an actual hit)
 // or not at all (the pixel id) — 8 words per lane.  The dense build (6 waves per SIMD = 80 VGPRs) keeps them in LDS, one word
 // per lane per plane (lane-consecutive addresses: conflict-free ds_read/ds_write_b32), which takes them out of the register
@@ -1354,7 +1361,13 @@ namespace bhray {
 // (position, hit, triangle) are stored where the ray's first hit arises (the places that run HIT_SET(1), while the flag is still clear; the lane holds its index in the
 // cold state), words 5-7 (iterations, closest, transmittance) in the epilogue from `it`, `closest`, `amount`, which also stores words 0-4 for a ray that never hit.
 // Kernels of their own again: every other instantiation is the text it was.
-template <int METHOD, bool MODELS, bool COUNT, bool DENSE, int EVAL = 0, bool ORIGIN = false, bool LENSED = false, bool RAYS = false, bool RECORDS = false>
+// PATHS (bhray_trace_rays_paths; implies RECORDS): besides result and record idx the launch writes the ray's sampled path - bhray_path_point, 16 bytes, row idx
+// of the array FrameLaunch::need points at - and its point count to FrameLaunch::stamp[idx]; stride_log2 travels in FrameLaunch::radius, max_points in FrameLaunch::stamp_value
+// (members of the classification and of temporal speculation: a ray-list launch reads none of them).  Point 0 (the origin) is stored at the refill, a sampled point wherever a
+// ray that goes on gets its final it++ (path_sample: the step text, the shade phase, the flat phase), the end point and the count in the epilogue.  These builds march with the
+// general step text (UNIFIED is false for them, as for LENSED): the unified march forms no cpos inside a pair, and the two forms are the same operations on the same values.
+// Kernels of their own once more: every other instantiation is the text it was.
+template <int METHOD, bool MODELS, bool COUNT, bool DENSE, int EVAL = 0, bool ORIGIN = false, bool LENSED = false, bool RAYS = false, bool RECORDS = false, bool PATHS = false>
 __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS ? (DENSE ? BHRAY_TRACE_WAVES_MESH_DENSE : BHRAY_TRACE_WAVES_MESH) : (DENSE ? BHRAY_TRACE_WAVES_DENSE : (RECORDS && METHOD == 0) ? BHRAY_TRACE_WAVES_RECORDS_EULER : BHRAY_TRACE_WAVES)) void trace_kernel(const FrameParams* __restrict__ Pb, const FrameLaunch* __restrict__ Fb, const int nb, int* __restrict__ err_flag) {
     const int lane = threadIdx.x & 63;
     int err = 0;
@@ -1379,7 +1392,8 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
     static_assert(!LENSED || (MODELS && !DENSE && EVAL == 0 && !ORIGIN), "the lensed-mesh kernels: mesh variant, latency build, the contract's evaluation, general hole position");
     static_assert(!RAYS || (!COUNT && !DENSE && EVAL == 0 && !ORIGIN && !LENSED), "the ray-list kernels: latency build, the contract's evaluation, general hole position, no counting, flat-space models");
     static_assert(!RECORDS || RAYS, "the record kernels are ray-list kernels");
-    constexpr bool UNIFIED = BHRAY_UNIFIED != 0 && EVAL == 0 && (!MODELS || BHRAY_UNIFIED_MESH != 0) && !COUNT && !LENSED;           // the unified march (bhray_step_u.inc) in the contract kernels that do not count (the lensed-mesh kernels: the general step, whose ppos / pdir a paused lane keeps)
+    static_assert(!PATHS || RECORDS, "the path kernels are record kernels");
+    constexpr bool UNIFIED = BHRAY_UNIFIED != 0 && EVAL == 0 && (!MODELS || BHRAY_UNIFIED_MESH != 0) && !COUNT && !LENSED && !PATHS;           // the unified march (bhray_step_u.inc) in the contract kernels that do not count (the lensed-mesh kernels: the general step, whose ppos / pdir a paused lane keeps)
     constexpr bool ONE_TEST = UNIFIED && !MODELS && (((BHRAY_ONE_TEST & 1) != 0 && !DENSE) || ((BHRAY_ONE_TEST & 2) != 0 && DENSE));
     // the RK step's error estimate behind a wave-uniform bound (next_ray_rk_t): 0 the full text, 1 skipped where the bound holds, 2 the full text and the bound's counters
     constexpr int ERR_SKIP = (METHOD != 1 || EVAL != 0 || BHRAY_ERR_SKIP == 0) ? 0 : COUNT ? 2
@@ -1415,6 +1429,10 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
     uint32_t* __restrict__ qhead = F.qctl + 1;
     Counters64* __restrict__ counters = F.counters;
     [[maybe_unused]] float4* __restrict__ records = RECORDS ? reinterpret_cast<float4*>(F.row_work) : nullptr;      // (RECORDS: row_work holds the n records; see the template's comment)
+    // (PATHS: the points, the counts, s and max_points in members a ray-list launch does not read otherwise; see the template's comment)
+    [[maybe_unused]] float4* __restrict__ path_points = PATHS ? reinterpret_cast<float4*>(F.need) : nullptr;
+    [[maybe_unused]] uint32_t* __restrict__ path_counts = PATHS ? const_cast<uint32_t*>(F.stamp) : nullptr;
+    [[maybe_unused]] const uint32_t path_s = PATHS ? (uint32_t)F.radius : 0u, path_max = PATHS ? F.stamp_value : 0u;
     const uint32_t qcount = F.qctl[0];
     // A queue that is (nearly) used up when this wave arrives is seen with a plain load, before any atomic: 4 096 waves hitting one
     // word with failing atomics cost ~50 us per launch (11-13 ns each) - what an empty queue (a fix-up launch of the temporal mode)
@@ -1550,7 +1568,9 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                             records[2 * (size_t)idx] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float((uint32_t)BHRAY_HIT_UNUSABLE));
                             records[2 * (size_t)idx + 1] = make_float4(__int_as_float(-1), 0.0f, 0.0f, 0.0f);
                         }
+                        if constexpr (PATHS) path_counts[idx] = 0u;             // no point
                     } else {
+                        if constexpr (PATHS) path_points[(size_t)idx * path_max] = make_float4(org.x, org.y, org.z, 0.0f);     // point 0: (origin, 0) - max_points >= 2
                         cold.set_pix(idx);
                         cold.set_rdir(rdir);
                         cpos = org; cdir = rdir; ppos = org; pdir = rdir;
@@ -1686,7 +1706,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                 if constexpr (RECORDS) { if (!HIT_GET()) record_first_hit(records, cold.pix(), cpos, (uint32_t)BHRAY_HIT_DISK, -1); }
                 HIT_SET(1);
                 if (amount < 0.005f) mode = M_FINISH;
-                else { it++; mode = (mode == M_SHADE_FLAT) ? M_FLAT : M_REL; }
+                else { it++; mode = (mode == M_SHADE_FLAT) ? M_FLAT : M_REL; if constexpr (PATHS) path_sample(path_points, cold.pix(), path_s, path_max, cpos, it); }
             }
         }
 
@@ -1852,7 +1872,8 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                             }
                             HIT_SET(1);
                         }
-                        if (amount < 0.005f) mode = M_FINISH; else it++;
+                        if (amount < 0.005f) mode = M_FINISH;
+                        else { it++; if constexpr (PATHS) path_sample(path_points, cold.pix(), path_s, path_max, cpos, it); }
                     }
                 }
             }
@@ -1910,6 +1931,12 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                             rec[0] = make_float4(cpos.x, cpos.y, cpos.z, __uint_as_float((uint32_t)BHRAY_HIT_NONE));
                             rec[1] = make_float4(__int_as_float(-1), __int_as_float(it), closest, amount);
                         }
+                    }
+                    if constexpr (PATHS) {
+                        // the end point: curr.position and i where the loop ended, always, at k = (i >> s) + 1; the count whatever the row holds
+                        const uint32_t k = ((uint32_t)it >> path_s) + 1u;
+                        if (k < path_max) path_points[(size_t)pix * path_max + k] = make_float4(cpos.x, cpos.y, cpos.z, __int_as_float(it));
+                        path_counts[pix] = k + 1u;
                     }
                 } else {
                     const int ox = (int)(pix & 0x7fffu), oy = (int)((pix >> 15) & 0x7fffu);
@@ -2190,7 +2217,7 @@ hipError_t launch_classify(const FrameParams* Pb, const FrameLaunch* Fb, int nb,
 }
 
 // Which builds of trace_kernel<METHOD, MODELS, COUNT, DENSE, EVAL, ORIGIN, LENSED> exist (16 x 2 integrators general builds + 2 x 2 ORIGIN builds + 2 x 2 lensed-mesh builds
-// + 2 x 2 ray-list builds + 2 x 2 record builds = 48 instantiations; 44 before the records, 40 before the ray lists, 36 in round 11, 32 in round 9, 48 in round 5, 72 in round 3).
+// + 2 x 2 ray-list builds + 2 x 2 record builds + 2 x 2 path builds = 52 instantiations; 48 before the paths, 44 before the records, 40 before the ray lists, 36 in round 11, 32 in round 9, 48 in round 5, 72 in round 3).
 // eval: 0 the numerics contract, 1 BHRAY_F_LITERAL, 2 BHRAY_F_EVAL_FMA.  Every variant has a build for lone launches (the latency build);
 // the build for a saturated device (dense) exists where throughput is reported: not for counting kernels (BHRAY_F_COUNTERS is a diagnosis
 // mode: the same counts whichever build marches) and, of the two measurement-only evaluations, not for the mesh variant.  A launch that
@@ -2204,7 +2231,7 @@ constexpr bool trace_variant_exists(int eval, bool models, bool dense, bool coun
 // latency build, counting or not) and what a launch gets that asks for a build that does not exist: trace_resolve (bhray_internal.h).  The builds instantiated are the variants
 // that resolve to themselves.  The loop order is the order the kernels stand in the code object (lensed first, then per integrator the evaluations 1, 2, 0, mesh / counting /
 // ORIGIN / dense before their opposites): kept, so the object does not change.
-struct TraceBuilds { int n; TraceVariant v[48]; };
+struct TraceBuilds { int n; TraceVariant v[52]; };
 constexpr TraceBuilds trace_builds() {
     TraceBuilds t{};
     for (int lensed = 1; lensed >= 0; lensed--) for (int method = 0; method < 2; method++) for (int e = 1; e <= 3; e++) for (int mesh = 1; mesh >= lensed; mesh--)
@@ -2222,10 +2249,15 @@ constexpr TraceBuilds trace_builds() {
         const TraceVariant v{method, mesh, false, false, 0, false, true, true};
         if (trace_resolve(v) == v) t.v[t.n++] = v;
     }
+    // the path kernels (trace_kernel's PATHS): the same four once more, behind them
+    for (int method = 0; method < 2; method++) for (int mesh = 1; mesh >= 0; mesh--) {
+        const TraceVariant v{method, mesh, false, false, 0, false, true, true, true};
+        if (trace_resolve(v) == v) t.v[t.n++] = v;
+    }
     return t;
 }
 constexpr TraceBuilds TRACE_BUILDS = trace_builds();
-static_assert(TRACE_BUILDS.n == 36 + (BHRAY_ORIGIN_KERNEL != 0 && BHRAY_UNIFIED != 0 ? 4 : 0) + 4 + 4, "instantiations of trace_kernel (the last eight: the ray-list kernels, then the record kernels)");
+static_assert(TRACE_BUILDS.n == 36 + (BHRAY_ORIGIN_KERNEL != 0 && BHRAY_UNIFIED != 0 ? 4 : 0) + 4 + 4 + 4, "instantiations of trace_kernel (the last twelve: the ray-list kernels, then the record kernels, then the path kernels)");
 constexpr bool trace_variant_exists_agrees() {     // trace_variant_exists is trace_resolve's rule for the dense builds
     for (int i = 0; i < 24; i++) {
         const TraceVariant v{0, i & 1, (i & 2) != 0, (i & 4) != 0, i >> 3, false};
@@ -2237,7 +2269,7 @@ static_assert(trace_variant_exists_agrees(), "trace_variant_exists / trace_resol
 template <int I>
 static const void* trace_kernel_at() {
     constexpr TraceVariant V = TRACE_BUILDS.v[I];
-    return (const void*)trace_kernel<V.method, V.models != 0, V.count, V.dense, V.eval, V.origin, V.models == 2, V.rays, V.records>;
+    return (const void*)trace_kernel<V.method, V.models != 0, V.count, V.dense, V.eval, V.origin, V.models == 2, V.rays, V.records, V.paths>;
 }
 template <int... I>
 static const void* trace_kernel_lookup(const TraceVariant& resolved, std::integer_sequence<int, I...>) {

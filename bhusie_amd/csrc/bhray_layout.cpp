@@ -67,6 +67,10 @@ static_assert(BHRAY_MAX_RAYS_PER_CALL == (1u << 26), "BHRAY_MAX_RAYS_PER_CALL");
 SZ(bhray_ray_record, 32);
 OFF(bhray_ray_record, position, 0); OFF(bhray_ray_record, hit, 12); OFF(bhray_ray_record, triangle, 16); OFF(bhray_ray_record, iterations, 20);
 OFF(bhray_ray_record, closest, 24); OFF(bhray_ray_record, transmittance, 28);
+// a point of bhray_trace_rays_paths: one 16-byte store of the path kernels
+SZ(bhray_path_point, 16);
+OFF(bhray_path_point, position, 0); OFF(bhray_path_point, iteration, 12);
+static_assert(BHRAY_MAX_PATH_STRIDE_LOG2 == 16 && BHRAY_MAX_PATH_POINTS_PER_CALL == (1u << 24), "BHRAY_MAX_PATH_*");
 static_assert(BHRAY_HIT_NONE == 0 && BHRAY_HIT_HORIZON == 1 && BHRAY_HIT_DISK == 2 && BHRAY_HIT_MESH == 3 && BHRAY_HIT_UNUSABLE == 255, "BHRAY_HIT_*");
 
 // not reference layouts, but ABI the bindings restate (bhusie_amd/layouts.py)

@@ -96,6 +96,8 @@
                     if (amount < 0.005f) { mode = M_FINISH; it--; }
                     }
                     }
+                    // PATHS: the count is final here - a lane that paused on the disk or finished took it back and left M_REL / M_FLAT; one that goes on (marching, or out of the sphere) keeps it
+                    if constexpr (PATHS) { if ((mode == M_REL) | (mode == M_FLAT)) path_sample(path_points, cold.pix(), path_s, path_max, cpos, it); }
                 }
             }
 #else
@@ -187,6 +189,8 @@
                     } else {
                         it++;
                     }
+                    // PATHS: as above - a lane that paused on the disk has left through `continue`, one that finished was not counted and is in M_FINISH
+                    if constexpr (PATHS) { if ((mode == M_REL) | (mode == M_FLAT)) path_sample(path_points, cold.pix(), path_s, path_max, cpos, it); }
                 }
             }
 #endif

@@ -1,7 +1,11 @@
 // bhray_render — minimal C++ host program over renderer.hpp: renders one frame of the reference's default scene
 // (camera (0,0,-19), hole at the origin, disk 2..10, R = 20; camera.rs:10-16, blackhole.rs:16-28) and writes the HDR frame
 // as raw little-endian f32 RGBA (row 0 = top).  Usage:
-//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--pick X Y]
+//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--pick X Y] [--path X Y [--path-stride S]]
+// --path X Y [--path-stride S]: after the frame, the pick line of pixel (X, Y) and then the light path behind it, one line per point - that pixel's pinhole ray through
+//   bhray_trace_rays_paths (Renderer::ray_path), a point every 2^S iterations (S = 0 by default) and the end point:
+//   ITERATION X Y Z
+// Not with --lensed-mesh, --devices or --panorama.
 // --pick X Y: after the frame, one line with the record of its pixel (X, Y) - that pixel's pinhole ray through bhray_trace_rays_records (Renderer::pick):
 //   pick X Y hit=none|horizon|disk|mesh model=M triangle=T position=PX PY PZ iterations=I closest=C transmittance=A
 // Not with --lensed-mesh, --devices or --panorama.
@@ -143,9 +147,9 @@ int main(int argc, char** argv) {
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
         return 0;
     }
-    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--pick X Y]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--pick X Y] [--path X Y [--path-stride S]]\n", argv[0]); return 2; }
     uint32_t bw = 72, bh = 41, levels = 4, disk = 256, pano_w = 0, pano_h = 0;
-    long pick_x = -1, pick_y = -1;
+    long pick_x = -1, pick_y = -1, path_x = -1, path_y = -1, path_stride = 0;
     bool rk = false, bvh_device = false, lensed = false, posed = false;
     float rotation[3] = {0.0f, 0.0f, 0.0f};
     std::vector<const char*> objs;
@@ -161,9 +165,12 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--lensed-mesh")) lensed = true;
         else if (!std::strcmp(argv[i], "--panorama") && i + 2 < argc) { pano_w = (uint32_t)std::atoi(argv[++i]); pano_h = (uint32_t)std::atoi(argv[++i]); if (pano_w < 1 || pano_h < 1) { std::fprintf(stderr, "--panorama needs W >= 1 and H >= 1\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--pick") && i + 2 < argc) { pick_x = std::atol(argv[++i]); pick_y = std::atol(argv[++i]); if (pick_x < 0 || pick_y < 0) { std::fprintf(stderr, "--pick needs X >= 0 and Y >= 0\n"); return 2; } }
+        else if (!std::strcmp(argv[i], "--path") && i + 2 < argc) { path_x = std::atol(argv[++i]); path_y = std::atol(argv[++i]); if (path_x < 0 || path_y < 0) { std::fprintf(stderr, "--path needs X >= 0 and Y >= 0\n"); return 2; } }
+        else if (!std::strcmp(argv[i], "--path-stride") && i + 1 < argc) { path_stride = std::atol(argv[++i]); if (path_stride < 0 || path_stride > BHRAY_MAX_PATH_STRIDE_LOG2) { std::fprintf(stderr, "--path-stride needs 0 <= S <= %d\n", BHRAY_MAX_PATH_STRIDE_LOG2); return 2; } }
         else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) { for (const char* p = argv[++i]; *p; ) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p) p++; } }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
+    if (path_x >= 0 && pano_w) { std::fprintf(stderr, "--path names a pixel of the pinhole frame: not with --panorama\n"); return 2; }
     if (pick_x >= 0 && pano_w) { std::fprintf(stderr, "--pick names a pixel of the pinhole frame: not with --panorama\n"); return 2; }
     if (posed && !bvh_device) { std::fprintf(stderr, "--pose needs --bvh device (a pose is applied to a tree built on the GPU)\n"); return 2; }
     try {
@@ -199,12 +206,17 @@ int main(int argc, char** argv) {
         std::fwrite(out.data(), sizeof(float), out.size(), f);
         std::fclose(f);
         std::printf("%ux%u\n", res.first, res.second);
-        if (pick_x >= 0) {
-            const bhray_ray_record p = r.pick((uint32_t)pick_x, (uint32_t)pick_y);
+        auto print_pick = [](long pick_x, long pick_y, const bhray_ray_record& p) {
             const uint32_t kind = p.hit & 0xffu;
             const char* name = kind == BHRAY_HIT_NONE ? "none" : kind == BHRAY_HIT_HORIZON ? "horizon" : kind == BHRAY_HIT_DISK ? "disk" : kind == BHRAY_HIT_MESH ? "mesh" : "unusable";
             std::printf("pick %ld %ld hit=%s model=%d triangle=%d position=%.9g %.9g %.9g iterations=%u closest=%.9g transmittance=%.9g\n", pick_x, pick_y, name,
                         kind == BHRAY_HIT_MESH ? (int)((p.hit >> 8) & 0xffu) : -1, (int)p.triangle, p.position[0], p.position[1], p.position[2], p.iterations, p.closest, p.transmittance);
+        };
+        if (pick_x >= 0) print_pick(pick_x, pick_y, r.pick((uint32_t)pick_x, (uint32_t)pick_y));
+        if (path_x >= 0) {
+            const auto path = r.ray_path((uint32_t)path_x, (uint32_t)path_y, (uint32_t)path_stride);
+            print_pick(path_x, path_y, path.record);
+            for (const bhray_path_point& q : path.points) std::printf("%u %.9g %.9g %.9g\n", q.iteration, q.position[0], q.position[1], q.position[2]);
         }
     } catch (const std::exception& e) {
         std::fprintf(stderr, "%s\n", e.what());

@@ -193,6 +193,20 @@ public:
         check(bhray_trace_rays_records(ctx_, rays.data(), (uint32_t)rays.size(), results ? results->data() : nullptr, records.data()), ctx_);
         return records;
     }
+    // ray paths (bhray_trace_rays_paths): trace_rays_records, and per ray the sampled curve the integrator walked - ray r's points at
+    // points[r * max_points + k], k < min(counts[r], max_points); counts[r] = (iterations >> stride_log2) + 2 whatever max_points is
+    struct RayPaths { std::vector<bhray_ray_record> records; std::vector<bhray_path_point> points; std::vector<uint32_t> counts; uint32_t max_points; };
+    RayPaths trace_rays_paths(const std::vector<bhray_ray>& rays, uint32_t stride_log2, uint32_t max_points, std::vector<float>* results = nullptr) {
+        RayPaths p;
+        p.max_points = max_points;
+        p.records.resize(rays.size());
+        p.points.resize(rays.size() * (size_t)max_points);
+        p.counts.resize(rays.size());
+        if (results) results->assign(rays.size() * 4, 0.0f);
+        check(bhray_trace_rays_paths(ctx_, rays.data(), (uint32_t)rays.size(), stride_log2, max_points, results ? results->data() : nullptr, p.records.data(),
+                                     p.points.data(), p.counts.data()), ctx_);
+        return p;
+    }
     bhray_ctx* ctx() { return ctx_; }
 private:
     bhray_config cfg_;
@@ -346,6 +360,22 @@ public:
         ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);
         apply_lensing();
         return ray_pipeline_.trace_rays_records({pinhole_ray(camera.position, camera.forward, camera.fov, res.first, res.second, x, y)})[0];
+    }
+    // the light path behind frame pixel (x, y): pick's record, and the points of that pixel's pinhole ray from the camera to where trace_ray's loop ended - one per
+    // 2^stride_log2 iterations and the end point; the row is sized from max_iterations, so nothing is dropped
+    struct RayPath { bhray_ray_record record; std::vector<bhray_path_point> points; };
+    RayPath ray_path(uint32_t x, uint32_t y, uint32_t stride_log2 = 0) {
+        const auto res = ray_pipeline_.resolution();
+        if (x >= res.first || y >= res.second) throw std::runtime_error("bhray: ray_path: the pixel lies outside the frame");
+        if (stride_log2 > BHRAY_MAX_PATH_STRIDE_LOG2) throw std::runtime_error("bhray: ray_path: the stride's logarithm is at most 16");
+        ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);
+        apply_lensing();
+        const uint32_t max_points = ((uint32_t)ray_details.max_iterations >> stride_log2) + 2u;
+        auto p = ray_pipeline_.trace_rays_paths({pinhole_ray(camera.position, camera.forward, camera.fov, res.first, res.second, x, y)}, stride_log2, max_points);
+        RayPath out;
+        out.record = p.records[0];
+        out.points.assign(p.points.begin(), p.points.begin() + (p.counts[0] < max_points ? p.counts[0] : max_points));
+        return out;
     }
 private:
     void apply_lensing() { if (mesh_lensing != lensing_applied_) { ray_pipeline_.set_mesh_lensing(mesh_lensing); lensing_applied_ = mesh_lensing; } }

@@ -79,6 +79,16 @@ class BhrayRayRecord(C.Structure):          # bhray_ray_record: what bhray_trace
                 ("closest", C.c_float), ("transmittance", C.c_float)]
 
 
+class BhrayPathPoint(C.Structure):          # bhray_path_point: one sample of a ray's path (bhray_trace_rays_paths), 16 bytes
+    _fields_ = [("position", C.c_float * 3), ("iteration", C.c_uint32)]
+
+
+# bhray_path_point as a NumPy structured type (numpy is imported here only for this: the package's other array types live in renderer.py / model.py)
+import numpy as _np  # noqa: E402
+PATH_POINT_DTYPE = _np.dtype([("position", _np.float32, 3), ("iteration", _np.uint32)])
+assert PATH_POINT_DTYPE.itemsize == C.sizeof(BhrayPathPoint) == 16
+MAX_PATH_STRIDE_LOG2 = 16                   # BHRAY_MAX_PATH_STRIDE_LOG2
+MAX_PATH_POINTS_PER_CALL = 1 << 24          # BHRAY_MAX_PATH_POINTS_PER_CALL
 HIT_NONE, HIT_HORIZON, HIT_DISK, HIT_MESH, HIT_UNUSABLE = 0, 1, 2, 3, 255      # BHRAY_HIT_*: bits 0-7 of bhray_ray_record.hit (bits 8-15: the model slot of a MESH hit)
 
 
@@ -150,6 +160,7 @@ class BhrayModelBuildInfo(C.Structure):
 assert C.sizeof(BhrayDetails) == 32 and C.sizeof(BhrayCameraUniform) == 32 and C.sizeof(BhrayBlackHoleUniform) == 132
 assert C.sizeof(BhrayNode) == 32 and C.sizeof(BhrayTriangle) == 24
 assert C.sizeof(BhrayRay) == 32 and BhrayRay.direction.offset == 16
+assert C.sizeof(BhrayPathPoint) == 16 and BhrayPathPoint.iteration.offset == 12
 assert C.sizeof(BhrayRayRecord) == 32 and BhrayRayRecord.hit.offset == 12 and BhrayRayRecord.triangle.offset == 16 and BhrayRayRecord.transmittance.offset == 28
 
 LEVEL_GRID_LAUNCHES = MAX_LEVELS + 2
@@ -226,6 +237,8 @@ SYMBOLS = {
     "bhray_trace_rays_sky": (C.c_int, [vp, P(BhrayRay), u32, P(C.c_float), vp]),
     "bhray_trace_rays_records": (C.c_int, [vp, P(BhrayRay), u32, P(C.c_float), P(BhrayRayRecord)]),
     "bhray_trace_rays_records_device": (C.c_int, [vp, vp, u32, vp, vp, vp]),
+    "bhray_trace_rays_paths": (C.c_int, [vp, P(BhrayRay), u32, u32, u32, P(C.c_float), P(BhrayRayRecord), P(BhrayPathPoint), P(C.c_uint32)]),
+    "bhray_trace_rays_paths_device": (C.c_int, [vp, vp, u32, u32, u32, vp, vp, vp, vp, vp]),
     "bhray_render": (C.c_int, [vp]),
     "bhray_flush": (C.c_int, [vp]),
     "bhray_sync": (C.c_int, [vp]),

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import lib
-from .layouts import (BhrayFxaaDetails, BhrayMixDetails, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters, BhrayRay, BhrayRayRecord, HIT_MESH, HIT_UNUSABLE,
+from .layouts import (BhrayFxaaDetails, BhrayMixDetails, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters, BhrayRay, BhrayRayRecord, BhrayPathPoint, PATH_POINT_DTYPE, HIT_MESH, HIT_UNUSABLE,
                       BhrayGatherInfo, BhrayModelBuildInfo, BhrayModelDesc, BhrayRebalanceInfo, BhrayTiming, check)
 from .model import NODE_DTYPE, Model
 from .scene import BlackHole, Camera, RayDetails
@@ -367,6 +367,32 @@ class RayPass:
         check(self._L.bhray_trace_rays_records_device(self._h, C.c_void_p(d_rays), int(n), C.c_void_p(d_out), C.c_void_p(d_records),
                                                       C.c_void_p(stream) if stream else None), self._h, self._L)
 
+    # -- ray paths (bhray_trace_rays_paths)
+    def trace_rays_paths(self, rays, stride_log2: int = 0, max_points: int = 1024):
+        """trace_rays_records, and per ray the curve the integrator walked, sampled every 2**stride_log2 iterations: (results, records, points, counts) - points an
+        (n, max_points) structured array (PATH_POINT_DTYPE: position, iteration), counts (n,) uint32.  Row r holds the origin (iteration 0), the sampled steps and the
+        end point - min(counts[r], max_points) points, the rest zero; counts[r] = (iterations >> stride_log2) + 2 whatever max_points is, so counts[r] > max_points says
+        that the row is cut short: ask again with a larger stride."""
+        rec = self._ray_records(rays)
+        n = rec.shape[0]
+        out = np.zeros((n, 4), dtype=np.float32)
+        records = np.zeros(n, dtype=RAY_RECORD_DTYPE)
+        points = np.zeros((n, int(max_points)), dtype=PATH_POINT_DTYPE)
+        counts = np.zeros(n, dtype=np.uint32)
+        check(self._L.bhray_trace_rays_paths(self._h, rec.ctypes.data_as(C.POINTER(BhrayRay)) if n else None, n, int(stride_log2), int(max_points),
+                                             out.ctypes.data_as(C.POINTER(C.c_float)) if n else None,
+                                             records.ctypes.data_as(C.POINTER(BhrayRayRecord)) if n else None,
+                                             points.ctypes.data_as(C.POINTER(BhrayPathPoint)) if n else None,
+                                             counts.ctypes.data_as(C.POINTER(C.c_uint32)) if n else None), self._h, self._L)
+        return out, records, points, counts
+
+    def trace_rays_paths_device(self, d_rays: int, n: int, stride_log2: int, max_points: int, d_out: int, d_records: int, d_points: int, d_counts: int,
+                                stream: int | None = None):
+        """The device form (trace_rays_records_device's rules): also n * max_points points of 16 bytes at the 16-byte aligned device address d_points and n counts at
+        d_counts.  Slots behind a ray's last point are not written; an unusable ray gets count 0 and no point (bhray_trace_rays_paths_device)."""
+        check(self._L.bhray_trace_rays_paths_device(self._h, C.c_void_p(d_rays), int(n), int(stride_log2), int(max_points), C.c_void_p(d_out), C.c_void_p(d_records),
+                                                    C.c_void_p(d_points), C.c_void_p(d_counts), C.c_void_p(stream) if stream else None), self._h, self._L)
+
     # -- per frame
     def set_uniforms(self, camera: bytes, black_hole: bytes, details: bytes):
         assert len(camera) == 32 and len(black_hole) == 132 and len(details) == 32
@@ -698,6 +724,24 @@ class Renderer:
         return {"hit": kind, "model": (int(r["hit"]) >> 8) & 0xFF if kind == HIT_MESH else None, "triangle": int(r["triangle"]),
                 "position": tuple(float(v) for v in r["position"]), "iterations": int(r["iterations"]),
                 "closest": float(r["closest"]), "transmittance": float(r["transmittance"])}
+
+    def ray_path(self, x: int, y: int, stride_log2: int = 0) -> dict:
+        """The light path behind frame pixel (x, y): pick's dictionary, and `path` - a (k, 3) float32 array, the points of that pixel's pinhole ray from the camera to where
+        trace_ray's loop ended, one per 2**stride_log2 iterations and the end point - and `path_iterations`, (k,) uint32: the iteration each point belongs to.  The row
+        is sized from max_iterations, so nothing is dropped."""
+        fw, fh = int(self.ray_pass.cfg.frame_w), int(self.ray_pass.cfg.frame_h)
+        if not (0 <= int(x) < fw and 0 <= int(y) < fh):
+            raise ValueError(f"ray_path: pixel ({x}, {y}) lies outside the {fw}x{fh} frame")
+        self._apply_uniforms()
+        max_points = (int(self.ray_details.max_iterations) >> int(stride_log2)) + 2
+        _, rec, pts, cnt = self.ray_pass.trace_rays_paths(pinhole_rays(self.camera, fw, fh, pixel=(int(x), int(y))), stride_log2, max_points)
+        r, k = rec[0], int(cnt[0])
+        assert k <= max_points
+        kind = int(r["hit"]) & 0xFF
+        return {"hit": kind, "model": (int(r["hit"]) >> 8) & 0xFF if kind == HIT_MESH else None, "triangle": int(r["triangle"]),
+                "position": tuple(float(v) for v in r["position"]), "iterations": int(r["iterations"]),
+                "closest": float(r["closest"]), "transmittance": float(r["transmittance"]),
+                "path": pts["position"][0, :k].copy(), "path_iterations": pts["iteration"][0, :k].copy()}
 
     def save_image(self, path):
         """The reference's Save Image (mod.rs:473-482): the display pass's RGBA8 image of the last frame, written with alpha 255

@@ -496,7 +496,7 @@ int bhray_trace_rays_sky(bhray_ctx* ctx, const bhray_ray* rays, uint32_t n, floa
  * must be 16-byte aligned (BHRAY_E_INVALID).  The device form answers an unusable ray with hit = BHRAY_HIT_UNUSABLE,
  * triangle = -1 and every other word zero, beside the result (0, 0, 0, -1).
  * Not built: records under mesh lensing, on a ctx with device_count >= 2 (both BHRAY_E_STATE, as bhray_trace_rays), and
- * for the pixels of a ladder frame (copied and interpolated pixels have no ray); the path length is not recorded.     */
+ * for the pixels of a ladder frame (copied and interpolated pixels have no ray); the path length is not recorded (the path: below). */
 enum { BHRAY_HIT_NONE = 0, BHRAY_HIT_HORIZON = 1, BHRAY_HIT_DISK = 2, BHRAY_HIT_MESH = 3, BHRAY_HIT_UNUSABLE = 255 };
 typedef struct bhray_ray_record {
     float    position[3];
@@ -508,6 +508,36 @@ typedef struct bhray_ray_record {
 } bhray_ray_record;          /* 32 bytes, two 16-byte halves */
 int bhray_trace_rays_records(bhray_ctx* ctx, const bhray_ray* rays, uint32_t n, float* out_rgba32f /* may be NULL */, bhray_ray_record* out_records);
 int bhray_trace_rays_records_device(bhray_ctx* ctx, const void* d_rays, uint32_t n, void* d_out_rgba32f, void* d_records, void* hip_stream);
+
+/* Ray paths (not in the reference): bhray_trace_rays_records, and per ray the curve the integrator
+ * walked, sampled every 2^stride_log2 iterations.  In terms of trace_ray's loop (ray.wgsl), with s = stride_log2, ray
+ * r's points lie at points[r * max_points + k]:
+ *   k = 0                 (origin, 0)
+ *   a sampled step        whenever the loop executes its i++ (a body ended and the ray goes on) and the new i is a
+ *                         multiple of 2^s: (curr.position, i) at k = i >> s - curr.position at that moment, i.e. after
+ *                         curr + prev.direction * t on a hit and after the move to the sphere's surface on an entry
+ *   the end point         when the loop ends, by any break or by the iteration limit: (curr.position, i) at
+ *                         k = (i >> s) + 1, always, even where it repeats the point before it; its iteration is the
+ *                         record's `iterations`, and for a BHRAY_HIT_NONE ray its position is the record's `position`
+ *   counts[r]             (iterations >> s) + 2, whatever max_points is.  A point with k >= max_points is not stored: a
+ *                         caller that sees counts[r] > max_points asks again with a larger stride.
+ * Slots k >= min(counts[r], max_points) of a ray's row are not written by the device form; the host form returns them
+ * as zero bytes.  The device form answers an unusable ray with counts[r] = 0 and no point, beside the record and result
+ * of bhray_trace_rays_records_device.  Results and records are bit for bit bhray_trace_rays_records' for the same rays,
+ * and every rule of bhray_trace_rays / bhray_trace_rays_records holds unchanged (the refused states, the limits on n,
+ * n == 0, the synchronisation, BHRAY_F_COUNTERS).  BHRAY_E_INVALID, nothing enqueued and no output touched:
+ * max_points < 2; stride_log2 > BHRAY_MAX_PATH_STRIDE_LOG2; n * max_points > BHRAY_MAX_PATH_POINTS_PER_CALL; for
+ * n != 0 a NULL out_points / out_counts (out_rgba32f and out_records of the host form may be NULL); in the device form
+ * a NULL d_out_rgba32f / d_records, a d_points or d_records that is not 16-byte aligned, a d_counts that is not 4-byte
+ * aligned.  Not built: paths under mesh lensing or on a ctx with device_count >= 2 (BHRAY_E_STATE, as above).         */
+typedef struct bhray_path_point { float position[3]; uint32_t iteration; } bhray_path_point;   /* 16 bytes */
+#define BHRAY_MAX_PATH_STRIDE_LOG2     16
+#define BHRAY_MAX_PATH_POINTS_PER_CALL (1u << 24)      /* n * max_points: 256 MiB of points */
+int bhray_trace_rays_paths(bhray_ctx* ctx, const bhray_ray* rays, uint32_t n, uint32_t stride_log2, uint32_t max_points,
+                           float* out_rgba32f /* may be NULL */, bhray_ray_record* out_records /* may be NULL */,
+                           bhray_path_point* out_points /* n * max_points */, uint32_t* out_counts /* n */);
+int bhray_trace_rays_paths_device(bhray_ctx* ctx, const void* d_rays, uint32_t n, uint32_t stride_log2, uint32_t max_points,
+                                  void* d_out_rgba32f, void* d_records, void* d_points, void* d_counts, void* hip_stream);
 
 /* Dispatch — replaces `for rp in ray_pipelines { rp.pass() }` (mod.rs:415-417,
  * ray_pipeline.rs:301-309).  Asynchronous on the ctx stream; levels ordered.                 */
