@@ -92,18 +92,32 @@ def _camera_fields(camera):
     return u[0:3].copy(), u[4:7].copy(), F(u[7])
 
 
-def pinhole_rays(camera, w: int, h: int, pixel=None) -> np.ndarray:
+def r2_offset(s: int):
+    """(dx, dy) of sample s of the accumulation image (bhray_accum_sample_offset): the R2 sequence in 32-bit integer arithmetic, cut to 24 bits so
+    that every step is exact in binary32.  Sample 0: (0, 0), the pixel centre; every offset lies in [-0.5, 0.5)."""
+    s = int(s)
+    u = (0x80000000 + s * 0xC13FA9A9) & 0xFFFFFFFF
+    v = (0x80000000 + s * 0x91E10DA5) & 0xFFFFFFFF
+    return F(F(F(u >> 8) * F(2.0 ** -24)) - F(0.5)), F(F(F(v >> 8) * F(2.0 ** -24)) - F(0.5))
+
+
+def pinhole_rays(camera, w: int, h: int, pixel=None, offset=(0.0, 0.0), level=None, crop=(0, 0)) -> np.ndarray:
     """create_ray for every pixel of a w x h level (ray.wgsl:269-285).  pixel=(x, y): that one pixel's ray only, as a (1, 8) array - the same
-    arithmetic, so the same bits as row y * w + x of the whole level (Renderer.pick)."""
+    arithmetic, so the same bits as row y * w + x of the whole level (Renderer.pick).
+    offset=(dx, dy): the rays through (x + dx, y + dy) instead of the pixel centres, one rounded add per coordinate (r2_offset: the accumulation image's samples;
+    (0, 0) changes no bit).  level=(lw, lh), crop=(cx, cy): the w x h pixels are the window at (cx, cy) of an lw x lh level, whose geometry the rays take
+    (a cropped frame on its ladder's last level)."""
     w, h = int(w), int(h)
-    assert w >= 2 and h >= 2, "create_ray divides by min(w, h) - 1"
+    lw, lh = (w, h) if level is None else (int(level[0]), int(level[1]))
+    cx, cy = int(crop[0]), int(crop[1])
+    assert lw >= 2 and lh >= 2, "create_ray divides by min(w, h) - 1"
+    assert cx >= 0 and cy >= 0 and cx + w <= lw and cy + h <= lh, "pinhole_rays: the window leaves the level"
     pos, forward, fov = _camera_fields(camera)
     fwd, right, up = _basis(forward)
-    sm = min(w - 1, h - 1)
+    sm = min(lw - 1, lh - 1)
     increment = F(1.0) / F(sm)
-    px = np.arange(w, dtype=F)[None, :]
-    py = np.arange(h, dtype=F)[:, None]
-    lw, lh = w, h
+    px = (np.arange(cx, cx + w, dtype=F) + F(offset[0])).astype(F)[None, :]
+    py = (np.arange(cy, cy + h, dtype=F) + F(offset[1])).astype(F)[:, None]
     if pixel is not None:
         x, y = int(pixel[0]), int(pixel[1])
         assert 0 <= x < w and 0 <= y < h, "pinhole_rays: the pixel lies outside the level"

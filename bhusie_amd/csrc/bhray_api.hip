@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "bhray_accum.h"
 #include "bhray_bvh_core.h"
 #include "bhray_dev.h"
 #include "bhray_internal.h"
@@ -208,6 +209,14 @@ struct bhray_dev {
     bhray_path_point* q_hpts = nullptr; bhray_path_point* q_dpts = nullptr;      // the paths' staging (bhray_trace_rays_paths): grow-only, allocated by the first paths batch
     uint32_t* q_hcnt = nullptr; uint32_t* q_dcnt = nullptr;
     size_t q_pts_cap = 0, q_cnt_cap = 0;   // points / rays the staging holds
+    // the accumulation image (dev_accum_*): allocated by the first dev_accum_begin; everything runs on q_stream
+    float4* a_sum = nullptr; float4* a_mean = nullptr;       // frame_w * frame_h each: (sum of colours, samples taken), and the mean of the last read
+    uint2* a_mean16 = nullptr; uint2* a_scratch = nullptr; uint32_t* a_disp = nullptr;   // the display read: the mean as RGBA16F, the display pass's scratch, its RGBA8 image (first dev_accum_read_display)
+    float4* a_rays = nullptr; float4* a_res = nullptr;       // one launch's generated records (2 float4 each) and results: grow-only (the stream is idle when they grow)
+    size_t a_cap = 0;                      // rays that staging holds
+    uint32_t a_samples = 0;                // sample indices enqueued since the last begin: the next add starts there
+    uint32_t a_launch_rays = 0;            // dev_accum_set_launch_rays: rays per trace launch (0: BHRAY_ACCUM_LAUNCH_RAYS)
+    bool a_begun = false;
     bhray::ReadRing reads;                 // tickets of the asynchronous hand-off (dev_read_async)
     std::string err;
 };
@@ -429,6 +438,7 @@ void dev_destroy(bhray_dev* c) {
     if (c->q_dpts) (void)hipFree(c->q_dpts);
     if (c->q_hcnt) (void)hipHostFree(c->q_hcnt);
     if (c->q_dcnt) (void)hipFree(c->q_dcnt);
+    for (void* p : {(void*)c->a_sum, (void*)c->a_mean, (void*)c->a_mean16, (void*)c->a_scratch, (void*)c->a_disp, (void*)c->a_rays, (void*)c->a_res}) if (p) (void)hipFree(p);
     for (hipEvent_t e : {c->q_begin, c->q_done, c->q_uploaded}) if (e) (void)hipEventDestroy(e);
     if (c->q_stream) (void)hipStreamDestroy(c->q_stream);
     for (Slot& S : c->slots) {
@@ -1285,6 +1295,166 @@ int dev_trace_rays_device(bhray_dev* c, const void* d_rays, uint32_t n, void* d_
     { int rc = enqueue_rays(c, (const float4*)d_rays, n, (float4*)d_out, d_records, paths ? &pa : nullptr); if (rc) return rc; }
     HIPCHK(c, hipEventRecord(c->q_done, c->q_stream));            // ... and what `s` gets from now on starts behind the batch
     HIPCHK(c, hipStreamWaitEvent(s, c->q_done, 0));
+    return BHRAY_OK;
+}
+
+// ---- the accumulation image (include/bhray.h: bhray_accum_*) ----------------------------------------------------
+// Sub-pixel samples of every frame pixel, generated, traced (enqueue_rays: the ray-list kernels), resolved and summed on the query stream, so whatever waits for
+// the ray batches (sync_all, dev_destroy) waits for the accumulation too.
+namespace {
+constexpr uint32_t ACCUM_LAUNCH_RAYS = 1u << 22;                  // rays per trace launch unless dev_accum_set_launch_rays says otherwise
+int display_whole_frame(bhray_dev* c);                            // (with the frame images, below)
+
+// what a ctx is created with and keeps: refused by every accumulation call
+int accum_refused(bhray_dev* c, const char* name) {
+    if (c->cfg.flags & (BHRAY_F_LITERAL | BHRAY_F_EVAL_FMA)) return fail(c, BHRAY_E_STATE, "%s: no ray-list kernel for BHRAY_F_LITERAL / BHRAY_F_EVAL_FMA", name);
+    if (c->cfg.row_world > 1 || c->local_rows.size() != (size_t)c->cfg.frame_h)
+        return fail(c, BHRAY_E_STATE, "%s: the accumulation needs the whole frame: this ctx renders %zu of %u rows", name, c->local_rows.size(), c->cfg.frame_h);
+    return BHRAY_OK;
+}
+
+// the query stream's work is complete, and the kernels' error word as dev_sync reads it for the frames
+int query_wait(bhray_dev* c) {
+    HIPCHK(c, hipStreamSynchronize(c->q_stream));
+    int e = 0;
+    HIPCHK(c, hipMemcpy(&e, c->d_err, sizeof e, hipMemcpyDeviceToHost));
+    if (e != 0) {
+        HIPCHK(c, hipMemset(c->d_err, 0, sizeof(int)));
+        return fail(c, e, "kernel reported: %s", bhray_strerror(e));
+    }
+    return BHRAY_OK;
+}
+
+// the generator's arguments under the current uniforms: the camera members of a frame's FrameParams, the last level's constants with create_ray's operations
+void accum_gen_args(bhray_dev* c, AccumGen& g) {
+    FrameParams P;
+    derive_frame(c, P);
+    memset(&g, 0, sizeof g);
+    memcpy(g.cam, P.cam, 12); memcpy(g.right, P.right, 12); memcpy(g.up, P.up, 12); memcpy(g.fwd_ff, P.fwd_ff, 12);
+    const int lw = (int)c->cfg.level_w[c->cfg.levels - 1], lh = (int)c->cfg.level_h[c->cfg.levels - 1];
+    const int sm = (lw - 1) < (lh - 1) ? (lw - 1) : (lh - 1);
+    g.half_w = (float)(lw - 1) * 0.5f; g.half_h = (float)(lh - 1) * 0.5f;
+    g.increment = 1.0f / (float)sm;
+    g.crop_x = c->cfg.crop_x; g.crop_y = c->cfg.crop_y; g.frame_w = c->cfg.frame_w;
+    g.npix = c->cfg.frame_w * c->cfg.frame_h;
+}
+}  // namespace
+
+int dev_accum_begin(bhray_dev* c) {
+    if (!c) return BHRAY_E_INVALID;
+    { int rc = accum_refused(c, "bhray_accum_begin"); if (rc) return rc; }
+    const size_t npix = (size_t)c->cfg.frame_w * c->cfg.frame_h;
+    if (npix > BHRAY_MAX_RAYS_PER_CALL) return fail(c, BHRAY_E_INVALID, "bhray_accum_begin: the frame has more pixels than a ray batch holds");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = ensure_query(c); if (rc) return rc; }
+    if (!c->a_sum) HIPCHK(c, hipMalloc(&c->a_sum, npix * sizeof(float4)));
+    if (!c->a_mean) HIPCHK(c, hipMalloc(&c->a_mean, npix * sizeof(float4)));
+    HIPCHK(c, hipMemsetAsync(c->a_sum, 0, npix * sizeof(float4), c->q_stream));          // behind the samples of the accumulation before
+    c->a_samples = 0;
+    c->a_begun = true;
+    return BHRAY_OK;
+}
+
+int dev_accum_add(bhray_dev* c, uint32_t samples) {
+    if (!c) return BHRAY_E_INVALID;
+    if (!c->a_begun) return fail(c, BHRAY_E_STATE, "bhray_accum_add: bhray_accum_begin has not been called");
+    { int rc = accum_refused(c, "bhray_accum_add"); if (rc) return rc; }
+    { int rc = rays_refused(c, "bhray_accum_add"); if (rc) return rc; }
+    if (samples > BHRAY_ACCUM_MAX_SAMPLES - c->a_samples)
+        return fail(c, BHRAY_E_INVALID, "bhray_accum_add: %u + %u samples exceed BHRAY_ACCUM_MAX_SAMPLES", c->a_samples, samples);
+    if (samples == 0) return BHRAY_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = launch_batch(c); if (rc) return rc; }              // the staged frames first: they keep the uniforms they were staged with
+    { int rc = ensure_query(c); if (rc) return rc; }
+    AccumGen g;
+    accum_gen_args(c, g);
+    const uint32_t launch_rays = c->a_launch_rays ? c->a_launch_rays : ACCUM_LAUNCH_RAYS;
+    const uint32_t kmax = std::max<uint32_t>(1u, launch_rays / g.npix);                   // a small frame takes several samples per launch: the device stays filled
+    const size_t need = (size_t)std::min(samples, kmax) * g.npix;
+    if (need > c->a_cap) {                                        // grow-only staging
+        HIPCHK(c, hipStreamSynchronize(c->q_stream));
+        if (c->a_rays) (void)hipFree(c->a_rays);
+        if (c->a_res) (void)hipFree(c->a_res);
+        c->a_rays = c->a_res = nullptr; c->a_cap = 0;
+        HIPCHK(c, hipMalloc(&c->a_rays, need * sizeof(bhray_ray)));
+        HIPCHK(c, hipMalloc(&c->a_res, need * sizeof(float4)));
+        c->a_cap = need;
+    }
+    TexDev sky; sky.rgba = c->tex[BHRAY_TEX_SKY]; sky.w = c->tex_w[BHRAY_TEX_SKY]; sky.h = c->tex_h[BHRAY_TEX_SKY];
+    for (uint32_t left = samples; left != 0;) {                   // in stream order: launch i + 1 rewrites the staging behind launch i's add
+        const uint32_t k = std::min(left, kmax);
+        g.s0 = c->a_samples; g.k = k;
+        HIPCHK(c, launch_accum_gen(g, c->a_rays, c->q_stream));
+        { int rc = enqueue_rays(c, c->a_rays, k * g.npix, c->a_res); if (rc) return rc; }
+        HIPCHK(c, launch_accum_add(sky, c->a_res, c->a_sum, g.npix, k, c->q_stream));
+        c->a_samples += k; left -= k;
+    }
+    return BHRAY_OK;
+}
+
+int dev_accum_samples(const bhray_dev* c, uint32_t* total) {
+    if (!c || !total) return BHRAY_E_INVALID;
+    *total = c->a_samples;
+    return BHRAY_OK;
+}
+
+int dev_accum_read(bhray_dev* c, float* dst, size_t pitch) {
+    if (!c) return BHRAY_E_INVALID;
+    if (!c->a_begun) return fail(c, BHRAY_E_STATE, "bhray_accum_read: bhray_accum_begin has not been called");
+    const size_t rowb = (size_t)c->cfg.frame_w * sizeof(float4);
+    if (!dst || pitch < rowb) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_accum_mean(c->a_sum, c->a_mean, nullptr, c->cfg.frame_w * c->cfg.frame_h, c->q_stream));
+    { int rc = query_wait(c); if (rc) return rc; }
+    HIPCHK(c, hipMemcpy2D(dst, pitch, c->a_mean, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost));
+    return BHRAY_OK;
+}
+
+// mean -> RGBA16F -> the display pass (launch_display, unchanged) with the ctx's post uniforms -> RGBA8
+int dev_accum_read_display(bhray_dev* c, uint8_t* dst, size_t pitch, const bhray_fxaa_details* fx, const bhray_mix_details* mx) {
+    if (!c || !fx || !mx) return BHRAY_E_INVALID;
+    if (!c->a_begun) return fail(c, BHRAY_E_STATE, "bhray_accum_read_display: bhray_accum_begin has not been called");
+    { int rc = display_whole_frame(c); if (rc) return rc; }
+    const size_t rowb = (size_t)c->cfg.frame_w * sizeof(uint32_t);
+    if (!dst || pitch < rowb) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint32_t npix = c->cfg.frame_w * c->cfg.frame_h;
+    if (!c->a_mean16) HIPCHK(c, hipMalloc(&c->a_mean16, (size_t)npix * sizeof(uint2)));
+    if (!c->a_scratch) HIPCHK(c, hipMalloc(&c->a_scratch, display_scratch_bytes(c->cfg.frame_w, c->cfg.frame_h)));
+    if (!c->a_disp) HIPCHK(c, hipMalloc(&c->a_disp, (size_t)npix * sizeof(uint32_t)));
+    HIPCHK(c, launch_accum_mean(c->a_sum, c->a_mean, c->a_mean16, npix, c->q_stream));
+    HIPCHK(c, launch_display(c->a_mean16, c->a_scratch, c->a_disp, c->cfg.frame_w, c->cfg.frame_h, *fx, *mx, c->q_stream));
+    { int rc = query_wait(c); if (rc) return rc; }
+    HIPCHK(c, hipMemcpy2D(dst, pitch, c->a_disp, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost));
+    return BHRAY_OK;
+}
+
+// bhray_diag.h: the generated records of sample s under the current uniforms, frame_w * frame_h of them
+int dev_accum_sample_rays(bhray_dev* c, uint32_t s, bhray_ray* out) {
+    if (!c) return BHRAY_E_INVALID;
+    if (!out || s >= BHRAY_ACCUM_MAX_SAMPLES) return fail(c, BHRAY_E_INVALID, "bhray_accum_sample_rays: bad arguments");
+    { int rc = accum_refused(c, "bhray_accum_sample_rays"); if (rc) return rc; }
+    if (!c->have_uniforms) return fail(c, BHRAY_E_STATE, "bhray_accum_sample_rays: bhray_set_uniforms has not been called");
+    AccumGen g;
+    accum_gen_args(c, g);
+    if (g.npix > BHRAY_MAX_RAYS_PER_CALL) return fail(c, BHRAY_E_INVALID, "bhray_accum_sample_rays: the frame has more pixels than a ray batch holds");
+    g.s0 = s; g.k = 1;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = ensure_query(c); if (rc) return rc; }
+    float4* d = nullptr;
+    HIPCHK(c, hipMalloc(&d, (size_t)g.npix * sizeof(bhray_ray)));
+    hipError_t e = launch_accum_gen(g, d, c->q_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->q_stream);
+    if (e == hipSuccess) e = hipMemcpy(out, d, (size_t)g.npix * sizeof(bhray_ray), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIPCHK(c, e);
+    return BHRAY_OK;
+}
+
+int dev_accum_set_launch_rays(bhray_dev* c, uint32_t max_rays) {
+    if (!c) return BHRAY_E_INVALID;
+    if (max_rays > BHRAY_MAX_RAYS_PER_CALL) return fail(c, BHRAY_E_INVALID, "bhray_accum_set_launch_rays: more rays than a ray batch holds");
+    c->a_launch_rays = max_rays;
     return BHRAY_OK;
 }
 

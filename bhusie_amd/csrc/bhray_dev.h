@@ -118,6 +118,15 @@ struct bhray_dev_paths { uint32_t stride_log2, max_points; bhray_path_point* poi
 int  dev_trace_rays(bhray_dev* c, const bhray_ray* rays, uint32_t n, float* out_rgba32f, uint16_t* sky_rgba16f /* NULL: no sky pass over the results */, bhray_ray_record* records = nullptr,
                     const bhray_dev_paths* paths = nullptr);
 int  dev_trace_rays_device(bhray_dev* c, const void* d_rays, uint32_t n, void* d_out_rgba32f, void* d_records, hipStream_t s, const bhray_dev_paths* paths = nullptr);
+// the accumulation image: sub-pixel samples of every frame pixel generated, traced, resolved and summed on the query stream; begin clears, add enqueues
+// the next sample indices under the current uniforms, the reads wait.  fxaa / mix: the ctx's display uniforms
+int  dev_accum_begin(bhray_dev* c);
+int  dev_accum_add(bhray_dev* c, uint32_t samples);
+int  dev_accum_samples(const bhray_dev* c, uint32_t* total);
+int  dev_accum_read(bhray_dev* c, float* dst_rgba32f, size_t pitch);
+int  dev_accum_read_display(bhray_dev* c, uint8_t* dst_rgba8, size_t pitch, const bhray_fxaa_details* fxaa, const bhray_mix_details* mix);
+int  dev_accum_sample_rays(bhray_dev* c, uint32_t s, bhray_ray* out);   // the generated records of sample s: frame_w * frame_h
+int  dev_accum_set_launch_rays(bhray_dev* c, uint32_t max_rays);        // rays per trace launch of dev_accum_add; 0: the default
 int  dev_set_mesh_lensing(bhray_dev* c, int32_t on);       // from the next dev_render; BHRAY_E_STATE for on != 0 on a BHRAY_F_LITERAL / BHRAY_F_EVAL_FMA engine
 // another row partition (bhray_config.partition / stripe_rows / slab_row0 / row_rank / row_world) for the same frame; synchronises the engine
 int  dev_set_partition(bhray_dev* c, uint32_t partition, uint32_t stripe_rows, const uint32_t* slab_row0, uint32_t row_rank, uint32_t row_world);

@@ -1617,6 +1617,55 @@ int bhray_trace_rays_paths_device(bhray_ctx* c, const void* d_rays, uint32_t n, 
     DEV(c, c->parts[0].dev, dev_trace_rays_device(c->parts[0].dev, d_rays, n, d_out, d_records, (hipStream_t)s, &p));
     return BHRAY_OK;
 }
+// The accumulation image: the ray batches' engine and stream, so their rule - one partition, no gather - and the engine's own refusals.
+int bhray_accum_begin(bhray_ctx* c) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_accum_begin"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_accum_begin(c->parts[0].dev));
+    return BHRAY_OK;
+}
+int bhray_accum_add(bhray_ctx* c, uint32_t samples) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_accum_add"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_accum_add(c->parts[0].dev, samples));
+    return BHRAY_OK;
+}
+int bhray_accum_samples(const bhray_ctx* c, uint32_t* total) {
+    if (!c || !total) return BHRAY_E_INVALID;
+    *total = 0;                                                   // a ctx that cannot accumulate has taken no sample
+    if (c->cfg.device_count >= 2 || !c->single) return BHRAY_OK;
+    return dev_accum_samples(c->parts[0].dev, total);
+}
+int bhray_accum_read(bhray_ctx* c, float* dst, size_t pitch) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_accum_read"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_accum_read(c->parts[0].dev, dst, pitch));
+    return BHRAY_OK;
+}
+int bhray_accum_read_display(bhray_ctx* c, uint8_t* dst, size_t pitch) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_accum_read_display"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_accum_read_display(c->parts[0].dev, dst, pitch, &c->post_fxaa, &c->post_mix));
+    return BHRAY_OK;
+}
+int bhray_accum_sample_rays(bhray_ctx* c, uint32_t s, bhray_ray* out) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_accum_sample_rays"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_accum_sample_rays(c->parts[0].dev, s, out));
+    return BHRAY_OK;
+}
+int bhray_accum_set_launch_rays(bhray_ctx* c, uint32_t max_rays) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_accum_set_launch_rays"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_accum_set_launch_rays(c->parts[0].dev, max_rays));
+    return BHRAY_OK;
+}
 int bhray_set_uniforms(bhray_ctx* c, const void* cam32, const void* bh132, const void* det32) {
     if (!c) return BHRAY_E_INVALID;
     if (c->gather && cam32 && bh132) track_hole_row(c, cam32, bh132);

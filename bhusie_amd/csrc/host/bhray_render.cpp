@@ -1,7 +1,9 @@
 // bhray_render — minimal C++ host program over renderer.hpp: renders one frame of the reference's default scene
 // (camera (0,0,-19), hole at the origin, disk 2..10, R = 20; camera.rs:10-16, blackhole.rs:16-28) and writes the HDR frame
 // as raw little-endian f32 RGBA (row 0 = top).  Usage:
-//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--pick X Y] [--path X Y [--path-stride S]]
+//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--spp N] [--pick X Y] [--path X Y [--path-stride S]]
+// --spp N: instead of the ladder's frame, a supersampled still - the mean of N jittered samples per frame pixel, sky resolved, accumulated on the GPU
+//   (Renderer::render_still: bhray_accum_*); written the same way.  Not with --lensed-mesh, --devices or --panorama.
 // --path X Y [--path-stride S]: after the frame, the pick line of pixel (X, Y) and then the light path behind it, one line per point - that pixel's pinhole ray through
 //   bhray_trace_rays_paths (Renderer::ray_path), a point every 2^S iterations (S = 0 by default) and the end point:
 //   ITERATION X Y Z
@@ -147,9 +149,9 @@ int main(int argc, char** argv) {
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
         return 0;
     }
-    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--pick X Y] [--path X Y [--path-stride S]]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--spp N] [--pick X Y] [--path X Y [--path-stride S]]\n", argv[0]); return 2; }
     uint32_t bw = 72, bh = 41, levels = 4, disk = 256, pano_w = 0, pano_h = 0;
-    long pick_x = -1, pick_y = -1, path_x = -1, path_y = -1, path_stride = 0;
+    long pick_x = -1, pick_y = -1, path_x = -1, path_y = -1, path_stride = 0, spp = 0;
     bool rk = false, bvh_device = false, lensed = false, posed = false;
     float rotation[3] = {0.0f, 0.0f, 0.0f};
     std::vector<const char*> objs;
@@ -164,12 +166,14 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--pose") && i + 3 < argc) { posed = true; for (int a = 0; a < 3; a++) rotation[a] = (float)std::atof(argv[++i]); }
         else if (!std::strcmp(argv[i], "--lensed-mesh")) lensed = true;
         else if (!std::strcmp(argv[i], "--panorama") && i + 2 < argc) { pano_w = (uint32_t)std::atoi(argv[++i]); pano_h = (uint32_t)std::atoi(argv[++i]); if (pano_w < 1 || pano_h < 1) { std::fprintf(stderr, "--panorama needs W >= 1 and H >= 1\n"); return 2; } }
+        else if (!std::strcmp(argv[i], "--spp") && i + 1 < argc) { spp = std::atol(argv[++i]); if (spp < 1 || spp > (long)BHRAY_ACCUM_MAX_SAMPLES) { std::fprintf(stderr, "--spp needs 1 <= N <= %u\n", BHRAY_ACCUM_MAX_SAMPLES); return 2; } }
         else if (!std::strcmp(argv[i], "--pick") && i + 2 < argc) { pick_x = std::atol(argv[++i]); pick_y = std::atol(argv[++i]); if (pick_x < 0 || pick_y < 0) { std::fprintf(stderr, "--pick needs X >= 0 and Y >= 0\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--path") && i + 2 < argc) { path_x = std::atol(argv[++i]); path_y = std::atol(argv[++i]); if (path_x < 0 || path_y < 0) { std::fprintf(stderr, "--path needs X >= 0 and Y >= 0\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--path-stride") && i + 1 < argc) { path_stride = std::atol(argv[++i]); if (path_stride < 0 || path_stride > BHRAY_MAX_PATH_STRIDE_LOG2) { std::fprintf(stderr, "--path-stride needs 0 <= S <= %d\n", BHRAY_MAX_PATH_STRIDE_LOG2); return 2; } }
         else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) { for (const char* p = argv[++i]; *p; ) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p) p++; } }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
+    if (spp && pano_w) { std::fprintf(stderr, "--spp samples the pixels of the pinhole frame: not with --panorama\n"); return 2; }
     if (path_x >= 0 && pano_w) { std::fprintf(stderr, "--path names a pixel of the pinhole frame: not with --panorama\n"); return 2; }
     if (pick_x >= 0 && pano_w) { std::fprintf(stderr, "--pick names a pixel of the pinhole frame: not with --panorama\n"); return 2; }
     if (posed && !bvh_device) { std::fprintf(stderr, "--pose needs --bvh device (a pose is applied to a tree built on the GPU)\n"); return 2; }
@@ -197,6 +201,8 @@ int main(int argc, char** argv) {
         if (pano_w) {
             out = r.render_rays(bhusie::equirect_rays(r.camera.position, r.camera.forward, pano_w, pano_h));
             res = {pano_w, pano_h};
+        } else if (spp) {
+            out = r.render_still((uint32_t)spp);
         } else {
             r.render(0.0f);
             out = r.ray_pipeline().output();

@@ -207,6 +207,15 @@ public:
                                      p.points.data(), p.counts.data()), ctx_);
         return p;
     }
+    // supersampled stills (bhray_accum_*): the accumulation image cleared, `samples` jittered samples per frame pixel added under the current uniforms,
+    // and their mean - RGBA32F, sky resolved, 4 f32 per pixel.  Sample 0 is the pixel centre.
+    std::vector<float> accumulate(uint32_t samples) {
+        check(bhray_accum_begin(ctx_), ctx_);
+        check(bhray_accum_add(ctx_, samples), ctx_);
+        std::vector<float> out((size_t)cfg_.frame_w * cfg_.frame_h * 4);
+        check(bhray_accum_read(ctx_, out.data(), (size_t)cfg_.frame_w * 16), ctx_);
+        return out;
+    }
     bhray_ctx* ctx() { return ctx_; }
 private:
     bhray_config cfg_;
@@ -352,6 +361,12 @@ public:
         ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);
         apply_lensing();
         return ray_pipeline_.trace_rays(rays);
+    }
+    // a supersampled still of the current scene: the mean of `samples` jittered samples per frame pixel (RayPipeline::accumulate), RGBA32F as output() after the sky pass
+    std::vector<float> render_still(uint32_t samples) {
+        ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);
+        apply_lensing();
+        return ray_pipeline_.accumulate(samples);
     }
     // what is under frame pixel (x, y): the record of that pixel's pinhole ray under the current scene (hit & 0xff: BHRAY_HIT_*; (hit >> 8) & 0xff: the model slot of a mesh hit)
     bhray_ray_record pick(uint32_t x, uint32_t y) {

@@ -21,6 +21,7 @@ F_GATHER_SKY = 128
 TEX_TEMP_LUT, TEX_DISK, TEX_SKY = 0, 1, 2
 FXAA_MAX_ITERATIONS = 1024
 MAX_RAYS_PER_CALL = 1 << 26          # BHRAY_MAX_RAYS_PER_CALL
+ACCUM_MAX_SAMPLES = 65536            # BHRAY_ACCUM_MAX_SAMPLES
 
 
 class BhrayError(RuntimeError):
@@ -239,6 +240,12 @@ SYMBOLS = {
     "bhray_trace_rays_records_device": (C.c_int, [vp, vp, u32, vp, vp, vp]),
     "bhray_trace_rays_paths": (C.c_int, [vp, P(BhrayRay), u32, u32, u32, P(C.c_float), P(BhrayRayRecord), P(BhrayPathPoint), P(C.c_uint32)]),
     "bhray_trace_rays_paths_device": (C.c_int, [vp, vp, u32, u32, u32, vp, vp, vp, vp, vp]),
+    "bhray_accum_begin": (C.c_int, [vp]),
+    "bhray_accum_add": (C.c_int, [vp, u32]),
+    "bhray_accum_samples": (C.c_int, [vp, P(u32)]),
+    "bhray_accum_read": (C.c_int, [vp, vp, sz]),
+    "bhray_accum_read_display": (C.c_int, [vp, vp, sz]),
+    "bhray_accum_sample_offset": (None, [u32, P(C.c_float), P(C.c_float)]),
     "bhray_render": (C.c_int, [vp]),
     "bhray_flush": (C.c_int, [vp]),
     "bhray_sync": (C.c_int, [vp]),
@@ -302,6 +309,8 @@ DIAG_SYMBOLS = {
     "bhray_get_model_build_info": (C.c_int, [vp, u32, P(BhrayModelBuildInfo)]),
     "bhray_read_model_bvh": (C.c_int, [vp, u32, vp, u32, vp, u32, P(u32), P(u32)]),
     "bhray_read_model_vertices": (C.c_int, [vp, u32, vp, u32, vp, u32, P(u32), P(u32)]),
+    "bhray_accum_sample_rays": (C.c_int, [vp, u32, P(BhrayRay)]),
+    "bhray_accum_set_launch_rays": (C.c_int, [vp, u32]),
 }
 
 

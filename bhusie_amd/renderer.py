@@ -393,6 +393,45 @@ class RayPass:
         check(self._L.bhray_trace_rays_paths_device(self._h, C.c_void_p(d_rays), int(n), int(stride_log2), int(max_points), C.c_void_p(d_out), C.c_void_p(d_records),
                                                     C.c_void_p(d_points), C.c_void_p(d_counts), C.c_void_p(stream) if stream else None), self._h, self._L)
 
+    # -- supersampled stills: the accumulation image (bhray_accum_*)
+    def accum_begin(self):
+        """Clear the accumulation image (allocated on first use); the sample count becomes 0."""
+        check(self._L.bhray_accum_begin(self._h), self._h, self._L)
+
+    def accum_add(self, samples: int = 1):
+        """Enqueue the next `samples` sub-pixel samples of every frame pixel under the ctx's current uniforms, textures and models: generated, traced, sky-resolved
+        and summed on the device.  Returns without waiting.  Before accum_begin, and in the states trace_rays refuses: BhrayError (BHRAY_E_STATE)."""
+        check(self._L.bhray_accum_add(self._h, int(samples)), self._h, self._L)
+
+    def accum_samples(self) -> int:
+        n = C.c_uint32()
+        check(self._L.bhray_accum_samples(self._h, C.byref(n)), self._h, self._L)
+        return int(n.value)
+
+    def accum_read(self) -> np.ndarray:
+        """The mean of the samples taken so far: (frame_h, frame_w, 4) float32, alpha 1 (0, with a black pixel, where every sample was skipped).  Waits."""
+        w, h = int(self.cfg.frame_w), int(self.cfg.frame_h)
+        out = np.empty((h, w, 4), dtype=np.float32)
+        check(self._L.bhray_accum_read(self._h, out.ctypes.data, w * 16), self._h, self._L)
+        return out
+
+    def accum_read_display(self) -> np.ndarray:
+        """The mean through the display pass (set_post_uniforms' uniforms): uint8 (frame_h, frame_w, 4) as read_display.  Waits."""
+        w, h = int(self.cfg.frame_w), int(self.cfg.frame_h)
+        out = np.empty((h, w, 4), dtype=np.uint8)
+        check(self._L.bhray_accum_read_display(self._h, out.ctypes.data, w * 4), self._h, self._L)
+        return out
+
+    def accum_sample_rays(self, s: int) -> np.ndarray:
+        """The records the device generates for sample s under the current uniforms: (frame_h * frame_w, 8) float32 (bhray_diag.h)."""
+        out = np.empty((int(self.cfg.frame_w) * int(self.cfg.frame_h), 8), dtype=np.float32)
+        check(self._L.bhray_accum_sample_rays(self._h, int(s), out.ctypes.data_as(C.POINTER(BhrayRay))), self._h, self._L)
+        return out
+
+    def accum_set_launch_rays(self, max_rays: int = 0):
+        """At most max_rays rays per trace launch of accum_add (0: the default, 2**22); the image does not depend on it (bhray_diag.h)."""
+        check(self._L.bhray_accum_set_launch_rays(self._h, int(max_rays)), self._h, self._L)
+
     # -- per frame
     def set_uniforms(self, camera: bytes, black_hole: bytes, details: bytes):
         assert len(camera) == 32 and len(black_hole) == 132 and len(details) == 32
@@ -742,6 +781,39 @@ class Renderer:
                 "position": tuple(float(v) for v in r["position"]), "iterations": int(r["iterations"]),
                 "closest": float(r["closest"]), "transmittance": float(r["transmittance"]),
                 "path": pts["position"][0, :k].copy(), "path_iterations": pts["iteration"][0, :k].copy()}
+
+    def _accumulate(self, samples: int, shutter: float):
+        samples = int(samples)
+        if samples < 1:
+            raise ValueError(f"render_still: samples must be at least 1, got {samples}")
+        self._apply_uniforms()
+        self.ray_pass.accum_begin()
+        if not shutter > 0.0:
+            self.ray_pass.accum_add(samples)
+            return
+        t0 = self.ray_details.time
+        try:
+            for s in range(samples):                         # one sample per call: each under its own `time`
+                self.ray_details.time = t0 + float(shutter) * s / samples
+                self._apply_uniforms()
+                self.ray_pass.accum_add(1)
+        finally:
+            self.ray_details.time = t0
+
+    def render_still(self, samples: int = 16, shutter: float = 0.0) -> np.ndarray:
+        """A supersampled still of the current scene (RayPass.accum_*): the mean of `samples` jittered samples per frame pixel, sky resolved,
+        (frame_h, frame_w, 4) float32.  Sample 0 is the pixel centre, so samples=1 is the frame a `levels = 1` ladder renders, after the sky pass in binary32.
+        shutter > 0: motion blur - sample s is rendered at ray_details.time + shutter * s / samples (the disk turns with `time`); ray_details.time is left as it was."""
+        self._accumulate(samples, shutter)
+        return self.ray_pass.accum_read()
+
+    def save_still(self, path, samples: int = 16):
+        """save_image for a supersampled still: the mean of `samples` samples per pixel through the display pass, written with alpha 255."""
+        from PIL import Image
+        self._accumulate(samples, 0.0)
+        img = self.ray_pass.accum_read_display()
+        img[..., 3] = 255
+        Image.fromarray(img, "RGBA").save(path)
 
     def save_image(self, path):
         """The reference's Save Image (mod.rs:473-482): the display pass's RGBA8 image of the last frame, written with alpha 255

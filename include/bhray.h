@@ -539,6 +539,46 @@ int bhray_trace_rays_paths(bhray_ctx* ctx, const bhray_ray* rays, uint32_t n, ui
 int bhray_trace_rays_paths_device(bhray_ctx* ctx, const void* d_rays, uint32_t n, uint32_t stride_log2, uint32_t max_points,
                                   void* d_out_rgba32f, void* d_records, void* d_points, void* d_counts, void* hip_stream);
 
+/* Supersampled stills (not in the reference, whose only smoothing is FXAA): an accumulation image per
+ * ctx.  Sub-pixel samples of every frame pixel are generated, traced, sky-resolved and summed on the device; the mean
+ * comes back as RGBA32F, or through the display pass as the RGBA8 image Save Image writes.
+ *   image    frame_w x frame_h; frame pixel (x, y) is pixel (crop_x + x, crop_y + y) of the LAST ladder level
+ *            (lw x lh).  The ladder's other levels and every form of speculation play no part.
+ *   sample s (s = 0, 1, ...) has ONE offset for all pixels, the R2 sequence in integer arithmetic (mod 2^32):
+ *            u = 0x80000000 + s * 0xC13FA9A9, v = 0x80000000 + s * 0x91E10DA5, dx = float(u >> 8) * 2^-24 - 0.5, dy
+ *            likewise from v - every step exact in binary32 (bhray_accum_sample_offset: host arithmetic).  Sample 0
+ *            has offset (0, 0), the pixel centre; every offset lies in [-0.5, 0.5).
+ *   ray      create_ray (ray.wgsl:269-285) on the lw x lh level at px = float(crop_x + x) + dx, py = float(crop_y + y)
+ *            + dy (one rounded add each), then the frames' operation sequence: posx = (2 * (px - float(lw - 1) * 0.5))
+ *            * increment, ...; so sample 0 is bit for bit the ray of a levels = 1 frame of that size.
+ *   trace    bhray_trace_rays' kernels under the ctx's state at the time of the bhray_accum_add call: the camera, black
+ *            hole and details of the last bhray_set_uniforms, the textures, the models.
+ *   resolve  alpha == 0: sky^4 with alpha 1 by the sky pass's operations, kept in binary32 (no binary16 rounding);
+ *            every other result passes through.
+ *   sum      sum[p] += (r, g, b, 1) in binary32, in increasing s - whatever the grouping of samples into calls.  A
+ *            sample whose r, g or b is not finite is skipped, so sum.w is the number of samples the pixel took.
+ *   mean     (sum.x / n, sum.y / n, sum.z / n, 1), n = sum.w, IEEE division; n == 0: (0, 0, 0, 0).
+ *   display  the mean rounded to RGBA16F (nearest even) through the display pass of bhray_resolve_display, unchanged:
+ *            the ctx's post uniforms, the 32 x 32 minimum (BHRAY_E_INVALID), a scratch of its own.
+ * bhray_accum_begin allocates on first use, clears the sum and sets the sample count to 0.  bhray_accum_add enqueues the
+ * next `samples` sample indices on the ctx's query stream and returns; staged frames are launched first, as by
+ * bhray_trace_rays.  samples == 0: BHRAY_OK, nothing happens.  A total above BHRAY_ACCUM_MAX_SAMPLES: BHRAY_E_INVALID,
+ * nothing enqueued.  Before bhray_accum_begin: BHRAY_E_STATE (bhray_accum_read and bhray_accum_read_display too).  The
+ * scene may change between calls - `time`, the camera: motion blur, depth of field -; a caller that does not want that
+ * clears with bhray_accum_begin.  bhray_accum_read and bhray_accum_read_display wait and deliver frame_h rows.
+ * BHRAY_E_STATE, as for bhray_trace_rays: before the first bhray_set_uniforms (bhray_accum_add), on a ctx created with
+ * BHRAY_F_LITERAL or BHRAY_F_EVAL_FMA, while mesh lensing is on (bhray_accum_add), on a ctx with device_count >= 2 or a
+ * gather; and on a row-partitioned ctx (row_world > 1).  A frame of more than BHRAY_MAX_RAYS_PER_CALL pixels:
+ * BHRAY_E_INVALID.  Every call that waits for the outstanding ray batches - the uploads, the poses, bhray_sync,
+ * bhray_destroy - waits for the accumulation too, and a device fault surfaces as a batch's does.                    */
+#define BHRAY_ACCUM_MAX_SAMPLES 65536u
+int bhray_accum_begin(bhray_ctx* ctx);
+int bhray_accum_add(bhray_ctx* ctx, uint32_t samples);
+int bhray_accum_samples(const bhray_ctx* ctx, uint32_t* total);
+int bhray_accum_read(bhray_ctx* ctx, float* dst_rgba32f, size_t row_pitch_bytes);
+int bhray_accum_read_display(bhray_ctx* ctx, uint8_t* dst_rgba8, size_t row_pitch_bytes);
+void bhray_accum_sample_offset(uint32_t s, float* dx, float* dy);
+
 /* Dispatch — replaces `for rp in ray_pipelines { rp.pass() }` (mod.rs:415-417,
  * ray_pipeline.rs:301-309).  Asynchronous on the ctx stream; levels ordered.                 */
 int bhray_render(bhray_ctx* ctx);

@@ -169,6 +169,18 @@ int bhray_read_model_vertices(bhray_ctx* ctx, uint32_t model_index, float* point
                               uint32_t* point_count, uint32_t* normal_count);
 
 /* ------------------------------------------------------------------------------------------
+ * The accumulation image (bhray_accum_*)
+ * ---------------------------------------------------------------------------------------- */
+/* The records the generator kernel writes for sample s under the current uniforms: frame_w * frame_h of them, row 0
+ * the top, x fastest.  Needs no bhray_accum_begin; s >= BHRAY_ACCUM_MAX_SAMPLES or a NULL out: BHRAY_E_INVALID; the
+ * refused states of bhray_accum_add apart from mesh lensing (the generator does not trace).  Waits.                   */
+int bhray_accum_sample_rays(bhray_ctx* ctx, uint32_t s, bhray_ray* out);
+/* At most max_rays rays per trace launch of bhray_accum_add: K = max(1, max_rays / (frame_w * frame_h)) samples go
+ * into one launch.  0 restores the default, 2^22; more than BHRAY_MAX_RAYS_PER_CALL: BHRAY_E_INVALID.  The image
+ * does not depend on it.                                                                                             */
+int bhray_accum_set_launch_rays(bhray_ctx* ctx, uint32_t max_rays);
+
+/* ------------------------------------------------------------------------------------------
  * Gather statistics (multi-GPU)
  * ---------------------------------------------------------------------------------------- */
 /* What a ctx gathers with.                                                                                          */
