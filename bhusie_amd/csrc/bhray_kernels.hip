@@ -740,7 +740,34 @@ __device__ constexpr float DB1 = KF(37.0 / 378.0 - 2825.0 / 27648.0),
 // computes for such lanes; when one lane fails, all lanes run the full text as before.  Same values either way: byte-identical frames (tests/test_gpu_err_skip.py against
 // libbhray_errskip0.so; the bound itself: tests/test_err_bound_cpu.py).  SKIP 2 (the counting kernels): the full text always, and three counters - cnt[13] wave-steps, cnt[14]
 // wave-steps whose active lanes all passed, cnt[15] lane-steps that passed with e_max above the threshold (the proof's claim on the device: must be 0) - bhray_get_err_skip.
+//
+// SKIP 3 (BHRAY_ERR_SKIP bit 3: the dense no-mesh builds) - the same branch behind a sharper bound in ONE fused operation:
+//
+//     m = fma(dist, |sh|, |sh|) = (dist + 1) |sh| <= ERR_SKIP_C3 = 0.129     =>     e_max <= 9.64e-6 < 1.0e-5 < 0.00002.
+//
+// Proof.  The bound above uses only sum DB_i = 0.  But f is linear in the hole-relative position with the frozen scalar s, so in exact arithmetic every stage is a polynomial
+// in t = sh times q0: K_i = kappa_i(t) q0, kappa_1 = t, kappa_i = t (1 + sum_j a_ij kappa_j), and e = P(t) q0 with P = sum DB_i kappa_i.  With the binary32 constants taken as
+// rationals and the tableau as it is applied here - K4 takes K2 twice, the zero terms dropped - (tests/test_err_bound3_cpu.py, fractions.Fraction):
+//     P(t) = -1.397e-9 t - 5.754e-9 t^2 + 0.0040986 t^3 + 0.0029715 t^4 - 9.393e-5 t^5
+// (the t and t^2 terms are the constants' rounding: sum DB_i = sum DB_i c_i = 0 for the row sums c_i as used; K4 without K3 leaves the t^3 term; the rational tableau with K3 in
+// K4 gives zero below t^5 - the same test).  Write g = |sh|, D = |q0|_inf <= dist (1 + 4u) as above, c' = 0.129 (1 + 2u): m is one rounding below (dist + 1) g, so m <= C3 gives
+// (dist + 1) g <= c', hence g <= c' AND dist g <= c' - whatever dist: the proof assumes no range of it (the march keeps a lane in M_REL at dist <= R up to rounding - the exit
+// test behind every step, bhray_step_u.inc - which is not needed here) beyond a finite dist below 1e38, where the stages' sums cannot overflow.
+//  (1) Exact arithmetic.  |e|_inf <= D g (|p_1| + |p_2| g + A(g) g^2), A(g) = sum_{k>=3} |p_k| g^(k-3) <= A(c') = 0.0044835.
+//  (2) Rounding, redone for g <= c' (R11.1's step (3) held for g <= 0.006).  |kappa_i| <= kbar_i g with kbar = 1, 1.0258, 1.0394, 1.0784, 1.1374, 1.1194 (the coefficients' absolute
+//      values at c'); the partial sums of stage i are at most S_i D, S_i = 1 + c' sum_j |a_ij| kbar_j = 1, 1.026, 1.039, 1.317, 1.885, 1.119.  A stage is n_i = i - 1 fused
+//      operations and one product, each off by at most u times its result, and hands the rounding of the earlier stages on times |a_ij| g: the computed K_i is within
+//      g r_i D of the exact one, r_i = (n_i + 1) u S_i (1 + 1e-3) + c' sum_j |a_ij| r_j (the 1e-3 covers the second-order terms).  The e chain is one product and four fused
+//      operations on values <= sum |DB_i| kbar_i D g.  Together the computed e is within rho D g of P(t) q0, rho = sum |DB_i| r_i + 5 u sum |DB_i| kbar_i (1 + 1e-3) = 1.415 u
+//      = 8.43e-8.  Denormal results (flushed or not) move it by less than 1e-36.
+//  (3) Together e_max <= D g (|p_1| + |p_2| c' + A(c') c'^2 + rho) <= c' (1 + 4u) (1.4e-9 + 7.4e-10 + 7.461e-5 + 8.43e-8) = 9.64e-6: R11.1's factor 2 to the threshold, and
+//      C3 is within 1 % of the largest constant for which this closes (the test asserts both).  Slack that is left: g <= c' / (dist + 1), so dist g^3 <= (4 / 27) c'^3.
+//  (4) NaN, inf: a NaN in dist or sh makes m a NaN (the fused operation propagates it; |.| is an operand modifier, no max / min), dist = inf with sh = 0 makes it inf * 0 = NaN,
+//      an infinite or overflowing product +inf: `m <= C3` is false for all of them, the lane fails the bound and its wave runs the full text.
+// On the bench frame (the measurement build, `make shares`): 12.8 % of the dense kernel's wave-steps hold a lane that fails R11.1's bound, 2.2 % one that fails this one, and no
+// lane-step passes it with e_max above the threshold (profiles/EXPERIMENTS.md R19.1); tests/test_gpu_exit_light.py against libbhray_exit0.so: the same bytes.
 __device__ constexpr float ERR_SKIP_C = 3.6e-5f;
+__device__ constexpr float ERR_SKIP_C3 = 0.129f;
 template <bool FAST, int SKIP = 0>
 __device__ __forceinline__ bool next_ray_rk_t(const F3 q0, const F3 p0, F3& pos, F3& dir, float& h_io, float dist, unsigned long long* cnt = nullptr) {
     const F3 d0 = dir;                     // q0 = p0 - bpos (N9), carried by the caller together with dist = flength(q0)
@@ -757,9 +784,25 @@ __device__ __forceinline__ bool next_ray_rk_t(const F3 q0, const F3 p0, F3& pos,
     const F3 K4 = fmadd3(K2, A43, fmadd3(K2, A42, fmadd3(K1, A41, q0))) * sh;
     const F3 K5 = fmadd3(K4, A54, fmadd3(K3, A53, fmadd3(K2, A52, fmadd3(K1, A51, q0)))) * sh;
     const F3 K6 = fmadd3(K5, A65, fmadd3(K4, A64, fmadd3(K3, A63, fmadd3(K2, A62, fmadd3(K1, A61, q0))))) * sh;
-    if constexpr (SKIP == 1) {
+    if constexpr (SKIP == 1 || SKIP == 3) {
+        bool calm;
+        if constexpr (SKIP == 3) calm = __builtin_fmaf(dist, fabsf(sh), fabsf(sh)) <= ERR_SKIP_C3;      // NaN: false
+        else {
         const float sh2 = sh * sh;
-        const bool calm = __builtin_fmaf(sh2, dist, sh2) <= ERR_SKIP_C;          // NaN: false
+        calm = __builtin_fmaf(sh2, dist, sh2) <= ERR_SKIP_C;          // NaN: false
+        }
+#ifdef BHRAY_SHARE_LOG      // the measurement build: both bounds' shares, and the estimate itself under the third-order bound (see g_share_log)
+        if (cnt) {
+            const float sh2m = sh * sh;
+            const bool calm2 = __builtin_fmaf(sh2m, dist, sh2m) <= ERR_SKIP_C, calm3 = __builtin_fmaf(dist, fabsf(sh), fabsf(sh)) <= ERR_SKIP_C3;
+            const F3 em = fmadd3(K6, DB6, fmadd3(K5, DB5, fmadd3(K4, DB4, fmadd3(K3, DB3, K1 * DB1))));
+            const unsigned long long active = __ballot(true), pass2 = __ballot(calm2), pass3 = __ballot(calm3);
+            if ((int)(threadIdx.x & 63u) == (int)__builtin_ctzll(active)) { cnt[0]++; if (pass2 == active) cnt[1]++; if (pass3 == active) cnt[4]++; }
+            if (calm3 && !(max3_abs(em.x, em.y, em.z) <= 0.00002f)) cnt[5]++;
+            if (!calm2) cnt[6]++;
+            cnt[7]++;
+        }
+#endif
         // the small terms are summed first and added to the unit-length direction once (one rounding at magnitude 1)
         const F3 ds = fmadd3(K6, BA6, fmadd3(K5, BA5, fmadd3(K4, BA4, fmadd3(K3, BA3, K1 * BA1))));
         float hn = h * 1.0001f;
@@ -1184,10 +1227,13 @@ __device__ __forceinline__ bool lens_near_mesh(const FrameParams& P, F3 pos, F3 
 #define BHRAY_PNUMER_EARLY 1
 #endif
 #ifndef BHRAY_ERR_SKIP
-#define BHRAY_ERR_SKIP 1        // the Cash-Karp step without its error estimate where a bound proves the estimate below the step-size controller's threshold for every active lane of the wave
+#define BHRAY_ERR_SKIP 9        // the Cash-Karp step without its error estimate where a bound proves the estimate below the step-size controller's threshold for every active lane of the wave
                                 // (next_ray_rk_t's SKIP: the proof stands there) - bit 0: the dense no-mesh builds (the flagship's: profiles/EXPERIMENTS.md R11.1), bit 1: the latency no-mesh
                                 // builds, bit 2: the mesh builds (bits 1 and 2: built, byte-identical, not measured to win - off).  Any bit set: the counting kernels count how often the bound
                                 // holds (bhray_get_err_skip).  0 (`make errskip0`: libbhray_errskip0.so, what tests/test_gpu_err_skip.py and the A/B of R11.1 compare with): the kernel text before.
+                                // Bit 3: the builds of bit 0 test the third-order bound (dist + 1) |s h| <= ERR_SKIP_C3 (one fused operation; next_ray_rk_t's SKIP 3) instead of
+                                // R11.1's: 12.8 % of the bench frame's wave-steps fail R11.1's bound, 2.2 % this one (profiles/EXPERIMENTS.md R19.1); the counting kernels keep counting
+                                // R11.1's bound.  1 (`make exit0`: libbhray_exit0.so, what tests/test_gpu_exit_light.py and the A/B of R19.1 compare with): R11.1's bound everywhere.
 #endif
 #ifndef BHRAY_ORIGIN_KERNEL
 #define BHRAY_ORIGIN_KERNEL 1    // the hole at the scene's origin (all three position words +0) is a property of a kernel BUILD, chosen by the host per launch (trace_kernel's ORIGIN): such a
@@ -1312,6 +1358,22 @@ extern "C" __attribute__((visibility("default"))) int bhray_debug_wave_log(unsig
 }
 namespace bhray {
 #endif
+#ifdef BHRAY_SHARE_LOG     // a measurement build (`make shares`, profiles/skip_exit_shares.py, EXPERIMENTS.md R19.1): the dense no-mesh RK kernels count, over all their launches,
+                           // [0] wave-steps of the unified pairs, [1] those whose active lanes all pass R11.1's bound, [2] rare-region visits, [3] visits without a lane near the horizon
+                           // or the disk (lanes that only leave the sphere or end at the iteration limit), [4] as [1] for the third-order bound, [5] lane-steps that pass the
+                           // third-order bound with an estimate above the controller's threshold (the proof's claim on the device: must be 0), [6] lane-steps that fail R11.1's bound,
+                           // [7] lane-steps.  Same frames as the shipped kernels; the counters cost registers, so nothing is timed with it.
+__device__ unsigned long long g_share_log[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+}  // namespace bhray
+extern "C" __attribute__((visibility("default"))) int bhray_debug_share_log(unsigned long long* out8, int reset) {
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (out8 && hipMemcpyFromSymbol(out8, HIP_SYMBOL(bhray::g_share_log), 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
+    const unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(bhray::g_share_log), zero, sizeof(zero)) != hipSuccess) return -1;
+    return 0;
+}
+namespace bhray {
+#endif
 #ifndef BHRAY_TRACE_WAVES_RECORDS_EULER
 #define BHRAY_TRACE_WAVES_RECORDS_EULER 5     // the Euler no-mesh record kernel is budgeted for the 5 waves per SIMD its ray-list twin reaches unasked (88 VGPRs under the latency build's
                                               // budget of 4): with the record stores on the rare paths the allocator otherwise settles at 103 VGPRs and 4 waves
@@ -1364,9 +1426,15 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
     static_assert(!PATHS || RECORDS, "the path kernels are record kernels");
     constexpr bool UNIFIED = BHRAY_UNIFIED != 0 && EVAL == 0 && (!MODELS || BHRAY_UNIFIED_MESH != 0) && !COUNT && !LENSED && !PATHS;           // the unified march (bhray_step_u.inc) in the contract kernels that do not count (the lensed-mesh kernels: the general step, whose ppos / pdir a paused lane keeps)
     constexpr bool ONE_TEST = UNIFIED && !MODELS && (((BHRAY_ONE_TEST & 1) != 0 && !DENSE) || ((BHRAY_ONE_TEST & 2) != 0 && DENSE));
-    // the RK step's error estimate behind a wave-uniform bound (next_ray_rk_t): 0 the full text, 1 skipped where the bound holds, 2 the full text and the bound's counters
+    // the RK step's error estimate behind a wave-uniform bound (next_ray_rk_t): 0 the full text, 1 skipped where R11.1's bound holds, 2 the full text and that bound's counters,
+    // 3 skipped where the third-order bound holds (BHRAY_ERR_SKIP bit 3: the dense no-mesh builds)
     constexpr int ERR_SKIP = (METHOD != 1 || EVAL != 0 || BHRAY_ERR_SKIP == 0) ? 0 : COUNT ? 2
-                           : (MODELS ? (BHRAY_ERR_SKIP & 4) != 0 : DENSE ? (BHRAY_ERR_SKIP & 1) != 0 : (BHRAY_ERR_SKIP & 2) != 0) ? 1 : 0;
+                           : (MODELS ? (BHRAY_ERR_SKIP & 4) != 0 : DENSE ? (BHRAY_ERR_SKIP & 1) != 0 : (BHRAY_ERR_SKIP & 2) != 0) ? ((DENSE && !MODELS && (BHRAY_ERR_SKIP & 8) != 0) ? 3 : 1) : 0;
+#ifdef BHRAY_SHARE_LOG
+    constexpr bool SHARE_LOG = UNIFIED && METHOD == 1 && DENSE && !MODELS && !RAYS;
+    unsigned long long slog_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long* const slog = SHARE_LOG ? slog_ : nullptr;
+#endif
     constexpr bool PH = phase_seq_build(MODELS, DENSE);          // the phases' short exact sequences (BHRAY_PHASE_SEQ) in this build
     constexpr bool COLD_LDS = (DENSE && !MODELS) || (MODELS && BHRAY_MESH_COLD_LDS != 0);
     constexpr bool MESH_DENSE = MODELS && DENSE;                                              // the mesh variant's build for a saturated device
@@ -1970,6 +2038,15 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
     if (Fb[0].span && threadIdx.x == 0) atomicMax(&Fb[0].span[1], (unsigned long long)wall_clock64());
 #endif
     if (err) *err_flag = err;
+#ifdef BHRAY_SHARE_LOG
+    if constexpr (SHARE_LOG) {
+        for (int k = 0; k < 8; k++) {
+            unsigned long long v = slog_[k];
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+            if (lane == 0 && v) atomicAdd(&g_share_log[k], v);
+        }
+    }
+#endif
 #ifdef BHRAY_WAVE_LOG
     if (g_wave_log && lanes_below(~0ull) == 0u) {      // one record per wave: start, end (100 MHz), where it ran, how many integrator steps it issued
         const unsigned i = atomicAdd(&g_wave_log_n, 1u);

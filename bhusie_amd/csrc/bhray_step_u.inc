@@ -27,6 +27,11 @@
 #define U_QIN qrel
 #define U_QOUT qrel
 #endif
+#ifdef BHRAY_SHARE_LOG
+#define U_SLOG , slog
+#else
+#define U_SLOG
+#endif
             {
                 // (The iteration limit, ray.wgsl:522, is tested where `it` changes - behind the step, in the rare-path test - and once in front of the pairs:
                 // a lane in M_REL here has iterations left.)
@@ -44,7 +49,7 @@
                     float cd;
                     if (ONE_TEST) {
                         if (METHOD == 0) redo = next_ray_euler_t<true>(U_QIN, U_PIN, U_POUT, udir, H.step_size, dist_c);
-                        else redo = next_ray_rk_t<true, ERR_SKIP>(U_QIN, U_PIN, U_POUT, udir, rkh, dist_c);
+                        else redo = next_ray_rk_t<true, ERR_SKIP>(U_QIN, U_PIN, U_POUT, udir, rkh, dist_c U_SLOG);
                         if (!BHRAY_U_ORIGIN) qrel = U_POUT - bpos;
                         const float qq = fdot(U_QOUT, U_QOUT);
                         cd = sqrt_corrected(qq);
@@ -52,7 +57,7 @@
                         if (BHRAY_ONE_TEST & 4) redo |= ((((unsigned)it * 2654435761u) ^ (cold.pix() * 40503u)) & 0x1c0u) == 0u;     // (test build: an eighth of the steps)
                     } else {
                         if (METHOD == 0) next_ray_euler_to(U_QIN, U_PIN, U_POUT, udir, H.step_size, dist_c);
-                        else (void)next_ray_rk_t<false, ERR_SKIP>(U_QIN, U_PIN, U_POUT, udir, rkh, dist_c);
+                        else (void)next_ray_rk_t<false, ERR_SKIP>(U_QIN, U_PIN, U_POUT, udir, rkh, dist_c U_SLOG);
                         if (!BHRAY_U_ORIGIN) qrel = U_POUT - bpos;
                         cd = sqrt_rn(fdot(U_QOUT, U_QOUT));                 // N7: the integrator's distance (ray.wgsl:533)
                     }
@@ -78,6 +83,14 @@
                                 black_hole_culls_rel<MODELS>(H, pnumer, pdist, seg, near_horizon, near_disk);
                             }
                         }
+#ifdef BHRAY_SHARE_LOG
+                        if (slog) {
+                            const unsigned long long active = __ballot(true), heavy_m = __ballot(near_horizon || near_disk || redo);
+                            if ((int)(threadIdx.x & 63u) == (int)__builtin_ctzll(active)) { slog[2]++; if (heavy_m == 0ull) slog[3]++; }
+                        }
+#endif
+                        // (A wave whose lanes here only leave the sphere or end at the iteration limit does not run the hit tests: the compiler branches round hit_sphere,
+                        // hit_torus2d, the horizon arm and the disk arm when no lane takes them.  An arm of its own for such waves was built and lost 1.3 %: EXPERIMENTS.md R19.1.)
                         Hit crs; float td;
                         const bool disk = hit_black_hole_geom<PH>(H, U_PIN, udir, near_horizon, near_disk, t_min, seg, crs, td);
                         F3 ncpos = U_POUT, ncdir = udir;                    // what cpos / cdir become for a lane that leaves
@@ -123,3 +136,4 @@
 #undef U_POUT
 #undef U_QIN
 #undef U_QOUT
+#undef U_SLOG

@@ -24,7 +24,7 @@ def regions_of(src_path):
         raise SystemExit(f"marker not found: {marker}")
     k = line("void trace_kernel(const FrameParams*")
     refill = line("// ---- refill finished lanes", k)
-    refill_end = line("if (!__any(mode != M_EMPTY)) break;", refill)
+    refill_end = line("if (!__any(mode != M_EMPTY))", refill)
     lens = line("// ---- lensed meshes", refill_end)
     shade = line("// ---- deferred disk shading", lens)
     flat = line("// ---- flat-space iterations", shade)
