@@ -21,6 +21,7 @@
 #include "bhray_dev.h"
 #include "bhray_internal.h"
 #include "bhray_math.h"
+#include "bhray_skyfilter.h"
 
 using namespace bhray;
 
@@ -157,6 +158,9 @@ struct bhray_dev {
     // scene
     uint8_t* tex[3] = {nullptr, nullptr, nullptr};
     int tex_w[3] = {0, 0, 0}, tex_h[3] = {0, 0, 0};
+    int sky_filter = 0;                    // dev_set_sky_filter: 1 = dev_resolve_sky runs the footprint filter
+    uint2* pyr_buf = nullptr;              // ... and the sky texture's pyramid, levels 1 .. top: held only while the mode is on
+    bhray::SkyPyr pyr{};
     ModelStore models[BHRAY_MAX_MODELS];
     bhray_camera_uniform cam{};
     bhray_black_hole_uniform bh{};
@@ -472,6 +476,7 @@ void dev_destroy(bhray_dev* c) {
         if (L.d_rowmap) (void)hipFree(L.d_rowmap);
     }
     for (auto& t : c->tex) if (t) (void)hipFree(t);
+    if (c->pyr_buf) (void)hipFree(c->pyr_buf);
     for (auto& m : c->models) free_model(m);
     for (auto& e : c->events) if (e) (void)hipEventDestroy(e);
     if (c->d_err) (void)hipFree(c->d_err);
@@ -775,6 +780,29 @@ int dev_create(const bhray_config* cfg, const bhray::DevOptions& opt, bhray_dev*
     return BHRAY_OK;
 }
 
+namespace {
+// The pyramid of the resident sky texture, one launch per level on the legacy stream, complete on return.  Called with the engine idle (sync_all).
+int build_sky_pyramid(bhray_dev* c) {
+    if (c->pyr_buf) { (void)hipFree(c->pyr_buf); c->pyr_buf = nullptr; }
+    c->pyr = SkyPyr{};
+    if (!c->tex[BHRAY_TEX_SKY]) return BHRAY_OK;
+    TexDev sky; sky.rgba = c->tex[BHRAY_TEX_SKY]; sky.w = c->tex_w[BHRAY_TEX_SKY]; sky.h = c->tex_h[BHRAY_TEX_SKY];
+    SkyPyr P;
+    const size_t texels = sky_pyramid_layout(sky.w, sky.h, &P);
+    if (P.levels < 1) return fail(c, BHRAY_E_INVALID, "sky pyramid: bad texture size %d x %d", sky.w, sky.h);
+    if (texels) {
+        HIPCHK(c, hipMalloc(&c->pyr_buf, texels * sizeof(uint2)));
+        HIPCHK(c, launch_sky_pyramid_first(sky, c->pyr_buf + P.off[1], nullptr));
+        for (int l = 1; l + 1 < P.levels; l++)
+            HIPCHK(c, launch_sky_pyramid_next(c->pyr_buf + P.off[l], sky_pyr_dim(sky.w, l), sky_pyr_dim(sky.h, l), c->pyr_buf + P.off[l + 1], nullptr));
+        HIPCHK(c, hipStreamSynchronize(nullptr));
+    }
+    P.base = c->pyr_buf;
+    c->pyr = P;
+    return BHRAY_OK;
+}
+}  // namespace
+
 int dev_set_texture(bhray_dev* c, int slot, const uint8_t* rgba8, uint32_t w, uint32_t h) {
     if (!c) return BHRAY_E_INVALID;
     if (slot < 0 || slot > 2 || !rgba8 || w < 1 || h < 1 || w > 32768 || h > 32768) return fail(c, BHRAY_E_INVALID, "bad texture arguments");
@@ -788,6 +816,39 @@ int dev_set_texture(bhray_dev* c, int slot, const uint8_t* rgba8, uint32_t w, ui
     if (e != hipSuccess) { (void)hipFree(d); return fail(c, BHRAY_E_HIP, "texture upload: %s", hipGetErrorString(e)); }
     if (c->tex[slot]) (void)hipFree(c->tex[slot]);
     c->tex[slot] = d; c->tex_w[slot] = (int)w; c->tex_h[slot] = (int)h;
+    if (slot == BHRAY_TEX_SKY && c->sky_filter != 0) return build_sky_pyramid(c);
+    return BHRAY_OK;
+}
+
+// The footprint-filtered sky pass: per-engine state, applied from the next dev_resolve_sky.  bhray_set_texture's rule: staged frames are launched
+// and the frames in flight waited for, since a resolve enqueued under the other mode may still be reading the pyramid.
+int dev_set_sky_filter(bhray_dev* c, int32_t mode) {
+    if (!c) return BHRAY_E_INVALID;
+    if (mode != 0 && mode != 1) return fail(c, BHRAY_E_INVALID, "bhray_set_sky_filter: mode %d (0: off, 1: footprint filter)", (int)mode);
+    if (mode != 0 && (c->cfg.row_world > 1 || c->local_rows.size() != (size_t)c->cfg.frame_h))
+        return fail(c, BHRAY_E_STATE, "bhray_set_sky_filter: not built for a row partition (a partition does not hold its neighbours' rows)");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = launch_batch(c); if (rc) return rc; }
+    HIPCHK(c, sync_all(c));
+    c->sky_filter = mode;
+    if (mode == 0) {
+        if (c->pyr_buf) { (void)hipFree(c->pyr_buf); c->pyr_buf = nullptr; }
+        c->pyr = SkyPyr{};
+        return BHRAY_OK;
+    }
+    int rc = build_sky_pyramid(c);
+    if (rc) c->sky_filter = 0;
+    return rc;
+}
+
+int dev_read_sky_pyramid_level(bhray_dev* c, uint32_t level, uint16_t* dst, size_t texels) {
+    if (!c) return BHRAY_E_INVALID;
+    if (c->sky_filter == 0 || !c->tex[BHRAY_TEX_SKY] || c->pyr.levels < 1) return fail(c, BHRAY_E_STATE, "bhray_read_sky_pyramid_level: the sky filter is off (bhray_set_sky_filter)");
+    if (level == 0 || level >= (uint32_t)c->pyr.levels) return fail(c, BHRAY_E_INVALID, "bhray_read_sky_pyramid_level: level %u of a pyramid with levels 1 .. %d", level, c->pyr.levels - 1);
+    const size_t n = (size_t)sky_pyr_dim(c->tex_w[BHRAY_TEX_SKY], (int)level) * (size_t)sky_pyr_dim(c->tex_h[BHRAY_TEX_SKY], (int)level);
+    if (!dst || texels != n) return fail(c, BHRAY_E_INVALID, "bhray_read_sky_pyramid_level: level %u holds %zu texels", level, n);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy(dst, c->pyr_buf + c->pyr.off[level], n * sizeof(uint2), hipMemcpyDeviceToHost));    // the pyramid was complete when its build returned
     return BHRAY_OK;
 }
 
@@ -2155,7 +2216,9 @@ int dev_resolve_sky(bhray_dev* c) {
     const size_t ring = (size_t)(S.batch_id % BHRAY_TIMING_RING);
     hipEvent_t* ev = timing ? batch_events(c, ring) : nullptr;
     if (timing) HIPCHK(c, hipEventRecord(ev[ev_sky_begin(c->cfg.levels)], S.stream));
-    HIPCHK(c, launch_sky(sky, R.out, R.sky_out, npix, S.stream));
+    if (c->sky_filter != 0 && c->local_rows.size() != (size_t)c->cfg.frame_h) return fail(c, BHRAY_E_STATE, "the sky filter needs the whole frame on this engine");
+    if (c->sky_filter == 0) HIPCHK(c, launch_sky(sky, R.out, R.sky_out, npix, S.stream));
+    else HIPCHK(c, launch_sky_filter(sky, c->pyr, R.out, R.sky_out, c->cfg.frame_w, c->cfg.frame_h, S.stream));     // the whole frame: dev_set_sky_filter refuses a partition
     R.sky_frame_id = R.frame_id;
     if (timing) { HIPCHK(c, hipEventRecord(ev[ev_sky_end(c->cfg.levels)], S.stream)); c->sky_recorded[ring] = 1; }
     HIPCHK(c, hipEventRecord(S.done, S.stream));

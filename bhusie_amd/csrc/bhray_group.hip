@@ -2059,6 +2059,25 @@ int bhray_sky_device_ptr(bhray_ctx* c, void** p, size_t* bytes) {
     return group_device_ptr(c, IMAGE_SKY, p, bytes);
 }
 
+// ---- footprint-filtered sky pass (bhray_skyfilter.hip): one engine that holds the whole frame ------------------------
+int bhray_set_sky_filter(bhray_ctx* c, int32_t mode) {
+    if (!c) return BHRAY_E_INVALID;
+    if (mode != 0 && mode != 1) return gfail(c, BHRAY_E_INVALID, "bhray_set_sky_filter: mode %d (0: off, 1: footprint filter)", (int)mode);
+    ENTER(c);
+    if (mode != 0 && (c->cfg.device_count >= 2 || !c->single || c->world > 1))
+        return gfail(c, BHRAY_E_STATE, "bhray_set_sky_filter: not built for a ctx that splits the frame (device_count >= 2, gather = BHRAY_GATHER_RCCL or row_world > 1): a partition does not hold its neighbours' rows");
+    if (!c->single) return BHRAY_OK;                             // mode 0 on a ctx that never had the filter: nothing to do
+    DEV(c, c->parts[0].dev, dev_set_sky_filter(c->parts[0].dev, mode));
+    return BHRAY_OK;
+}
+int bhray_read_sky_pyramid_level(bhray_ctx* c, uint32_t level, uint16_t* dst, size_t texels) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    if (!c->single) return gfail(c, BHRAY_E_STATE, "bhray_read_sky_pyramid_level: the sky filter is off (bhray_set_sky_filter)");
+    DEV(c, c->parts[0].dev, dev_read_sky_pyramid_level(c->parts[0].dev, level, dst, texels));
+    return BHRAY_OK;
+}
+
 // ---- display pass (bhray_post.hip) ---------------------------------------------------------------------------
 int bhray_set_post_uniforms(bhray_ctx* c, const void* fxaa16, const void* mix4) {
     if (!c || !fxaa16 || !mix4) return BHRAY_E_INVALID;

@@ -170,6 +170,7 @@ public:
     void set_uniforms(const bhray_camera_uniform& c, const bhray_black_hole_uniform& b, const bhray_details& d) { check(bhray_set_uniforms(ctx_, &c, &b, &d), ctx_); }
     void pass() { check(bhray_render(ctx_), ctx_); }                                            // ray_pipeline.rs:301-309
     void flush() { check(bhray_flush(ctx_), ctx_); }
+    void set_sky_filter(bool on) { check(bhray_set_sky_filter(ctx_, on ? 1 : 0), ctx_); }        // footprint-filtered sky pass: from the next resolve_sky / resolve_display on
     void resolve_sky() { check(bhray_resolve_sky(ctx_), ctx_); }                                // sky_pipeline.rs pass
     // bloom / mix / hdr / fxaa passes (mod.rs:425-431), with the uniforms Renderer::render uploads unless set_post_uniforms changed them
     void resolve_display() { check(bhray_resolve_display(ctx_), ctx_); }

@@ -264,6 +264,8 @@ SYMBOLS = {
     "bhray_resolve_sky": (C.c_int, [vp]),
     "bhray_read_sky": (C.c_int, [vp, vp, sz]),
     "bhray_sky_device_ptr": (C.c_int, [vp, P(vp), P(sz)]),
+    "bhray_set_sky_filter": (C.c_int, [vp, i32]),
+    "bhray_sky_pyramid_sizes": (C.c_int, [u32, u32, P(u32), P(u32), P(u32)]),
     "bhray_post_defaults": (C.c_int, [P(BhrayFxaaDetails), P(BhrayMixDetails)]),
     "bhray_bloom_sizes": (C.c_int, [u32, u32, P(u32), P(u32)]),
     "bhray_set_post_uniforms": (C.c_int, [vp, vp, vp]),
@@ -311,6 +313,7 @@ DIAG_SYMBOLS = {
     "bhray_read_model_vertices": (C.c_int, [vp, u32, vp, u32, vp, u32, P(u32), P(u32)]),
     "bhray_accum_sample_rays": (C.c_int, [vp, u32, P(BhrayRay)]),
     "bhray_accum_set_launch_rays": (C.c_int, [vp, u32]),
+    "bhray_read_sky_pyramid_level": (C.c_int, [vp, u32, vp, sz]),
 }
 
 

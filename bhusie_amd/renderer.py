@@ -51,6 +51,13 @@ def bloom_sizes(frame_w: int, frame_h: int):
     return [(int(a), int(b)) for a, b in zip(w, h)]
 
 
+def sky_pyramid_sizes(w: int, h: int):
+    """[(w, h)] of the levels of the sky filter's pyramid over a w x h texture, level 0 (the texture) included (bhray_sky_pyramid_sizes: host arithmetic)."""
+    n, lw, lh = C.c_uint32(), (C.c_uint32 * 32)(), (C.c_uint32 * 32)()
+    check(lib().bhray_sky_pyramid_sizes(int(w), int(h), C.byref(n), lw, lh))
+    return [(int(lw[i]), int(lh[i])) for i in range(n.value)]
+
+
 def pose_from_euler(rotation, pivot=(0.0, 0.0, 0.0), scale=1.0) -> np.ndarray:
     """The (3, 4) float32 pose [A | t] of RayPass.set_model_pose for a rotation (Euler angles, BlackHole's convention) about `pivot` with a uniform
     scale: A = R * scale, t = pivot - A pivot (bhray_pose_from_euler: host arithmetic)."""
@@ -507,6 +514,20 @@ class RayPass:
         check(self._L.bhray_read_sky(self._h, out.ctypes.data, int(self.cfg.frame_w) * 8), self._h, self._L)
         return out
 
+    # -- footprint-filtered sky pass
+    def set_sky_filter(self, mode):
+        """0 / False: the sky pass is sky.wgsl (the default).  1 / True: from the next resolve_sky (and the sky pass resolve_display runs) every direction pixel whose
+        footprint - the difference to its neighbours' directions - exceeds one sky texel takes 1 to 8 taps from a mip pyramid of the sky texture.  Waits for the
+        frames in flight and builds the pyramid.  BhrayError (BHRAY_E_STATE) on a ctx that splits the frame; trace_rays(sky=True) and accum_* are not affected."""
+        check(self._L.bhray_set_sky_filter(self._h, int(mode)), self._h, self._L)
+
+    def read_sky_pyramid_level(self, level: int, size) -> np.ndarray:
+        """Level `level` >= 1 of the sky pyramid, (h, w, 4) float16; size = (w, h) of that level (sky_pyramid_sizes).  Needs the filter on (bhray_diag.h)."""
+        w, h = int(size[0]), int(size[1])
+        out = np.empty((h, w, 4), dtype=np.float16)
+        check(self._L.bhray_read_sky_pyramid_level(self._h, int(level), out.ctypes.data, w * h), self._h, self._L)
+        return out
+
     # -- display pass: bloom, mix, ACES, FXAA into the RGBA8 sRGB image (DESIGN.md §10)
     def set_post_uniforms(self, fxaa: BhrayFxaaDetails | bytes | None = None, mix: BhrayMixDetails | bytes | float | None = None):
         """The FXAA (16 B) and mix (4 B) uniform blocks, applied from the next resolve_display; None = the reference's defaults."""
@@ -654,6 +675,8 @@ class Renderer:
         self._device_built: list[bool] = []                  # ... and whether its tree was built on the GPU (add_model(build="device"))
         self.mesh_lensing = False                            # lensed meshes (RayPass.set_mesh_lensing): applied before each render
         self._lensing_applied = False                        # what the ctx was last told (its default: off)
+        self.sky_filter = False                              # footprint-filtered sky pass (RayPass.set_sky_filter): applied before save_image's display pass
+        self._sky_filter_applied = False
 
     @property
     def model(self) -> Model | None:
@@ -819,6 +842,10 @@ class Renderer:
         """The reference's Save Image (mod.rs:473-482): the display pass's RGBA8 image of the last frame, written with alpha 255
         (PIL picks the format from the file name; PNG as the reference does)."""
         from PIL import Image
+        if bool(self.sky_filter) != self._sky_filter_applied:
+            self.ray_pass.set_sky_filter(bool(self.sky_filter))
+            self._sky_filter_applied = bool(self.sky_filter)
+            self.ray_pass.resolve_sky()                      # a sky image this frame already has was made under the other mode
         self.ray_pass.resolve_display()
         img = self.ray_pass.read_display()
         img[..., 3] = 255

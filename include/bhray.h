@@ -666,6 +666,31 @@ int bhray_resolve_sky(bhray_ctx* ctx);
 int bhray_read_sky(bhray_ctx* ctx, uint16_t* dst_rgba16f, size_t row_pitch_bytes);
 int bhray_sky_device_ptr(bhray_ctx* ctx, void** dev_ptr, size_t* bytes);
 
+/* Footprint-filtered sky pass.  sky.wgsl takes ONE bilinear sample of the sky texture per direction pixel; near the
+ * Einstein ring a pixel covers tens to hundreds of texels, and the star field aliases.  mode 1: every direction pixel measures its
+ * footprint from the difference between its direction and its neighbours' in the frame (the first of right / left and of below /
+ * above that is a direction pixel too), and where the footprint exceeds one texel takes 1, 2, 4 or 8 taps along the longer
+ * difference from a mip pyramid of the sky texture (level 1 averages sky^4; RGBA16F levels, box filter, clamp-to-edge), each tap a
+ * linear blend of two levels.  A pixel whose footprint is at most one texel, that has no direction neighbour, or whose footprint
+ * is not finite keeps sky.wgsl's value bit for bit; colour pixels pass through as before.  mode 0 (the default): the pass is
+ * sky.wgsl, nothing is allocated or built.  Anything else: BHRAY_E_INVALID.
+ *
+ * Per-ctx state like bhray_set_post_uniforms, applied from the next bhray_resolve_sky on - hence also to the sky pass
+ * bhray_resolve_display runs and to every read of the sky and display images.  The call follows bhray_set_texture's rule: staged
+ * frames are launched and the frames in flight waited for; it then builds the pyramid of the resident sky texture and returns once
+ * it is built (about a third of the texture's texels at 8 bytes each).  bhray_set_texture(BHRAY_TEX_SKY) rebuilds it while the
+ * mode is on; mode 0 frees it.
+ * Not built (mode != 0: BHRAY_E_STATE) for a ctx with device_count >= 2, with gather = BHRAY_GATHER_RCCL or with row_world > 1: a
+ * partition does not hold its neighbours' rows.
+ * Not affected: bhray_trace_rays_sky (a ray list has no neighbours), bhray_accum_* (supersampled already), and the sky sample the
+ * trace kernels take behind a half-transparent disk (those are colour pixels).
+ * Known properties: the footprint is isotropic in angle (towards the poles of the equirect image a texel is narrower in u than assumed);
+ * the u seam is clamp-to-edge, as sky.wgsl's; the differences are one-sided, so they may point left or up.                         */
+int bhray_set_sky_filter(bhray_ctx* ctx, int32_t mode);
+/* Sizes of the pyramid's levels for a w x h texture, level 0 (the texture) included: w[l+1] = (w[l] + 1) >> 1, the same for h, until
+ * both are 1.  Pure host arithmetic.  w or h == 0 or above 2^31 (33 levels), or a NULL pointer: BHRAY_E_INVALID, nothing written.  */
+int bhray_sky_pyramid_sizes(uint32_t w, uint32_t h, uint32_t* levels, uint32_t lw[32], uint32_t lh[32]);
+
 /* Display pass — the rest of the reference's GPU frame after the sky pass (mod.rs:209-324, run at 425-431): 5 bloom-down and
  * 5 bloom-up passes (bloom_down.wgsl, bloom_up.wgsl), mix (mix.wgsl), ACES tone mapping (hdr.wgsl) and FXAA (fxaa.wgsl) into the
  * Rgba8UnormSrgb target the reference's `Save Image` copies out (texture_to_output_buffer, mod.rs:491-526): frame_w x frame_h x 4

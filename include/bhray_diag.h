@@ -181,6 +181,14 @@ int bhray_accum_sample_rays(bhray_ctx* ctx, uint32_t s, bhray_ray* out);
 int bhray_accum_set_launch_rays(bhray_ctx* ctx, uint32_t max_rays);
 
 /* ------------------------------------------------------------------------------------------
+ * The footprint-filtered sky pass (bhray_set_sky_filter)
+ * ---------------------------------------------------------------------------------------- */
+/* Level `level` >= 1 of the sky pyramid as the filter kernel reads it: lw x lh texels (bhray_sky_pyramid_sizes) of four binary16,
+ * row 0 the top; `texels` must be lw * lh.  BHRAY_E_STATE while the mode is off or no sky texture is resident; BHRAY_E_INVALID for
+ * level 0 (that is the texture), a level beyond the top, a NULL dst or another texel count.  Waits.                               */
+int bhray_read_sky_pyramid_level(bhray_ctx* ctx, uint32_t level, uint16_t* dst_rgba16f, size_t texels);
+
+/* ------------------------------------------------------------------------------------------
  * Gather statistics (multi-GPU)
  * ---------------------------------------------------------------------------------------- */
 /* What a ctx gathers with.                                                                                          */
