@@ -291,12 +291,15 @@ size_t display_scratch_bytes(uint32_t fw, uint32_t fh) {
     return (n + (size_t)fw * fh) * sizeof(uint2);          // the nine intermediate bloom levels, then the tone-mapped image
 }
 
-// the decision thresholds of the sRGB encoding: byte >= k <=> v >= srgb_decode((k - 0.5) / 255), formed in double and rounded to f32 once
+// the decision thresholds of the sRGB encoding: byte >= k <=> v >= srgb_decode((k - 0.5) / 255), formed in double and rounded UP to f32 (the
+// smallest f32 not below the threshold): a value equal to a threshold that had been rounded down lies below the real one and takes byte k - 1
 static void srgb_thresholds(float* t) {
     for (int k = 1; k <= 255; k++) {
         const double c = ((double)k - 0.5) / 255.0;
         const double lin = c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4);
-        t[k - 1] = (float)lin;
+        float f = (float)lin;
+        if ((double)f < lin) f = nextafterf(f, INFINITY);
+        t[k - 1] = f;
     }
 }
 

@@ -13,6 +13,10 @@ the frames can be compared bit for bit:
     vector / scalar = vector * (1 / scalar); pow(x, 2 | 4 | 5) by multiplication, pow(x, -0.001) / acos / atan2 / sin / cos / tan by
     the portable forms (oracle/wgsl_builtins.py: a transcription of its own, shared with no restatement), pow(x, 1.3) by glibc powf; min / max / clamp by compare-select; textures RGBA8 unorm,
     bilinear, clamp-to-edge (src/renderer/texture.rs:16-69); float % = truncated remainder; out-of-range textureLoad clamped.
+Beyond what ray.wgsl and sky.wgsl use, the subset holds what the display-pass shaders need (oracle/wgsl_exec_post.py runs them): `switch` with
+multi-value cases and `default` anywhere, entry-point / member / parameter / binding attributes (kept in __meta__), struct value constructors,
+assignment to one component of a vector (`v.y = ...`), `select`, mat3x3 of nine scalars, and compile_source(count=True): a tally of every
+statement, condition outcome and scalar select as it runs.
 Deviation D1 (the Runge-Kutta retry loop of ray.wgsl:425-451 cannot terminate once e_max > 1, because it cannot change h): a `while` loop
 whose variables are bit-identical at the top of two successive passes is left there - which yields exactly what one pass computed.
 
@@ -66,6 +70,8 @@ TEMPLATED = {"vec2", "vec3", "vec4", "mat3x3", "array", "texture_2d", "texture_s
 class Parser:
     def __init__(self, toks):
         self.t, self.i = toks, 0
+        self.pos = {}                   # id(statement | select call node) -> index of its first token (the key of the hit counts)
+        self.meta = {}                  # ("fn", f) | ("param", f, p) | ("field", s, m) | ("gvar", v) -> [(attribute, [argument tokens])]
 
     def peek(self, k=0):
         return self.t[self.i + k]
@@ -110,19 +116,24 @@ class Parser:
         return (name, ())
 
     def attributes(self):
+        out = []
         while self.accept("@"):
-            self.ident()
+            name, args = self.ident(), []
             if self.accept("("):
                 depth = 1
                 while depth:
                     v = self.next()[1]
                     depth += (v == "(") - (v == ")")
+                    if depth and v != ",":
+                        args.append(v)
+            out.append((name, args))
+        return out
 
     # -- module
     def module(self):
         decls = []
         while self.peek()[0] != "eof":
-            self.attributes()
+            attrs = self.attributes()
             kw = self.peek()[1]
             if kw == "const":
                 self.next(); name = self.ident()
@@ -135,23 +146,27 @@ class Parser:
                     while not self.accept(">"):
                         self.next()
                 name = self.ident(); self.expect(":"); ty = self.type_(); self.expect(";")
+                self.meta[("gvar", name)] = attrs
                 decls.append(("gvar", name, ty))
             elif kw == "struct":
                 self.next(); name = self.ident(); self.expect("{")
                 fields = []
                 while not self.accept("}"):
-                    self.attributes()
+                    fattrs = self.attributes()
                     fn = self.ident(); self.expect(":"); ft = self.type_()
+                    self.meta[("field", name, fn)] = fattrs
                     fields.append((fn, ft))
                     self.accept(",")
                 self.accept(";")
                 decls.append(("struct", name, fields))
             elif kw == "fn":
                 self.next(); name = self.ident(); self.expect("(")
+                self.meta[("fn", name)] = attrs
                 params = []
                 while not self.accept(")"):
-                    self.attributes()
+                    pattrs = self.attributes()
                     pn = self.ident(); self.expect(":"); pt = self.type_()
+                    self.meta[("param", name, pn)] = pattrs
                     params.append((pn, pt))
                     self.accept(",")
                 ret = None
@@ -171,9 +186,32 @@ class Parser:
         return out
 
     def statement(self):
+        i0 = self.i
+        st = self._statement()
+        self.pos[id(st)] = i0
+        return st
+
+    def _statement(self):
         k, v = self.peek()
         if v == "{":
             return ("block", self.block())
+        if v == "switch":                   # switch e { case a, b: {..} default: {..} } - `default` in any position, also among a case's values
+            self.next(); sel = self.expr(); self.expect("{")
+            clauses = []
+            while not self.accept("}"):
+                vals = []
+                if self.accept("default"):
+                    vals.append(None)
+                else:
+                    self.expect("case")
+                    while self.peek()[1] not in (":", "{"):
+                        vals.append(None if self.accept("default") else self.expr())
+                        self.accept(",")
+                self.accept(":")
+                clauses.append((vals, self.block()))
+            if sum(v_ is None for vals, _ in clauses for v_ in vals) != 1:
+                raise SyntaxError("wgsl: a switch has exactly one default")
+            return ("switch", sel, clauses)
         if v in ("let", "var"):
             self.next(); name = self.ident()
             ty = self.type_() if self.accept(":") else None
@@ -198,7 +236,7 @@ class Parser:
             self.expect(")")
             return ("for", init, cond, upd, self.block())
         if v == "break":
-            self.next(); self.expect(";"); return ("break",)
+            self.next(); self.expect(";"); return ("break", self.i)          # (its own object: statements are keyed by identity)
         if v == "continue":
             raise SyntaxError("wgsl: `continue` is not in the subset (the shader does not use it)")
         if v == "return":
@@ -253,7 +291,7 @@ class Parser:
         if v in ("true", "false"):
             return ("bool", v == "true")
         if k == "id":
-            targs = ()
+            targs, i0 = (), self.i - 1
             if v in TEMPLATED and self.peek()[1] == "<":
                 self.i -= 1
                 ty = self.type_()
@@ -263,7 +301,9 @@ class Parser:
                 args = []
                 while not self.accept(")"):
                     args.append(self.expr()); self.accept(",")
-                return ("call", v, targs, args)
+                node = ("call", v, targs, args)
+                self.pos[id(node)] = i0
+                return node
             return ("id", v)
         raise SyntaxError("wgsl: unexpected token %r in an expression" % v)
 
@@ -379,6 +419,10 @@ class Struct:
     def __setattr__(self, n, v):
         object.__setattr__(self, n, cv(self.TYPES[n], v))
 
+    @classmethod
+    def zero(cls):
+        return cls(*[zero(t) for _, t in cls.FIELDS])
+
     def copy(self):
         o = object.__new__(type(self))
         for n, _ in self.FIELDS:
@@ -442,6 +486,29 @@ def mk_vec(n, elem, *args):
     if elem in ("i32", "u32"):
         return Vec(int(x) for x in comps)                    # f32 -> i32: truncation toward zero (int() of a float32)
     return Vec(bool(x) for x in comps)
+
+
+def mk_mat3(*args):                   # mat3x3(c0, c1, c2) of three column vectors, or of nine scalars in column-major order
+    if len(args) == 9:
+        return Mat3([Vec(F(x) for x in args[i:i + 3]) for i in (0, 3, 6)])
+    if len(args) != 3 or not all(isinstance(a, Vec) and len(a.c) == 3 for a in args):
+        raise TypeError("mat3x3 from %d arguments" % len(args))
+    return Mat3(args)
+
+
+def set_member(obj, name, v):         # `obj.name = v`: a component of a vector (vectors are immutable here: a new one is returned) or a field
+    if isinstance(obj, Vec):
+        comps = list(obj.c)
+        comps[SWZ[name]] = int(v) if obj._is_int() else (bool(v) if isinstance(comps[0], (bool, np.bool_)) else F(v))
+        return Vec(comps)
+    setattr(obj, name, v)
+    return obj
+
+
+def bi_select(f, t, cond):            # select(f, t, cond): t where cond, else f; a vector condition selects per component
+    if isinstance(cond, Vec):
+        return Vec((y if c else x) for x, y, c in zip(f.c, t.c, cond.c))
+    return conc(t) if cond else conc(f)
 
 
 def _div(a, b):
@@ -639,12 +706,15 @@ class StorageArray:
 # ------------------------------------------------------------------------------------------------------------------ code generation
 BUILTINS = {"normalize", "pow", "length", "dot", "abs", "distance", "max", "cross", "textureStore", "min", "clamp", "textureLoad", "sqrt", "mix",
             "determinant", "all", "textureSampleLevel", "sin", "cos", "atan2", "tan", "smoothstep", "inverseSqrt", "floor", "acos",
-            "textureDimensions", "i32", "f32", "u32"}
+            "textureDimensions", "i32", "f32", "u32", "select", "textureSample"}
 
 
 class Gen:
-    def __init__(self, decls):
+    def __init__(self, decls, pos=None, count=False):
         self.decls = decls
+        self.pos, self.count = pos or {}, count          # count: every statement, condition outcome and scalar select is tallied as it runs
+        self.sites = {"stmt": {}, "cond": {}, "select": {}}   # kind -> function -> [token index]
+        self.breakable = []
         self.fns = {d[1]: d for d in decls if d[0] == "fn"}
         self.structs = {d[1]: d for d in decls if d[0] == "struct"}
         self.consts = [d for d in decls if d[0] == "const"]
@@ -710,7 +780,11 @@ class Gen:
                 elem = targs[0][0] if targs else "f32"
                 return "mk_vec(%d, %r, %s)" % (int(name[3]), elem, ", ".join(args))
             if name == "mat3x3":
-                return "Mat3([%s])" % ", ".join(args)
+                return "mk_mat3(%s)" % ", ".join(args)
+            if name == "select" and self.count and name not in self.fns:
+                i = self.pos[id(e)]
+                self.sites["select"].setdefault(self.fname, []).append(i)
+                return "bi_select(%s, %s, _sel(%d, %s))" % (args[0], args[1], i, args[2])
             if name == "array":
                 return "zero(%s)" % self.ty(("array", targs))
             if name in self.structs:
@@ -741,6 +815,9 @@ class Gen:
                 out |= self.assigned(st[2])
             elif k == "for":
                 out |= self.assigned([x for x in (st[1], st[3]) if x is not None]) | self.assigned(st[4])
+            elif k == "switch":
+                for _, body in st[2]:
+                    out |= self.assigned(body)
         return out
 
     def emit(self, ind, s):
@@ -754,13 +831,26 @@ class Gen:
             self.stmt(st, ind)
         self.scopes.pop()
 
+    def cond(self, st, e):                # the condition of an `if` / a loop: its outcome is tallied under the statement's token index
+        if not self.count or id(st) not in self.pos:
+            return self.expr(e)
+        i = self.pos[id(st)]
+        self.sites["cond"].setdefault(self.fname, []).append(i)
+        return "_br(%d, %s)" % (i, self.expr(e))
+
     def stmt(self, st, ind):
         k = st[0]
+        if self.count and id(st) in self.pos:
+            i = self.pos[id(st)]
+            self.sites["stmt"].setdefault(self.fname, []).append(i)
+            self.emit(ind, "_HIT[%d] += 1" % i)
         if k in ("let", "var"):
             _, name, ty, e = st
             val = None
             if e is not None:
                 val = "cv(%s, %s)" % (self.ty(ty), self.expr(e)) if ty is not None else "conc(%s)" % self.expr(e)
+            elif ty[0] in self.structs:
+                val = "S_%s.zero()" % ty[0]                   # this module's own struct of that name (another module may declare one too)
             else:
                 val = "zero(%s)" % self.ty(ty)
             py = self.fresh(name)
@@ -772,14 +862,18 @@ class Gen:
             if op != "=":
                 b = op[0]
                 r = "_div(%s, %s)" % (tgt, r) if b == "/" else ("_mod(%s, %s)" % (tgt, r) if b == "%" else "(%s %s %s)" % (tgt, b, r))
-            self.emit(ind, "%s = conc(%s)" % (tgt, r))
+            if lhs[0] == "member" and len(lhs[2]) == 1 and lhs[2] in SWZ:     # `v.y = ...`: one component of a vector (or a field so named)
+                base = self.expr(lhs[1])
+                self.emit(ind, "%s = set_member(%s, %r, conc(%s))" % (base, base, lhs[2], r))
+            else:
+                self.emit(ind, "%s = conc(%s)" % (tgt, r))
         elif k == "expr":
             self.emit(ind, self.expr(st[1]))
         elif k == "block":
             self.emit(ind, "if True:")
             self.stmts(st[1], ind + 1)
         elif k == "if":
-            self.emit(ind, "if %s:" % self.expr(st[1]))
+            self.emit(ind, "if %s:" % self.cond(st, st[1]))
             self.stmts(st[2], ind + 1)
             if st[3] is not None:
                 self.emit(ind, "else:")
@@ -800,18 +894,40 @@ class Gen:
             self.emit(ind + 1, "_k = _key((%s,))" % ", ".join(roots))
             self.emit(ind + 1, "if _k == %s: break" % prev)
             self.emit(ind + 1, "%s = _k" % prev)
+            self.breakable.append("loop")
             self.stmts(st[2], ind + 1)
+            self.breakable.pop()
         elif k == "for":
             _, init, cond, upd, body = st
             self.scopes.append({})
             if init is not None:
                 self.stmt(init, ind)
-            self.emit(ind, "while %s:" % (self.expr(cond) if cond is not None else "True"))
+            self.emit(ind, "while %s:" % (self.cond(st, cond) if cond is not None else "True"))
+            self.breakable.append("loop")
             self.stmts(body, ind + 1)                         # (no `continue` in the subset: the update always runs)
+            self.breakable.pop()
             if upd is not None:
                 self.stmt(upd, ind + 1)
             self.scopes.pop()
+        elif k == "switch":
+            _, sel, clauses = st
+            t = self.fresh("switch")
+            self.emit(ind, "%s = %s" % (t, self.expr(sel)))
+            self.breakable.append("switch")
+            kw = "if"
+            for vals, body in clauses:                        # the clause holding `default` is the else, wherever it stands in the text
+                if None in vals:
+                    default = body
+                    continue
+                self.emit(ind, "%s %s in (%s,):" % (kw, t, ", ".join(self.expr(v) for v in vals)))
+                self.stmts(body, ind + 1)
+                kw = "elif"
+            self.emit(ind, "else:" if kw == "elif" else "if True:")
+            self.stmts(default, ind + 1)
+            self.breakable.pop()
         elif k == "break":
+            if self.breakable and self.breakable[-1] == "switch":
+                raise SyntaxError("wgsl: `break` out of a switch clause is not in the subset")
             self.emit(ind, "break")
         elif k == "return":
             self.emit(ind, "return" if st[1] is None else "return %s" % ("cv(%s, %s)" % (self.ty(self.ret), self.expr(st[1])) if self.ret else self.expr(st[1])))
@@ -830,7 +946,7 @@ class Gen:
             self.emit(0, "C_%s = %s" % (name, "cv(%s, %s)" % (self.ty(ty), val) if ty is not None else val))
             self.emit(0, "CONST_SIZES[%r] = C_%s" % (name, name))
         for _, name, params, ret, body in [d for d in self.decls if d[0] == "fn"]:
-            self.ret = ret
+            self.ret, self.fname = ret, name
             self.scopes = [{p: "p_" + p for p, _ in params}]
             self.emit(0, "def fn_%s(%s):" % (name, ", ".join("p_" + p for p, _ in params)))
             self.stmts(body, 1)
@@ -841,14 +957,33 @@ SKY_SHADER = "/root/reference/src/renderer/shaders/sky.wgsl"
 _COMPILED = {}
 
 
-def compile_source(src, name="<wgsl>"):
+def compile_source(src, name="<wgsl>", count=False):
     """Translates WGSL text (the subset above) and returns the namespace holding its functions (fn_<name>), constants (C_<name>) and
-    struct classes (S_<name>); module-scope `var`s are looked up as G_<name> and must be bound by the caller."""
-    decls = Parser(tokenize(src)).module()
-    code = Gen(decls).module()
+    struct classes (S_<name>); module-scope `var`s are looked up as G_<name> and must be bound by the caller.  __decls__ is the parsed
+    module, __meta__ the attributes of its functions, parameters, struct members and module-scope variables.
+    count=True: every statement of every function is tallied as it runs - _HIT[token index of the statement], _BR[(token index of the
+    `if` / `for`, outcome of its condition)], _SEL[(token index of a select() with a scalar condition, the condition)]; __sites__ lists
+    the counted places per function, so that a place never reached shows as a missing key."""
+    import collections
+    parser = Parser(tokenize(src))
+    decls = parser.module()
+    gen = Gen(decls, parser.pos, count)
+    code = gen.module()
     ns = {k: v for k, v in globals().items() if not k.startswith("__")}
+    hit, br, sel = collections.Counter(), collections.Counter(), collections.Counter()
+
+    def _br(i, c):
+        c = bool(c)
+        br[(i, c)] += 1
+        return c
+
+    def _sel(i, c):
+        if not isinstance(c, Vec):
+            sel[(i, bool(c))] += 1
+        return c
+    ns.update(_HIT=hit, _BR=br, _SEL=sel, _br=_br, _sel=_sel)
     exec(compile(code, name, "exec"), ns)
-    ns["__source__"] = code
+    ns.update(__source__=code, __decls__=decls, __meta__=parser.meta, __sites__=gen.sites)
     return ns
 
 

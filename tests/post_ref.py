@@ -140,13 +140,22 @@ def aces(hdr):
     return np.fmin(np.fmax(matvec(M2, q), F(0.0)), F(1.0))
 
 
-def mix_hdr(sky, bloom_rgb, ratio):
-    """mix.wgsl (r * sky + (1 - r) * bloom, alpha included: bloom alpha is 1.0) -> fp16, then hdr.wgsl -> fp16 (alpha kept)"""
+def mix(sky, bloom_rgb, ratio):
+    """mix.wgsl (r * sky + (1 - r) * bloom, alpha included: bloom alpha is 1.0) -> fp16"""
     r = F(ratio)
     r1 = F(1.0) - r
     bl = np.concatenate([bloom_rgb, np.ones(bloom_rgb.shape[:2] + (1,), dtype=f32)], axis=-1)
-    mx = to16(r * sky + r1 * bl)
+    return to16(r * sky + r1 * bl)
+
+
+def hdr(mx):
+    """hdr.wgsl over the mixed image -> fp16 (alpha kept)"""
     return to16(np.concatenate([aces(mx[..., :3]), mx[..., 3:4]], axis=-1))
+
+
+def mix_hdr(sky, bloom_rgb, ratio):
+    """mix.wgsl -> fp16, then hdr.wgsl -> fp16"""
+    return hdr(mix(sky, bloom_rgb, ratio))
 
 
 def luma(c):
@@ -247,9 +256,12 @@ def fxaa(tone, details=FXAA_DEFAULT):
 
 
 def srgb_thresholds():
-    """t_k = srgb_decode((k - 0.5) / 255), k = 1..255, in double, rounded to f32: byte >= k <=> value >= t_k"""
+    """t_k = srgb_decode((k - 0.5) / 255), k = 1..255, in double, rounded UP to f32 (the smallest f32 >= the threshold, so that for every
+    f32 value: value >= t_k <=> value >= the double threshold): byte >= k <=> value >= t_k"""
     c = (np.arange(1, 256, dtype=np.float64) - 0.5) / 255.0
-    return np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4).astype(f32)
+    lin = np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4)
+    t = lin.astype(f32)
+    return np.where(t.astype(np.float64) < lin, np.nextafter(t, f32(np.inf)), t).astype(f32)
 
 
 _THR = srgb_thresholds()
