@@ -17,10 +17,10 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 
 from ._lib import lib, LibraryMissing, LIB_PATH  # noqa: F401
 from .layouts import (BhrayConfig, BhrayCounters, BhrayTiming, BhrayDetails, BhrayCameraUniform,  # noqa: F401
-                      BhrayBlackHoleUniform, BhrayBlackHole, BhrayFxaaDetails, BhrayMixDetails, BhrayModelDesc, BhrayNode, BhrayRay, BhrayRayRecord, BhrayPathPoint, PATH_POINT_DTYPE, BhrayTriangle,
+                      BhrayBlackHoleUniform, BhrayBlackHole, BhrayFxaaDetails, BhrayMixDetails, BhrayModelDesc, BhrayNode, BhrayRay, BhrayRayRecord, BhrayPathPoint, PATH_POINT_DTYPE, BhrayTriangle, BhrayAccumAdaptive, BhrayAccumAdaptiveInfo,
                       HIT_NONE, HIT_HORIZON, HIT_DISK, HIT_MESH, HIT_UNUSABLE,
                       BhrayError, check)
 from .scene import Camera, BlackHole, RayDetails  # noqa: F401
 from .model import Model, load_model  # noqa: F401
 from . import cameras  # noqa: F401
-from .renderer import RAY_RECORD_DTYPE, RayPass, Renderer, PinnedFrame, ladder_from_base, ladder_for_frame, comm_unique_id, post_defaults, bloom_sizes, sky_pyramid_sizes, partition_rows, config_partition_rows, balance_slabs, rebalance_slabs, pose_from_euler  # noqa: F401
+from .renderer import RAY_RECORD_DTYPE, AdaptiveStill, RayPass, Renderer, PinnedFrame, ladder_from_base, ladder_for_frame, comm_unique_id, post_defaults, bloom_sizes, sky_pyramid_sizes, partition_rows, config_partition_rows, balance_slabs, rebalance_slabs, pose_from_euler  # noqa: F401

@@ -16,8 +16,6 @@
 namespace bhray {
 namespace {
 
-__device__ __forceinline__ bool finite_(float x) { return (f2u(x) & 0x7f800000u) != 0x7f800000u; }
-
 // record i = j * npix + p: sample s0 + j through frame pixel p = y * frame_w + x, i.e. pixel (crop_x + x, crop_y + y) of the last level
 __global__ __launch_bounds__(256) void accum_gen_kernel(const AccumGen g, float4* __restrict__ rays) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -33,21 +31,6 @@ __global__ __launch_bounds__(256) void accum_gen_kernel(const AccumGen g, float4
     const F3 rdir = normalize((ld3(g.right) * posx + ld3(g.up) * posy) + ld3(g.fwd_ff));
     rays[2 * i] = make_float4(g.cam[0], g.cam[1], g.cam[2], 0.0f);
     rays[2 * i + 1] = make_float4(rdir.x, rdir.y, rdir.z, 0.0f);
-}
-
-// sky.wgsl:19-26 without the store's binary16 rounding: sky_kernel's operations (bhray_kernels.hip)
-__device__ __forceinline__ float4 resolve(const TexDev& sky, float4 p) {
-    if (p.w == 0.0f) {
-        const float theta = bh_atan2(sqrtf(p.x * p.x + p.z * p.z), p.y);
-        const float phi = bh_atan2(p.z, p.x);
-        const float PI_F = 3.1415926f;
-        float u = (phi + 2.6f * PI_F) / (2.0f * PI_F);
-        float v = (PI_F - theta) / PI_F;
-        u = u - truncf(u); v = v - truncf(v);
-        const float4 sc = sample_bilinear<false>(sky, u, v);
-        p = make_float4((sc.x * sc.x) * (sc.x * sc.x), (sc.y * sc.y) * (sc.y * sc.y), (sc.z * sc.z) * (sc.z * sc.z), 1.0f);
-    }
-    return p;
 }
 
 __global__ __launch_bounds__(256) void accum_add_kernel(const TexDev sky, const float4* __restrict__ results, float4* __restrict__ sum, uint32_t npix, uint32_t k) {

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "bhray_accum.h"
+#include "bhray_adapt.h"
 #include "bhray_bvh_core.h"
 #include "bhray_dev.h"
 #include "bhray_internal.h"
@@ -221,6 +222,12 @@ struct bhray_dev {
     uint32_t a_samples = 0;                // sample indices enqueued since the last begin: the next add starts there
     uint32_t a_launch_rays = 0;            // dev_accum_set_launch_rays: rays per trace launch (0: BHRAY_ACCUM_LAUNCH_RAYS)
     bool a_begun = false;
+    // adaptive stills (dev_accum_add_adaptive): allocated by the first adaptive call or selection; everything runs on q_stream
+    uint4* a_state = nullptr;              // frame_w * frame_h records (S1, S2, issued, 0) beside a_sum
+    uint32_t* a_list = nullptr;            // the selection's compacted pixel indices, frame_w * frame_h words; the counts read's staging too
+    uint32_t* a_ctl = nullptr; uint32_t* a_hctl = nullptr;   // the selection's control block ([0] count, [1] largest issued): device, and the pinned word it is copied to
+    int a_mode = 0;                        // since the last begin: 0 no sample yet, 1 dev_accum_add's, 2 adaptive (a_samples is then `reach`)
+    uint32_t a_min = 0, a_round = 0;       // the first adaptive call's min_samples / round_samples since begin: what later calls must repeat
     bhray::ReadRing reads;                 // tickets of the asynchronous hand-off (dev_read_async)
     std::string err;
 };
@@ -442,7 +449,8 @@ void dev_destroy(bhray_dev* c) {
     if (c->q_dpts) (void)hipFree(c->q_dpts);
     if (c->q_hcnt) (void)hipHostFree(c->q_hcnt);
     if (c->q_dcnt) (void)hipFree(c->q_dcnt);
-    for (void* p : {(void*)c->a_sum, (void*)c->a_mean, (void*)c->a_mean16, (void*)c->a_scratch, (void*)c->a_disp, (void*)c->a_rays, (void*)c->a_res}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)c->a_sum, (void*)c->a_mean, (void*)c->a_mean16, (void*)c->a_scratch, (void*)c->a_disp, (void*)c->a_rays, (void*)c->a_res, (void*)c->a_state, (void*)c->a_list, (void*)c->a_ctl}) if (p) (void)hipFree(p);
+    if (c->a_hctl) (void)hipHostFree(c->a_hctl);
     for (hipEvent_t e : {c->q_begin, c->q_done, c->q_uploaded}) if (e) (void)hipEventDestroy(e);
     if (c->q_stream) (void)hipStreamDestroy(c->q_stream);
     for (Slot& S : c->slots) {
@@ -1399,6 +1407,19 @@ void accum_gen_args(bhray_dev* c, AccumGen& g) {
     g.crop_x = c->cfg.crop_x; g.crop_y = c->cfg.crop_y; g.frame_w = c->cfg.frame_w;
     g.npix = c->cfg.frame_w * c->cfg.frame_h;
 }
+
+// a_rays / a_res hold `need` rays: grow-only, behind a wait for the stream
+int accum_staging(bhray_dev* c, size_t need) {
+    if (need <= c->a_cap) return BHRAY_OK;
+    HIPCHK(c, hipStreamSynchronize(c->q_stream));
+    if (c->a_rays) (void)hipFree(c->a_rays);
+    if (c->a_res) (void)hipFree(c->a_res);
+    c->a_rays = c->a_res = nullptr; c->a_cap = 0;
+    HIPCHK(c, hipMalloc(&c->a_rays, need * sizeof(bhray_ray)));
+    HIPCHK(c, hipMalloc(&c->a_res, need * sizeof(float4)));
+    c->a_cap = need;
+    return BHRAY_OK;
+}
 }  // namespace
 
 int dev_accum_begin(bhray_dev* c) {
@@ -1411,7 +1432,9 @@ int dev_accum_begin(bhray_dev* c) {
     if (!c->a_sum) HIPCHK(c, hipMalloc(&c->a_sum, npix * sizeof(float4)));
     if (!c->a_mean) HIPCHK(c, hipMalloc(&c->a_mean, npix * sizeof(float4)));
     HIPCHK(c, hipMemsetAsync(c->a_sum, 0, npix * sizeof(float4), c->q_stream));          // behind the samples of the accumulation before
+    if (c->a_state) HIPCHK(c, hipMemsetAsync(c->a_state, 0, npix * sizeof(uint4), c->q_stream));
     c->a_samples = 0;
+    c->a_mode = 0; c->a_min = c->a_round = 0;
     c->a_begun = true;
     return BHRAY_OK;
 }
@@ -1421,6 +1444,7 @@ int dev_accum_add(bhray_dev* c, uint32_t samples) {
     if (!c->a_begun) return fail(c, BHRAY_E_STATE, "bhray_accum_add: bhray_accum_begin has not been called");
     { int rc = accum_refused(c, "bhray_accum_add"); if (rc) return rc; }
     { int rc = rays_refused(c, "bhray_accum_add"); if (rc) return rc; }
+    if (c->a_mode == 2) return fail(c, BHRAY_E_STATE, "bhray_accum_add: this accumulation is adaptive (bhray_accum_add_adaptive); bhray_accum_begin starts another");
     if (samples > BHRAY_ACCUM_MAX_SAMPLES - c->a_samples)
         return fail(c, BHRAY_E_INVALID, "bhray_accum_add: %u + %u samples exceed BHRAY_ACCUM_MAX_SAMPLES", c->a_samples, samples);
     if (samples == 0) return BHRAY_OK;
@@ -1431,16 +1455,7 @@ int dev_accum_add(bhray_dev* c, uint32_t samples) {
     accum_gen_args(c, g);
     const uint32_t launch_rays = c->a_launch_rays ? c->a_launch_rays : ACCUM_LAUNCH_RAYS;
     const uint32_t kmax = std::max<uint32_t>(1u, launch_rays / g.npix);                   // a small frame takes several samples per launch: the device stays filled
-    const size_t need = (size_t)std::min(samples, kmax) * g.npix;
-    if (need > c->a_cap) {                                        // grow-only staging
-        HIPCHK(c, hipStreamSynchronize(c->q_stream));
-        if (c->a_rays) (void)hipFree(c->a_rays);
-        if (c->a_res) (void)hipFree(c->a_res);
-        c->a_rays = c->a_res = nullptr; c->a_cap = 0;
-        HIPCHK(c, hipMalloc(&c->a_rays, need * sizeof(bhray_ray)));
-        HIPCHK(c, hipMalloc(&c->a_res, need * sizeof(float4)));
-        c->a_cap = need;
-    }
+    { int rc = accum_staging(c, (size_t)std::min(samples, kmax) * g.npix); if (rc) return rc; }
     TexDev sky; sky.rgba = c->tex[BHRAY_TEX_SKY]; sky.w = c->tex_w[BHRAY_TEX_SKY]; sky.h = c->tex_h[BHRAY_TEX_SKY];
     for (uint32_t left = samples; left != 0;) {                   // in stream order: launch i + 1 rewrites the staging behind launch i's add
         const uint32_t k = std::min(left, kmax);
@@ -1449,7 +1464,133 @@ int dev_accum_add(bhray_dev* c, uint32_t samples) {
         { int rc = enqueue_rays(c, c->a_rays, k * g.npix, c->a_res); if (rc) return rc; }
         HIPCHK(c, launch_accum_add(sky, c->a_res, c->a_sum, g.npix, k, c->q_stream));
         c->a_samples += k; left -= k;
+        c->a_mode = 1;
     }
+    return BHRAY_OK;
+}
+
+// ---- adaptive stills (include/bhray.h: bhray_accum_add_adaptive) -------------------------------------------------
+namespace {
+int adaptive_params_bad(bhray_dev* c, const char* name, const bhray_accum_adaptive* a) {
+    if (!a) return fail(c, BHRAY_E_INVALID, "%s: NULL params", name);
+    if (a->struct_size != sizeof(bhray_accum_adaptive)) return fail(c, BHRAY_E_INVALID, "%s: struct_size %u, expected %zu", name, a->struct_size, sizeof(bhray_accum_adaptive));
+    if (a->min_samples < 2 || a->max_samples < a->min_samples || a->max_samples > BHRAY_ACCUM_MAX_SAMPLES || a->round_samples == 0 ||
+        (a->max_samples - a->min_samples) % a->round_samples != 0)
+        return fail(c, BHRAY_E_INVALID, "%s: min_samples %u, max_samples %u, round_samples %u: need 2 <= min <= max <= %u, round >= 1 and (max - min) %% round == 0", name,
+                    a->min_samples, a->max_samples, a->round_samples, BHRAY_ACCUM_MAX_SAMPLES);
+    if (!std::isfinite(a->tolerance) || !std::isfinite(a->dark) || a->tolerance < 0.0f || a->dark < 0.0f)
+        return fail(c, BHRAY_E_INVALID, "%s: tolerance and dark must be finite and >= 0", name);
+    if (c->a_mode == 2 && (a->min_samples != c->a_min || a->round_samples != c->a_round))
+        return fail(c, BHRAY_E_INVALID, "%s: min_samples %u / round_samples %u differ from this accumulation's %u / %u", name, a->min_samples, a->round_samples, c->a_min, c->a_round);
+    return BHRAY_OK;
+}
+
+// the state records, the list and the control block: allocated on first use, the records cleared behind whatever the stream holds
+int ensure_adaptive(bhray_dev* c) {
+    const size_t npix = (size_t)c->cfg.frame_w * c->cfg.frame_h;
+    if (!c->a_state) {
+        HIPCHK(c, hipMalloc(&c->a_state, npix * sizeof(uint4)));
+        HIPCHK(c, hipMemsetAsync(c->a_state, 0, npix * sizeof(uint4), c->q_stream));
+    }
+    if (!c->a_list) HIPCHK(c, hipMalloc(&c->a_list, npix * sizeof(uint32_t)));
+    if (!c->a_ctl) HIPCHK(c, hipMalloc(&c->a_ctl, 2 * sizeof(uint32_t)));
+    if (!c->a_hctl) HIPCHK(c, hipHostMalloc(&c->a_hctl, 2 * sizeof(uint32_t)));
+    return BHRAY_OK;
+}
+
+// one selection: clear the control block, select, copy the block to the pinned word and wait for it.  n: pixels selected, top: the largest issued among them
+int adaptive_select(bhray_dev* c, const bhray_accum_adaptive& a, uint32_t& n, uint32_t& top) {
+    const uint32_t npix = c->cfg.frame_w * c->cfg.frame_h;
+    HIPCHK(c, hipMemsetAsync(c->a_ctl, 0, 2 * sizeof(uint32_t), c->q_stream));
+    HIPCHK(c, launch_adapt_select(c->a_sum, c->a_state, npix, a.max_samples, a.tolerance, a.dark, c->a_list, c->a_ctl, c->q_stream));
+    HIPCHK(c, hipMemcpyAsync(c->a_hctl, c->a_ctl, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->q_stream));
+    HIPCHK(c, hipStreamSynchronize(c->q_stream));
+    n = c->a_hctl[0]; top = c->a_hctl[1];
+    if (n > npix) return fail(c, BHRAY_E_HIP, "the adaptive selection returned %u of %u pixels", n, npix);
+    return BHRAY_OK;
+}
+
+// `count` more samples for the n listed pixels (list == nullptr: every pixel), in chunks of launch_rays / n sub-samples: gen, trace, add; the last add advances issued
+int adaptive_round(bhray_dev* c, AccumGen& g, const TexDev& sky, const uint32_t* list, uint32_t n, uint32_t count) {
+    const uint32_t launch_rays = c->a_launch_rays ? c->a_launch_rays : ACCUM_LAUNCH_RAYS;
+    const uint32_t kmax = std::max<uint32_t>(1u, launch_rays / n);
+    { int rc = accum_staging(c, (size_t)std::min(count, kmax) * n); if (rc) return rc; }
+    for (uint32_t j0 = 0; j0 < count;) {                          // in stream order: chunk i + 1 rewrites the staging behind chunk i's add
+        const uint32_t k = std::min(count - j0, kmax);
+        g.k = k;
+        HIPCHK(c, launch_adapt_gen(g, list, n, j0, c->a_state, c->a_rays, c->q_stream));
+        { int rc = enqueue_rays(c, c->a_rays, k * n, c->a_res); if (rc) return rc; }
+        j0 += k;
+        HIPCHK(c, launch_adapt_add(sky, c->a_res, list, n, k, j0 == count ? count : 0u, c->a_sum, c->a_state, c->q_stream));
+    }
+    return BHRAY_OK;
+}
+}  // namespace
+
+int dev_accum_add_adaptive(bhray_dev* c, const bhray_accum_adaptive* params, bhray_accum_adaptive_info* info) {
+    if (!c) return BHRAY_E_INVALID;
+    if (!c->a_begun) return fail(c, BHRAY_E_STATE, "bhray_accum_add_adaptive: bhray_accum_begin has not been called");
+    { int rc = accum_refused(c, "bhray_accum_add_adaptive"); if (rc) return rc; }
+    { int rc = rays_refused(c, "bhray_accum_add_adaptive"); if (rc) return rc; }
+    if (c->a_mode == 1) return fail(c, BHRAY_E_STATE, "bhray_accum_add_adaptive: this accumulation holds bhray_accum_add's samples; bhray_accum_begin starts another");
+    { int rc = adaptive_params_bad(c, "bhray_accum_add_adaptive", params); if (rc) return rc; }
+    const bhray_accum_adaptive a = *params;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = launch_batch(c); if (rc) return rc; }              // the staged frames first: they keep the uniforms they were staged with
+    { int rc = ensure_query(c); if (rc) return rc; }
+    { int rc = ensure_adaptive(c); if (rc) return rc; }
+    AccumGen g;
+    accum_gen_args(c, g);
+    TexDev sky; sky.rgba = c->tex[BHRAY_TEX_SKY]; sky.w = c->tex_w[BHRAY_TEX_SKY]; sky.h = c->tex_h[BHRAY_TEX_SKY];
+    bhray_accum_adaptive_info I{};
+    if (c->a_mode == 0) {                                         // the first round: every pixel, no test
+        { int rc = adaptive_round(c, g, sky, nullptr, g.npix, a.min_samples); if (rc) return rc; }
+        c->a_mode = 2; c->a_min = a.min_samples; c->a_round = a.round_samples; c->a_samples = a.min_samples;
+        I.rounds = 1; I.rays = (uint64_t)g.npix * a.min_samples;
+    }
+    for (;;) {
+        uint32_t n = 0, top = 0;
+        { int rc = adaptive_select(c, a, n, top); if (rc) return rc; }
+        I.active_last = n;
+        if (n == 0) break;
+        { int rc = adaptive_round(c, g, sky, c->a_list, n, a.round_samples); if (rc) return rc; }
+        c->a_samples = std::max(c->a_samples, top + a.round_samples);
+        I.rounds++; I.rays += (uint64_t)n * a.round_samples;
+    }
+    I.reach = c->a_samples;
+    if (info) *info = I;
+    return BHRAY_OK;
+}
+
+int dev_accum_read_counts(bhray_dev* c, uint32_t* dst, size_t pitch) {
+    if (!c) return BHRAY_E_INVALID;
+    if (!c->a_begun) return fail(c, BHRAY_E_STATE, "bhray_accum_read_counts: bhray_accum_begin has not been called");
+    if (c->a_mode != 2) return fail(c, BHRAY_E_STATE, "bhray_accum_read_counts: this accumulation is not adaptive");
+    const size_t rowb = (size_t)c->cfg.frame_w * sizeof(uint32_t);
+    if (!dst || pitch < rowb) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_adapt_counts(c->a_state, c->a_list, c->cfg.frame_w * c->cfg.frame_h, c->q_stream));   // (the list is idle between two selections)
+    { int rc = query_wait(c); if (rc) return rc; }
+    HIPCHK(c, hipMemcpy2D(dst, pitch, c->a_list, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost));
+    return BHRAY_OK;
+}
+
+// bhray_diag.h: one selection under `params`, no sampling
+int dev_accum_active_pixels(bhray_dev* c, const bhray_accum_adaptive* params, uint32_t* out, uint32_t cap, uint32_t* n_out) {
+    if (!c) return BHRAY_E_INVALID;
+    if (!n_out || (cap != 0 && !out)) return fail(c, BHRAY_E_INVALID, "bhray_accum_active_pixels: bad arguments");
+    if (!c->a_begun) return fail(c, BHRAY_E_STATE, "bhray_accum_active_pixels: bhray_accum_begin has not been called");
+    { int rc = accum_refused(c, "bhray_accum_active_pixels"); if (rc) return rc; }
+    if (c->a_mode == 1) return fail(c, BHRAY_E_STATE, "bhray_accum_active_pixels: this accumulation is not adaptive");
+    { int rc = adaptive_params_bad(c, "bhray_accum_active_pixels", params); if (rc) return rc; }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = ensure_query(c); if (rc) return rc; }
+    { int rc = ensure_adaptive(c); if (rc) return rc; }
+    uint32_t n = 0, top = 0;
+    { int rc = adaptive_select(c, *params, n, top); if (rc) return rc; }
+    *n_out = n;
+    const uint32_t m = std::min(n, cap);
+    if (m) HIPCHK(c, hipMemcpy(out, c->a_list, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return BHRAY_OK;
 }
 

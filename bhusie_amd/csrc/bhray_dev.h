@@ -127,6 +127,10 @@ int  dev_accum_read(bhray_dev* c, float* dst_rgba32f, size_t pitch);
 int  dev_accum_read_display(bhray_dev* c, uint8_t* dst_rgba8, size_t pitch, const bhray_fxaa_details* fxaa, const bhray_mix_details* mix);
 int  dev_accum_sample_rays(bhray_dev* c, uint32_t s, bhray_ray* out);   // the generated records of sample s: frame_w * frame_h
 int  dev_accum_set_launch_rays(bhray_dev* c, uint32_t max_rays);        // rays per trace launch of dev_accum_add; 0: the default
+// adaptive stills: min_samples for every pixel, then rounds of select - wait for the count - sample the failing pixels, until a selection is empty; blocks
+int  dev_accum_add_adaptive(bhray_dev* c, const bhray_accum_adaptive* params, bhray_accum_adaptive_info* info);
+int  dev_accum_read_counts(bhray_dev* c, uint32_t* dst, size_t pitch);  // issued per pixel; BHRAY_E_STATE unless the accumulation is adaptive
+int  dev_accum_active_pixels(bhray_dev* c, const bhray_accum_adaptive* params, uint32_t* out, uint32_t cap, uint32_t* n);   // one selection, no sampling
 int  dev_set_mesh_lensing(bhray_dev* c, int32_t on);       // from the next dev_render; BHRAY_E_STATE for on != 0 on a BHRAY_F_LITERAL / BHRAY_F_EVAL_FMA engine
 // another row partition (bhray_config.partition / stripe_rows / slab_row0 / row_rank / row_world) for the same frame; synchronises the engine
 int  dev_set_partition(bhray_dev* c, uint32_t partition, uint32_t stripe_rows, const uint32_t* slab_row0, uint32_t row_rank, uint32_t row_world);

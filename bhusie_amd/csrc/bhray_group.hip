@@ -1652,6 +1652,29 @@ int bhray_accum_read_display(bhray_ctx* c, uint8_t* dst, size_t pitch) {
     DEV(c, c->parts[0].dev, dev_accum_read_display(c->parts[0].dev, dst, pitch, &c->post_fxaa, &c->post_mix));
     return BHRAY_OK;
 }
+int bhray_accum_add_adaptive(bhray_ctx* c, const bhray_accum_adaptive* params, bhray_accum_adaptive_info* info) {
+    if (!c) return BHRAY_E_INVALID;
+    if (!params) return gfail(c, BHRAY_E_INVALID, "bhray_accum_add_adaptive: NULL params");
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_accum_add_adaptive"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_accum_add_adaptive(c->parts[0].dev, params, info));
+    return BHRAY_OK;
+}
+int bhray_accum_read_counts(bhray_ctx* c, uint32_t* dst, size_t pitch) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_accum_read_counts"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_accum_read_counts(c->parts[0].dev, dst, pitch));
+    return BHRAY_OK;
+}
+int bhray_accum_active_pixels(bhray_ctx* c, const bhray_accum_adaptive* params, uint32_t* out, uint32_t cap, uint32_t* n) {
+    if (!c) return BHRAY_E_INVALID;
+    if (!params) return gfail(c, BHRAY_E_INVALID, "bhray_accum_active_pixels: NULL params");
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_accum_active_pixels"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_accum_active_pixels(c->parts[0].dev, params, out, cap, n));
+    return BHRAY_OK;
+}
 int bhray_accum_sample_rays(bhray_ctx* c, uint32_t s, bhray_ray* out) {
     if (!c) return BHRAY_E_INVALID;
     ENTER(c);

@@ -70,6 +70,12 @@ OFF(bhray_ray_record, closest, 24); OFF(bhray_ray_record, transmittance, 28);
 // a point of bhray_trace_rays_paths: one 16-byte store of the path kernels
 SZ(bhray_path_point, 16);
 OFF(bhray_path_point, position, 0); OFF(bhray_path_point, iteration, 12);
+// the parameters and the report of bhray_accum_add_adaptive
+SZ(bhray_accum_adaptive, 24);
+OFF(bhray_accum_adaptive, struct_size, 0); OFF(bhray_accum_adaptive, min_samples, 4); OFF(bhray_accum_adaptive, max_samples, 8); OFF(bhray_accum_adaptive, round_samples, 12);
+OFF(bhray_accum_adaptive, tolerance, 16); OFF(bhray_accum_adaptive, dark, 20);
+SZ(bhray_accum_adaptive_info, 24);
+OFF(bhray_accum_adaptive_info, rounds, 0); OFF(bhray_accum_adaptive_info, active_last, 4); OFF(bhray_accum_adaptive_info, rays, 8); OFF(bhray_accum_adaptive_info, reach, 16);
 static_assert(BHRAY_MAX_PATH_STRIDE_LOG2 == 16 && BHRAY_MAX_PATH_POINTS_PER_CALL == (1u << 24), "BHRAY_MAX_PATH_*");
 static_assert(BHRAY_HIT_NONE == 0 && BHRAY_HIT_HORIZON == 1 && BHRAY_HIT_DISK == 2 && BHRAY_HIT_MESH == 3 && BHRAY_HIT_UNUSABLE == 255, "BHRAY_HIT_*");
 

@@ -1,4 +1,5 @@
-// bhray_tex.h — the texture sample shared by the trace kernels, the sky pass (bhray_kernels.hip) and the accumulation's resolve (bhray_accum.hip).
+// bhray_tex.h — the texture sample shared by the trace kernels, the sky pass (bhray_kernels.hip) and the accumulation's resolve, and that resolve (bhray_accum.hip,
+// bhray_adapt.hip).
 // Device code only; included behind bhray_internal.h (TexDev) and bhray_math.h (mix_).
 #pragma once
 
@@ -41,6 +42,26 @@ __device__ __forceinline__ float4 sample_bilinear(const TexDev& t, float u, floa
     r.z = mix_(mix_(a.z, b.z, fx), mix_(c.z, d.z, fx), fy);
     r.w = mix_(mix_(a.w, b.w, fx), mix_(c.w, d.w, fx), fy);
     return r;
+}
+
+// ------------------------------------------------------------------------------------------
+// the accumulation's resolve (bhray_accum.hip, bhray_adapt.hip): a traced result as the colour that is summed
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool finite_(float x) { return (f2u(x) & 0x7f800000u) != 0x7f800000u; }
+
+// sky.wgsl:19-26 without the store's binary16 rounding: sky_kernel's operations (bhray_kernels.hip)
+__device__ __forceinline__ float4 resolve(const TexDev& sky, float4 p) {
+    if (p.w == 0.0f) {
+        const float theta = bh_atan2(sqrtf(p.x * p.x + p.z * p.z), p.y);
+        const float phi = bh_atan2(p.z, p.x);
+        const float PI_F = 3.1415926f;
+        float u = (phi + 2.6f * PI_F) / (2.0f * PI_F);
+        float v = (PI_F - theta) / PI_F;
+        u = u - truncf(u); v = v - truncf(v);
+        const float4 sc = sample_bilinear<false>(sky, u, v);
+        p = make_float4((sc.x * sc.x) * (sc.x * sc.x), (sc.y * sc.y) * (sc.y * sc.y), (sc.z * sc.z) * (sc.z * sc.z), 1.0f);
+    }
+    return p;
 }
 
 }  // namespace bhray

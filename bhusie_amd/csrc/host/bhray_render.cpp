@@ -1,9 +1,14 @@
 // bhray_render — minimal C++ host program over renderer.hpp: renders one frame of the reference's default scene
 // (camera (0,0,-19), hole at the origin, disk 2..10, R = 20; camera.rs:10-16, blackhole.rs:16-28) and writes the HDR frame
 // as raw little-endian f32 RGBA (row 0 = top).  Usage:
-//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--spp N] [--pick X Y] [--path X Y [--path-stride S]]
+//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--pick X Y] [--path X Y [--path-stride S]]
 // --spp N: instead of the ladder's frame, a supersampled still - the mean of N jittered samples per frame pixel, sky resolved, accumulated on the GPU
 //   (Renderer::render_still: bhray_accum_*); written the same way.  Not with --lensed-mesh, --devices or --panorama.
+// --spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]: an adaptive still instead - every pixel takes MIN samples, then R more (4 by default) for as long as the
+//   relative standard error of its mean compressed luminance, with D (0.01 by default) added to the mean, exceeds TOL, and at most MAX
+//   (Renderer::render_still_adaptive: bhray_accum_add_adaptive); written the same way, followed by one line
+//   adaptive rounds=N rays=N mean_count=F
+//   Not with --spp, --lensed-mesh, --devices or --panorama.
 // --path X Y [--path-stride S]: after the frame, the pick line of pixel (X, Y) and then the light path behind it, one line per point - that pixel's pinhole ray through
 //   bhray_trace_rays_paths (Renderer::ray_path), a point every 2^S iterations (S = 0 by default) and the end point:
 //   ITERATION X Y Z
@@ -152,10 +157,12 @@ int main(int argc, char** argv) {
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
         return 0;
     }
-    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--spp N] [--pick X Y] [--path X Y [--path-stride S]]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--pick X Y] [--path X Y [--path-stride S]]\n", argv[0]); return 2; }
     uint32_t bw = 72, bh = 41, levels = 4, disk = 256, pano_w = 0, pano_h = 0;
     long pick_x = -1, pick_y = -1, path_x = -1, path_y = -1, path_stride = 0, spp = 0;
-    bool rk = false, bvh_device = false, lensed = false, posed = false;
+    bool rk = false, bvh_device = false, lensed = false, posed = false, adaptive = false;
+    long a_min = 0, a_max = 0, a_round = 4;
+    double a_tol = 0.0, a_dark = 0.01;
     float rotation[3] = {0.0f, 0.0f, 0.0f};
     std::vector<const char*> objs;
     std::vector<int> devices;
@@ -170,12 +177,22 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--lensed-mesh")) lensed = true;
         else if (!std::strcmp(argv[i], "--panorama") && i + 2 < argc) { pano_w = (uint32_t)std::atoi(argv[++i]); pano_h = (uint32_t)std::atoi(argv[++i]); if (pano_w < 1 || pano_h < 1) { std::fprintf(stderr, "--panorama needs W >= 1 and H >= 1\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--spp") && i + 1 < argc) { spp = std::atol(argv[++i]); if (spp < 1 || spp > (long)BHRAY_ACCUM_MAX_SAMPLES) { std::fprintf(stderr, "--spp needs 1 <= N <= %u\n", BHRAY_ACCUM_MAX_SAMPLES); return 2; } }
+        else if (!std::strcmp(argv[i], "--spp-adaptive") && i + 3 < argc) {
+            adaptive = true; a_min = std::atol(argv[++i]); a_max = std::atol(argv[++i]); a_tol = std::atof(argv[++i]);
+            if (a_min < 2 || a_max < a_min || a_max > (long)BHRAY_ACCUM_MAX_SAMPLES) { std::fprintf(stderr, "--spp-adaptive needs 2 <= MIN <= MAX <= %u\n", BHRAY_ACCUM_MAX_SAMPLES); return 2; }
+            if (!std::isfinite(a_tol) || a_tol < 0.0) { std::fprintf(stderr, "--spp-adaptive needs a finite TOL >= 0\n"); return 2; }
+        }
+        else if (!std::strcmp(argv[i], "--spp-round") && i + 1 < argc) { a_round = std::atol(argv[++i]); if (a_round < 1 || a_round > (long)BHRAY_ACCUM_MAX_SAMPLES) { std::fprintf(stderr, "--spp-round needs 1 <= R <= %u\n", BHRAY_ACCUM_MAX_SAMPLES); return 2; } }
+        else if (!std::strcmp(argv[i], "--spp-dark") && i + 1 < argc) { a_dark = std::atof(argv[++i]); if (!std::isfinite(a_dark) || a_dark < 0.0) { std::fprintf(stderr, "--spp-dark needs a finite D >= 0\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--pick") && i + 2 < argc) { pick_x = std::atol(argv[++i]); pick_y = std::atol(argv[++i]); if (pick_x < 0 || pick_y < 0) { std::fprintf(stderr, "--pick needs X >= 0 and Y >= 0\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--path") && i + 2 < argc) { path_x = std::atol(argv[++i]); path_y = std::atol(argv[++i]); if (path_x < 0 || path_y < 0) { std::fprintf(stderr, "--path needs X >= 0 and Y >= 0\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--path-stride") && i + 1 < argc) { path_stride = std::atol(argv[++i]); if (path_stride < 0 || path_stride > BHRAY_MAX_PATH_STRIDE_LOG2) { std::fprintf(stderr, "--path-stride needs 0 <= S <= %d\n", BHRAY_MAX_PATH_STRIDE_LOG2); return 2; } }
         else if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) { for (const char* p = argv[++i]; *p; ) { devices.push_back(std::atoi(p)); while (*p && *p != ',') p++; if (*p) p++; } }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
+    if (adaptive && spp) { std::fprintf(stderr, "--spp-adaptive and --spp are two ways to fill the same image: give one\n"); return 2; }
+    if (adaptive && pano_w) { std::fprintf(stderr, "--spp-adaptive samples the pixels of the pinhole frame: not with --panorama\n"); return 2; }
+    if (adaptive && (a_max - a_min) % a_round != 0) { std::fprintf(stderr, "--spp-adaptive needs MAX - MIN to be a multiple of the round (--spp-round, 4 by default)\n"); return 2; }
     if (spp && pano_w) { std::fprintf(stderr, "--spp samples the pixels of the pinhole frame: not with --panorama\n"); return 2; }
     if (path_x >= 0 && pano_w) { std::fprintf(stderr, "--path names a pixel of the pinhole frame: not with --panorama\n"); return 2; }
     if (pick_x >= 0 && pano_w) { std::fprintf(stderr, "--pick names a pixel of the pinhole frame: not with --panorama\n"); return 2; }
@@ -200,10 +217,16 @@ int main(int argc, char** argv) {
         r.ray_details.integration_method = rk ? 1 : 0;
         r.mesh_lensing = lensed;
         std::vector<float> out;
+        std::vector<uint32_t> counts;
+        bhray_accum_adaptive_info ainfo{};
         auto res = r.ray_pipeline().resolution();
         if (pano_w) {
             out = r.render_rays(bhusie::equirect_rays(r.camera.position, r.camera.forward, pano_w, pano_h));
             res = {pano_w, pano_h};
+        } else if (adaptive) {
+            bhray_accum_adaptive a{};
+            a.min_samples = (uint32_t)a_min; a.max_samples = (uint32_t)a_max; a.round_samples = (uint32_t)a_round; a.tolerance = (float)a_tol; a.dark = (float)a_dark;
+            out = r.render_still_adaptive(a, &ainfo, &counts);
         } else if (spp) {
             out = r.render_still((uint32_t)spp);
         } else {
@@ -215,6 +238,11 @@ int main(int argc, char** argv) {
         std::fwrite(out.data(), sizeof(float), out.size(), f);
         std::fclose(f);
         std::printf("%ux%u\n", res.first, res.second);
+        if (adaptive) {
+            double total = 0.0;
+            for (uint32_t n : counts) total += (double)n;
+            std::printf("adaptive rounds=%u rays=%llu mean_count=%.6f\n", ainfo.rounds, (unsigned long long)ainfo.rays, counts.empty() ? 0.0 : total / (double)counts.size());
+        }
         auto print_pick = [](long pick_x, long pick_y, const bhray_ray_record& p) {
             const uint32_t kind = p.hit & 0xffu;
             const char* name = kind == BHRAY_HIT_NONE ? "none" : kind == BHRAY_HIT_HORIZON ? "horizon" : kind == BHRAY_HIT_DISK ? "disk" : kind == BHRAY_HIT_MESH ? "mesh" : "unusable";

@@ -217,6 +217,19 @@ public:
         check(bhray_accum_read(ctx_, out.data(), (size_t)cfg_.frame_w * 16), ctx_);
         return out;
     }
+    // adaptive stills (bhray_accum_add_adaptive): the accumulation image cleared, every pixel sampled until the error of its mean is under the bound
+    // or it has max_samples, and the mean as accumulate() delivers it.  info (may be null): what the call did; counts (may be null): the samples issued per pixel.
+    std::vector<float> accumulate_adaptive(const bhray_accum_adaptive& params, bhray_accum_adaptive_info* info = nullptr, std::vector<uint32_t>* counts = nullptr) {
+        check(bhray_accum_begin(ctx_), ctx_);
+        check(bhray_accum_add_adaptive(ctx_, &params, info), ctx_);
+        std::vector<float> out((size_t)cfg_.frame_w * cfg_.frame_h * 4);
+        check(bhray_accum_read(ctx_, out.data(), (size_t)cfg_.frame_w * 16), ctx_);
+        if (counts) {
+            counts->resize((size_t)cfg_.frame_w * cfg_.frame_h);
+            check(bhray_accum_read_counts(ctx_, counts->data(), (size_t)cfg_.frame_w * 4), ctx_);
+        }
+        return out;
+    }
     bhray_ctx* ctx() { return ctx_; }
 private:
     bhray_config cfg_;
@@ -368,6 +381,13 @@ public:
         ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);
         apply_lensing();
         return ray_pipeline_.accumulate(samples);
+    }
+    // an adaptive still of the current scene (RayPipeline::accumulate_adaptive): params.struct_size is filled in here
+    std::vector<float> render_still_adaptive(bhray_accum_adaptive params, bhray_accum_adaptive_info* info = nullptr, std::vector<uint32_t>* counts = nullptr) {
+        params.struct_size = (uint32_t)sizeof(bhray_accum_adaptive);
+        ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);
+        apply_lensing();
+        return ray_pipeline_.accumulate_adaptive(params, info, counts);
     }
     // what is under frame pixel (x, y): the record of that pixel's pinhole ray under the current scene (hit & 0xff: BHRAY_HIT_*; (hit >> 8) & 0xff: the model slot of a mesh hit)
     bhray_ray_record pick(uint32_t x, uint32_t y) {

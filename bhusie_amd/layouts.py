@@ -93,6 +93,21 @@ MAX_PATH_POINTS_PER_CALL = 1 << 24          # BHRAY_MAX_PATH_POINTS_PER_CALL
 HIT_NONE, HIT_HORIZON, HIT_DISK, HIT_MESH, HIT_UNUSABLE = 0, 1, 2, 3, 255      # BHRAY_HIT_*: bits 0-7 of bhray_ray_record.hit (bits 8-15: the model slot of a MESH hit)
 
 
+class BhrayAccumAdaptive(C.Structure):      # bhray_accum_adaptive: the parameters of bhray_accum_add_adaptive
+    _fields_ = [("struct_size", C.c_uint32), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("round_samples", C.c_uint32),
+                ("tolerance", C.c_float), ("dark", C.c_float)]
+
+
+class BhrayAccumAdaptiveInfo(C.Structure):  # bhray_accum_adaptive_info: what one bhray_accum_add_adaptive call did
+    _fields_ = [("rounds", C.c_uint32), ("active_last", C.c_uint32), ("rays", C.c_uint64), ("reach", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+assert C.sizeof(BhrayAccumAdaptive) == 24 and C.sizeof(BhrayAccumAdaptiveInfo) == 24 and BhrayAccumAdaptiveInfo.rays.offset == 8
+
+
 class BhrayModelDesc(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("visible", C.c_int32),
                 ("points", C.c_void_p), ("normals", C.c_void_p), ("triangles", C.c_void_p),
@@ -246,6 +261,8 @@ SYMBOLS = {
     "bhray_accum_read": (C.c_int, [vp, vp, sz]),
     "bhray_accum_read_display": (C.c_int, [vp, vp, sz]),
     "bhray_accum_sample_offset": (None, [u32, P(C.c_float), P(C.c_float)]),
+    "bhray_accum_add_adaptive": (C.c_int, [vp, P(BhrayAccumAdaptive), P(BhrayAccumAdaptiveInfo)]),
+    "bhray_accum_read_counts": (C.c_int, [vp, vp, sz]),
     "bhray_render": (C.c_int, [vp]),
     "bhray_flush": (C.c_int, [vp]),
     "bhray_sync": (C.c_int, [vp]),
@@ -313,6 +330,7 @@ DIAG_SYMBOLS = {
     "bhray_read_model_vertices": (C.c_int, [vp, u32, vp, u32, vp, u32, P(u32), P(u32)]),
     "bhray_accum_sample_rays": (C.c_int, [vp, u32, P(BhrayRay)]),
     "bhray_accum_set_launch_rays": (C.c_int, [vp, u32]),
+    "bhray_accum_active_pixels": (C.c_int, [vp, P(BhrayAccumAdaptive), P(u32), u32, P(u32)]),
     "bhray_read_sky_pyramid_level": (C.c_int, [vp, u32, vp, sz]),
 }
 

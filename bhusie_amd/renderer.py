@@ -14,6 +14,7 @@ import numpy as np
 
 from ._lib import lib
 from .layouts import (BhrayFxaaDetails, BhrayMixDetails, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters, BhrayRay, BhrayRayRecord, BhrayPathPoint, PATH_POINT_DTYPE, HIT_MESH, HIT_UNUSABLE,
+                      BhrayAccumAdaptive, BhrayAccumAdaptiveInfo,
                       BhrayGatherInfo, BhrayModelBuildInfo, BhrayModelDesc, BhrayRebalanceInfo, BhrayTiming, check)
 from .model import NODE_DTYPE, Model
 from .scene import BlackHole, Camera, RayDetails
@@ -23,6 +24,17 @@ from .cameras import pinhole_rays
 RAY_RECORD_DTYPE = np.dtype([("position", np.float32, 3), ("hit", np.uint32), ("triangle", np.int32), ("iterations", np.uint32),
                              ("closest", np.float32), ("transmittance", np.float32)])
 assert RAY_RECORD_DTYPE.itemsize == C.sizeof(BhrayRayRecord) == 32
+
+
+class AdaptiveStill:
+    """The parameters of an adaptive still (Renderer.render_still(adaptive=...), RayPass.accum_add_adaptive)."""
+
+    def __init__(self, min_samples: int = 4, max_samples: int = 64, round_samples: int = 4, tolerance: float = 0.05, dark: float = 0.01):
+        self.min_samples, self.max_samples, self.round_samples = int(min_samples), int(max_samples), int(round_samples)
+        self.tolerance, self.dark = float(tolerance), float(dark)
+
+    def as_kwargs(self) -> dict:
+        return {"min_samples": self.min_samples, "max_samples": self.max_samples, "round_samples": self.round_samples, "tolerance": self.tolerance, "dark": self.dark}
 
 
 def ladder_from_base(base=(72, 41), multiplier=3, levels=4) -> BhrayConfig:
@@ -439,6 +451,36 @@ class RayPass:
         """At most max_rays rays per trace launch of accum_add (0: the default, 2**22); the image does not depend on it (bhray_diag.h)."""
         check(self._L.bhray_accum_set_launch_rays(self._h, int(max_rays)), self._h, self._L)
 
+    # -- adaptive stills: each pixel sampled until the error of its mean is under a bound (bhray_accum_add_adaptive, DESIGN.md §20)
+    @staticmethod
+    def _adaptive_params(min_samples, max_samples, round_samples, tolerance, dark) -> BhrayAccumAdaptive:
+        return BhrayAccumAdaptive(C.sizeof(BhrayAccumAdaptive), int(min_samples), int(max_samples), int(round_samples), float(tolerance), float(dark))
+
+    def accum_add_adaptive(self, min_samples: int = 4, max_samples: int = 64, round_samples: int = 4, tolerance: float = 0.05, dark: float = 0.01) -> dict:
+        """After accum_begin: min_samples samples for every pixel, then rounds that give the pixels failing the test of include/bhray.h round_samples more, until every
+        pixel passes or has max_samples.  Blocks while the rounds run; the reads wait.  Returns {"rounds", "active_last", "rays", "reach"} of this call.  A later call
+        (a smaller tolerance, a larger max_samples; the same min_samples and round_samples) continues the accumulation; accum_add does not mix with it."""
+        a = self._adaptive_params(min_samples, max_samples, round_samples, tolerance, dark)
+        info = BhrayAccumAdaptiveInfo()
+        check(self._L.bhray_accum_add_adaptive(self._h, C.byref(a), C.byref(info)), self._h, self._L)
+        return info.as_dict()
+
+    def accum_read_counts(self) -> np.ndarray:
+        """The number of samples issued to each pixel of an adaptive accumulation: (frame_h, frame_w) uint32.  Waits."""
+        w, h = int(self.cfg.frame_w), int(self.cfg.frame_h)
+        out = np.empty((h, w), dtype=np.uint32)
+        check(self._L.bhray_accum_read_counts(self._h, out.ctypes.data, w * 4), self._h, self._L)
+        return out
+
+    def accum_active_pixels(self, min_samples: int = 4, max_samples: int = 64, round_samples: int = 4, tolerance: float = 0.05, dark: float = 0.01) -> np.ndarray:
+        """One selection under these parameters without sampling: the indices y * frame_w + x of the pixels that would take more samples, in the order the device
+        compacted them (bhray_diag.h)."""
+        a = self._adaptive_params(min_samples, max_samples, round_samples, tolerance, dark)
+        out = np.empty(int(self.cfg.frame_w) * int(self.cfg.frame_h), dtype=np.uint32)
+        n = C.c_uint32()
+        check(self._L.bhray_accum_active_pixels(self._h, C.byref(a), out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size, C.byref(n)), self._h, self._L)
+        return out[:int(n.value)].copy()
+
     # -- per frame
     def set_uniforms(self, camera: bytes, black_hole: bytes, details: bytes):
         assert len(camera) == 32 and len(black_hole) == 132 and len(details) == 32
@@ -675,6 +717,7 @@ class Renderer:
         self._device_built: list[bool] = []                  # ... and whether its tree was built on the GPU (add_model(build="device"))
         self.mesh_lensing = False                            # lensed meshes (RayPass.set_mesh_lensing): applied before each render
         self._lensing_applied = False                        # what the ctx was last told (its default: off)
+        self.still_info = None                               # what the last adaptive still did (render_still(adaptive=...)): rounds, active_last, rays, reach
         self.sky_filter = False                              # footprint-filtered sky pass (RayPass.set_sky_filter): applied before save_image's display pass
         self._sky_filter_applied = False
 
@@ -823,12 +866,25 @@ class Renderer:
         finally:
             self.ray_details.time = t0
 
-    def render_still(self, samples: int = 16, shutter: float = 0.0) -> np.ndarray:
+    def render_still(self, samples: int = 16, shutter: float = 0.0, adaptive: AdaptiveStill | None = None) -> np.ndarray:
         """A supersampled still of the current scene (RayPass.accum_*): the mean of `samples` jittered samples per frame pixel, sky resolved,
         (frame_h, frame_w, 4) float32.  Sample 0 is the pixel centre, so samples=1 is the frame a `levels = 1` ladder renders, after the sky pass in binary32.
-        shutter > 0: motion blur - sample s is rendered at ray_details.time + shutter * s / samples (the disk turns with `time`); ray_details.time is left as it was."""
-        self._accumulate(samples, shutter)
+        shutter > 0: motion blur - sample s is rendered at ray_details.time + shutter * s / samples (the disk turns with `time`); ray_details.time is left as it was.
+        adaptive: an AdaptiveStill - each pixel is sampled until the error of its mean is under the bound; `samples` is then not read, the motion blur is
+        not available (ValueError), still_info holds what the call did and still_counts() delivers the per-pixel sample counts."""
+        if adaptive is None:
+            self._accumulate(samples, shutter)
+            return self.ray_pass.accum_read()
+        if shutter > 0.0:
+            raise ValueError("render_still: an adaptive still has no shutter (every pixel takes its own number of samples)")
+        self._apply_uniforms()
+        self.ray_pass.accum_begin()
+        self.still_info = self.ray_pass.accum_add_adaptive(**adaptive.as_kwargs())
         return self.ray_pass.accum_read()
+
+    def still_counts(self) -> np.ndarray:
+        """The sample-count heat map of the last adaptive still: (frame_h, frame_w) uint32."""
+        return self.ray_pass.accum_read_counts()
 
     def save_still(self, path, samples: int = 16):
         """save_image for a supersampled still: the mean of `samples` samples per pixel through the display pass, written with alpha 255."""

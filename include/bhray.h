@@ -579,6 +579,56 @@ int bhray_accum_read(bhray_ctx* ctx, float* dst_rgba32f, size_t row_pitch_bytes)
 int bhray_accum_read_display(bhray_ctx* ctx, uint8_t* dst_rgba8, size_t row_pitch_bytes);
 void bhray_accum_sample_offset(uint32_t s, float* dx, float* dy);
 
+/* Adaptive stills: a second way to fill the accumulation image.  After bhray_accum_begin,
+ * bhray_accum_add_adaptive gives every pixel min_samples samples, then runs rounds: each round tests every pixel and
+ * gives those that fail round_samples more, until every pixel passes or has max_samples.  bhray_accum_read and
+ * bhray_accum_read_display deliver the mean as they do for bhray_accum_add (they divide by sum.w, a per-pixel count);
+ * bhray_accum_read_counts delivers the number of samples issued to each pixel.
+ * The rule, all of it binary32, every operation rounded on its own in the order written:
+ *   state    per pixel p: sum[p] (above), S1[p], S2[p] (binary32), issued[p] (uint32); all zero after bhray_accum_begin.
+ *   samples  sample s of pixel p is sample s above - the same offset, ray, trace and resolve.  A pixel's samples are
+ *            taken in increasing s, starting at issued[p].
+ *   adding   a sample whose resolved r, g or b is not finite is skipped (issued still advances).  Otherwise
+ *            sum[p] += (r, g, b, 1);  Y = (0.2126f * r + 0.7152f * g) + 0.0722f * b;  Y = Y < 0 ? 0 : Y;
+ *            t = Y >= 0x1p100f ? 1.0f : Y / (1.0f + Y);  S1 += t;  S2 += t * t.
+ *   test     n = sum[p].w;  m = S1 / n;  q = S2 / n;  v = q - m * m;  v = v < 0 ? 0 : v;  e = tolerance * (m + dark);
+ *            the pixel is converged iff v <= (e * e) * n.  A comparison with a NaN is false, so a pixel all of whose
+ *            samples were skipped (n == 0) is not converged and goes on to max_samples.
+ *   rounds   if no sample has been issued since bhray_accum_begin, the first round gives every pixel samples
+ *            0 .. min_samples - 1 with no test.  Every later round selects the pixels with issued[p] < max_samples that
+ *            are not converged and gives each samples issued[p] .. issued[p] + round_samples - 1.  The call ends when a
+ *            selection is empty.  issued[p] is always 0 or min_samples + i * round_samples.
+ * The image is a function of each pixel's own sample stream and of the sequence of parameter sets: not of the order of
+ * the selected pixels, of how a round is cut into launches, or of whether one call or several reach a max_samples.
+ * Repeated calls continue the accumulation (a smaller tolerance, a larger max_samples); min_samples and round_samples
+ * must equal those of the first adaptive call since bhray_accum_begin (BHRAY_E_INVALID otherwise).
+ * The two modes do not mix - BHRAY_E_STATE, until the next bhray_accum_begin: bhray_accum_add after an adaptive call,
+ * bhray_accum_add_adaptive after a bhray_accum_add, bhray_accum_read_counts in a uniform accumulation (or before
+ * bhray_accum_begin).  After adaptive calls bhray_accum_samples returns `reach`.
+ * Every refusal of bhray_accum_add holds.  BHRAY_E_INVALID, nothing enqueued, sum and counts untouched: a NULL params,
+ * a struct_size other than sizeof(bhray_accum_adaptive), min_samples < 2, max_samples < min_samples or above
+ * BHRAY_ACCUM_MAX_SAMPLES, round_samples == 0, (max_samples - min_samples) % round_samples != 0, a tolerance or dark
+ * that is negative or not finite.
+ * The call blocks while it runs - each round's selection count comes back to the host - and returns once the last
+ * round is enqueued; the reads wait.  A stopping rule on the running variance biases the estimate slightly towards
+ * pixels that looked quiet early: min_samples is the guard, nothing more is claimed.                                */
+typedef struct bhray_accum_adaptive {
+    uint32_t struct_size;     /* = sizeof(bhray_accum_adaptive) */
+    uint32_t min_samples;     /* every pixel takes at least this many; >= 2 */
+    uint32_t max_samples;     /* no pixel takes more; >= min_samples, <= BHRAY_ACCUM_MAX_SAMPLES, (max - min) % round_samples == 0 */
+    uint32_t round_samples;   /* samples a failing pixel takes between two tests; >= 1 */
+    float    tolerance;       /* bound on the relative standard error of the pixel's mean compressed luminance; finite, >= 0 */
+    float    dark;            /* added to the mean before the relative bound is formed; finite, >= 0 */
+} bhray_accum_adaptive;
+typedef struct bhray_accum_adaptive_info {
+    uint32_t rounds;          /* rounds this call ran (the initial min_samples round included) */
+    uint32_t active_last;     /* pixels that failed the last test this call made (0: every pixel converged or is at max_samples) */
+    uint64_t rays;            /* rays this call traced */
+    uint32_t reach;           /* largest sample count issued to any pixel so far */
+} bhray_accum_adaptive_info;
+int bhray_accum_add_adaptive(bhray_ctx* ctx, const bhray_accum_adaptive* params, bhray_accum_adaptive_info* info /* may be NULL */);
+int bhray_accum_read_counts(bhray_ctx* ctx, uint32_t* dst, size_t row_pitch_bytes);   /* frame_h rows of frame_w uint32 */
+
 /* Dispatch — replaces `for rp in ray_pipelines { rp.pass() }` (mod.rs:415-417,
  * ray_pipeline.rs:301-309).  Asynchronous on the ctx stream; levels ordered.                 */
 int bhray_render(bhray_ctx* ctx);

@@ -179,6 +179,13 @@ int bhray_accum_sample_rays(bhray_ctx* ctx, uint32_t s, bhray_ray* out);
  * into one launch.  0 restores the default, 2^22; more than BHRAY_MAX_RAYS_PER_CALL: BHRAY_E_INVALID.  The image
  * does not depend on it.                                                                                             */
 int bhray_accum_set_launch_rays(bhray_ctx* ctx, uint32_t max_rays);
+/* One selection of bhray_accum_add_adaptive under `params` without sampling: the frame pixels
+ * (y * frame_w + x) with issued < max_samples that are not converged, in the order the selection kernel compacted them
+ * (unspecified between blocks).  *n is their number, the first min(*n, cap) go to out (out may be NULL when cap is
+ * 0).  params is checked as bhray_accum_add_adaptive checks it (min_samples / round_samples against the first adaptive
+ * call's, if there was one); BHRAY_E_STATE before bhray_accum_begin and in a uniform accumulation.  Changes nothing.
+ * Waits.                                                                                                             */
+int bhray_accum_active_pixels(bhray_ctx* ctx, const bhray_accum_adaptive* params, uint32_t* out, uint32_t cap, uint32_t* n);
 
 /* ------------------------------------------------------------------------------------------
  * The footprint-filtered sky pass (bhray_set_sky_filter)
