@@ -5,11 +5,14 @@ Each returns an (h * w, 8) float32 array of ray records - origin, pad, direction
 pinhole_rays    the shader's create_ray (ray.wgsl:269-285), operation by operation: the rays of a `levels = 1` frame, bit for bit
 equirect_rays   a 360 x 180 degree panorama: the centre column looks along `forward`
 fisheye_rays    an equidistant fisheye of opening angle `fov` about `forward`; pixels outside the image circle get a zero direction (not traced: alpha -1)
+still_rays      the rays of sample s of the accumulation image under a StillCamera (bhray_accum_set_camera): what the device generates, bit for bit
 
 All three use create_ray's basis: plane_up = (0, -1, 0), right = normalize(cross(forward, plane_up)), up = normalize(cross(forward, right)) - `up` is the direction in
 which the image's rows increase.  Directions are unit as a binary32 normalise leaves them (v * (1 / sqrt(dot(v, v)))), which is what the trace kernels expect.
 """
 from __future__ import annotations
+
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -171,3 +174,112 @@ def fisheye_rays(position, forward, w: int, h: int, fov: float) -> np.ndarray:
     d = _normalize(v.astype(F))
     d = np.where(inside[..., None], d, F(0.0)).astype(F)
     return _records(position, d.reshape(h * w, 3))
+
+
+STILL_PINHOLE, STILL_EQUIRECT, STILL_FISHEYE = 0, 1, 2         # BHRAY_STILL_*
+
+
+@dataclass(frozen=True)
+class StillCamera:
+    """The camera model of the accumulation image (bhray_still_camera): StillCamera.pinhole(), .pinhole(lens_radius, focus_distance) - a thin lens
+    with a spherical surface of focus -, .equirect() and .fisheye(fov).  Position, forward and the pinhole's fov stay the scene camera's."""
+    projection: int = STILL_PINHOLE
+    fisheye_fov: float = float(_PI)
+    lens_radius: float = 0.0
+    focus_distance: float = 1.0
+
+    @classmethod
+    def pinhole(cls, lens_radius: float = 0.0, focus_distance: float = 1.0) -> "StillCamera":
+        return cls(STILL_PINHOLE, float(_PI), float(lens_radius), float(focus_distance))
+
+    @classmethod
+    def equirect(cls) -> "StillCamera":
+        return cls(STILL_EQUIRECT)
+
+    @classmethod
+    def fisheye(cls, fov: float) -> "StillCamera":
+        return cls(STILL_FISHEYE, float(fov))
+
+    @property
+    def is_default(self) -> bool:
+        return self.projection == STILL_PINHOLE and not self.lens_radius > 0.0
+
+    def struct(self):
+        """the bhray_still_camera the library takes"""
+        import ctypes as C
+        from .layouts import BhrayStillCamera
+        return BhrayStillCamera(C.sizeof(BhrayStillCamera), int(self.projection), float(self.fisheye_fov), float(self.lens_radius), float(self.focus_distance))
+
+
+def _vsincos(x, kind):
+    return np.array([_sincos(v, kind) for v in np.asarray(x, dtype=F).ravel()], dtype=F).reshape(np.shape(x))
+
+
+def _still_hash(v):
+    v = np.asarray(v, dtype=np.uint64) & 0xFFFFFFFF
+    v = v ^ (v >> 16)
+    v = (v * 0x7FEB352D) & 0xFFFFFFFF
+    v = v ^ (v >> 15)
+    v = (v * 0x846CA68B) & 0xFFFFFFFF
+    return v ^ (v >> 16)
+
+
+def still_rays(camera, cfg, still_camera: StillCamera | None, s: int) -> np.ndarray:
+    """The (frame_h * frame_w, 8) records of sample s of the accumulation image of `cfg` (a BhrayConfig) under `still_camera` (None: the default), every step of
+    include/bhray.h's contract one rounded binary32 operation: r2_offset's sub-pixel offset, the projection on the ladder's last level at the frame's window, the
+    lens point of the thin lens.  The pinhole without a lens is pinhole_rays(offset=..., level=..., crop=...)."""
+    sc = still_camera if still_camera is not None else StillCamera()
+    s = int(s)
+    lw, lh = int(cfg.level_w[cfg.levels - 1]), int(cfg.level_h[cfg.levels - 1])
+    w, h, cx, cy = int(cfg.frame_w), int(cfg.frame_h), int(cfg.crop_x), int(cfg.crop_y)
+    dx, dy = r2_offset(s)
+    if sc.projection == STILL_PINHOLE:
+        rec = pinhole_rays(camera, w, h, offset=(dx, dy), level=(lw, lh), crop=(cx, cy))
+        if not sc.lens_radius > 0.0:
+            return rec
+        pos, forward, _ = _camera_fields(camera)
+        _, right, up = _basis(forward)
+        q = ((np.arange(cy, cy + h, dtype=np.uint64)[:, None] * lw + np.arange(cx, cx + w, dtype=np.uint64)[None, :]) & 0xFFFFFFFF).reshape(-1)
+        a = (_still_hash(q) + s * 0x9E3779B9) & 0xFFFFFFFF
+        b = (_still_hash(q ^ 0x9E3779B9) + s * 0x6A09E667) & 0xFFFFFFFF
+        ru = ((a >> 8).astype(F) * F(2.0 ** -24)).astype(F)
+        rv = ((b >> 8).astype(F) * F(2.0 ** -24)).astype(F)
+        rr = np.sqrt(ru, dtype=F)
+        ang = (rv * F(6.28318548)).astype(F)
+        ex = ((rr * _vsincos(ang, 1)).astype(F) * F(sc.lens_radius)).astype(F)
+        ey = ((rr * _vsincos(ang, 0)).astype(F) * F(sc.lens_radius)).astype(F)
+        off = ((right[None, :] * ex[:, None]).astype(F) + (up[None, :] * ey[:, None]).astype(F)).astype(F)
+        out = rec.copy()
+        out[:, 0:3] = (pos[None, :] + off).astype(F)
+        out[:, 4:7] = _normalize(((rec[:, 4:7] * F(sc.focus_distance)).astype(F) - off).astype(F))
+        return out
+    pos, forward, _ = _camera_fields(camera)
+    fwd, right, up = _basis(forward)
+    fwd = _normalize(fwd)
+    px = (np.arange(cx, cx + w, dtype=F) + dx).astype(F)
+    py = (np.arange(cy, cy + h, dtype=F) + dy).astype(F)
+    half_w, half_h = F(F(lw - 1) * F(0.5)), F(F(lh - 1) * F(0.5))
+    if sc.projection == STILL_EQUIRECT:
+        lon = ((px - half_w) * F(F(6.28318548) / F(lw))).astype(F)
+        lat = ((py - half_h) * F(F(3.14159274) / F(lh))).astype(F)
+        cl, sl = _vsincos(lon, 1)[None, :], _vsincos(lon, 0)[None, :]
+        cp, sp = _vsincos(lat, 1)[:, None], _vsincos(lat, 0)[:, None]
+        a = (cp * cl).astype(F)[..., None]
+        b = (cp * sl).astype(F)[..., None]
+        c = np.broadcast_to(sp, (h, w)).astype(F)[..., None]
+        v = ((fwd * a).astype(F) + (right * b).astype(F)).astype(F) + (up * c).astype(F)
+        return _records(pos, _normalize(v.astype(F)).reshape(h * w, 3))
+    assert sc.projection == STILL_FISHEYE, "still_rays: unknown projection"
+    radius = F(F(min(lw - 1, lh - 1)) * F(0.5))
+    x = np.broadcast_to(((px - half_w) / radius).astype(F)[None, :], (h, w)).astype(F)
+    y = np.broadcast_to(((py - half_h) / radius).astype(F)[:, None], (h, w)).astype(F)
+    r = np.sqrt(((x * x).astype(F) + (y * y).astype(F)).astype(F), dtype=F)
+    inside = r <= F(1.0)
+    theta = (r * F(F(sc.fisheye_fov) * F(0.5))).astype(F)
+    safe = np.where(r > F(0.0), r, F(1.0)).astype(F)
+    cphi, sphi = (x / safe).astype(F), (y / safe).astype(F)
+    st, ct = _vsincos(theta, 0), _vsincos(theta, 1)
+    v = ((fwd * ct[..., None]).astype(F) + (right * (st * cphi).astype(F)[..., None]).astype(F)).astype(F) + (up * (st * sphi).astype(F)[..., None]).astype(F)
+    d = _normalize(v.astype(F))
+    d = np.where(inside[..., None], d, F(0.0)).astype(F)
+    return _records(pos, d.reshape(h * w, 3))

@@ -18,6 +18,7 @@
 
 #include "bhray_accum.h"
 #include "bhray_adapt.h"
+#include "bhray_stillcam.h"
 #include "bhray_bvh_core.h"
 #include "bhray_dev.h"
 #include "bhray_internal.h"
@@ -228,6 +229,8 @@ struct bhray_dev {
     uint32_t* a_ctl = nullptr; uint32_t* a_hctl = nullptr;   // the selection's control block ([0] count, [1] largest issued): device, and the pinned word it is copied to
     int a_mode = 0;                        // since the last begin: 0 no sample yet, 1 dev_accum_add's, 2 adaptive (a_samples is then `reach`)
     uint32_t a_min = 0, a_round = 0;       // the first adaptive call's min_samples / round_samples since begin: what later calls must repeat
+    // still cameras (dev_accum_set_camera): read by every dev_accum_add / dev_accum_add_adaptive / dev_accum_sample_rays at the time of the call
+    bhray_still_camera a_cam{(uint32_t)sizeof(bhray_still_camera), BHRAY_STILL_PINHOLE, 3.14159274f, 0.0f, 1.0f};
     bhray::ReadRing reads;                 // tickets of the asynchronous hand-off (dev_read_async)
     std::string err;
 };
@@ -1453,6 +1456,9 @@ int dev_accum_add(bhray_dev* c, uint32_t samples) {
     { int rc = ensure_query(c); if (rc) return rc; }
     AccumGen g;
     accum_gen_args(c, g);
+    const bool still = !still_camera_is_default(c->a_cam);        // another projection or a lens: bhray_stillcam.hip's generator in accum_gen_kernel's place
+    StillGen sg;
+    if (still) still_gen_fill(sg, c->cfg, c->cam, c->a_cam);
     const uint32_t launch_rays = c->a_launch_rays ? c->a_launch_rays : ACCUM_LAUNCH_RAYS;
     const uint32_t kmax = std::max<uint32_t>(1u, launch_rays / g.npix);                   // a small frame takes several samples per launch: the device stays filled
     { int rc = accum_staging(c, (size_t)std::min(samples, kmax) * g.npix); if (rc) return rc; }
@@ -1460,7 +1466,8 @@ int dev_accum_add(bhray_dev* c, uint32_t samples) {
     for (uint32_t left = samples; left != 0;) {                   // in stream order: launch i + 1 rewrites the staging behind launch i's add
         const uint32_t k = std::min(left, kmax);
         g.s0 = c->a_samples; g.k = k;
-        HIPCHK(c, launch_accum_gen(g, c->a_rays, c->q_stream));
+        if (still) { sg.a.s0 = g.s0; sg.a.k = k; HIPCHK(c, launch_still_gen(sg, c->a_rays, c->q_stream)); }
+        else HIPCHK(c, launch_accum_gen(g, c->a_rays, c->q_stream));
         { int rc = enqueue_rays(c, c->a_rays, k * g.npix, c->a_res); if (rc) return rc; }
         HIPCHK(c, launch_accum_add(sky, c->a_res, c->a_sum, g.npix, k, c->q_stream));
         c->a_samples += k; left -= k;
@@ -1511,14 +1518,16 @@ int adaptive_select(bhray_dev* c, const bhray_accum_adaptive& a, uint32_t& n, ui
 }
 
 // `count` more samples for the n listed pixels (list == nullptr: every pixel), in chunks of launch_rays / n sub-samples: gen, trace, add; the last add advances issued
-int adaptive_round(bhray_dev* c, AccumGen& g, const TexDev& sky, const uint32_t* list, uint32_t n, uint32_t count) {
+// (sg != nullptr: the still camera's list generator in adapt_gen_kernel's place)
+int adaptive_round(bhray_dev* c, AccumGen& g, StillGen* sg, const TexDev& sky, const uint32_t* list, uint32_t n, uint32_t count) {
     const uint32_t launch_rays = c->a_launch_rays ? c->a_launch_rays : ACCUM_LAUNCH_RAYS;
     const uint32_t kmax = std::max<uint32_t>(1u, launch_rays / n);
     { int rc = accum_staging(c, (size_t)std::min(count, kmax) * n); if (rc) return rc; }
     for (uint32_t j0 = 0; j0 < count;) {                          // in stream order: chunk i + 1 rewrites the staging behind chunk i's add
         const uint32_t k = std::min(count - j0, kmax);
         g.k = k;
-        HIPCHK(c, launch_adapt_gen(g, list, n, j0, c->a_state, c->a_rays, c->q_stream));
+        if (sg) { sg->a.k = k; HIPCHK(c, launch_still_gen_list(*sg, list, n, j0, c->a_state, c->a_rays, c->q_stream)); }
+        else HIPCHK(c, launch_adapt_gen(g, list, n, j0, c->a_state, c->a_rays, c->q_stream));
         { int rc = enqueue_rays(c, c->a_rays, k * n, c->a_res); if (rc) return rc; }
         j0 += k;
         HIPCHK(c, launch_adapt_add(sky, c->a_res, list, n, k, j0 == count ? count : 0u, c->a_sum, c->a_state, c->q_stream));
@@ -1541,10 +1550,13 @@ int dev_accum_add_adaptive(bhray_dev* c, const bhray_accum_adaptive* params, bhr
     { int rc = ensure_adaptive(c); if (rc) return rc; }
     AccumGen g;
     accum_gen_args(c, g);
+    StillGen sgen;
+    StillGen* sg = nullptr;
+    if (!still_camera_is_default(c->a_cam)) { still_gen_fill(sgen, c->cfg, c->cam, c->a_cam); sg = &sgen; }
     TexDev sky; sky.rgba = c->tex[BHRAY_TEX_SKY]; sky.w = c->tex_w[BHRAY_TEX_SKY]; sky.h = c->tex_h[BHRAY_TEX_SKY];
     bhray_accum_adaptive_info I{};
     if (c->a_mode == 0) {                                         // the first round: every pixel, no test
-        { int rc = adaptive_round(c, g, sky, nullptr, g.npix, a.min_samples); if (rc) return rc; }
+        { int rc = adaptive_round(c, g, sg, sky, nullptr, g.npix, a.min_samples); if (rc) return rc; }
         c->a_mode = 2; c->a_min = a.min_samples; c->a_round = a.round_samples; c->a_samples = a.min_samples;
         I.rounds = 1; I.rays = (uint64_t)g.npix * a.min_samples;
     }
@@ -1553,7 +1565,7 @@ int dev_accum_add_adaptive(bhray_dev* c, const bhray_accum_adaptive* params, bhr
         { int rc = adaptive_select(c, a, n, top); if (rc) return rc; }
         I.active_last = n;
         if (n == 0) break;
-        { int rc = adaptive_round(c, g, sky, c->a_list, n, a.round_samples); if (rc) return rc; }
+        { int rc = adaptive_round(c, g, sg, sky, c->a_list, n, a.round_samples); if (rc) return rc; }
         c->a_samples = std::max(c->a_samples, top + a.round_samples);
         I.rounds++; I.rays += (uint64_t)n * a.round_samples;
     }
@@ -1645,11 +1657,26 @@ int dev_accum_sample_rays(bhray_dev* c, uint32_t s, bhray_ray* out) {
     { int rc = ensure_query(c); if (rc) return rc; }
     float4* d = nullptr;
     HIPCHK(c, hipMalloc(&d, (size_t)g.npix * sizeof(bhray_ray)));
-    hipError_t e = launch_accum_gen(g, d, c->q_stream);
+    hipError_t e;
+    if (still_camera_is_default(c->a_cam)) e = launch_accum_gen(g, d, c->q_stream);
+    else {
+        StillGen sg;
+        still_gen_fill(sg, c->cfg, c->cam, c->a_cam);
+        sg.a.s0 = s; sg.a.k = 1;
+        e = launch_still_gen(sg, d, c->q_stream);
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(c->q_stream);
     if (e == hipSuccess) e = hipMemcpy(out, d, (size_t)g.npix * sizeof(bhray_ray), hipMemcpyDeviceToHost);
     (void)hipFree(d);
     HIPCHK(c, e);
+    return BHRAY_OK;
+}
+
+// validates and stores: no device call, no image touched (NULL: the default)
+int dev_accum_set_camera(bhray_dev* c, const bhray_still_camera* cam) {
+    if (!c) return BHRAY_E_INVALID;
+    if (const char* why = still_camera_error(cam)) return fail(c, BHRAY_E_INVALID, "bhray_accum_set_camera: %s", why);
+    if (cam) c->a_cam = *cam; else bhray_still_camera_default(&c->a_cam);
     return BHRAY_OK;
 }
 

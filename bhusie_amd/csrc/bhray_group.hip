@@ -1682,6 +1682,12 @@ int bhray_accum_sample_rays(bhray_ctx* c, uint32_t s, bhray_ray* out) {
     DEV(c, c->parts[0].dev, dev_accum_sample_rays(c->parts[0].dev, s, out));
     return BHRAY_OK;
 }
+// Still cameras: state of every local engine, accepted on any ctx - what cannot accumulate refuses bhray_accum_add as before.
+int bhray_accum_set_camera(bhray_ctx* c, const bhray_still_camera* cam) {
+    if (!c) return BHRAY_E_INVALID;
+    for (Part& p : c->parts) if (p.dev) DEV(c, p.dev, dev_accum_set_camera(p.dev, cam));
+    return BHRAY_OK;
+}
 int bhray_accum_set_launch_rays(bhray_ctx* c, uint32_t max_rays) {
     if (!c) return BHRAY_E_INVALID;
     ENTER(c);

@@ -76,6 +76,11 @@ OFF(bhray_accum_adaptive, struct_size, 0); OFF(bhray_accum_adaptive, min_samples
 OFF(bhray_accum_adaptive, tolerance, 16); OFF(bhray_accum_adaptive, dark, 20);
 SZ(bhray_accum_adaptive_info, 24);
 OFF(bhray_accum_adaptive_info, rounds, 0); OFF(bhray_accum_adaptive_info, active_last, 4); OFF(bhray_accum_adaptive_info, rays, 8); OFF(bhray_accum_adaptive_info, reach, 16);
+// the still camera of bhray_accum_set_camera
+SZ(bhray_still_camera, 20);
+OFF(bhray_still_camera, struct_size, 0); OFF(bhray_still_camera, projection, 4); OFF(bhray_still_camera, fisheye_fov, 8); OFF(bhray_still_camera, lens_radius, 12);
+OFF(bhray_still_camera, focus_distance, 16);
+static_assert(BHRAY_STILL_PINHOLE == 0 && BHRAY_STILL_EQUIRECT == 1 && BHRAY_STILL_FISHEYE == 2, "BHRAY_STILL_*");
 static_assert(BHRAY_MAX_PATH_STRIDE_LOG2 == 16 && BHRAY_MAX_PATH_POINTS_PER_CALL == (1u << 24), "BHRAY_MAX_PATH_*");
 static_assert(BHRAY_HIT_NONE == 0 && BHRAY_HIT_HORIZON == 1 && BHRAY_HIT_DISK == 2 && BHRAY_HIT_MESH == 3 && BHRAY_HIT_UNUSABLE == 255, "BHRAY_HIT_*");
 

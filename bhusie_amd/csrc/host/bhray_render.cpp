@@ -1,7 +1,7 @@
 // bhray_render — minimal C++ host program over renderer.hpp: renders one frame of the reference's default scene
 // (camera (0,0,-19), hole at the origin, disk 2..10, R = 20; camera.rs:10-16, blackhole.rs:16-28) and writes the HDR frame
 // as raw little-endian f32 RGBA (row 0 = top).  Usage:
-//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--pick X Y] [--path X Y [--path-stride S]]
+//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--pick X Y] [--path X Y [--path-stride S]]
 // --spp N: instead of the ladder's frame, a supersampled still - the mean of N jittered samples per frame pixel, sky resolved, accumulated on the GPU
 //   (Renderer::render_still: bhray_accum_*); written the same way.  Not with --lensed-mesh, --devices or --panorama.
 // --spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]: an adaptive still instead - every pixel takes MIN samples, then R more (4 by default) for as long as the
@@ -9,6 +9,9 @@
 //   (Renderer::render_still_adaptive: bhray_accum_add_adaptive); written the same way, followed by one line
 //   adaptive rounds=N rays=N mean_count=F
 //   Not with --spp, --lensed-mesh, --devices or --panorama.
+// --still-camera pinhole|equirect|fisheye FOV, --lens RADIUS FOCUS (with --spp or --spp-adaptive): the still's camera model, evaluated on the GPU (bhray_accum_set_camera,
+//   DESIGN.md §21) - a 360 x 180 degree panorama over the frame, an equidistant fisheye of full opening angle FOV (radians, 0 < FOV <= 2 pi), or the pinhole (the
+//   default); --lens gives the pinhole a thin lens of aperture radius RADIUS > 0 focused at distance FOCUS > 0 (depth of field) and goes with no other projection.
 // --path X Y [--path-stride S]: after the frame, the pick line of pixel (X, Y) and then the light path behind it, one line per point - that pixel's pinhole ray through
 //   bhray_trace_rays_paths (Renderer::ray_path), a point every 2^S iterations (S = 0 by default) and the end point:
 //   ITERATION X Y Z
@@ -157,12 +160,15 @@ int main(int argc, char** argv) {
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
         return 0;
     }
-    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--pick X Y] [--path X Y [--path-stride S]]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--pick X Y] [--path X Y [--path-stride S]]\n", argv[0]); return 2; }
     uint32_t bw = 72, bh = 41, levels = 4, disk = 256, pano_w = 0, pano_h = 0;
     long pick_x = -1, pick_y = -1, path_x = -1, path_y = -1, path_stride = 0, spp = 0;
     bool rk = false, bvh_device = false, lensed = false, posed = false, adaptive = false;
     long a_min = 0, a_max = 0, a_round = 4;
     double a_tol = 0.0, a_dark = 0.01;
+    bool still_given = false, lens_given = false;
+    bhray_still_camera still{};
+    bhray_still_camera_default(&still);
     float rotation[3] = {0.0f, 0.0f, 0.0f};
     std::vector<const char*> objs;
     std::vector<int> devices;
@@ -184,6 +190,24 @@ int main(int argc, char** argv) {
         }
         else if (!std::strcmp(argv[i], "--spp-round") && i + 1 < argc) { a_round = std::atol(argv[++i]); if (a_round < 1 || a_round > (long)BHRAY_ACCUM_MAX_SAMPLES) { std::fprintf(stderr, "--spp-round needs 1 <= R <= %u\n", BHRAY_ACCUM_MAX_SAMPLES); return 2; } }
         else if (!std::strcmp(argv[i], "--spp-dark") && i + 1 < argc) { a_dark = std::atof(argv[++i]); if (!std::isfinite(a_dark) || a_dark < 0.0) { std::fprintf(stderr, "--spp-dark needs a finite D >= 0\n"); return 2; } }
+        else if (!std::strcmp(argv[i], "--still-camera") && i + 1 < argc) {
+            const char* kind = argv[++i];
+            still_given = true;
+            if (!std::strcmp(kind, "pinhole")) still.projection = BHRAY_STILL_PINHOLE;
+            else if (!std::strcmp(kind, "equirect")) still.projection = BHRAY_STILL_EQUIRECT;
+            else if (!std::strcmp(kind, "fisheye") && i + 1 < argc) {
+                still.projection = BHRAY_STILL_FISHEYE;
+                const double fov = std::atof(argv[++i]);
+                if (!std::isfinite(fov) || !(fov > 0.0) || (float)fov > 6.28318548f) { std::fprintf(stderr, "--still-camera fisheye needs 0 < FOV <= 2 pi (radians)\n"); return 2; }
+                still.fisheye_fov = (float)fov;
+            }
+            else { std::fprintf(stderr, "--still-camera needs pinhole, equirect or fisheye FOV\n"); return 2; }
+        }
+        else if (!std::strcmp(argv[i], "--lens") && i + 2 < argc) {
+            const double radius = std::atof(argv[++i]), focus = std::atof(argv[++i]);
+            if (!std::isfinite(radius) || !(radius > 0.0) || !std::isfinite(focus) || !(focus > 0.0)) { std::fprintf(stderr, "--lens needs RADIUS > 0 and FOCUS > 0\n"); return 2; }
+            lens_given = true; still.lens_radius = (float)radius; still.focus_distance = (float)focus;
+        }
         else if (!std::strcmp(argv[i], "--pick") && i + 2 < argc) { pick_x = std::atol(argv[++i]); pick_y = std::atol(argv[++i]); if (pick_x < 0 || pick_y < 0) { std::fprintf(stderr, "--pick needs X >= 0 and Y >= 0\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--path") && i + 2 < argc) { path_x = std::atol(argv[++i]); path_y = std::atol(argv[++i]); if (path_x < 0 || path_y < 0) { std::fprintf(stderr, "--path needs X >= 0 and Y >= 0\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--path-stride") && i + 1 < argc) { path_stride = std::atol(argv[++i]); if (path_stride < 0 || path_stride > BHRAY_MAX_PATH_STRIDE_LOG2) { std::fprintf(stderr, "--path-stride needs 0 <= S <= %d\n", BHRAY_MAX_PATH_STRIDE_LOG2); return 2; } }
@@ -193,6 +217,8 @@ int main(int argc, char** argv) {
     if (adaptive && spp) { std::fprintf(stderr, "--spp-adaptive and --spp are two ways to fill the same image: give one\n"); return 2; }
     if (adaptive && pano_w) { std::fprintf(stderr, "--spp-adaptive samples the pixels of the pinhole frame: not with --panorama\n"); return 2; }
     if (adaptive && (a_max - a_min) % a_round != 0) { std::fprintf(stderr, "--spp-adaptive needs MAX - MIN to be a multiple of the round (--spp-round, 4 by default)\n"); return 2; }
+    if ((still_given || lens_given) && !spp && !adaptive) { std::fprintf(stderr, "--still-camera and --lens are the camera of a still: give --spp or --spp-adaptive\n"); return 2; }
+    if (lens_given && still.projection != BHRAY_STILL_PINHOLE) { std::fprintf(stderr, "--lens goes with the pinhole projection only\n"); return 2; }
     if (spp && pano_w) { std::fprintf(stderr, "--spp samples the pixels of the pinhole frame: not with --panorama\n"); return 2; }
     if (path_x >= 0 && pano_w) { std::fprintf(stderr, "--path names a pixel of the pinhole frame: not with --panorama\n"); return 2; }
     if (pick_x >= 0 && pano_w) { std::fprintf(stderr, "--pick names a pixel of the pinhole frame: not with --panorama\n"); return 2; }
@@ -226,9 +252,9 @@ int main(int argc, char** argv) {
         } else if (adaptive) {
             bhray_accum_adaptive a{};
             a.min_samples = (uint32_t)a_min; a.max_samples = (uint32_t)a_max; a.round_samples = (uint32_t)a_round; a.tolerance = (float)a_tol; a.dark = (float)a_dark;
-            out = r.render_still_adaptive(a, &ainfo, &counts);
+            out = r.render_still_adaptive(a, &ainfo, &counts, &still);
         } else if (spp) {
-            out = r.render_still((uint32_t)spp);
+            out = r.render_still((uint32_t)spp, &still);
         } else {
             r.render(0.0f);
             out = r.ray_pipeline().output();

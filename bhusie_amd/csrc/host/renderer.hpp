@@ -230,6 +230,14 @@ public:
         }
         return out;
     }
+    // still cameras (bhray_accum_set_camera): the camera model of accumulate() / accumulate_adaptive() from the next call on; null: pinhole, no lens.
+    // struct_size is filled in here.
+    void set_still_camera(const bhray_still_camera* camera) {
+        if (!camera) { check(bhray_accum_set_camera(ctx_, nullptr), ctx_); return; }
+        bhray_still_camera c = *camera;
+        c.struct_size = (uint32_t)sizeof(bhray_still_camera);
+        check(bhray_accum_set_camera(ctx_, &c), ctx_);
+    }
     bhray_ctx* ctx() { return ctx_; }
 private:
     bhray_config cfg_;
@@ -377,16 +385,21 @@ public:
         return ray_pipeline_.trace_rays(rays);
     }
     // a supersampled still of the current scene: the mean of `samples` jittered samples per frame pixel (RayPipeline::accumulate), RGBA32F as output() after the sky pass
-    std::vector<float> render_still(uint32_t samples) {
+    // still_camera (may be null: the pinhole): the still as a panorama, a fisheye or through a thin lens from the camera's position along its forward
+    // (RayPipeline::set_still_camera)
+    std::vector<float> render_still(uint32_t samples, const bhray_still_camera* still_camera = nullptr) {
         ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);
         apply_lensing();
+        ray_pipeline_.set_still_camera(still_camera);
         return ray_pipeline_.accumulate(samples);
     }
     // an adaptive still of the current scene (RayPipeline::accumulate_adaptive): params.struct_size is filled in here
-    std::vector<float> render_still_adaptive(bhray_accum_adaptive params, bhray_accum_adaptive_info* info = nullptr, std::vector<uint32_t>* counts = nullptr) {
+    std::vector<float> render_still_adaptive(bhray_accum_adaptive params, bhray_accum_adaptive_info* info = nullptr, std::vector<uint32_t>* counts = nullptr,
+                                             const bhray_still_camera* still_camera = nullptr) {
         params.struct_size = (uint32_t)sizeof(bhray_accum_adaptive);
         ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);
         apply_lensing();
+        ray_pipeline_.set_still_camera(still_camera);
         return ray_pipeline_.accumulate_adaptive(params, info, counts);
     }
     // what is under frame pixel (x, y): the record of that pixel's pinhole ray under the current scene (hit & 0xff: BHRAY_HIT_*; (hit >> 8) & 0xff: the model slot of a mesh hit)

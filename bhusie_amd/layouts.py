@@ -107,6 +107,15 @@ class BhrayAccumAdaptiveInfo(C.Structure):  # bhray_accum_adaptive_info: what on
 
 assert C.sizeof(BhrayAccumAdaptive) == 24 and C.sizeof(BhrayAccumAdaptiveInfo) == 24 and BhrayAccumAdaptiveInfo.rays.offset == 8
 
+STILL_PINHOLE, STILL_EQUIRECT, STILL_FISHEYE = 0, 1, 2      # BHRAY_STILL_*
+
+
+class BhrayStillCamera(C.Structure):        # bhray_still_camera: the accumulation image's camera (bhray_accum_set_camera)
+    _fields_ = [("struct_size", C.c_uint32), ("projection", C.c_uint32), ("fisheye_fov", C.c_float), ("lens_radius", C.c_float), ("focus_distance", C.c_float)]
+
+
+assert C.sizeof(BhrayStillCamera) == 20 and BhrayStillCamera.focus_distance.offset == 16
+
 
 class BhrayModelDesc(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("visible", C.c_int32),
@@ -263,6 +272,8 @@ SYMBOLS = {
     "bhray_accum_sample_offset": (None, [u32, P(C.c_float), P(C.c_float)]),
     "bhray_accum_add_adaptive": (C.c_int, [vp, P(BhrayAccumAdaptive), P(BhrayAccumAdaptiveInfo)]),
     "bhray_accum_read_counts": (C.c_int, [vp, vp, sz]),
+    "bhray_accum_set_camera": (C.c_int, [vp, P(BhrayStillCamera)]),
+    "bhray_still_camera_default": (None, [P(BhrayStillCamera)]),
     "bhray_render": (C.c_int, [vp]),
     "bhray_flush": (C.c_int, [vp]),
     "bhray_sync": (C.c_int, [vp]),
@@ -330,6 +341,7 @@ DIAG_SYMBOLS = {
     "bhray_read_model_vertices": (C.c_int, [vp, u32, vp, u32, vp, u32, P(u32), P(u32)]),
     "bhray_accum_sample_rays": (C.c_int, [vp, u32, P(BhrayRay)]),
     "bhray_accum_set_launch_rays": (C.c_int, [vp, u32]),
+    "bhray_still_sample_rays_host": (C.c_int, [P(BhrayConfig), vp, P(BhrayStillCamera), u32, P(BhrayRay)]),
     "bhray_accum_active_pixels": (C.c_int, [vp, P(BhrayAccumAdaptive), P(u32), u32, P(u32)]),
     "bhray_read_sky_pyramid_level": (C.c_int, [vp, u32, vp, sz]),
 }

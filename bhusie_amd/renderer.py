@@ -451,6 +451,13 @@ class RayPass:
         """At most max_rays rays per trace launch of accum_add (0: the default, 2**22); the image does not depend on it (bhray_diag.h)."""
         check(self._L.bhray_accum_set_launch_rays(self._h, int(max_rays)), self._h, self._L)
 
+    def accum_set_camera(self, still_camera=None):
+        """The camera model of the accumulation image from the next accum_add / accum_add_adaptive on (bhray_accum_set_camera): a cameras.StillCamera
+        - .equirect(), .fisheye(fov), .pinhole(lens_radius, focus_distance) - or None for the default, the pinhole without a lens.  Position, forward and the
+        pinhole's fov stay those of set_uniforms' camera block.  Validates and stores only; a camera the library refuses: BhrayError (BHRAY_E_INVALID)."""
+        s = still_camera.struct() if still_camera is not None else None
+        check(self._L.bhray_accum_set_camera(self._h, C.byref(s) if s is not None else None), self._h, self._L)
+
     # -- adaptive stills: each pixel sampled until the error of its mean is under a bound (bhray_accum_add_adaptive, DESIGN.md §20)
     @staticmethod
     def _adaptive_params(min_samples, max_samples, round_samples, tolerance, dark) -> BhrayAccumAdaptive:
@@ -848,11 +855,12 @@ class Renderer:
                 "closest": float(r["closest"]), "transmittance": float(r["transmittance"]),
                 "path": pts["position"][0, :k].copy(), "path_iterations": pts["iteration"][0, :k].copy()}
 
-    def _accumulate(self, samples: int, shutter: float):
+    def _accumulate(self, samples: int, shutter: float, camera=None):
         samples = int(samples)
         if samples < 1:
             raise ValueError(f"render_still: samples must be at least 1, got {samples}")
         self._apply_uniforms()
+        self.ray_pass.accum_set_camera(camera)
         self.ray_pass.accum_begin()
         if not shutter > 0.0:
             self.ray_pass.accum_add(samples)
@@ -866,18 +874,22 @@ class Renderer:
         finally:
             self.ray_details.time = t0
 
-    def render_still(self, samples: int = 16, shutter: float = 0.0, adaptive: AdaptiveStill | None = None) -> np.ndarray:
+    def render_still(self, samples: int = 16, shutter: float = 0.0, adaptive: AdaptiveStill | None = None, camera=None) -> np.ndarray:
         """A supersampled still of the current scene (RayPass.accum_*): the mean of `samples` jittered samples per frame pixel, sky resolved,
         (frame_h, frame_w, 4) float32.  Sample 0 is the pixel centre, so samples=1 is the frame a `levels = 1` ladder renders, after the sky pass in binary32.
         shutter > 0: motion blur - sample s is rendered at ray_details.time + shutter * s / samples (the disk turns with `time`); ray_details.time is left as it was.
         adaptive: an AdaptiveStill - each pixel is sampled until the error of its mean is under the bound; `samples` is then not read, the motion blur is
-        not available (ValueError), still_info holds what the call did and still_counts() delivers the per-pixel sample counts."""
+        not available (ValueError), still_info holds what the call did and still_counts() delivers the per-pixel sample counts.
+        camera: a cameras.StillCamera - the still as a 360 x 180 degree panorama (.equirect()), a fisheye (.fisheye(fov)) or through a thin lens
+        (.pinhole(lens_radius, focus_distance): depth of field; sample 0 is then a lens sample, not the centre ray) from the scene camera's position along its forward
+        (DESIGN.md §21); None: the pinhole.  The ctx keeps the camera of the last still."""
         if adaptive is None:
-            self._accumulate(samples, shutter)
+            self._accumulate(samples, shutter, camera)
             return self.ray_pass.accum_read()
         if shutter > 0.0:
             raise ValueError("render_still: an adaptive still has no shutter (every pixel takes its own number of samples)")
         self._apply_uniforms()
+        self.ray_pass.accum_set_camera(camera)
         self.ray_pass.accum_begin()
         self.still_info = self.ray_pass.accum_add_adaptive(**adaptive.as_kwargs())
         return self.ray_pass.accum_read()
@@ -886,10 +898,10 @@ class Renderer:
         """The sample-count heat map of the last adaptive still: (frame_h, frame_w) uint32."""
         return self.ray_pass.accum_read_counts()
 
-    def save_still(self, path, samples: int = 16):
-        """save_image for a supersampled still: the mean of `samples` samples per pixel through the display pass, written with alpha 255."""
+    def save_still(self, path, samples: int = 16, camera=None):
+        """save_image for a supersampled still: the mean of `samples` samples per pixel through the display pass, written with alpha 255.  camera: as render_still's."""
         from PIL import Image
-        self._accumulate(samples, 0.0)
+        self._accumulate(samples, 0.0, camera)
         img = self.ray_pass.accum_read_display()
         img[..., 3] = 255
         Image.fromarray(img, "RGBA").save(path)

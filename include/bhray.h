@@ -629,6 +629,56 @@ typedef struct bhray_accum_adaptive_info {
 int bhray_accum_add_adaptive(bhray_ctx* ctx, const bhray_accum_adaptive* params, bhray_accum_adaptive_info* info /* may be NULL */);
 int bhray_accum_read_counts(bhray_ctx* ctx, uint32_t* dst, size_t row_pitch_bytes);   /* frame_h rows of frame_w uint32 */
 
+/* Still cameras: the camera model of the accumulation image, evaluated on the device.  Per-ctx state,
+ * read by each bhray_accum_add / bhray_accum_add_adaptive call at the time of the call, like the uniforms: changing it
+ * between calls of one accumulation is the caller's business.  It plays no part in frames (bhray_render), whose camera
+ * stays create_ray's pinhole.  Everything behind the generated rays - trace, resolve, sum, the adaptive rule, the reads -
+ * is as above.
+ * Shared by all projections: the position, `forward` and `fov` of the camera block of the last bhray_set_uniforms;
+ * right = normalize(cross(forward, (0, -1, 0))), up = normalize(cross(forward, right)), fwd_ff = forward * (1 /
+ * tan(fov / 2)) as a frame forms them; fwd_n = normalize(forward).  Sample s of frame pixel (x, y) has the offset
+ * (dx, dy) above, unchanged: px = float(crop_x + x) + dx, py = float(crop_y + y) + dy; half_w = float(lw - 1) * 0.5f,
+ * half_h = float(lh - 1) * 0.5f on the ladder's last level lw x lh, so a cropped frame is a window of the whole level's
+ * still for every projection.  Every step is one rounded binary32 operation in the order written, no FMA; sin and cos
+ * are the library's own polynomial forms (the kernels' bh_sincos), normalize(v) = v * (1 / sqrt((x*x + y*y) + z*z)).
+ *   PINHOLE, lens_radius == 0 (the default)   the ray above: the same kernels, the same bits as without this call.
+ *   EQUIRECT   360 x 180 degrees over the level: lon = (px - half_w) * (6.28318548f / float(lw)), lat = (py - half_h) *
+ *              (3.14159274f / float(lh)); cl, sl = cos, sin(lon); cp, sp = cos, sin(lat);
+ *              d = normalize((fwd_n * (cp * cl) + right * (cp * sl)) + up * sp).  The origin is the camera position.
+ *   FISHEYE    equidistant, full opening angle fisheye_fov: radius = float(min(lw - 1, lh - 1)) * 0.5f, X = (px -
+ *              half_w) / radius, Y = (py - half_h) / radius (IEEE division), r = sqrt(X * X + Y * Y), theta = r *
+ *              (fisheye_fov * 0.5f), safe = r > 0 ? r : 1, cphi = X / safe, sphi = Y / safe, st, ct = sin, cos(theta);
+ *              d = normalize((fwd_n * ct + right * (st * cphi)) + up * (st * sphi)).  A sample with !(r <= 1) lies
+ *              outside the image circle and gets an all-zero direction: the trace answers such a record (0, 0, 0, -1),
+ *              the resolve passes it through and the sum counts it (a finite black sample), so the rim of the circle is
+ *              an antialiased edge to black and the pixels wholly outside are black with alpha 1.
+ *   PINHOLE, lens_radius > 0   a thin lens with a spherical surface of focus.  d = the pinhole direction above;
+ *              q = (crop_y + y) * lw + (crop_x + x), the level pixel index; h(v): v ^= v >> 16; v *= 0x7feb352d;
+ *              v ^= v >> 15; v *= 0x846ca68b; v ^= v >> 16 (uint32); a = h(q) + s * 0x9E3779B9, b = h(q ^ 0x9E3779B9) +
+ *              s * 0x6A09E667 (mod 2^32); ru = float(a >> 8) * 2^-24, rv = float(b >> 8) * 2^-24; rr = sqrt(ru),
+ *              ang = rv * 6.28318548f; lx = (rr * cos(ang)) * lens_radius, ly = (rr * sin(ang)) * lens_radius;
+ *              off = right * lx + up * ly; origin = position + off; direction = normalize(d * focus_distance - off).
+ *              The lens coordinates are Kronecker sequences on the golden ratio and sqrt 2, rotated per pixel by the
+ *              hash so that neighbouring pixels do not share a lens point; sample 0 is then NOT the centre ray, and a
+ *              one-sample still is not the frame.  Origins differ per ray; the trace forms its per-ray terms as for any
+ *              ray batch.
+ * bhray_accum_set_camera only validates and stores: it needs no device, touches no image, and is accepted in every
+ * state (the refusals of bhray_accum_add stay on bhray_accum_add, on the same calls).  NULL restores the default.
+ * BHRAY_E_INVALID, the camera in force untouched: a struct_size other than sizeof(bhray_still_camera); an unknown
+ * projection; FISHEYE with a fisheye_fov that is not finite or outside (0, 2 pi] (6.28318548f); a lens_radius that is
+ * negative or not finite; lens_radius > 0 with a projection other than PINHOLE, or with a focus_distance that is not
+ * finite and positive.  bhray_still_camera_default fills in the default: pinhole, no lens.                           */
+enum { BHRAY_STILL_PINHOLE = 0, BHRAY_STILL_EQUIRECT = 1, BHRAY_STILL_FISHEYE = 2 };
+typedef struct bhray_still_camera {
+    uint32_t struct_size;      /* = sizeof(bhray_still_camera) */
+    uint32_t projection;       /* BHRAY_STILL_* */
+    float    fisheye_fov;      /* FISHEYE: full opening angle in radians, finite, 0 < fov <= 2 pi; otherwise not read */
+    float    lens_radius;      /* PINHOLE only: aperture radius in scene units; 0 = no lens */
+    float    focus_distance;   /* read when lens_radius > 0: finite, > 0 */
+} bhray_still_camera;
+int  bhray_accum_set_camera(bhray_ctx* ctx, const bhray_still_camera* camera);   /* NULL = the default: pinhole, no lens */
+void bhray_still_camera_default(bhray_still_camera* camera);
+
 /* Dispatch — replaces `for rp in ray_pipelines { rp.pass() }` (mod.rs:415-417,
  * ray_pipeline.rs:301-309).  Asynchronous on the ctx stream; levels ordered.                 */
 int bhray_render(bhray_ctx* ctx);

@@ -171,10 +171,17 @@ int bhray_read_model_vertices(bhray_ctx* ctx, uint32_t model_index, float* point
 /* ------------------------------------------------------------------------------------------
  * The accumulation image (bhray_accum_*)
  * ---------------------------------------------------------------------------------------- */
-/* The records the generator kernel writes for sample s under the current uniforms: frame_w * frame_h of them, row 0
- * the top, x fastest.  Needs no bhray_accum_begin; s >= BHRAY_ACCUM_MAX_SAMPLES or a NULL out: BHRAY_E_INVALID; the
- * refused states of bhray_accum_add apart from mesh lensing (the generator does not trace).  Waits.                   */
+/* The records the generator kernel writes for sample s under the current uniforms and the still camera in force
+ * (bhray_accum_set_camera): frame_w * frame_h of them, row 0 the top, x fastest.  Needs no bhray_accum_begin; s >=
+ * BHRAY_ACCUM_MAX_SAMPLES or a NULL out: BHRAY_E_INVALID; the refused states of bhray_accum_add apart from mesh lensing
+ * (the generator does not trace).  Waits.                                                                             */
 int bhray_accum_sample_rays(bhray_ctx* ctx, uint32_t s, bhray_ray* out);
+/* The same records by host arithmetic: the function the still-camera kernels call, compiled for the
+ * host, over the frame of `cfg`, the 32 bytes of a bhray_camera_uniform and `camera` (NULL: the default; then the
+ * records are those of the pinhole generator).  Needs no ctx and no device.  BHRAY_E_INVALID: a NULL cfg, uniform or
+ * out, s >= BHRAY_ACCUM_MAX_SAMPLES, a cfg that is no ladder with a frame inside its last level, a camera that
+ * bhray_accum_set_camera refuses.                                                                                     */
+int bhray_still_sample_rays_host(const bhray_config* cfg, const void* camera_uniform_32, const bhray_still_camera* camera, uint32_t s, bhray_ray* out);
 /* At most max_rays rays per trace launch of bhray_accum_add: K = max(1, max_rays / (frame_w * frame_h)) samples go
  * into one launch.  0 restores the default, 2^22; more than BHRAY_MAX_RAYS_PER_CALL: BHRAY_E_INVALID.  The image
  * does not depend on it.                                                                                             */
