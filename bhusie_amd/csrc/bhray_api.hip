@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "bhray_accum.h"
+#include "bhray_accum_filter.h"
 #include "bhray_adapt.h"
 #include "bhray_stillcam.h"
 #include "bhray_bvh_core.h"
@@ -231,6 +232,8 @@ struct bhray_dev {
     uint32_t a_min = 0, a_round = 0;       // the first adaptive call's min_samples / round_samples since begin: what later calls must repeat
     // still cameras (dev_accum_set_camera): read by every dev_accum_add / dev_accum_add_adaptive / dev_accum_sample_rays at the time of the call
     bhray_still_camera a_cam{(uint32_t)sizeof(bhray_still_camera), BHRAY_STILL_PINHOLE, 3.14159274f, 0.0f, 1.0f};
+    // still pixel filters (dev_accum_set_filter): read by every dev_accum_add at the time of the call; the box runs accum_add_kernel
+    bhray_still_filter a_filter{(uint32_t)sizeof(bhray_still_filter), BHRAY_FILTER_BOX, 2.0f, 1.0f / 3.0f, 1.0f / 3.0f};
     bhray::ReadRing reads;                 // tickets of the asynchronous hand-off (dev_read_async)
     std::string err;
 };
@@ -1459,6 +1462,9 @@ int dev_accum_add(bhray_dev* c, uint32_t samples) {
     const bool still = !still_camera_is_default(c->a_cam);        // another projection or a lens: bhray_stillcam.hip's generator in accum_gen_kernel's place
     StillGen sg;
     if (still) still_gen_fill(sg, c->cfg, c->cam, c->a_cam);
+    const bool filtered = c->a_filter.kind != BHRAY_FILTER_BOX;   // a tent or a cubic: bhray_accum_filter.hip's stencil in accum_add_kernel's place
+    AccumFilter af;
+    if (filtered) accum_filter_fill(af, c->a_filter);
     const uint32_t launch_rays = c->a_launch_rays ? c->a_launch_rays : ACCUM_LAUNCH_RAYS;
     const uint32_t kmax = std::max<uint32_t>(1u, launch_rays / g.npix);                   // a small frame takes several samples per launch: the device stays filled
     { int rc = accum_staging(c, (size_t)std::min(samples, kmax) * g.npix); if (rc) return rc; }
@@ -1469,7 +1475,8 @@ int dev_accum_add(bhray_dev* c, uint32_t samples) {
         if (still) { sg.a.s0 = g.s0; sg.a.k = k; HIPCHK(c, launch_still_gen(sg, c->a_rays, c->q_stream)); }
         else HIPCHK(c, launch_accum_gen(g, c->a_rays, c->q_stream));
         { int rc = enqueue_rays(c, c->a_rays, k * g.npix, c->a_res); if (rc) return rc; }
-        HIPCHK(c, launch_accum_add(sky, c->a_res, c->a_sum, g.npix, k, c->q_stream));
+        if (filtered) HIPCHK(c, launch_accum_filter_add(sky, af, c->a_res, c->a_sum, c->cfg.frame_w, c->cfg.frame_h, g.s0, k, c->q_stream));
+        else HIPCHK(c, launch_accum_add(sky, c->a_res, c->a_sum, g.npix, k, c->q_stream));
         c->a_samples += k; left -= k;
         c->a_mode = 1;
     }
@@ -1542,6 +1549,8 @@ int dev_accum_add_adaptive(bhray_dev* c, const bhray_accum_adaptive* params, bhr
     { int rc = accum_refused(c, "bhray_accum_add_adaptive"); if (rc) return rc; }
     { int rc = rays_refused(c, "bhray_accum_add_adaptive"); if (rc) return rc; }
     if (c->a_mode == 1) return fail(c, BHRAY_E_STATE, "bhray_accum_add_adaptive: this accumulation holds bhray_accum_add's samples; bhray_accum_begin starts another");
+    if (c->a_filter.kind != BHRAY_FILTER_BOX)
+        return fail(c, BHRAY_E_STATE, "bhray_accum_add_adaptive: a still filter other than the box is in force (bhray_accum_set_filter): a round's pixels take different samples");
     { int rc = adaptive_params_bad(c, "bhray_accum_add_adaptive", params); if (rc) return rc; }
     const bhray_accum_adaptive a = *params;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1677,6 +1686,14 @@ int dev_accum_set_camera(bhray_dev* c, const bhray_still_camera* cam) {
     if (!c) return BHRAY_E_INVALID;
     if (const char* why = still_camera_error(cam)) return fail(c, BHRAY_E_INVALID, "bhray_accum_set_camera: %s", why);
     if (cam) c->a_cam = *cam; else bhray_still_camera_default(&c->a_cam);
+    return BHRAY_OK;
+}
+
+// validates and stores: no device call, no image touched (NULL: the default, the box)
+int dev_accum_set_filter(bhray_dev* c, const bhray_still_filter* filter) {
+    if (!c) return BHRAY_E_INVALID;
+    if (const char* why = still_filter_error(filter)) return fail(c, BHRAY_E_INVALID, "bhray_accum_set_filter: %s", why);
+    if (filter) c->a_filter = *filter; else bhray_still_filter_default(&c->a_filter);
     return BHRAY_OK;
 }
 

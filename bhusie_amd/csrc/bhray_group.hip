@@ -1688,6 +1688,12 @@ int bhray_accum_set_camera(bhray_ctx* c, const bhray_still_camera* cam) {
     for (Part& p : c->parts) if (p.dev) DEV(c, p.dev, dev_accum_set_camera(p.dev, cam));
     return BHRAY_OK;
 }
+// Still pixel filters: state of every local engine, accepted on any ctx - what cannot accumulate refuses bhray_accum_add as before.
+int bhray_accum_set_filter(bhray_ctx* c, const bhray_still_filter* filter) {
+    if (!c) return BHRAY_E_INVALID;
+    for (Part& p : c->parts) if (p.dev) DEV(c, p.dev, dev_accum_set_filter(p.dev, filter));
+    return BHRAY_OK;
+}
 int bhray_accum_set_launch_rays(bhray_ctx* c, uint32_t max_rays) {
     if (!c) return BHRAY_E_INVALID;
     ENTER(c);

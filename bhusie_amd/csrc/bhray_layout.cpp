@@ -81,6 +81,10 @@ SZ(bhray_still_camera, 20);
 OFF(bhray_still_camera, struct_size, 0); OFF(bhray_still_camera, projection, 4); OFF(bhray_still_camera, fisheye_fov, 8); OFF(bhray_still_camera, lens_radius, 12);
 OFF(bhray_still_camera, focus_distance, 16);
 static_assert(BHRAY_STILL_PINHOLE == 0 && BHRAY_STILL_EQUIRECT == 1 && BHRAY_STILL_FISHEYE == 2, "BHRAY_STILL_*");
+// the still filter of bhray_accum_set_filter
+SZ(bhray_still_filter, 20);
+OFF(bhray_still_filter, struct_size, 0); OFF(bhray_still_filter, kind, 4); OFF(bhray_still_filter, radius, 8); OFF(bhray_still_filter, b, 12); OFF(bhray_still_filter, c, 16);
+static_assert(BHRAY_FILTER_BOX == 0 && BHRAY_FILTER_TENT == 1 && BHRAY_FILTER_CUBIC == 2, "BHRAY_FILTER_*");
 static_assert(BHRAY_MAX_PATH_STRIDE_LOG2 == 16 && BHRAY_MAX_PATH_POINTS_PER_CALL == (1u << 24), "BHRAY_MAX_PATH_*");
 static_assert(BHRAY_HIT_NONE == 0 && BHRAY_HIT_HORIZON == 1 && BHRAY_HIT_DISK == 2 && BHRAY_HIT_MESH == 3 && BHRAY_HIT_UNUSABLE == 255, "BHRAY_HIT_*");
 

@@ -238,6 +238,14 @@ public:
         c.struct_size = (uint32_t)sizeof(bhray_still_camera);
         check(bhray_accum_set_camera(ctx_, &c), ctx_);
     }
+    // still pixel filters (bhray_accum_set_filter): the reconstruction filter of accumulate() from the next call on; null: the box.
+    // struct_size is filled in here.  accumulate_adaptive() is refused under a filter other than the box.
+    void set_still_filter(const bhray_still_filter* filter) {
+        if (!filter) { check(bhray_accum_set_filter(ctx_, nullptr), ctx_); return; }
+        bhray_still_filter f = *filter;
+        f.struct_size = (uint32_t)sizeof(bhray_still_filter);
+        check(bhray_accum_set_filter(ctx_, &f), ctx_);
+    }
     bhray_ctx* ctx() { return ctx_; }
 private:
     bhray_config cfg_;
@@ -387,10 +395,13 @@ public:
     // a supersampled still of the current scene: the mean of `samples` jittered samples per frame pixel (RayPipeline::accumulate), RGBA32F as output() after the sky pass
     // still_camera (may be null: the pinhole): the still as a panorama, a fisheye or through a thin lens from the camera's position along its forward
     // (RayPipeline::set_still_camera)
-    std::vector<float> render_still(uint32_t samples, const bhray_still_camera* still_camera = nullptr) {
+    // still_filter (may be null: the box): the pixel reconstruction filter, a tent or a Mitchell-Netravali cubic (RayPipeline::set_still_filter)
+    std::vector<float> render_still(uint32_t samples, const bhray_still_camera* still_camera = nullptr) { return render_still(samples, still_camera, nullptr); }
+    std::vector<float> render_still(uint32_t samples, const bhray_still_camera* still_camera, const bhray_still_filter* still_filter) {
         ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);
         apply_lensing();
         ray_pipeline_.set_still_camera(still_camera);
+        ray_pipeline_.set_still_filter(still_filter);
         return ray_pipeline_.accumulate(samples);
     }
     // an adaptive still of the current scene (RayPipeline::accumulate_adaptive): params.struct_size is filled in here
@@ -400,6 +411,7 @@ public:
         ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);
         apply_lensing();
         ray_pipeline_.set_still_camera(still_camera);
+        ray_pipeline_.set_still_filter(nullptr);                  // an adaptive still has no filter but the box
         return ray_pipeline_.accumulate_adaptive(params, info, counts);
     }
     // what is under frame pixel (x, y): the record of that pixel's pinhole ray under the current scene (hit & 0xff: BHRAY_HIT_*; (hit >> 8) & 0xff: the model slot of a mesh hit)

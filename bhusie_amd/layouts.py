@@ -116,6 +116,15 @@ class BhrayStillCamera(C.Structure):        # bhray_still_camera: the accumulati
 
 assert C.sizeof(BhrayStillCamera) == 20 and BhrayStillCamera.focus_distance.offset == 16
 
+FILTER_BOX, FILTER_TENT, FILTER_CUBIC = 0, 1, 2             # BHRAY_FILTER_*
+
+
+class BhrayStillFilter(C.Structure):        # bhray_still_filter: the accumulation image's reconstruction filter (bhray_accum_set_filter)
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_uint32), ("radius", C.c_float), ("b", C.c_float), ("c", C.c_float)]
+
+
+assert C.sizeof(BhrayStillFilter) == 20 and BhrayStillFilter.c.offset == 16
+
 
 class BhrayModelDesc(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("visible", C.c_int32),
@@ -274,6 +283,9 @@ SYMBOLS = {
     "bhray_accum_read_counts": (C.c_int, [vp, vp, sz]),
     "bhray_accum_set_camera": (C.c_int, [vp, P(BhrayStillCamera)]),
     "bhray_still_camera_default": (None, [P(BhrayStillCamera)]),
+    "bhray_accum_set_filter": (C.c_int, [vp, P(BhrayStillFilter)]),
+    "bhray_still_filter_default": (None, [P(BhrayStillFilter)]),
+    "bhray_accum_filter_weights": (C.c_int, [P(BhrayStillFilter), u32, P(C.c_float), P(C.c_float)]),
     "bhray_render": (C.c_int, [vp]),
     "bhray_flush": (C.c_int, [vp]),
     "bhray_sync": (C.c_int, [vp]),

@@ -14,7 +14,7 @@ import numpy as np
 
 from ._lib import lib
 from .layouts import (BhrayFxaaDetails, BhrayMixDetails, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters, BhrayRay, BhrayRayRecord, BhrayPathPoint, PATH_POINT_DTYPE, HIT_MESH, HIT_UNUSABLE,
-                      BhrayAccumAdaptive, BhrayAccumAdaptiveInfo,
+                      BhrayAccumAdaptive, BhrayAccumAdaptiveInfo, BhrayStillFilter, FILTER_BOX, FILTER_TENT, FILTER_CUBIC,
                       BhrayGatherInfo, BhrayModelBuildInfo, BhrayModelDesc, BhrayRebalanceInfo, BhrayTiming, check)
 from .model import NODE_DTYPE, Model
 from .scene import BlackHole, Camera, RayDetails
@@ -35,6 +35,41 @@ class AdaptiveStill:
 
     def as_kwargs(self) -> dict:
         return {"min_samples": self.min_samples, "max_samples": self.max_samples, "round_samples": self.round_samples, "tolerance": self.tolerance, "dark": self.dark}
+
+
+class StillFilter:
+    """The reconstruction filter of a still (Renderer.render_still(filter=...), RayPass.accum_set_filter; bhray_still_filter): StillFilter.tent(radius),
+    StillFilter.mitchell(radius) (B = C = 1/3), StillFilter.bspline(radius) (B = 1, C = 0), or StillFilter(FILTER_CUBIC, radius, b, c); radius is the support's half
+    width in pixels.  StillFilter() is the box.  A cubic with c > 0 has negative lobes: a mean may be slightly negative."""
+
+    def __init__(self, kind: int = FILTER_BOX, radius: float = 2.0, b: float = 1.0 / 3.0, c: float = 1.0 / 3.0):
+        self.kind, self.radius, self.b, self.c = int(kind), float(radius), float(b), float(c)
+
+    @classmethod
+    def tent(cls, radius: float = 1.0) -> "StillFilter":
+        return cls(FILTER_TENT, radius)
+
+    @classmethod
+    def mitchell(cls, radius: float = 2.0) -> "StillFilter":
+        return cls(FILTER_CUBIC, radius, 1.0 / 3.0, 1.0 / 3.0)
+
+    @classmethod
+    def bspline(cls, radius: float = 2.0) -> "StillFilter":
+        return cls(FILTER_CUBIC, radius, 1.0, 0.0)
+
+    def struct(self) -> BhrayStillFilter:
+        """the bhray_still_filter the library takes"""
+        return BhrayStillFilter(C.sizeof(BhrayStillFilter), self.kind, self.radius, self.b, self.c)
+
+    def weights(self, s: int):
+        """(wx, wy): the five horizontal and five vertical weights of sample s (bhray_accum_filter_weights: host arithmetic), float32"""
+        wx, wy = np.zeros(5, np.float32), np.zeros(5, np.float32)
+        st = self.struct()
+        check(lib().bhray_accum_filter_weights(C.byref(st), int(s), wx.ctypes.data_as(C.POINTER(C.c_float)), wy.ctypes.data_as(C.POINTER(C.c_float))))
+        return wx, wy
+
+    def __repr__(self):
+        return f"StillFilter(kind={self.kind}, radius={self.radius}, b={self.b}, c={self.c})"
 
 
 def ladder_from_base(base=(72, 41), multiplier=3, levels=4) -> BhrayConfig:
@@ -458,6 +493,14 @@ class RayPass:
         s = still_camera.struct() if still_camera is not None else None
         check(self._L.bhray_accum_set_camera(self._h, C.byref(s) if s is not None else None), self._h, self._L)
 
+    def accum_set_filter(self, filter=None):
+        """The reconstruction filter of the accumulation image from the next accum_add on (bhray_accum_set_filter): a StillFilter - .tent(radius),
+        .mitchell(radius), .bspline(radius) - or None for the default, the box.  Under a tent or a cubic each sample also feeds the pixels around its own with
+        weights that depend on the sample's sub-pixel offset; accum_add_adaptive is then refused (BHRAY_E_STATE).  Validates and stores only; a filter the library
+        refuses: BhrayError (BHRAY_E_INVALID)."""
+        s = filter.struct() if filter is not None else None
+        check(self._L.bhray_accum_set_filter(self._h, C.byref(s) if s is not None else None), self._h, self._L)
+
     # -- adaptive stills: each pixel sampled until the error of its mean is under a bound (bhray_accum_add_adaptive, DESIGN.md §20)
     @staticmethod
     def _adaptive_params(min_samples, max_samples, round_samples, tolerance, dark) -> BhrayAccumAdaptive:
@@ -855,12 +898,13 @@ class Renderer:
                 "closest": float(r["closest"]), "transmittance": float(r["transmittance"]),
                 "path": pts["position"][0, :k].copy(), "path_iterations": pts["iteration"][0, :k].copy()}
 
-    def _accumulate(self, samples: int, shutter: float, camera=None):
+    def _accumulate(self, samples: int, shutter: float, camera=None, filter=None):
         samples = int(samples)
         if samples < 1:
             raise ValueError(f"render_still: samples must be at least 1, got {samples}")
         self._apply_uniforms()
         self.ray_pass.accum_set_camera(camera)
+        self.ray_pass.accum_set_filter(filter)
         self.ray_pass.accum_begin()
         if not shutter > 0.0:
             self.ray_pass.accum_add(samples)
@@ -874,7 +918,7 @@ class Renderer:
         finally:
             self.ray_details.time = t0
 
-    def render_still(self, samples: int = 16, shutter: float = 0.0, adaptive: AdaptiveStill | None = None, camera=None) -> np.ndarray:
+    def render_still(self, samples: int = 16, shutter: float = 0.0, adaptive: AdaptiveStill | None = None, camera=None, filter=None) -> np.ndarray:
         """A supersampled still of the current scene (RayPass.accum_*): the mean of `samples` jittered samples per frame pixel, sky resolved,
         (frame_h, frame_w, 4) float32.  Sample 0 is the pixel centre, so samples=1 is the frame a `levels = 1` ladder renders, after the sky pass in binary32.
         shutter > 0: motion blur - sample s is rendered at ray_details.time + shutter * s / samples (the disk turns with `time`); ray_details.time is left as it was.
@@ -882,14 +926,19 @@ class Renderer:
         not available (ValueError), still_info holds what the call did and still_counts() delivers the per-pixel sample counts.
         camera: a cameras.StillCamera - the still as a 360 x 180 degree panorama (.equirect()), a fisheye (.fisheye(fov)) or through a thin lens
         (.pinhole(lens_radius, focus_distance): depth of field; sample 0 is then a lens sample, not the centre ray) from the scene camera's position along its forward
-        (DESIGN.md §21); None: the pinhole.  The ctx keeps the camera of the last still."""
+        (DESIGN.md §21); None: the pinhole.  The ctx keeps the camera of the last still.
+        filter: a StillFilter - the pixel reconstruction filter, StillFilter.tent(radius), .mitchell(radius) or .bspline(radius); None: the box.  Not
+        with `adaptive` (ValueError).  The ctx keeps the filter of the last still."""
         if adaptive is None:
-            self._accumulate(samples, shutter, camera)
+            self._accumulate(samples, shutter, camera, filter)
             return self.ray_pass.accum_read()
+        if filter is not None and filter.kind != FILTER_BOX:
+            raise ValueError("render_still: an adaptive still has no filter but the box (a round's pixels take different samples)")
         if shutter > 0.0:
             raise ValueError("render_still: an adaptive still has no shutter (every pixel takes its own number of samples)")
         self._apply_uniforms()
         self.ray_pass.accum_set_camera(camera)
+        self.ray_pass.accum_set_filter(None)
         self.ray_pass.accum_begin()
         self.still_info = self.ray_pass.accum_add_adaptive(**adaptive.as_kwargs())
         return self.ray_pass.accum_read()
@@ -898,10 +947,11 @@ class Renderer:
         """The sample-count heat map of the last adaptive still: (frame_h, frame_w) uint32."""
         return self.ray_pass.accum_read_counts()
 
-    def save_still(self, path, samples: int = 16, camera=None):
-        """save_image for a supersampled still: the mean of `samples` samples per pixel through the display pass, written with alpha 255.  camera: as render_still's."""
+    def save_still(self, path, samples: int = 16, camera=None, filter=None):
+        """save_image for a supersampled still: the mean of `samples` samples per pixel through the display pass, written with alpha 255.  camera, filter: as
+        render_still's."""
         from PIL import Image
-        self._accumulate(samples, 0.0, camera)
+        self._accumulate(samples, 0.0, camera, filter)
         img = self.ray_pass.accum_read_display()
         img[..., 3] = 255
         Image.fromarray(img, "RGBA").save(path)

@@ -679,6 +679,52 @@ typedef struct bhray_still_camera {
 int  bhray_accum_set_camera(bhray_ctx* ctx, const bhray_still_camera* camera);   /* NULL = the default: pinhole, no lens */
 void bhray_still_camera_default(bhray_still_camera* camera);
 
+/* Still pixel filters: the reconstruction filter of the accumulation image.  Per-ctx state, read by each
+ * bhray_accum_add at the time of the call, like the still camera: changing it between calls of one accumulation is the
+ * caller's business (the sums stay meaningful: sum.w is a sum of weights).  Under the default, BHRAY_FILTER_BOX, a
+ * pixel's value is the mean of the samples inside its own square: the kernels and every image are those of §18.  Under
+ * TENT and CUBIC sample s of a pixel also feeds the pixels around it: sample s has one offset (dx, dy) for all pixels
+ * (bhray_accum_sample_offset), so for each sample the sum is a 5 x 5 separable stencil over that sample's result image,
+ * with ten weights that are the same for every pixel.
+ *   weights  every step one rounded binary32 operation in the order written, no FMA.  For tap i = -2 .. 2:
+ *            tx = float(i) + dx, wx[i + 2] = k(|tx|); wy likewise from dy.
+ *            TENT   a = t / radius;  k = a < 1 ? 1 - a : 0.
+ *            CUBIC  (Mitchell-Netravali, its support [-2, 2] scaled to `radius`)  inv = 2.0f / radius, x = t * inv;
+ *                   x < 1: k = ((p3 * x + p2) * (x * x)) + p0;  x < 2: k = (((q3 * x + q2) * x + q1) * x) + q0;  else 0;
+ *                   the coefficients are formed in binary64 from the binary32 b (B) and c (C) and rounded once:
+ *                   p3 = (12 - 9B - 6C)/6, p2 = (-18 + 12B + 6C)/6, p0 = (6 - 2B)/6,
+ *                   q3 = (-B - 6C)/6, q2 = (6B + 30C)/6, q1 = (-12B - 48C)/6, q0 = (8B + 24C)/6.
+ *            |dx| <= 0.5, so taps +-3 lie at |t| >= 2.5 and weigh 0 at every allowed radius: five taps are complete.
+ *            bhray_accum_filter_weights delivers the ten weights of sample s by host arithmetic, through the function
+ *            the kernel calls (BOX: 0, 0, 1, 0, 0 twice).  It needs no ctx and no device.
+ *   sum      V(x', y') is the resolved result of sample s at frame pixel (x', y'): (r, g, b, 1) when (x', y') lies inside
+ *            the frame and r, g, b are finite, (0, 0, 0, 0) otherwise - a select, never 0 * NaN.  Per component,
+ *              c = 0;  for j = -2 .. 2: { row = 0;  for i = -2 .. 2: row = row + wx[i+2] * V(x+i, y+j);  c = c + wy[j+2] * row }
+ *              sum[p] = sum[p] + c          in increasing s, whatever the grouping of samples into calls and launches.
+ *            sum.w is the weight the pixel received and the mean divides by it: border pixels and pixels beside skipped
+ *            samples renormalise by themselves.  A CUBIC filter with c > 0 has negative lobes, so a mean may be slightly
+ *            negative: nothing is clamped.  At s = 0, TENT with radius 1 and CUBIC with B = 0 at radius 2 weigh
+ *            (0, 0, 1, 0, 0): one such sample is the box's.
+ * bhray_accum_read, bhray_accum_read_display and bhray_accum_samples are unchanged, and so are the still cameras: the
+ * filter works in image space under every projection (a fisheye's out-of-circle (0, 0, 0, -1) is a finite black sample).
+ * Every refusal of bhray_accum_add holds.  bhray_accum_add_adaptive under a filter other than the box: BHRAY_E_STATE,
+ * nothing enqueued (a round's pixels take different sample indices, so a neighbour has no result for "sample s").
+ * bhray_accum_set_filter only validates and stores: it needs no device, touches no image and is accepted in every state.
+ * NULL restores the default.  BHRAY_E_INVALID, the filter in force untouched: a struct_size other than
+ * sizeof(bhray_still_filter); an unknown kind; a radius, b or c that the kind reads and that is not finite or lies
+ * outside its range.  bhray_still_filter_default fills in the default: the box (radius 2, b = c = 1/3 for a caller who
+ * only changes the kind).  bhray_accum_filter_weights: BHRAY_E_INVALID for a NULL argument or such a struct.         */
+enum { BHRAY_FILTER_BOX = 0, BHRAY_FILTER_TENT = 1, BHRAY_FILTER_CUBIC = 2 };
+typedef struct bhray_still_filter {
+    uint32_t struct_size;   /* = sizeof(bhray_still_filter) */
+    uint32_t kind;          /* BHRAY_FILTER_* */
+    float    radius;        /* TENT: 0.5 <= radius <= 2.5; CUBIC: 1 <= radius <= 2.5 (the support's half width in pixels); BOX: not read */
+    float    b, c;          /* CUBIC: Mitchell-Netravali B and C, each in [0, 1]; otherwise not read */
+} bhray_still_filter;
+int  bhray_accum_set_filter(bhray_ctx* ctx, const bhray_still_filter* filter);   /* NULL = the default: box */
+void bhray_still_filter_default(bhray_still_filter* filter);
+int  bhray_accum_filter_weights(const bhray_still_filter* filter, uint32_t s, float wx[5], float wy[5]);   /* host arithmetic, no device */
+
 /* Dispatch — replaces `for rp in ray_pipelines { rp.pass() }` (mod.rs:415-417,
  * ray_pipeline.rs:301-309).  Asynchronous on the ctx stream; levels ordered.                 */
 int bhray_render(bhray_ctx* ctx);
