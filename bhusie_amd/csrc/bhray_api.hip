@@ -399,6 +399,50 @@ int bhray_device_count(void) {
     return n;
 }
 
+// bhray_diag.h: the display pass over a caller's image - no ctx.  Allocate, copy in, the product's launch_display (or launch_fxaa), wait, copy out, free.
+int bhray_diag_display_image(int device, const uint16_t* rgba16f, uint32_t w, uint32_t h, const void* fxaa16, const void* mix4, uint32_t flags,
+                             uint8_t* dst_rgba8, uint16_t* stages_rgba16f, size_t stage_texels) {
+    if (!rgba16f || !dst_rgba8) return fail(nullptr, BHRAY_E_INVALID, "bhray_diag_display_image: NULL image or destination");
+    if (flags & ~(uint32_t)BHRAY_DIAG_DISPLAY_FXAA_ONLY) return fail(nullptr, BHRAY_E_INVALID, "bhray_diag_display_image: unknown flag bits 0x%x", flags);
+    const bool fxaa_only = (flags & BHRAY_DIAG_DISPLAY_FXAA_ONLY) != 0;
+    const size_t scratch_bytes = display_scratch_bytes(w, h);
+    if (scratch_bytes == 0 || w > 32767 || h > 32767)               // the ladder's largest frame: the kernels index pixels with an int
+        return fail(nullptr, BHRAY_E_INVALID, "bhray_diag_display_image: the display pass takes frames from 32 x 32 to 32767 x 32767 pixels (got %u x %u)", w, h);
+    bhray_fxaa_details fx; bhray_mix_details mx;
+    (void)bhray_post_defaults(&fx, &mx);
+    if (fxaa16) memcpy(&fx, fxaa16, sizeof fx);
+    if (mix4) memcpy(&mx, mix4, sizeof mx);
+    if (fx.iterations > BHRAY_FXAA_MAX_ITERATIONS)
+        return fail(nullptr, BHRAY_E_INVALID, "fxaa iterations %d > BHRAY_FXAA_MAX_ITERATIONS (%d)", fx.iterations, BHRAY_FXAA_MAX_ITERATIONS);
+    if (stages_rgba16f && fxaa_only) return fail(nullptr, BHRAY_E_INVALID, "bhray_diag_display_image: BHRAY_DIAG_DISPLAY_FXAA_ONLY has no stage output");
+    if (stages_rgba16f && stage_texels != scratch_bytes / sizeof(uint2))
+        return fail(nullptr, BHRAY_E_INVALID, "bhray_diag_display_image: the stage output of a %u x %u frame is %zu texels, not %zu", w, h, scratch_bytes / sizeof(uint2), stage_texels);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, BHRAY_E_NO_DEVICE, "no HIP device visible (libbhray has no CPU path)");
+    if (device < 0 || device >= ndev) return fail(nullptr, BHRAY_E_NO_DEVICE, "device %d not present (%d visible)", device, ndev);
+    const size_t npix = (size_t)w * h;
+    uint2 *d_in = nullptr, *d_scratch = nullptr;
+    uint32_t* d_out = nullptr;
+    const char* what = "hipSetDevice";
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) { what = "hipMalloc"; e = hipMalloc(&d_in, npix * sizeof(uint2)); }
+    if (e == hipSuccess) e = hipMalloc(&d_out, npix * sizeof(uint32_t));
+    if (e == hipSuccess && !fxaa_only) e = hipMalloc(&d_scratch, scratch_bytes);
+    if (e == hipSuccess) { what = "hipMemcpy"; e = hipMemcpy(d_in, rgba16f, npix * sizeof(uint2), hipMemcpyHostToDevice); }
+    if (e == hipSuccess) {
+        what = fxaa_only ? "launch_fxaa" : "launch_display";
+        e = fxaa_only ? launch_fxaa(d_in, d_out, w, h, fx, nullptr) : launch_display(d_in, d_scratch, d_out, w, h, fx, mx, nullptr);
+    }
+    if (e == hipSuccess) { what = "hipStreamSynchronize"; e = hipStreamSynchronize(nullptr); }
+    if (e == hipSuccess) { what = "hipMemcpy"; e = hipMemcpy(dst_rgba8, d_out, npix * sizeof(uint32_t), hipMemcpyDeviceToHost); }
+    if (e == hipSuccess && stages_rgba16f) e = hipMemcpy(stages_rgba16f, d_scratch, scratch_bytes, hipMemcpyDeviceToHost);
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (d_scratch) (void)hipFree(d_scratch);
+    if (e != hipSuccess) return fail(nullptr, e == hipErrorOutOfMemory ? BHRAY_E_NOMEM : BHRAY_E_HIP, "bhray_diag_display_image: %s: %s", what, hipGetErrorString(e));
+    return BHRAY_OK;
+}
+
 int bhray_ladder_from_base(uint32_t base_w, uint32_t base_h, uint32_t m, uint32_t levels, bhray_config* cfg) {
     if (!cfg || levels < 1 || levels > BHRAY_MAX_LEVELS || base_w < 2 || base_h < 2 || m < 2) return BHRAY_E_INVALID;
     uint64_t w = base_w, h = base_h;

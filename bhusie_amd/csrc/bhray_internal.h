@@ -226,6 +226,8 @@ size_t display_scratch_bytes(uint32_t frame_w, uint32_t frame_h);               
 // the 11 launches of the display pass on stream s: RGBA16F sky image (frame_w x frame_h) -> RGBA8 sRGB image
 hipError_t launch_display(const uint2* sky, uint2* scratch, uint32_t* dst_rgba8, uint32_t frame_w, uint32_t frame_h,
                           const bhray_fxaa_details& fxaa, const bhray_mix_details& mix, hipStream_t s);
+// launch_display's last launch alone: fxaa_kernel over a tone-mapped RGBA16F image (bhray_diag_display_image's BHRAY_DIAG_DISPLAY_FXAA_ONLY)
+hipError_t launch_fxaa(const uint2* tone, uint32_t* dst_rgba8, uint32_t frame_w, uint32_t frame_h, const bhray_fxaa_details& fxaa, hipStream_t s);
 
 // mesh BVH built on the device (bhray_bvh.hip)
 struct BvhBuild;                         // scratch of one model slot's builder: allocated once per upload, reused by every vertex update

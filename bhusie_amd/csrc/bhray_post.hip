@@ -303,11 +303,26 @@ static void srgb_thresholds(float* t) {
     }
 }
 
+// fxaa_kernel's arguments for one uniform block
+static PostArgs post_args(const bhray_fxaa_details& fx) {
+    static PostArgs base = [] { PostArgs a; memset(&a, 0, sizeof a); srgb_thresholds(a.srgb_thr); a.one_twelfth = (float)(1.0 / 12.0); return a; }();
+    PostArgs P = base;
+    P.edge_min = fx.edge_threshold_min; P.edge_max = fx.edge_threshold_max; P.iterations = fx.iterations; P.subpix = fx.subpixel_quality;
+    return P;
+}
+
+hipError_t launch_fxaa(const uint2* tone, uint32_t* dst_rgba8, uint32_t fw, uint32_t fh, const bhray_fxaa_details& fx, hipStream_t s) {
+    uint32_t w[BHRAY_BLOOM_LEVELS], h[BHRAY_BLOOM_LEVELS];
+    if (bloom_sizes(fw, fh, w, h)) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(fxaa_kernel, dim3(blocks_for((size_t)fw * fh)), dim3(256), 0, s, Img{tone, (int)fw, (int)fh}, dst_rgba8, post_args(fx));
+    return hipGetLastError();
+}
+
 hipError_t launch_display(const uint2* sky, uint2* scratch, uint32_t* dst_rgba8, uint32_t fw, uint32_t fh,
                           const bhray_fxaa_details& fx, const bhray_mix_details& mx, hipStream_t s) {
     uint32_t w[BHRAY_BLOOM_LEVELS], h[BHRAY_BLOOM_LEVELS];
     if (bloom_sizes(fw, fh, w, h)) return hipErrorInvalidValue;
-    static PostArgs base = [] { PostArgs a; memset(&a, 0, sizeof a); srgb_thresholds(a.srgb_thr); a.one_twelfth = (float)(1.0 / 12.0); return a; }();
     (void)hipGetLastError();
     Img src{sky, (int)fw, (int)fh};
     uint2* level = scratch;
@@ -320,9 +335,7 @@ hipError_t launch_display(const uint2* sky, uint2* scratch, uint32_t* dst_rgba8,
     uint2* tone = level;
     const size_t npix = (size_t)fw * fh;
     hipLaunchKernelGGL(final_kernel, dim3(blocks_for(npix)), dim3(256), 0, s, src, sky, tone, (int)fw, (int)fh, mx.mix_ratio);
-    PostArgs P = base;
-    P.edge_min = fx.edge_threshold_min; P.edge_max = fx.edge_threshold_max; P.iterations = fx.iterations; P.subpix = fx.subpixel_quality;
-    hipLaunchKernelGGL(fxaa_kernel, dim3(blocks_for(npix)), dim3(256), 0, s, Img{tone, (int)fw, (int)fh}, dst_rgba8, P);
+    hipLaunchKernelGGL(fxaa_kernel, dim3(blocks_for(npix)), dim3(256), 0, s, Img{tone, (int)fw, (int)fh}, dst_rgba8, post_args(fx));
     return hipGetLastError();
 }
 

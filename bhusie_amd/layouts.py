@@ -356,7 +356,9 @@ DIAG_SYMBOLS = {
     "bhray_still_sample_rays_host": (C.c_int, [P(BhrayConfig), vp, P(BhrayStillCamera), u32, P(BhrayRay)]),
     "bhray_accum_active_pixels": (C.c_int, [vp, P(BhrayAccumAdaptive), P(u32), u32, P(u32)]),
     "bhray_read_sky_pyramid_level": (C.c_int, [vp, u32, vp, sz]),
+    "bhray_diag_display_image": (C.c_int, [C.c_int, vp, u32, u32, vp, vp, u32, vp, vp, sz]),
 }
+DIAG_DISPLAY_FXAA_ONLY = 1           # BHRAY_DIAG_DISPLAY_FXAA_ONLY
 
 
 def declare(L):

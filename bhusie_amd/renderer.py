@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import lib
-from .layouts import (BhrayFxaaDetails, BhrayMixDetails, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters, BhrayRay, BhrayRayRecord, BhrayPathPoint, PATH_POINT_DTYPE, HIT_MESH, HIT_UNUSABLE,
+from .layouts import (BhrayFxaaDetails, BhrayMixDetails, DIAG_DISPLAY_FXAA_ONLY, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters, BhrayRay, BhrayRayRecord, BhrayPathPoint, PATH_POINT_DTYPE, HIT_MESH, HIT_UNUSABLE,
                       BhrayAccumAdaptive, BhrayAccumAdaptiveInfo, BhrayStillFilter, FILTER_BOX, FILTER_TENT, FILTER_CUBIC,
                       BhrayGatherInfo, BhrayModelBuildInfo, BhrayModelDesc, BhrayRebalanceInfo, BhrayTiming, check)
 from .model import NODE_DTYPE, Model
@@ -96,6 +96,38 @@ def bloom_sizes(frame_w: int, frame_h: int):
     w, h = (C.c_uint32 * 10)(), (C.c_uint32 * 10)()
     check(lib().bhray_bloom_sizes(int(frame_w), int(frame_h), w, h))
     return [(int(a), int(b)) for a, b in zip(w, h)]
+
+
+def display_image(sky16, fxaa=None, mix=None, device=0, fxaa_only=False, stages=False):
+    """The display pass over a supplied RGBA16F image (bhray_diag_display_image: the launches resolve_display runs, no ctx): sky16 is
+    (H, W, 4) float16 or its uint16 words; fxaa / mix are the uniform blocks as RayPass.set_post_uniforms takes them.  Returns the
+    uint8 (H, W, 4) image; with stages=True also the nine intermediate bloom levels [(h_i, w_i, 4) uint16] and the tone-mapped
+    (H, W, 4) uint16 image.  fxaa_only: sky16 is taken as the tone-mapped image and only FXAA and the RGBA8 store run."""
+    a = np.asarray(sky16)
+    if a.dtype != np.float16 and a.dtype != np.uint16:
+        raise TypeError("display_image takes binary16 pixels (float16, or their uint16 words)")
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError("display_image takes an (H, W, 4) image")
+    a = np.ascontiguousarray(a)
+    h, w = a.shape[:2]
+    f = bytes(fxaa) if fxaa is not None else None
+    m = bytes(BhrayMixDetails(float(mix))) if isinstance(mix, (int, float, np.floating)) else (bytes(mix) if mix is not None else None)
+    assert (f is None or len(f) == 16) and (m is None or len(m) == 4)
+    out = np.empty((h, w, 4), dtype=np.uint8)
+    buf, texels = None, 0
+    if stages:
+        sizes = bloom_sizes(w, h)[:9]
+        texels = sum(lw * lh for lw, lh in sizes) + w * h
+        buf = np.empty((texels, 4), dtype=np.uint16)
+    check(lib().bhray_diag_display_image(int(device), a.ctypes.data, w, h, f, m, DIAG_DISPLAY_FXAA_ONLY if fxaa_only else 0, out.ctypes.data,
+                                         buf.ctypes.data if buf is not None else None, texels))
+    if not stages:
+        return out
+    levels, at = [], 0
+    for lw, lh in sizes:
+        levels.append(buf[at:at + lw * lh].reshape(lh, lw, 4))
+        at += lw * lh
+    return out, levels, buf[at:].reshape(h, w, 4)
 
 
 def sky_pyramid_sizes(w: int, h: int):

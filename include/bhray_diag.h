@@ -3,7 +3,7 @@
  *
  * bhray.h is what a renderer calls (a RayPipeline shim; the C++ host, host/renderer.hpp).  This header
  * adds what exists to MEASURE or VERIFY the library rather than to render a frame: the counters and the row work of the
- * counting build, the HIP-event timing, the device self-test, the read-back of any ladder level and the gather statistics.
+ * counting build, the HIP-event timing, the device self-test, the read-back of any ladder level, the display pass over a supplied image and the gather statistics.
  * The tests, bench.py and the profiling scripts use them; a product host needs none.  It includes bhray.h, so a diagnostic
  * consumer includes this file only.  The conventions of bhray.h hold here too.
  */
@@ -201,6 +201,26 @@ int bhray_accum_active_pixels(bhray_ctx* ctx, const bhray_accum_adaptive* params
  * row 0 the top; `texels` must be lw * lh.  BHRAY_E_STATE while the mode is off or no sky texture is resident; BHRAY_E_INVALID for
  * level 0 (that is the texture), a level beyond the top, a NULL dst or another texel count.  Waits.                               */
 int bhray_read_sky_pyramid_level(bhray_ctx* ctx, uint32_t level, uint16_t* dst_rgba16f, size_t texels);
+
+/* ------------------------------------------------------------------------------------------
+ * The display pass over a supplied image
+ * ---------------------------------------------------------------------------------------- */
+/* Runs the display pass a ctx runs behind its sky pass - the same launches - over a caller's image, so that the kernels can be
+ * held to images no device rendered.  No ctx: device memory is allocated, the w x h RGBA16F image (four binary16 per pixel, row
+ * 0 the top, tightly packed) copied in, the pass run and waited for, dst_rgba8 (w x h x 4 bytes) copied back, everything freed.
+ * fxaa_16 / mix_4: the bytes of a bhray_fxaa_details / bhray_mix_details; NULL: what bhray_post_defaults gives.
+ * stages_rgba16f, if not NULL, receives what the pass leaves in its scratch, in its order: bloom levels 0 to 8 (sizes from
+ * bhray_bloom_sizes), then the tone-mapped w x h image; stage_texels must be exactly that many texels (ignored when the pointer
+ * is NULL).  Level 9 and the mixed image are never in memory: the last kernel fuses them.
+ * BHRAY_DIAG_DISPLAY_FXAA_ONLY: the image is taken as the tone-mapped one and the last launch (FXAA and the RGBA8 store) runs
+ * alone; mix_4 is not read and stages_rgba16f must be NULL.
+ * BHRAY_E_INVALID: a NULL image or dst, an unknown flag bit, a frame bhray_bloom_sizes refuses (with the flag too) or wider or
+ * higher than 32767, iterations above BHRAY_FXAA_MAX_ITERATIONS, a stage buffer of another size or beside the flag - all
+ * checked before the device is touched.  BHRAY_E_NO_DEVICE: no device, or `device` not among the visible ones.  The message
+ * is bhray_last_error(NULL)'s.                                                                                                  */
+#define BHRAY_DIAG_DISPLAY_FXAA_ONLY 1u
+int bhray_diag_display_image(int device, const uint16_t* rgba16f, uint32_t w, uint32_t h, const void* fxaa_16, const void* mix_4, uint32_t flags,
+                             uint8_t* dst_rgba8, uint16_t* stages_rgba16f, size_t stage_texels);
 
 /* ------------------------------------------------------------------------------------------
  * Gather statistics (multi-GPU)
