@@ -83,6 +83,47 @@ def sky_texture(w: int = 4096, h: int = 2048, seed: int = 2) -> np.ndarray:
     return np.ascontiguousarray(np.round(np.clip(img, 0, 1) * 255.0).astype(np.uint8))
 
 
+def star_catalogue(n: int, seed: int = 1, flux_min: float = 2e-7) -> np.ndarray:
+    """(n, 6) float32 rows (dir x y z, flux r g b): a seeded catalogue of point stars for RayPass.set_stars.  Directions uniform on the sphere (Marsaglia's
+    method, the rejected draws re-hashed), fluxes a power law flux_min / t^2 with t uniform in [1/32, 1) (radiance x steradian), a warm-to-cool tint.  Binary64
+    + - * / sqrt on hashed integers only, then one rounding to binary32: the same bytes on every machine, and what bhray_render --stars-seeded computes."""
+    i = np.arange(n, dtype=np.uint32)
+    out = np.zeros((n, 6), dtype=np.float32)
+    out[:, 2] = 1.0
+    todo = np.arange(n)
+    for k in range(64):
+        if todo.size == 0:
+            break
+        salt = _hash_u32(np.full(todo.size, (seed * 7919 + 13 + k) & 0xFFFFFFFF, dtype=np.uint32))
+        h0 = _hash_u32(i[todo] * np.uint32(0x9E3779B1) ^ salt)
+        h1 = _hash_u32(h0 ^ np.uint32(0x68E31DA4))
+        h2 = _hash_u32(h1 ^ np.uint32(0xB5297A4D))
+        h3 = _hash_u32(h2 ^ np.uint32(0x1B56C4E9))
+        x1 = (h0 >> np.uint32(8)).astype(np.float64) / float(1 << 24) * 2.0 - 1.0
+        x2 = (h1 >> np.uint32(8)).astype(np.float64) / float(1 << 24) * 2.0 - 1.0
+        s = x1 * x1 + x2 * x2
+        ok = s < 1.0
+        r = np.sqrt(np.where(ok, 1.0 - s, 0.0))
+        t = 1.0 - (h2 >> np.uint32(8)).astype(np.float64) / float(1 << 24) * (31.0 / 32.0)
+        f = flux_min / (t * t)
+        tint = (h3 >> np.uint32(8)).astype(np.float64) / float(1 << 24)
+        row = np.stack([2.0 * x1 * r, 2.0 * x2 * r, 1.0 - 2.0 * s, f * (0.85 + 0.15 * tint), f * 0.9, f * (1.0 - 0.15 * tint)], axis=1)
+        out[todo[ok]] = row[ok].astype(np.float32)
+        todo = todo[~ok]
+    return out
+
+
+def stars_from_uv(u, v) -> np.ndarray:
+    """(n, 3) float32 directions whose sky-pass texture coordinates are (u, v): the inverse of sky.wgsl's direction -> (u, v) (theta = atan2(|xz|, y),
+    phi = atan2(z, x), u = fract((phi + 2.6 pi) / 2 pi), v = fract((pi - theta) / pi)), in binary64 - to place a catalogue star on a texel, to no bit."""
+    u = np.asarray(u, dtype=np.float64).reshape(-1)
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    phi = 2.0 * np.pi * u - 2.6 * np.pi
+    theta = np.pi * (1.0 - v)
+    st = np.sin(theta)
+    return np.stack([st * np.cos(phi), np.cos(theta), st * np.sin(phi)], axis=1).astype(np.float32)
+
+
 def sphere_mesh_obj(n_lat: int = 24, n_lon: int = 32, radius: float = 8.0, bump: float = 0.15,
                     seed: int = 3, with_normals: bool = True) -> str:
     """OBJ text of a lat-long sphere with seeded radial noise; 2*n_lon*(n_lat-1) triangles.

@@ -25,6 +25,7 @@
 #include "bhray_internal.h"
 #include "bhray_math.h"
 #include "bhray_skyfilter.h"
+#include "bhray_stars.h"
 
 using namespace bhray;
 
@@ -164,6 +165,10 @@ struct bhray_dev {
     int sky_filter = 0;                    // dev_set_sky_filter: 1 = dev_resolve_sky runs the footprint filter
     uint2* pyr_buf = nullptr;              // ... and the sky texture's pyramid, levels 1 .. top: held only while the mode is on
     bhray::SkyPyr pyr{};
+    float4* star_buf = nullptr;            // dev_set_stars: the catalogue sorted by cell, two float4 per star; held only while a catalogue is set
+    uint32_t* star_prefix = nullptr;       // ... and its cells' prefix array
+    bhray::StarSet stars{};                // what star_kernel reads; stars.stars == nullptr: no catalogue, dev_resolve_sky launches nothing more
+    uint32_t star_count = 0;
     ModelStore models[BHRAY_MAX_MODELS];
     bhray_camera_uniform cam{};
     bhray_black_hole_uniform bh{};
@@ -535,6 +540,8 @@ void dev_destroy(bhray_dev* c) {
     }
     for (auto& t : c->tex) if (t) (void)hipFree(t);
     if (c->pyr_buf) (void)hipFree(c->pyr_buf);
+    if (c->star_buf) (void)hipFree(c->star_buf);
+    if (c->star_prefix) (void)hipFree(c->star_prefix);
     for (auto& m : c->models) free_model(m);
     for (auto& e : c->events) if (e) (void)hipEventDestroy(e);
     if (c->d_err) (void)hipFree(c->d_err);
@@ -897,6 +904,65 @@ int dev_set_sky_filter(bhray_dev* c, int32_t mode) {
     int rc = build_sky_pyramid(c);
     if (rc) c->sky_filter = 0;
     return rc;
+}
+
+// Point stars: per-engine state, applied from the next dev_resolve_sky.  bhray_set_texture's rule: staged frames are launched and the frames in
+// flight waited for, since a resolve enqueued earlier may still be reading the old catalogue.  Everything that can refuse comes before anything is changed.
+int dev_set_stars(bhray_dev* c, const bhray_star* stars, uint32_t n, const bhray_star_params* params) {
+    if (!c) return BHRAY_E_INVALID;
+    const bool on = stars != nullptr && n != 0;
+    if (const char* why = stars_error(on ? stars : nullptr, on ? n : 0, params)) return fail(c, BHRAY_E_INVALID, "bhray_set_stars: %s", why);
+    if (on && (c->cfg.row_world > 1 || c->local_rows.size() != (size_t)c->cfg.frame_h))
+        return fail(c, BHRAY_E_STATE, "bhray_set_stars: not built for a row partition (a partition does not hold its neighbours' rows)");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = launch_batch(c); if (rc) return rc; }
+    HIPCHK(c, sync_all(c));
+    float4* d_stars = nullptr; uint32_t* d_prefix = nullptr;
+    StarSet S{};
+    if (on) {
+        bhray_star_params P;
+        bhray_star_params_default(&P);
+        if (params) P = *params;
+        uint32_t G;
+        std::vector<float4> sorted; std::vector<uint32_t> prefix;
+        stars_build_index(stars, n, G, sorted, prefix);
+        hipError_t e = hipMalloc(&d_stars, sorted.size() * sizeof(float4));
+        if (e == hipSuccess) e = hipMalloc(&d_prefix, prefix.size() * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemcpy(d_stars, sorted.data(), sorted.size() * sizeof(float4), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_prefix, prefix.data(), prefix.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {                                       // the catalogue in force stays
+            if (d_stars) (void)hipFree(d_stars);
+            if (d_prefix) (void)hipFree(d_prefix);
+            return fail(c, e == hipErrorOutOfMemory ? BHRAY_E_NOMEM : BHRAY_E_HIP, "bhray_set_stars: catalogue upload: %s", hipGetErrorString(e));
+        }
+        S = StarSet{d_stars, d_prefix, G, P.gain, P.min_area, P.max_footprint * P.max_footprint};
+    }
+    if (c->star_buf) (void)hipFree(c->star_buf);
+    if (c->star_prefix) (void)hipFree(c->star_prefix);
+    c->star_buf = d_stars; c->star_prefix = d_prefix; c->stars = S; c->star_count = on ? n : 0;
+    return BHRAY_OK;
+}
+
+// bhray_diag.h: star_kernel with the engine's catalogue over a caller's frame.  Allocate, copy in, the product's launch_stars on the legacy stream, wait, copy out, free.
+int dev_diag_star_image(bhray_dev* c, const float* frame, uint32_t w, uint32_t h, const uint16_t* sky_in, uint16_t* sky_out) {
+    if (!c) return BHRAY_E_INVALID;
+    if (!frame || !sky_out || w == 0 || h == 0 || w > 32767 || h > 32767) return fail(c, BHRAY_E_INVALID, "bhray_diag_star_image: NULL frame or output, or a frame that is empty or above 32767 pixels a side");
+    if (!c->stars.stars) return fail(c, BHRAY_E_STATE, "bhray_diag_star_image: no catalogue (bhray_set_stars)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)w * h;
+    float4* d_frame = nullptr; uint2* d_img = nullptr;
+    const char* what = "hipMalloc";
+    hipError_t e = hipMalloc(&d_frame, npix * sizeof(float4));
+    if (e == hipSuccess) e = hipMalloc(&d_img, npix * sizeof(uint2));
+    if (e == hipSuccess) { what = "hipMemcpy"; e = hipMemcpy(d_frame, frame, npix * sizeof(float4), hipMemcpyHostToDevice); }
+    if (e == hipSuccess) e = sky_in ? hipMemcpy(d_img, sky_in, npix * sizeof(uint2), hipMemcpyHostToDevice) : hipMemset(d_img, 0, npix * sizeof(uint2));
+    if (e == hipSuccess) { what = "launch_stars"; e = launch_stars(c->stars, d_frame, d_img, w, h, nullptr); }
+    if (e == hipSuccess) { what = "hipStreamSynchronize"; e = hipStreamSynchronize(nullptr); }
+    if (e == hipSuccess) { what = "hipMemcpy"; e = hipMemcpy(sky_out, d_img, npix * sizeof(uint2), hipMemcpyDeviceToHost); }
+    if (d_frame) (void)hipFree(d_frame);
+    if (d_img) (void)hipFree(d_img);
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? BHRAY_E_NOMEM : BHRAY_E_HIP, "bhray_diag_star_image: %s: %s", what, hipGetErrorString(e));
+    return BHRAY_OK;
 }
 
 int dev_read_sky_pyramid_level(bhray_dev* c, uint32_t level, uint16_t* dst, size_t texels) {
@@ -2448,6 +2514,10 @@ int dev_resolve_sky(bhray_dev* c) {
     if (c->sky_filter != 0 && c->local_rows.size() != (size_t)c->cfg.frame_h) return fail(c, BHRAY_E_STATE, "the sky filter needs the whole frame on this engine");
     if (c->sky_filter == 0) HIPCHK(c, launch_sky(sky, R.out, R.sky_out, npix, S.stream));
     else HIPCHK(c, launch_sky_filter(sky, c->pyr, R.out, R.sky_out, c->cfg.frame_w, c->cfg.frame_h, S.stream));     // the whole frame: dev_set_sky_filter refuses a partition
+    if (c->stars.stars) {                                            // point stars: added into the image the sky kernel has just written, the whole frame
+        if (c->local_rows.size() != (size_t)c->cfg.frame_h) return fail(c, BHRAY_E_STATE, "point stars need the whole frame on this engine");
+        HIPCHK(c, launch_stars(c->stars, R.out, R.sky_out, c->cfg.frame_w, c->cfg.frame_h, S.stream));
+    }
     R.sky_frame_id = R.frame_id;
     if (timing) { HIPCHK(c, hipEventRecord(ev[ev_sky_end(c->cfg.levels)], S.stream)); c->sky_recorded[ring] = 1; }
     HIPCHK(c, hipEventRecord(S.done, S.stream));

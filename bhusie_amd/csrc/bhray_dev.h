@@ -150,6 +150,8 @@ int  dev_read_level(bhray_dev* c, uint32_t level, float* dst, size_t pitch);
 int  dev_bind_output(bhray_dev* c, void* p, size_t bytes);     // destination of the NEXT dev_render only
 int  dev_resolve_sky(bhray_dev* c);
 int  dev_set_sky_filter(bhray_dev* c, int32_t mode);          // 0: sky.wgsl; 1: the footprint filter from the next dev_resolve_sky; synchronises the engine, builds / frees the pyramid
+int  dev_set_stars(bhray_dev* c, const bhray_star* stars, uint32_t n, const bhray_star_params* params);   // point stars from the next dev_resolve_sky; n == 0 / NULL removes; synchronises the engine, uploads the index
+int  dev_diag_star_image(bhray_dev* c, const float* frame, uint32_t w, uint32_t h, const uint16_t* sky_in, uint16_t* sky_out);
 int  dev_read_sky_pyramid_level(bhray_dev* c, uint32_t level, uint16_t* dst_rgba16f, size_t texels);
 int  dev_resolve_display(bhray_dev* c, const bhray_fxaa_details* fxaa, const bhray_mix_details* mix);   // display pass (bhray_post.hip) behind the last frame
 int  dev_launch_display(bhray_dev* c, const void* sky, void* scratch, void* dst, const bhray_fxaa_details* fxaa, const bhray_mix_details* mix, hipStream_t stream);

@@ -41,6 +41,7 @@
 
 #include "bhray_dev.h"
 #include "bhray_internal.h"
+#include "bhray_stars.h"
 
 using namespace bhray;
 
@@ -2110,6 +2111,26 @@ int bhray_read_sky_pyramid_level(bhray_ctx* c, uint32_t level, uint16_t* dst, si
     ENTER(c);
     if (!c->single) return gfail(c, BHRAY_E_STATE, "bhray_read_sky_pyramid_level: the sky filter is off (bhray_set_sky_filter)");
     DEV(c, c->parts[0].dev, dev_read_sky_pyramid_level(c->parts[0].dev, level, dst, texels));
+    return BHRAY_OK;
+}
+
+// ---- point stars (bhray_stars.hip): one engine that holds the whole frame, as the sky filter ------------------------------
+int bhray_set_stars(bhray_ctx* c, const bhray_star* stars, uint32_t n, const bhray_star_params* params) {
+    if (!c) return BHRAY_E_INVALID;
+    const bool on = stars != nullptr && n != 0;
+    if (const char* why = bhray::stars_error(on ? stars : nullptr, on ? n : 0, params)) return gfail(c, BHRAY_E_INVALID, "bhray_set_stars: %s", why);
+    ENTER(c);
+    if (on && (c->cfg.device_count >= 2 || !c->single || c->world > 1))
+        return gfail(c, BHRAY_E_STATE, "bhray_set_stars: not built for a ctx that splits the frame (device_count >= 2, gather = BHRAY_GATHER_RCCL or row_world > 1): a partition does not hold its neighbours' rows");
+    if (!c->single) return BHRAY_OK;                             // removing on a ctx that never had a catalogue: nothing to do
+    DEV(c, c->parts[0].dev, dev_set_stars(c->parts[0].dev, stars, n, params));
+    return BHRAY_OK;
+}
+int bhray_diag_star_image(bhray_ctx* c, const float* frame, uint32_t w, uint32_t h, const uint16_t* sky_in, uint16_t* sky_out) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    if (!c->single) return gfail(c, BHRAY_E_STATE, "bhray_diag_star_image: no catalogue (bhray_set_stars)");
+    DEV(c, c->parts[0].dev, dev_diag_star_image(c->parts[0].dev, frame, w, h, sky_in, sky_out));
     return BHRAY_OK;
 }
 

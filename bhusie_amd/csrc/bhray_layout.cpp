@@ -85,6 +85,14 @@ static_assert(BHRAY_STILL_PINHOLE == 0 && BHRAY_STILL_EQUIRECT == 1 && BHRAY_STI
 SZ(bhray_still_filter, 20);
 OFF(bhray_still_filter, struct_size, 0); OFF(bhray_still_filter, kind, 4); OFF(bhray_still_filter, radius, 8); OFF(bhray_still_filter, b, 12); OFF(bhray_still_filter, c, 16);
 static_assert(BHRAY_FILTER_BOX == 0 && BHRAY_FILTER_TENT == 1 && BHRAY_FILTER_CUBIC == 2, "BHRAY_FILTER_*");
+// a star and the parameters of bhray_set_stars; the per-pixel report of bhray_diag_stars_pixel_info_host
+SZ(bhray_star, 24);
+OFF(bhray_star, dir, 0); OFF(bhray_star, flux, 12);
+SZ(bhray_star_params, 16);
+OFF(bhray_star_params, struct_size, 0); OFF(bhray_star_params, gain, 4); OFF(bhray_star_params, min_area, 8); OFF(bhray_star_params, max_footprint, 12);
+SZ(bhray_star_pixel_info, 32);
+OFF(bhray_star_pixel_info, state, 0); OFF(bhray_star_pixel_info, tested, 12); OFF(bhray_star_pixel_info, area, 24);
+static_assert(BHRAY_MAX_STARS == (1u << 22) && BHRAY_STARS_MAX_CELLS == 64u, "BHRAY_MAX_STARS / BHRAY_STARS_MAX_CELLS");
 static_assert(BHRAY_MAX_PATH_STRIDE_LOG2 == 16 && BHRAY_MAX_PATH_POINTS_PER_CALL == (1u << 24), "BHRAY_MAX_PATH_*");
 static_assert(BHRAY_HIT_NONE == 0 && BHRAY_HIT_HORIZON == 1 && BHRAY_HIT_DISK == 2 && BHRAY_HIT_MESH == 3 && BHRAY_HIT_UNUSABLE == 255, "BHRAY_HIT_*");
 

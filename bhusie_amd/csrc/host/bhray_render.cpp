@@ -29,11 +29,13 @@
 // --bvh device: every mesh's tree is built on the GPU (bhray_upload_model_build) instead of by the reference's host builder (the default).
 // --obj: repeatable; the i-th mesh goes to model slot i (Renderer::add_model), at the position its OBJ loader gives it.
 // --devices: row-tile the frame over several GPUs from this one process (RCCL gather to the first one, inside libbhray).
-//   bhray_render --handoff sync|hdr|sky|sky1|sky-temporal|display FRAMES OUT.bin [--rk] [--base W H] [--levels N] [--sky-filter]
+//   bhray_render --handoff sync|hdr|sky|sky1|sky-temporal|display FRAMES OUT.bin [--rk] [--base W H] [--levels N] [--sky-filter] [--stars-seeded N SEED]
 //   bhray_render --dropin FRAMES [--rk] [--base W H] [--levels N]
 // --handoff: FRAMES frames of the same scene (time += 1/60 per frame) through Renderer::render_handoff in the given form, every DELIVERED frame
 // appended to OUT.bin in delivery order (RGBA32F for sync / hdr, RGBA16F for sky, RGBA8 sRGB for display) - the tests compare them with the frames the Python host renders.
 // --sky-filter (with --handoff): the sky pass of the sky and display forms is the footprint-filtered one (bhray_set_sky_filter).
+// --stars-seeded N SEED (with --handoff): the sky pass of the sky and display forms receives a seeded catalogue of N point stars (bhusie::star_catalogue through
+//   RayPipeline::set_stars: bhray_set_stars), 1 <= N <= BHRAY_MAX_STARS.
 // --dropin: times the drop-in shim of INTEGRATION.md §3 the way the reference host drives it - one thread, `time += dt` every frame
 // (mod.rs:382), every frame handed to host memory - in its three hand-off forms, and prints one JSON object (bench.py embeds it as `dropin`).
 // Textures: the disk texture comes from the reference's own generator (bhray_generate_disk_texture); the LUT and the sky
@@ -98,9 +100,16 @@ int main(int argc, char** argv) {
     if (argc >= 5 && !std::strcmp(argv[1], "--handoff")) {
         const char* form = argv[2]; const int frames = std::atoi(argv[3]); const char* out_path = argv[4];
         uint32_t bw = 24, bh = 14, levels = 3; bool rk = false, sky_filter = false;
+        long stars_n = 0, stars_seed = 0;
         for (int i = 5; i < argc; i++) {
             if (!std::strcmp(argv[i], "--rk")) rk = true;
             else if (!std::strcmp(argv[i], "--sky-filter")) sky_filter = true;
+            else if (!std::strcmp(argv[i], "--stars-seeded")) {
+                char *e1 = nullptr, *e2 = nullptr;
+                if (i + 2 >= argc) { std::fprintf(stderr, "--stars-seeded needs N and SEED\n"); return 2; }
+                stars_n = std::strtol(argv[++i], &e1, 10); stars_seed = std::strtol(argv[++i], &e2, 10);
+                if (*e1 || *e2 || stars_n < 1 || stars_n > (long)BHRAY_MAX_STARS || stars_seed < 0) { std::fprintf(stderr, "--stars-seeded needs 1 <= N <= %u and SEED >= 0\n", BHRAY_MAX_STARS); return 2; }
+            }
             else if (!std::strcmp(argv[i], "--base") && i + 2 < argc) { bw = (uint32_t)std::atoi(argv[++i]); bh = (uint32_t)std::atoi(argv[++i]); }
             else if (!std::strcmp(argv[i], "--levels") && i + 1 < argc) levels = (uint32_t)std::atoi(argv[++i]);
         }
@@ -112,6 +121,7 @@ int main(int argc, char** argv) {
             bhusie::Renderer r({bw, bh}, 3, levels, 0, in_flight, h, temporal);
             fill_textures(r.ray_pipeline(), 128);
             if (sky_filter) r.ray_pipeline().set_sky_filter(true);
+            if (stars_n > 0) r.ray_pipeline().set_stars(bhusie::star_catalogue((uint32_t)stars_n, (uint32_t)stars_seed));
             r.ray_details.integration_method = rk ? 1 : 0;
             auto res = r.ray_pipeline().resolution();
             const size_t bytes = (size_t)res.first * res.second * (display ? 4 : (sky ? 8 : 16));

@@ -28,6 +28,34 @@ inline void check(int rc, const bhray_ctx* ctx = nullptr) {
     }
 }
 
+// A seeded catalogue of point stars for RayPipeline::set_stars: directions uniform on the sphere (Marsaglia's method, the rejected draws re-hashed), fluxes a power
+// law flux_min / t^2 with t uniform in [1/32, 1), a warm-to-cool tint.  Binary64 + - * / sqrt on hashed integers, then one rounding to binary32: the bytes of the
+// Python host's assets.star_catalogue(n, seed).
+inline uint32_t star_hash(uint32_t x) { x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16; return x; }
+inline std::vector<bhray_star> star_catalogue(uint32_t n, uint32_t seed, double flux_min = 2e-7) {
+    std::vector<bhray_star> out(n);
+    const double u24 = 1.0 / 16777216.0;
+    for (uint32_t i = 0; i < n; i++) {
+        bhray_star s = {{0.0f, 0.0f, 1.0f}, {0.0f, 0.0f, 0.0f}};
+        for (uint32_t k = 0; k < 64; k++) {
+            const uint32_t h0 = star_hash(i * 0x9E3779B1u ^ star_hash(seed * 7919u + 13u + k));
+            const uint32_t h1 = star_hash(h0 ^ 0x68E31DA4u), h2 = star_hash(h1 ^ 0xB5297A4Du), h3 = star_hash(h2 ^ 0x1B56C4E9u);
+            const double x1 = (double)(h0 >> 8) * u24 * 2.0 - 1.0, x2 = (double)(h1 >> 8) * u24 * 2.0 - 1.0;
+            const double q = x1 * x1 + x2 * x2;
+            if (!(q < 1.0)) continue;
+            const double r = std::sqrt(1.0 - q);
+            const double t = 1.0 - (double)(h2 >> 8) * u24 * (31.0 / 32.0);
+            const double f = flux_min / (t * t);
+            const double tint = (double)(h3 >> 8) * u24;
+            s.dir[0] = (float)(2.0 * x1 * r); s.dir[1] = (float)(2.0 * x2 * r); s.dir[2] = (float)(1.0 - 2.0 * q);
+            s.flux[0] = (float)(f * (0.85 + 0.15 * tint)); s.flux[1] = (float)(f * 0.9); s.flux[2] = (float)(f * (1.0 - 0.15 * tint));
+            break;
+        }
+        out[i] = s;
+    }
+    return out;
+}
+
 struct RayDetails : bhray_details {
     RayDetails() { bhray_details_default(this); }              // step_size 0.15, max_iterations 2000, threshold 0.02, Euler
 };
@@ -171,6 +199,10 @@ public:
     void pass() { check(bhray_render(ctx_), ctx_); }                                            // ray_pipeline.rs:301-309
     void flush() { check(bhray_flush(ctx_), ctx_); }
     void set_sky_filter(bool on) { check(bhray_set_sky_filter(ctx_, on ? 1 : 0), ctx_); }        // footprint-filtered sky pass: from the next resolve_sky / resolve_display on
+    // point stars: a catalogue lensed into the sky pass from the next resolve_sky / resolve_display on; an empty vector removes it
+    void set_stars(const std::vector<bhray_star>& stars, const bhray_star_params* params = nullptr) {
+        check(bhray_set_stars(ctx_, stars.empty() ? nullptr : stars.data(), (uint32_t)stars.size(), params), ctx_);
+    }
     void resolve_sky() { check(bhray_resolve_sky(ctx_), ctx_); }                                // sky_pipeline.rs pass
     // bloom / mix / hdr / fxaa passes (mod.rs:425-431), with the uniforms Renderer::render uploads unless set_post_uniforms changed them
     void resolve_display() { check(bhray_resolve_display(ctx_), ctx_); }

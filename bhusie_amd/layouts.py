@@ -125,6 +125,27 @@ class BhrayStillFilter(C.Structure):        # bhray_still_filter: the accumulati
 
 assert C.sizeof(BhrayStillFilter) == 20 and BhrayStillFilter.c.offset == 16
 
+MAX_STARS, STARS_MAX_CELLS = 1 << 22, 64                    # BHRAY_MAX_STARS, BHRAY_STARS_MAX_CELLS
+
+
+class BhrayStar(C.Structure):               # bhray_star: a point source of the catalogue (bhray_set_stars)
+    _fields_ = [("dir", C.c_float * 3), ("flux", C.c_float * 3)]
+
+
+class BhrayStarParams(C.Structure):         # bhray_star_params; BhrayStarParams.default() is bhray_star_params_default's
+    _fields_ = [("struct_size", C.c_uint32), ("gain", C.c_float), ("min_area", C.c_float), ("max_footprint", C.c_float)]
+
+    @classmethod
+    def default(cls, **kw):
+        p = cls(C.sizeof(cls), 1.0, 1e-7, 0.25)
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+
+assert C.sizeof(BhrayStar) == 24 and BhrayStar.flux.offset == 12
+assert C.sizeof(BhrayStarParams) == 16 and BhrayStarParams.max_footprint.offset == 12
+
 
 class BhrayModelDesc(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("visible", C.c_int32),
@@ -306,6 +327,11 @@ SYMBOLS = {
     "bhray_sky_device_ptr": (C.c_int, [vp, P(vp), P(sz)]),
     "bhray_set_sky_filter": (C.c_int, [vp, i32]),
     "bhray_sky_pyramid_sizes": (C.c_int, [u32, u32, P(u32), P(u32), P(u32)]),
+    "bhray_star_params_default": (None, [P(BhrayStarParams)]),
+    "bhray_set_stars": (C.c_int, [vp, vp, u32, P(BhrayStarParams)]),
+    "bhray_star_grid_size": (C.c_int, [u32, P(u32)]),
+    "bhray_star_cell": (C.c_int, [P(C.c_float), u32, P(u32)]),
+    "bhray_stars_resolve_host": (C.c_int, [vp, u32, u32, vp, u32, P(BhrayStarParams), vp]),
     "bhray_post_defaults": (C.c_int, [P(BhrayFxaaDetails), P(BhrayMixDetails)]),
     "bhray_bloom_sizes": (C.c_int, [u32, u32, P(u32), P(u32)]),
     "bhray_set_post_uniforms": (C.c_int, [vp, vp, vp]),
@@ -357,6 +383,8 @@ DIAG_SYMBOLS = {
     "bhray_accum_active_pixels": (C.c_int, [vp, P(BhrayAccumAdaptive), P(u32), u32, P(u32)]),
     "bhray_read_sky_pyramid_level": (C.c_int, [vp, u32, vp, sz]),
     "bhray_diag_display_image": (C.c_int, [C.c_int, vp, u32, u32, vp, vp, u32, vp, vp, sz]),
+    "bhray_diag_star_image": (C.c_int, [vp, vp, u32, u32, vp, vp]),
+    "bhray_diag_stars_pixel_info_host": (C.c_int, [vp, u32, u32, vp, u32, P(BhrayStarParams), vp]),
 }
 DIAG_DISPLAY_FXAA_ONLY = 1           # BHRAY_DIAG_DISPLAY_FXAA_ONLY
 

@@ -14,7 +14,7 @@ import numpy as np
 
 from ._lib import lib
 from .layouts import (BhrayFxaaDetails, BhrayMixDetails, DIAG_DISPLAY_FXAA_ONLY, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters, BhrayRay, BhrayRayRecord, BhrayPathPoint, PATH_POINT_DTYPE, HIT_MESH, HIT_UNUSABLE,
-                      BhrayAccumAdaptive, BhrayAccumAdaptiveInfo, BhrayStillFilter, FILTER_BOX, FILTER_TENT, FILTER_CUBIC,
+                      BhrayAccumAdaptive, BhrayAccumAdaptiveInfo, BhrayStar, BhrayStarParams, BhrayStillFilter, FILTER_BOX, FILTER_TENT, FILTER_CUBIC,
                       BhrayGatherInfo, BhrayModelBuildInfo, BhrayModelDesc, BhrayRebalanceInfo, BhrayTiming, check)
 from .model import NODE_DTYPE, Model
 from .scene import BlackHole, Camera, RayDetails
@@ -135,6 +135,60 @@ def sky_pyramid_sizes(w: int, h: int):
     n, lw, lh = C.c_uint32(), (C.c_uint32 * 32)(), (C.c_uint32 * 32)()
     check(lib().bhray_sky_pyramid_sizes(int(w), int(h), C.byref(n), lw, lh))
     return [(int(lw[i]), int(lh[i])) for i in range(n.value)]
+
+
+def star_array(stars):
+    """(a, n): a catalogue as the library takes it - a C-contiguous (n, 6) float32 array, rows (dir x y z, flux r g b), the bytes of n bhray_star.  Takes None, an
+    (n, 6) array, or a ctypes array of layouts.BhrayStar."""
+    if stars is None:
+        return np.zeros((0, 6), np.float32), 0
+    if isinstance(stars, C.Array) and getattr(stars, "_type_", None) is BhrayStar:
+        stars = np.frombuffer(stars, dtype=np.float32).reshape(-1, 6)
+    a = np.ascontiguousarray(stars, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != 6:
+        raise ValueError("a star catalogue is an (n, 6) array: dir x y z, flux r g b")
+    return a, int(a.shape[0])
+
+
+def star_grid_size(n: int) -> int:
+    """G of the catalogue index of n stars (bhray_star_grid_size: host arithmetic)."""
+    g = C.c_uint32()
+    check(lib().bhray_star_grid_size(int(n), C.byref(g)))
+    return int(g.value)
+
+
+def star_cells(dirs, G: int) -> np.ndarray:
+    """The index cell of every direction of an (n, 3) array in a grid of side G (bhray_star_cell: host arithmetic), uint32."""
+    d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    out = np.empty(len(d), np.uint32)
+    L, c = lib(), C.c_uint32()
+    for i in range(len(d)):
+        check(L.bhray_star_cell(d[i].ctypes.data_as(C.POINTER(C.c_float)), int(G), C.byref(c)))
+        out[i] = c.value
+    return out
+
+
+def stars_resolve_host(frame, stars, params=None) -> np.ndarray:
+    """The star pass's per-pixel rule over an (h, w, 4) float32 frame on the host (bhray_stars_resolve_host, no device): (h, w, 4) float32, what each pixel
+    receives (times the gain) and, in alpha, the number of stars it accepted."""
+    f = np.ascontiguousarray(frame, dtype=np.float32)
+    a, n = star_array(stars)
+    out = np.empty_like(f)
+    check(lib().bhray_stars_resolve_host(f.ctypes.data, f.shape[1], f.shape[0], a.ctypes.data, n, C.byref(params) if params is not None else None, out.ctypes.data))
+    return out
+
+
+STAR_PIXEL_INFO_DTYPE = np.dtype([("state", np.uint32), ("faces", np.uint32), ("cells", np.uint32), ("tested", np.uint32), ("accepted", np.uint32),
+                                  ("reversed", np.uint32), ("area", np.float32), ("pad", np.uint32)])
+
+
+def stars_pixel_info_host(frame, stars, params=None) -> np.ndarray:
+    """What the rule did at every pixel (bhray_diag_stars_pixel_info_host): an (h, w) array of STAR_PIXEL_INFO_DTYPE."""
+    f = np.ascontiguousarray(frame, dtype=np.float32)
+    a, n = star_array(stars)
+    out = np.empty(f.shape[:2], STAR_PIXEL_INFO_DTYPE)
+    check(lib().bhray_diag_stars_pixel_info_host(f.ctypes.data, f.shape[1], f.shape[0], a.ctypes.data, n, C.byref(params) if params is not None else None, out.ctypes.data))
+    return out
 
 
 def pose_from_euler(rotation, pivot=(0.0, 0.0, 0.0), scale=1.0) -> np.ndarray:
@@ -652,6 +706,32 @@ class RayPass:
         check(self._L.bhray_read_sky_pyramid_level(self._h, int(level), out.ctypes.data, w * h), self._h, self._L)
         return out
 
+    # -- point stars
+    def set_stars(self, stars, params=None):
+        """A star catalogue lensed into the sky pass: from the next resolve_sky (and the sky pass resolve_display runs) every direction pixel whose footprint is known
+        receives the flux of the catalogue stars inside it over the footprint's solid angle.  stars: None (or an empty array) removes the catalogue; otherwise an
+        (n, 6) float32 array of (dir x y z, flux r g b) rows, or an array of layouts.BhrayStar.  params: a layouts.BhrayStarParams, or None for the defaults.  Waits
+        for the frames in flight.  BhrayError (BHRAY_E_STATE) on a ctx that splits the frame; read_hdr, trace_rays(sky=True) and accum_* are not affected."""
+        a, n = star_array(stars)
+        p = C.byref(params) if params is not None else None
+        check(self._L.bhray_set_stars(self._h, a.ctypes.data if n else None, n, p), self._h, self._L)
+
+    def star_image(self, frame, sky_in=None) -> np.ndarray:
+        """The star kernel with this ctx's catalogue over a supplied (h, w, 4) float32 frame (bhray_diag_star_image): (h, w, 4) float16, the stars added to sky_in
+        (None: zeros)."""
+        f = np.ascontiguousarray(frame, dtype=np.float32)
+        if f.ndim != 3 or f.shape[2] != 4:
+            raise ValueError("star_image takes an (H, W, 4) float32 frame")
+        h, w = f.shape[:2]
+        s = None
+        if sky_in is not None:
+            s = np.ascontiguousarray(sky_in)
+            if s.dtype not in (np.float16, np.uint16) or s.shape != f.shape:
+                raise ValueError("sky_in is an (H, W, 4) binary16 image of the frame's size")
+        out = np.empty((h, w, 4), dtype=np.float16)
+        check(self._L.bhray_diag_star_image(self._h, f.ctypes.data, w, h, s.ctypes.data if s is not None else None, out.ctypes.data), self._h, self._L)
+        return out
+
     # -- display pass: bloom, mix, ACES, FXAA into the RGBA8 sRGB image (DESIGN.md §10)
     def set_post_uniforms(self, fxaa: BhrayFxaaDetails | bytes | None = None, mix: BhrayMixDetails | bytes | float | None = None):
         """The FXAA (16 B) and mix (4 B) uniform blocks, applied from the next resolve_display; None = the reference's defaults."""
@@ -802,6 +882,14 @@ class Renderer:
         self.still_info = None                               # what the last adaptive still did (render_still(adaptive=...)): rounds, active_last, rays, reach
         self.sky_filter = False                              # footprint-filtered sky pass (RayPass.set_sky_filter): applied before save_image's display pass
         self._sky_filter_applied = False
+        self.stars = None                                    # the point-star catalogue in force (set_stars): an (n, 6) float32 array, or None
+
+    def set_stars(self, stars, params=None):
+        """A star catalogue lensed into the sky pass (RayPass.set_stars): in force from the next resolve_sky / save_image on; None removes it.  A refused
+        call leaves Renderer.stars, like the ctx's catalogue, as it was."""
+        self.ray_pass.set_stars(stars, params)
+        a, n = star_array(stars)
+        self.stars = a.copy() if n else None
 
     @property
     def model(self) -> Model | None:

@@ -837,6 +837,66 @@ int bhray_set_sky_filter(bhray_ctx* ctx, int32_t mode);
  * both are 1.  Pure host arithmetic.  w or h == 0 or above 2^31 (33 levels), or a NULL pointer: BHRAY_E_INVALID, nothing written.  */
 int bhray_sky_pyramid_sizes(uint32_t w, uint32_t h, uint32_t* levels, uint32_t lw[32], uint32_t lh[32]);
 
+/* Point stars: a star catalogue lensed into the sky pass.  The sky texture bakes its stars into texels, so a star is
+ * a bilinear blob where the lens magnifies and aliases near the Einstein ring.  With a catalogue set, every direction pixel whose
+ * footprint on the sky is known receives, behind the sky kernel, the flux of the catalogue stars inside that footprint divided by
+ * the footprint's solid angle: surface brightness is conserved, so stars stay pixel-sharp, brighten by the lens's magnification and
+ * show their second image inside the ring.  Off by default: without a catalogue every image keeps its bits and no memory is held.
+ *
+ * bhray_star: dir is in the space of the frame's escape directions (world space, what sky.wgsl reads) and need not be unit length;
+ * flux is linear RGB, radiance x steradian, finite and >= 0.
+ * bhray_star_params (struct_size = sizeof; bhray_star_params_default: gain 1, min_area 1e-7, max_footprint 0.25): gain, finite and
+ * > 0, multiplies what a pixel receives; min_area, finite and > 0, in steradian, is the smallest solid angle a footprint is taken
+ * to have - the cap on the magnification at a critical curve; max_footprint, in (0, 0.25], is the longest chord a footprint may
+ * have between two of its corners: a larger footprint receives nothing.
+ *
+ * The rule, in binary32, one rounded operation at a time, + - * / sqrt and compares only (operation order: DESIGN.md §23; restated in
+ * NumPy in tests/stars_ref.py; bhray_stars_resolve_host runs the kernel's per-pixel function on the host):
+ *  1. The corner between pixels (x-1,y-1), (x,y-1), (x-1,y), (x,y) is ((d00 + d10) + (d01 + d11)) * 0.25f of their directions, and is
+ *     valid only if all four lie in the frame, are direction pixels (w == 0.0f) and have finite x, y, z.  A pixel has a footprint only
+ *     if its four corners are valid: frame-border pixels and pixels beside the disk, the horizon, a mesh or a NaN pixel receive nothing.
+ *  2. The pixel is skipped unless the squared chord of each of its four edges and two diagonals is <= max_footprint^2.
+ *  3. A = 0.5f * length(cross(c11 - c00, c10 - c01)); inv = 1.0f / max(A, min_area).
+ *  4. The stars are indexed in a cube-map grid of 6 G G cells, G = bhray_star_grid_size(n): a direction's face (0 .. 5 = +x -x +y -y
+ *     +z -z) is its largest |component| (ties: x, then y), (a, b) the other two components, in x y z order, over that magnitude, its
+ *     cell (face * G + cb) * G + ca with ca = floorf((a * 0.5f + 0.5f) * G) clamped to [0, G - 1], cb likewise from b.  A pixel
+ *     visits a face only if all four corners have a positive component along the face's axis and sign and the bounding box of their
+ *     (a, b), widened by 2^-12 on each side, meets [-1, 1]^2; the box, clamped to the face, names the cells.  A pixel whose boxes hold
+ *     more than BHRAY_STARS_MAX_CELLS cells in total is skipped.
+ *  5. Star s is inside if its four edge functions dot(s, cross(ca, cb)) - top c00 c10, right c10 c11, bottom c11 c01, left c01 c00 -
+ *     satisfy eT >= 0 && eL >= 0 && eB > 0 && eR > 0, or the same with every sign reversed (the parity-flipped images inside the
+ *     ring), and dot(s, d) > 0 for the pixel's own direction d.  A star on a shared edge or corner belongs to exactly one pixel.
+ *  6. In the order face 0 .. 5, cells row-major within the box, stars ascending within the cell (they are sorted by (cell, index)):
+ *     acc = acc + flux * inv per channel.
+ *  7. A pixel that accepted a star becomes half(min(float(sky_half) + acc * gain, 65504.0f)) per colour channel, alpha kept; every
+ *     other pixel keeps the sky kernel's 16-bit words.
+ *
+ * bhray_set_stars copies the stars, builds the index on the host, uploads it (32 bytes per star, 4 per cell) and returns.  It
+ * follows bhray_set_texture's rule: staged frames are launched and the frames in flight waited for.  Per-ctx state like
+ * bhray_set_sky_filter, applied from the next bhray_resolve_sky on - hence also to the sky pass bhray_resolve_display runs and to every
+ * read of the sky and display images -, with the sky filter on or off.  n == 0 or stars == NULL removes the catalogue and frees its
+ * memory.  BHRAY_E_INVALID, the catalogue in force untouched: a dir that is not finite or all zero, a flux that is not finite
+ * and >= 0, n > BHRAY_MAX_STARS, a params value out of range or another struct_size.
+ * Not built (a catalogue: BHRAY_E_STATE, the removing call is accepted) for a ctx with device_count >= 2, with gather =
+ * BHRAY_GATHER_RCCL or with row_world > 1: a partition does not hold its neighbours' rows.
+ * Not affected: bhray_read_hdr, bhray_trace_rays_sky, bhray_accum_*, and the sky sample the trace kernels take behind the disk.  */
+#define BHRAY_MAX_STARS (1u << 22)
+#define BHRAY_STARS_MAX_CELLS 64u
+typedef struct bhray_star { float dir[3]; float flux[3]; } bhray_star;     /* 24 B */
+typedef struct bhray_star_params { uint32_t struct_size; float gain; float min_area; float max_footprint; } bhray_star_params;   /* 16 B */
+void bhray_star_params_default(bhray_star_params* params);
+int  bhray_set_stars(bhray_ctx* ctx, const bhray_star* stars, uint32_t n, const bhray_star_params* params /* NULL = defaults */);
+/* The smallest power of two G in [1, 1024] with 12 G G >= n.  Pure host arithmetic.  n > BHRAY_MAX_STARS or NULL: BHRAY_E_INVALID. */
+int  bhray_star_grid_size(uint32_t n, uint32_t* G);
+/* The cell of a direction in a grid of side G (rule 4).  Pure host arithmetic.  BHRAY_E_INVALID: NULL, a dir that is not finite or
+ * all zero, a G that is not a power of two in [1, 1024].                                                                          */
+int  bhray_star_cell(const float dir[3], uint32_t G, uint32_t* cell);
+/* Rules 1 - 6 over a w x h RGBA32F frame on the host - the kernel's per-pixel function, no device: add_rgba32f (w x h x 4 floats)
+ * receives acc * gain per colour channel and the number of stars the pixel accepted in alpha (0, 0, 0, 0 for a pixel that received
+ * nothing).  BHRAY_E_INVALID: NULL, n == 0, w or h == 0 or above 32767, or what bhray_set_stars refuses.                          */
+int  bhray_stars_resolve_host(const float* frame_rgba32f, uint32_t w, uint32_t h, const bhray_star* stars, uint32_t n,
+                              const bhray_star_params* params, float* add_rgba32f);
+
 /* Display pass — the rest of the reference's GPU frame after the sky pass (mod.rs:209-324, run at 425-431): 5 bloom-down and
  * 5 bloom-up passes (bloom_down.wgsl, bloom_up.wgsl), mix (mix.wgsl), ACES tone mapping (hdr.wgsl) and FXAA (fxaa.wgsl) into the
  * Rgba8UnormSrgb target the reference's `Save Image` copies out (texture_to_output_buffer, mod.rs:491-526): frame_w x frame_h x 4

@@ -223,6 +223,28 @@ int bhray_diag_display_image(int device, const uint16_t* rgba16f, uint32_t w, ui
                              uint8_t* dst_rgba8, uint16_t* stages_rgba16f, size_t stage_texels);
 
 /* ------------------------------------------------------------------------------------------
+ * Point stars over a supplied image (bhray_set_stars)
+ * ---------------------------------------------------------------------------------------- */
+/* Runs the star kernel a ctx runs behind its sky pass, with the ctx's catalogue and parameters, over a caller's frame - so that the
+ * kernel can be held to frames the tracer would never produce (exact ties, frames smaller than a tile).  frame_rgba32f: w x h pixels
+ * of four floats, row 0 the top, tightly packed, as bhray_read_hdr delivers them; sky_in_rgba16f: the w x h RGBA16F image the stars
+ * are added to (NULL: zeros); sky_out_rgba16f receives the image.  Device memory is allocated, the pass run on the legacy stream and
+ * waited for, everything freed; the ctx's frames are not touched.  BHRAY_E_STATE: the ctx has no catalogue (or is not a
+ * single-device ctx).  BHRAY_E_INVALID: NULL frame or output, w or h == 0 or above 32767.                                        */
+int bhray_diag_star_image(bhray_ctx* ctx, const float* frame_rgba32f, uint32_t w, uint32_t h, const uint16_t* sky_in_rgba16f, uint16_t* sky_out_rgba16f);
+/* What rules 2 - 6 did at every pixel of a frame, on the host (bhray_stars_resolve_host's loop): what the cost measurement and the
+ * tests' coverage floors count.  Arguments and errors as bhray_stars_resolve_host's.                                              */
+typedef struct bhray_star_pixel_info {
+    uint32_t state;                     /* 0 summed, 1 skipped by max_footprint, 2 skipped by BHRAY_STARS_MAX_CELLS, 3 no footprint */
+    uint32_t faces, cells;              /* faces visited, cells in their boxes                                                   */
+    uint32_t tested, accepted, reversed;/* stars the inside test ran on, stars accepted, those of them by the reversed-sign form   */
+    float    area;                      /* A of rule 3 (before min_area)                                                         */
+    uint32_t pad;
+} bhray_star_pixel_info;                /* 32 B */
+int bhray_diag_stars_pixel_info_host(const float* frame_rgba32f, uint32_t w, uint32_t h, const bhray_star* stars, uint32_t n,
+                                     const bhray_star_params* params, bhray_star_pixel_info* info);
+
+/* ------------------------------------------------------------------------------------------
  * Gather statistics (multi-GPU)
  * ---------------------------------------------------------------------------------------- */
 /* What a ctx gathers with.                                                                                          */
