@@ -26,6 +26,7 @@
 #include "bhray_math.h"
 #include "bhray_skyfilter.h"
 #include "bhray_stars.h"
+#include "bhray_accum_stars.h"
 
 using namespace bhray;
 
@@ -239,6 +240,8 @@ struct bhray_dev {
     bhray_still_camera a_cam{(uint32_t)sizeof(bhray_still_camera), BHRAY_STILL_PINHOLE, 3.14159274f, 0.0f, 1.0f};
     // still pixel filters (dev_accum_set_filter): read by every dev_accum_add at the time of the call; the box runs accum_add_kernel
     bhray_still_filter a_filter{(uint32_t)sizeof(bhray_still_filter), BHRAY_FILTER_BOX, 2.0f, 1.0f / 3.0f, 1.0f / 3.0f};
+    // point stars in stills (dev_accum_set_stars): read by every dev_accum_add at the time of the call; acts only while a catalogue is in force (stars)
+    bool a_stars = false;
     bhray::ReadRing reads;                 // tickets of the asynchronous hand-off (dev_read_async)
     std::string err;
 };
@@ -1563,6 +1566,10 @@ int dev_accum_add(bhray_dev* c, uint32_t samples) {
     if (c->a_mode == 2) return fail(c, BHRAY_E_STATE, "bhray_accum_add: this accumulation is adaptive (bhray_accum_add_adaptive); bhray_accum_begin starts another");
     if (samples > BHRAY_ACCUM_MAX_SAMPLES - c->a_samples)
         return fail(c, BHRAY_E_INVALID, "bhray_accum_add: %u + %u samples exceed BHRAY_ACCUM_MAX_SAMPLES", c->a_samples, samples);
+    const bool starred = c->a_stars && c->stars.stars;            // point stars in stills: the switch is on and a catalogue is in force
+    if (starred && c->a_cam.lens_radius > 0.0f)
+        return fail(c, BHRAY_E_STATE, "bhray_accum_add: point stars (bhray_accum_set_stars) under a lens: neighbouring pixels look through different lens points, so their "
+                                      "escape directions bound no footprint");
     if (samples == 0) return BHRAY_OK;
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = launch_batch(c); if (rc) return rc; }              // the staged frames first: they keep the uniforms they were staged with
@@ -1579,14 +1586,21 @@ int dev_accum_add(bhray_dev* c, uint32_t samples) {
     const uint32_t kmax = std::max<uint32_t>(1u, launch_rays / g.npix);                   // a small frame takes several samples per launch: the device stays filled
     { int rc = accum_staging(c, (size_t)std::min(samples, kmax) * g.npix); if (rc) return rc; }
     TexDev sky; sky.rgba = c->tex[BHRAY_TEX_SKY]; sky.w = c->tex_w[BHRAY_TEX_SKY]; sky.h = c->tex_h[BHRAY_TEX_SKY];
+    // a whole 360 degree panorama is periodic in x (lon(x + lw) = lon(x) + 2 pi): its first and last columns are neighbours for the stars' footprints
+    const int star_wrap = c->a_cam.projection == BHRAY_STILL_EQUIRECT && c->cfg.crop_x == 0 && c->cfg.frame_w == c->cfg.level_w[c->cfg.levels - 1];
     for (uint32_t left = samples; left != 0;) {                   // in stream order: launch i + 1 rewrites the staging behind launch i's add
         const uint32_t k = std::min(left, kmax);
         g.s0 = c->a_samples; g.k = k;
         if (still) { sg.a.s0 = g.s0; sg.a.k = k; HIPCHK(c, launch_still_gen(sg, c->a_rays, c->q_stream)); }
         else HIPCHK(c, launch_accum_gen(g, c->a_rays, c->q_stream));
         { int rc = enqueue_rays(c, c->a_rays, k * g.npix, c->a_res); if (rc) return rc; }
-        if (filtered) HIPCHK(c, launch_accum_filter_add(sky, af, c->a_res, c->a_sum, c->cfg.frame_w, c->cfg.frame_h, g.s0, k, c->q_stream));
-        else HIPCHK(c, launch_accum_add(sky, c->a_res, c->a_sum, g.npix, k, c->q_stream));
+        const float4* res = c->a_res;
+        if (starred) {                                            // the starred images T go where the launch's records were: dead in stream order until the next generator
+            HIPCHK(c, launch_accum_stars(c->stars, sky, c->a_res, c->a_rays, c->cfg.frame_w, c->cfg.frame_h, k, star_wrap, c->q_stream));
+            res = c->a_rays;
+        }
+        if (filtered) HIPCHK(c, launch_accum_filter_add(sky, af, res, c->a_sum, c->cfg.frame_w, c->cfg.frame_h, g.s0, k, c->q_stream));
+        else HIPCHK(c, launch_accum_add(sky, res, c->a_sum, g.npix, k, c->q_stream));
         c->a_samples += k; left -= k;
         c->a_mode = 1;
     }
@@ -1661,6 +1675,9 @@ int dev_accum_add_adaptive(bhray_dev* c, const bhray_accum_adaptive* params, bhr
     if (c->a_mode == 1) return fail(c, BHRAY_E_STATE, "bhray_accum_add_adaptive: this accumulation holds bhray_accum_add's samples; bhray_accum_begin starts another");
     if (c->a_filter.kind != BHRAY_FILTER_BOX)
         return fail(c, BHRAY_E_STATE, "bhray_accum_add_adaptive: a still filter other than the box is in force (bhray_accum_set_filter): a round's pixels take different samples");
+    if (c->a_stars && c->stars.stars)
+        return fail(c, BHRAY_E_STATE, "bhray_accum_add_adaptive: point stars are on (bhray_accum_set_stars) and a catalogue is in force: a round's pixels take different samples, "
+                                      "so a neighbour has no direction for \"sample s\"");
     { int rc = adaptive_params_bad(c, "bhray_accum_add_adaptive", params); if (rc) return rc; }
     const bhray_accum_adaptive a = *params;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1804,6 +1821,14 @@ int dev_accum_set_filter(bhray_dev* c, const bhray_still_filter* filter) {
     if (!c) return BHRAY_E_INVALID;
     if (const char* why = still_filter_error(filter)) return fail(c, BHRAY_E_INVALID, "bhray_accum_set_filter: %s", why);
     if (filter) c->a_filter = *filter; else bhray_still_filter_default(&c->a_filter);
+    return BHRAY_OK;
+}
+
+// validates and stores: no device call, no image touched
+int dev_accum_set_stars(bhray_dev* c, int32_t on) {
+    if (!c) return BHRAY_E_INVALID;
+    if (on != 0 && on != 1) return fail(c, BHRAY_E_INVALID, "bhray_accum_set_stars: on must be 0 or 1");
+    c->a_stars = on == 1;
     return BHRAY_OK;
 }
 

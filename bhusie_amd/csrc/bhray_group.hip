@@ -1695,6 +1695,12 @@ int bhray_accum_set_filter(bhray_ctx* c, const bhray_still_filter* filter) {
     for (Part& p : c->parts) if (p.dev) DEV(c, p.dev, dev_accum_set_filter(p.dev, filter));
     return BHRAY_OK;
 }
+// Point stars in stills: state of every local engine, accepted on any ctx - what cannot accumulate refuses bhray_accum_add as before.
+int bhray_accum_set_stars(bhray_ctx* c, int32_t on) {
+    if (!c) return BHRAY_E_INVALID;
+    for (Part& p : c->parts) if (p.dev) DEV(c, p.dev, dev_accum_set_stars(p.dev, on));
+    return BHRAY_OK;
+}
 int bhray_accum_set_launch_rays(bhray_ctx* c, uint32_t max_rays) {
     if (!c) return BHRAY_E_INVALID;
     ENTER(c);

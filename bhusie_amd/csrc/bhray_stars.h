@@ -7,6 +7,8 @@
 #include "bhray_internal.h"
 #include "bhray_math.h"
 
+struct bhray_star_pixel_info;  // include/bhray_diag.h
+
 namespace bhray {
 
 // The catalogue as the kernel reads it: the stars sorted by (cell, original index), two float4 each - (dir.xyz, 0), (flux.rgb, 0) -, and the cells' prefix array
@@ -139,5 +141,9 @@ const char* stars_error(const bhray_star* stars, uint32_t n, const bhray_star_pa
 void stars_build_index(const bhray_star* stars, uint32_t n, uint32_t& G, std::vector<float4>& sorted, std::vector<uint32_t>& prefix);
 // the star pass over a whole frame_w x frame_h RGBA32F frame, added into the RGBA16F sky image in place.  Enqueues only.
 hipError_t launch_stars(const StarSet& S, const float4* frame, uint2* sky_rgba16f, uint32_t frame_w, uint32_t frame_h, hipStream_t s);
+// the host form over a frame (bhray_stars_resolve_host, bhray_diag_stars_pixel_info_host, bhray_accum_stars_resolve_host): add (w x h x 4 floats, may be NULL) and
+// per-pixel information (bhray_diag.h's struct, may be NULL).  wrap_x: the frame is periodic in x - column -1 is column w - 1, column w is column 0.
+int stars_resolve_host(const float* frame, uint32_t w, uint32_t h, bool wrap_x, const bhray_star* stars, uint32_t n, const bhray_star_params* params, float* add,
+                       bhray_star_pixel_info* info);
 
 }  // namespace bhray

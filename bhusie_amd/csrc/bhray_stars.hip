@@ -143,9 +143,9 @@ extern "C" int bhray_star_cell(const float dir[3], uint32_t G, uint32_t* cell) {
     return BHRAY_OK;
 }
 
-namespace {
 // the host form over a frame: add (w x h x 4 floats, may be NULL) and per-pixel information (may be NULL)
-int stars_resolve_host(const float* frame, uint32_t w, uint32_t h, const bhray_star* stars, uint32_t n, const bhray_star_params* params, float* add, bhray_star_pixel_info* info) {
+int bhray::stars_resolve_host(const float* frame, uint32_t w, uint32_t h, bool wrap_x, const bhray_star* stars, uint32_t n, const bhray_star_params* params, float* add,
+                              bhray_star_pixel_info* info) {
     if (!frame || !stars || n == 0 || w == 0 || h == 0 || w > 32767 || h > 32767 || (!add && !info)) return BHRAY_E_INVALID;
     if (stars_error(stars, n, params)) return BHRAY_E_INVALID;
     bhray_star_params P;
@@ -157,7 +157,10 @@ int stars_resolve_host(const float* frame, uint32_t w, uint32_t h, const bhray_s
     StarSet S{sorted.data(), prefix.data(), G, P.gain, P.min_area, P.max_footprint * P.max_footprint};
     const float4* F = (const float4*)frame;
     const float4 out_px = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-    auto px = [&](int x, int y) { return (x >= 0 && y >= 0 && x < (int)w && y < (int)h) ? F[(size_t)y * w + (size_t)x] : out_px; };
+    auto px = [&](int x, int y) {
+        if (wrap_x) x = x < 0 ? x + (int)w : x >= (int)w ? x - (int)w : x;   // §24: columns -1 and w are columns w - 1 and 0
+        return (x >= 0 && y >= 0 && x < (int)w && y < (int)h) ? F[(size_t)y * w + (size_t)x] : out_px;
+    };
     const size_t cw = (size_t)w + 1;
     std::vector<float4> corn(cw * ((size_t)h + 1));
     for (int y = 0; y <= (int)h; y++)
@@ -186,15 +189,14 @@ int stars_resolve_host(const float* frame, uint32_t w, uint32_t h, const bhray_s
         }
     return BHRAY_OK;
 }
-}  // namespace
 
 extern "C" int bhray_stars_resolve_host(const float* frame, uint32_t w, uint32_t h, const bhray_star* stars, uint32_t n, const bhray_star_params* params, float* add) {
     if (!add) return BHRAY_E_INVALID;
-    return stars_resolve_host(frame, w, h, stars, n, params, add, nullptr);
+    return stars_resolve_host(frame, w, h, false, stars, n, params, add, nullptr);
 }
 
 extern "C" int bhray_diag_stars_pixel_info_host(const float* frame, uint32_t w, uint32_t h, const bhray_star* stars, uint32_t n, const bhray_star_params* params,
                                                 bhray_star_pixel_info* info) {
     if (!info) return BHRAY_E_INVALID;
-    return stars_resolve_host(frame, w, h, stars, n, params, nullptr, info);
+    return stars_resolve_host(frame, w, h, false, stars, n, params, nullptr, info);
 }

@@ -1,7 +1,7 @@
 // bhray_render — minimal C++ host program over renderer.hpp: renders one frame of the reference's default scene
 // (camera (0,0,-19), hole at the origin, disk 2..10, R = 20; camera.rs:10-16, blackhole.rs:16-28) and writes the HDR frame
 // as raw little-endian f32 RGBA (row 0 = top).  Usage:
-//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--pick X Y] [--path X Y [--path-stride S]]
+//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--stars-seeded N SEED] [--pick X Y] [--path X Y [--path-stride S]]
 // --spp N: instead of the ladder's frame, a supersampled still - the mean of N jittered samples per frame pixel, sky resolved, accumulated on the GPU
 //   (Renderer::render_still: bhray_accum_*); written the same way.  Not with --lensed-mesh, --devices or --panorama.
 // --spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]: an adaptive still instead - every pixel takes MIN samples, then R more (4 by default) for as long as the
@@ -15,6 +15,8 @@
 // --filter tent RADIUS | cubic RADIUS B C (with --spp; not with --spp-adaptive): the still's pixel reconstruction filter in place of the box (bhray_accum_set_filter,
 //   DESIGN.md §22) - a tent of half width RADIUS pixels (0.5 <= RADIUS <= 2.5) or the Mitchell-Netravali cubic with parameters B and C, each in [0, 1], its support
 //   scaled to half width RADIUS (1 <= RADIUS <= 2.5).
+// --stars-seeded N SEED (with --spp; not with --spp-adaptive or --lens): a seeded catalogue of N point stars (bhusie::star_catalogue, 1 <= N <= BHRAY_MAX_STARS) lensed into
+//   every sample's image of the still (bhray_set_stars + bhray_accum_set_stars): pixel-sharp stars at sub-pixel accuracy, --filter their point spread function.
 // --path X Y [--path-stride S]: after the frame, the pick line of pixel (X, Y) and then the light path behind it, one line per point - that pixel's pinhole ray through
 //   bhray_trace_rays_paths (Renderer::ray_path), a point every 2^S iterations (S = 0 by default) and the end point:
 //   ITERATION X Y Z
@@ -173,11 +175,11 @@ int main(int argc, char** argv) {
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
         return 0;
     }
-    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--pick X Y] [--path X Y [--path-stride S]]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--stars-seeded N SEED] [--pick X Y] [--path X Y [--path-stride S]]\n", argv[0]); return 2; }
     uint32_t bw = 72, bh = 41, levels = 4, disk = 256, pano_w = 0, pano_h = 0;
     long pick_x = -1, pick_y = -1, path_x = -1, path_y = -1, path_stride = 0, spp = 0;
     bool rk = false, bvh_device = false, lensed = false, posed = false, adaptive = false;
-    long a_min = 0, a_max = 0, a_round = 4;
+    long a_min = 0, a_max = 0, a_round = 4, stars_n = 0, stars_seed = 0;
     double a_tol = 0.0, a_dark = 0.01;
     bool still_given = false, lens_given = false, filter_given = false;
     bhray_still_filter filter{};
@@ -239,6 +241,12 @@ int main(int argc, char** argv) {
             }
             else { std::fprintf(stderr, "--filter needs tent RADIUS or cubic RADIUS B C\n"); return 2; }
         }
+        else if (!std::strcmp(argv[i], "--stars-seeded")) {
+            char *e1 = nullptr, *e2 = nullptr;
+            if (i + 2 >= argc) { std::fprintf(stderr, "--stars-seeded needs N and SEED\n"); return 2; }
+            stars_n = std::strtol(argv[++i], &e1, 10); stars_seed = std::strtol(argv[++i], &e2, 10);
+            if (*e1 || *e2 || stars_n < 1 || stars_n > (long)BHRAY_MAX_STARS || stars_seed < 0) { std::fprintf(stderr, "--stars-seeded needs 1 <= N <= %u and SEED >= 0\n", BHRAY_MAX_STARS); return 2; }
+        }
         else if (!std::strcmp(argv[i], "--pick") && i + 2 < argc) { pick_x = std::atol(argv[++i]); pick_y = std::atol(argv[++i]); if (pick_x < 0 || pick_y < 0) { std::fprintf(stderr, "--pick needs X >= 0 and Y >= 0\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--path") && i + 2 < argc) { path_x = std::atol(argv[++i]); path_y = std::atol(argv[++i]); if (path_x < 0 || path_y < 0) { std::fprintf(stderr, "--path needs X >= 0 and Y >= 0\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--path-stride") && i + 1 < argc) { path_stride = std::atol(argv[++i]); if (path_stride < 0 || path_stride > BHRAY_MAX_PATH_STRIDE_LOG2) { std::fprintf(stderr, "--path-stride needs 0 <= S <= %d\n", BHRAY_MAX_PATH_STRIDE_LOG2); return 2; } }
@@ -251,6 +259,9 @@ int main(int argc, char** argv) {
     if ((still_given || lens_given) && !spp && !adaptive) { std::fprintf(stderr, "--still-camera and --lens are the camera of a still: give --spp or --spp-adaptive\n"); return 2; }
     if (filter_given && adaptive) { std::fprintf(stderr, "--filter weighs sample s of a pixel's neighbours: not with --spp-adaptive, whose pixels take different samples\n"); return 2; }
     if (filter_given && !spp) { std::fprintf(stderr, "--filter is the reconstruction filter of a still: give --spp\n"); return 2; }
+    if (stars_n && adaptive) { std::fprintf(stderr, "--stars-seeded lights a pixel from sample s of its neighbours: not with --spp-adaptive, whose pixels take different samples\n"); return 2; }
+    if (stars_n && lens_given) { std::fprintf(stderr, "--stars-seeded needs footprints: not with --lens, whose neighbouring pixels look through different lens points\n"); return 2; }
+    if (stars_n && !spp) { std::fprintf(stderr, "--stars-seeded in this mode is the star field of a still: give --spp\n"); return 2; }
     if (lens_given && still.projection != BHRAY_STILL_PINHOLE) { std::fprintf(stderr, "--lens goes with the pinhole projection only\n"); return 2; }
     if (spp && pano_w) { std::fprintf(stderr, "--spp samples the pixels of the pinhole frame: not with --panorama\n"); return 2; }
     if (path_x >= 0 && pano_w) { std::fprintf(stderr, "--path names a pixel of the pinhole frame: not with --panorama\n"); return 2; }
@@ -287,7 +298,8 @@ int main(int argc, char** argv) {
             a.min_samples = (uint32_t)a_min; a.max_samples = (uint32_t)a_max; a.round_samples = (uint32_t)a_round; a.tolerance = (float)a_tol; a.dark = (float)a_dark;
             out = r.render_still_adaptive(a, &ainfo, &counts, &still);
         } else if (spp) {
-            out = r.render_still((uint32_t)spp, &still, filter_given ? &filter : nullptr);
+            if (stars_n > 0) r.ray_pipeline().set_stars(bhusie::star_catalogue((uint32_t)stars_n, (uint32_t)stars_seed));
+            out = r.render_still((uint32_t)spp, &still, filter_given ? &filter : nullptr, stars_n > 0);
         } else {
             r.render(0.0f);
             out = r.ray_pipeline().output();

@@ -278,6 +278,9 @@ public:
         f.struct_size = (uint32_t)sizeof(bhray_still_filter);
         check(bhray_accum_set_filter(ctx_, &f), ctx_);
     }
+    // point stars in stills (bhray_accum_set_stars): with on and a catalogue in force (set_stars), every sample image of accumulate() receives the
+    // catalogue's stars before it is summed, from the next call on.  accumulate() under a lens and accumulate_adaptive() are then refused.
+    void set_still_stars(bool on) { check(bhray_accum_set_stars(ctx_, on ? 1 : 0), ctx_); }
     bhray_ctx* ctx() { return ctx_; }
 private:
     bhray_config cfg_;
@@ -429,11 +432,13 @@ public:
     // (RayPipeline::set_still_camera)
     // still_filter (may be null: the box): the pixel reconstruction filter, a tent or a Mitchell-Netravali cubic (RayPipeline::set_still_filter)
     std::vector<float> render_still(uint32_t samples, const bhray_still_camera* still_camera = nullptr) { return render_still(samples, still_camera, nullptr); }
-    std::vector<float> render_still(uint32_t samples, const bhray_still_camera* still_camera, const bhray_still_filter* still_filter) {
+    // stars: the catalogue of RayPipeline::set_stars lensed into every sample's image (RayPipeline::set_still_stars)
+    std::vector<float> render_still(uint32_t samples, const bhray_still_camera* still_camera, const bhray_still_filter* still_filter, bool stars = false) {
         ray_pipeline_.set_uniforms(camera.uniform(), black_hole.uniform(), ray_details);
         apply_lensing();
         ray_pipeline_.set_still_camera(still_camera);
         ray_pipeline_.set_still_filter(still_filter);
+        ray_pipeline_.set_still_stars(stars);
         return ray_pipeline_.accumulate(samples);
     }
     // an adaptive still of the current scene (RayPipeline::accumulate_adaptive): params.struct_size is filled in here
@@ -444,6 +449,7 @@ public:
         apply_lensing();
         ray_pipeline_.set_still_camera(still_camera);
         ray_pipeline_.set_still_filter(nullptr);                  // an adaptive still has no filter but the box
+        ray_pipeline_.set_still_stars(false);                     // and no point stars
         return ray_pipeline_.accumulate_adaptive(params, info, counts);
     }
     // what is under frame pixel (x, y): the record of that pixel's pinhole ray under the current scene (hit & 0xff: BHRAY_HIT_*; (hit >> 8) & 0xff: the model slot of a mesh hit)

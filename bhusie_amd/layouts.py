@@ -332,6 +332,8 @@ SYMBOLS = {
     "bhray_star_grid_size": (C.c_int, [u32, P(u32)]),
     "bhray_star_cell": (C.c_int, [P(C.c_float), u32, P(u32)]),
     "bhray_stars_resolve_host": (C.c_int, [vp, u32, u32, vp, u32, P(BhrayStarParams), vp]),
+    "bhray_accum_set_stars": (C.c_int, [vp, i32]),
+    "bhray_accum_stars_resolve_host": (C.c_int, [vp, u32, u32, i32, vp, u32, P(BhrayStarParams), vp]),
     "bhray_post_defaults": (C.c_int, [P(BhrayFxaaDetails), P(BhrayMixDetails)]),
     "bhray_bloom_sizes": (C.c_int, [u32, u32, P(u32), P(u32)]),
     "bhray_set_post_uniforms": (C.c_int, [vp, vp, vp]),

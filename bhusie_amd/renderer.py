@@ -178,6 +178,17 @@ def stars_resolve_host(frame, stars, params=None) -> np.ndarray:
     return out
 
 
+def accum_stars_resolve_host(results, stars, params=None, wrap_x=False) -> np.ndarray:
+    """stars_resolve_host over a still's sample image (bhray_accum_stars_resolve_host, DESIGN.md §24, no device): with wrap_x the image is periodic in x - column -1 is
+    column w - 1 and column w is column 0 -, as a whole equirect still's."""
+    f = np.ascontiguousarray(results, dtype=np.float32)
+    a, n = star_array(stars)
+    out = np.empty_like(f)
+    check(lib().bhray_accum_stars_resolve_host(f.ctypes.data, f.shape[1], f.shape[0], int(bool(wrap_x)), a.ctypes.data, n, C.byref(params) if params is not None else None,
+                                               out.ctypes.data))
+    return out
+
+
 STAR_PIXEL_INFO_DTYPE = np.dtype([("state", np.uint32), ("faces", np.uint32), ("cells", np.uint32), ("tested", np.uint32), ("accepted", np.uint32),
                                   ("reversed", np.uint32), ("area", np.float32), ("pad", np.uint32)])
 
@@ -586,6 +597,13 @@ class RayPass:
         refuses: BhrayError (BHRAY_E_INVALID)."""
         s = filter.struct() if filter is not None else None
         check(self._L.bhray_accum_set_filter(self._h, C.byref(s) if s is not None else None), self._h, self._L)
+
+    def accum_set_stars(self, on=False):
+        """Point stars in the accumulation image from the next accum_add on (bhray_accum_set_stars): with on and a catalogue in force (set_stars),
+        every sample image receives the catalogue's stars under the sky pass's footprint rule before it is summed, so the mean holds each star box-filtered at
+        sub-pixel accuracy and a filter of accum_set_filter is its point spread function.  Off (the default), or without a catalogue, every image keeps its bits.
+        accum_add under a lens and accum_add_adaptive are then refused (BHRAY_E_STATE).  Validates and stores only."""
+        check(self._L.bhray_accum_set_stars(self._h, int(on)), self._h, self._L)
 
     # -- adaptive stills: each pixel sampled until the error of its mean is under a bound (bhray_accum_add_adaptive, DESIGN.md §20)
     @staticmethod
@@ -1018,13 +1036,14 @@ class Renderer:
                 "closest": float(r["closest"]), "transmittance": float(r["transmittance"]),
                 "path": pts["position"][0, :k].copy(), "path_iterations": pts["iteration"][0, :k].copy()}
 
-    def _accumulate(self, samples: int, shutter: float, camera=None, filter=None):
+    def _accumulate(self, samples: int, shutter: float, camera=None, filter=None, stars=False):
         samples = int(samples)
         if samples < 1:
             raise ValueError(f"render_still: samples must be at least 1, got {samples}")
         self._apply_uniforms()
         self.ray_pass.accum_set_camera(camera)
         self.ray_pass.accum_set_filter(filter)
+        self.ray_pass.accum_set_stars(bool(stars))
         self.ray_pass.accum_begin()
         if not shutter > 0.0:
             self.ray_pass.accum_add(samples)
@@ -1038,7 +1057,7 @@ class Renderer:
         finally:
             self.ray_details.time = t0
 
-    def render_still(self, samples: int = 16, shutter: float = 0.0, adaptive: AdaptiveStill | None = None, camera=None, filter=None) -> np.ndarray:
+    def render_still(self, samples: int = 16, shutter: float = 0.0, adaptive: AdaptiveStill | None = None, camera=None, filter=None, stars: bool = False) -> np.ndarray:
         """A supersampled still of the current scene (RayPass.accum_*): the mean of `samples` jittered samples per frame pixel, sky resolved,
         (frame_h, frame_w, 4) float32.  Sample 0 is the pixel centre, so samples=1 is the frame a `levels = 1` ladder renders, after the sky pass in binary32.
         shutter > 0: motion blur - sample s is rendered at ray_details.time + shutter * s / samples (the disk turns with `time`); ray_details.time is left as it was.
@@ -1048,10 +1067,15 @@ class Renderer:
         (.pinhole(lens_radius, focus_distance): depth of field; sample 0 is then a lens sample, not the centre ray) from the scene camera's position along its forward
         (DESIGN.md §21); None: the pinhole.  The ctx keeps the camera of the last still.
         filter: a StillFilter - the pixel reconstruction filter, StillFilter.tent(radius), .mitchell(radius) or .bspline(radius); None: the box.  Not
-        with `adaptive` (ValueError).  The ctx keeps the filter of the last still."""
+        with `adaptive` (ValueError).  The ctx keeps the filter of the last still.
+        stars: the catalogue of set_stars lensed into every sample's image: pixel-sharp stars at sub-pixel accuracy, with `filter` as their point
+        spread function.  Without a catalogue it changes nothing.  Not with `adaptive` (ValueError) or a camera with a lens (BhrayError).  The ctx keeps the
+        switch of the last still."""
         if adaptive is None:
-            self._accumulate(samples, shutter, camera, filter)
+            self._accumulate(samples, shutter, camera, filter, stars)
             return self.ray_pass.accum_read()
+        if stars:
+            raise ValueError("render_still: an adaptive still has no point stars (a round's pixels take different samples)")
         if filter is not None and filter.kind != FILTER_BOX:
             raise ValueError("render_still: an adaptive still has no filter but the box (a round's pixels take different samples)")
         if shutter > 0.0:
@@ -1059,6 +1083,7 @@ class Renderer:
         self._apply_uniforms()
         self.ray_pass.accum_set_camera(camera)
         self.ray_pass.accum_set_filter(None)
+        self.ray_pass.accum_set_stars(False)
         self.ray_pass.accum_begin()
         self.still_info = self.ray_pass.accum_add_adaptive(**adaptive.as_kwargs())
         return self.ray_pass.accum_read()
@@ -1067,11 +1092,11 @@ class Renderer:
         """The sample-count heat map of the last adaptive still: (frame_h, frame_w) uint32."""
         return self.ray_pass.accum_read_counts()
 
-    def save_still(self, path, samples: int = 16, camera=None, filter=None):
-        """save_image for a supersampled still: the mean of `samples` samples per pixel through the display pass, written with alpha 255.  camera, filter: as
+    def save_still(self, path, samples: int = 16, camera=None, filter=None, stars: bool = False):
+        """save_image for a supersampled still: the mean of `samples` samples per pixel through the display pass, written with alpha 255.  camera, filter, stars: as
         render_still's."""
         from PIL import Image
-        self._accumulate(samples, 0.0, camera, filter)
+        self._accumulate(samples, 0.0, camera, filter, stars)
         img = self.ray_pass.accum_read_display()
         img[..., 3] = 255
         Image.fromarray(img, "RGBA").save(path)

@@ -879,7 +879,8 @@ int bhray_sky_pyramid_sizes(uint32_t w, uint32_t h, uint32_t* levels, uint32_t l
  * and >= 0, n > BHRAY_MAX_STARS, a params value out of range or another struct_size.
  * Not built (a catalogue: BHRAY_E_STATE, the removing call is accepted) for a ctx with device_count >= 2, with gather =
  * BHRAY_GATHER_RCCL or with row_world > 1: a partition does not hold its neighbours' rows.
- * Not affected: bhray_read_hdr, bhray_trace_rays_sky, bhray_accum_*, and the sky sample the trace kernels take behind the disk.  */
+ * Not affected: bhray_read_hdr, bhray_trace_rays_sky, bhray_accum_* (unless bhray_accum_set_stars below turns the stars of a still
+ * on), and the sky sample the trace kernels take behind the disk.                                                                 */
 #define BHRAY_MAX_STARS (1u << 22)
 #define BHRAY_STARS_MAX_CELLS 64u
 typedef struct bhray_star { float dir[3]; float flux[3]; } bhray_star;     /* 24 B */
@@ -896,6 +897,48 @@ int  bhray_star_cell(const float dir[3], uint32_t G, uint32_t* cell);
  * nothing).  BHRAY_E_INVALID: NULL, n == 0, w or h == 0 or above 32767, or what bhray_set_stars refuses.                          */
 int  bhray_stars_resolve_host(const float* frame_rgba32f, uint32_t w, uint32_t h, const bhray_star* stars, uint32_t n,
                               const bhray_star_params* params, float* add_rgba32f);
+
+/* Point stars in stills: the catalogue of bhray_set_stars lensed into every sample image of the accumulation.  Sample s
+ * of a still is a whole image on a pixel grid shifted by one common offset (dx, dy), so the footprint rule above applies to each sample
+ * image unchanged; the mean over the samples is then the star box-filtered at sub-pixel accuracy, and under bhray_accum_set_filter the
+ * tent or cubic is the star's point spread function.  An opt-in switch of the still, off by default: a catalogue alone leaves every
+ * bhray_accum_* image its bits.
+ *
+ * Per-ctx state like bhray_accum_set_camera and bhray_accum_set_filter: bhray_accum_set_stars only validates and stores, needs no
+ * device, touches no image and is accepted in every state; each bhray_accum_add reads it at the time of the call.  on: 0 (the default)
+ * or 1; anything else BHRAY_E_INVALID, the switch untouched.  With on == 1 and a catalogue in force, every sample image passes the
+ * stage below before it is summed.  With on == 0, or with no catalogue in force, nothing is launched, nothing is allocated and every
+ * image keeps its bits.  The catalogue and params are those in force at the time of the bhray_accum_add call (bhray_set_stars waits
+ * for the samples enqueued before it).
+ *
+ * R_s is sample s's trace results: a frame_w x frame_h RGBA32F image, pixel p = y * frame_w + x, what bhray_trace_rays returns for the
+ * rays of bhray_accum_sample_rays(s).
+ *  1. Star sum.  Rules 1 - 6 above run over R_s as "the frame" with the ctx's catalogue and params (a direction pixel has w == 0.0f
+ *     and finite x, y, z) and give acc and the accepted count per pixel - the same function as the sky pass's kernel runs.
+ *  2. Wrap.  Only when the still camera is BHRAY_STILL_EQUIRECT, crop_x == 0 and frame_w equals the last level's width: the image is
+ *     periodic in x (lon(x + lw) = lon(x) + 2 pi), and for rule 1 pixel (-1, y) is pixel (frame_w - 1, y) and pixel (frame_w, y) is
+ *     pixel (0, y) of the same sample - without it a 360 degree still has a starless seam two pixels wide straight behind the camera.
+ *     The top and bottom rows stay borders.  Under any other camera or window the frame border is rule 1's border.
+ *  3. Starred image T_s.  A pixel that accepted at least one star: b = the accumulation's resolve of R_s[p] (binary32 sky^4, alpha 1; the
+ *     pixel is a direction pixel by rule 1), T_s[p] = (min(b.x + acc.x * gain, 65504.0f), min(b.y + acc.y * gain, 65504.0f),
+ *     min(b.z + acc.z * gain, 65504.0f), 1.0f): one rounded product, one rounded add, then min(a, 65504) = 65504 < a ? 65504 : a; no
+ *     binary16 rounding.  Every other pixel: T_s[p] = R_s[p] bit for bit.
+ *  4. Everything downstream consumes T_s where it consumed R_s: the box's sum and the filter's stencil resolve at load, and a pixel
+ *     with alpha 1 passes through that resolve unchanged.  sum.w, skipped samples, the mean, bhray_accum_read and
+ *     bhray_accum_read_display are unchanged.
+ *  5. Refusals, checked on bhray_accum_add and bhray_accum_add_adaptive while on == 1 and a catalogue is in force (never on the
+ *     setter), each BHRAY_E_STATE with nothing enqueued and the sum untouched: a still camera with lens_radius > 0 (neighbouring pixels
+ *     look through different lens points, so their escape directions bound no footprint); bhray_accum_add_adaptive (a round's pixels
+ *     take different samples, so a neighbour has no result for "sample s").  Every existing refusal holds.
+ * Known property: under a CUBIC filter with c > 0 the negative lobes can carry a mean past 65504 beside a saturated star, and
+ * bhray_accum_read_display's binary16 rounding then yields infinity; nothing is clamped beyond step 3 - lower the gain.
+ *
+ * bhray_accum_stars_resolve_host is bhray_stars_resolve_host with the wrap of step 2 (wrap_x != 0): one change to how a neighbour
+ * outside [0, w) is fetched.  The same arguments otherwise, the same errors, the same output: acc * gain in rgb, the accepted count in
+ * alpha.  Host arithmetic, no device.                                                                                             */
+int  bhray_accum_set_stars(bhray_ctx* ctx, int32_t on);
+int  bhray_accum_stars_resolve_host(const float* results_rgba32f, uint32_t w, uint32_t h, int32_t wrap_x, const bhray_star* stars,
+                                    uint32_t n, const bhray_star_params* params, float* add_rgba32f);
 
 /* Display pass — the rest of the reference's GPU frame after the sky pass (mod.rs:209-324, run at 425-431): 5 bloom-down and
  * 5 bloom-up passes (bloom_down.wgsl, bloom_up.wgsl), mix (mix.wgsl), ACES tone mapping (hdr.wgsl) and FXAA (fxaa.wgsl) into the
