@@ -18,7 +18,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 from ._lib import lib, LibraryMissing, LIB_PATH  # noqa: F401
 from .layouts import (BhrayConfig, BhrayCounters, BhrayTiming, BhrayDetails, BhrayCameraUniform,  # noqa: F401
                       BhrayBlackHoleUniform, BhrayBlackHole, BhrayFxaaDetails, BhrayMixDetails, BhrayModelDesc, BhrayNode, BhrayRay, BhrayRayRecord, BhrayPathPoint, PATH_POINT_DTYPE, BhrayTriangle, BhrayAccumAdaptive, BhrayAccumAdaptiveInfo, BhrayStar, BhrayStarParams,
-                      HIT_NONE, HIT_HORIZON, HIT_DISK, HIT_MESH, HIT_UNUSABLE,
+                      HIT_NONE, HIT_HORIZON, HIT_DISK, HIT_MESH, HIT_UNUSABLE, LENS_FRAMES, LENS_RAYS,
                       BhrayError, check)
 from .scene import Camera, BlackHole, RayDetails  # noqa: F401
 from .model import Model, load_model  # noqa: F401

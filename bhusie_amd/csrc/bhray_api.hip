@@ -176,6 +176,7 @@ struct bhray_dev {
     bhray_details det{};
     bool have_uniforms = false;
     bool mesh_lensing = false;             // dev_set_mesh_lensing: models are tested on every step inside the relativity sphere too (from the next dev_render)
+    bool lens_rays = false;                // ... its BHRAY_LENS_RAYS bit: and in ray batches, ray records and what bhray_accum_* traces (from the next batch enqueued)
     std::vector<hipEvent_t> events;        // ring: [BHRAY_TIMING_RING][events_per_batch(levels)], indexed by ev_* (batch_events)
     uint64_t frame_counter = 0, timing_begin = 0;   // timing_begin: first batch not yet reported by dev_get_timing
     uint8_t sky_recorded[BHRAY_TIMING_RING] = {0};
@@ -1297,7 +1298,8 @@ int dev_set_mesh_lensing(bhray_dev* c, int32_t on) {
     if (!c) return BHRAY_E_INVALID;
     if (on != 0 && (c->cfg.flags & (BHRAY_F_LITERAL | BHRAY_F_EVAL_FMA)))
         return fail(c, BHRAY_E_STATE, "mesh lensing has no kernel for BHRAY_F_LITERAL / BHRAY_F_EVAL_FMA (no executed shader text to pin one against)");
-    c->mesh_lensing = on != 0;
+    c->mesh_lensing = on != 0;                                    // frames: any non-zero word (BHRAY_LENS_FRAMES is what `on != 0` has always meant)
+    c->lens_rays = (on & BHRAY_LENS_RAYS) != 0;
     return BHRAY_OK;
 }
 
@@ -1315,11 +1317,12 @@ namespace {
 constexpr size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 constexpr size_t Q_OFF_LAUNCH = align16(sizeof(FrameParams)), Q_OFF_CTL = Q_OFF_LAUNCH + align16(sizeof(FrameLaunch)), Q_ARGS_BYTES = Q_OFF_CTL + 16;
 
-// why this engine traces no ray batch now (the refused states), or BHRAY_OK
-int rays_refused(bhray_dev* c, const char* name) {
+// why this engine traces no ray batch now (the refused states), or BHRAY_OK.  Under mesh lensing a batch needs the setting's BHRAY_LENS_RAYS bit, and a path
+// call (path_call) is refused with either bit: there is no lensed path kernel
+int rays_refused(bhray_dev* c, const char* name, bool path_call = false) {
     if (!c->have_uniforms) return fail(c, BHRAY_E_STATE, "%s: bhray_set_uniforms has not been called", name);
     if (c->cfg.flags & (BHRAY_F_LITERAL | BHRAY_F_EVAL_FMA)) return fail(c, BHRAY_E_STATE, "%s: no ray-list kernel for BHRAY_F_LITERAL / BHRAY_F_EVAL_FMA", name);
-    if (c->mesh_lensing) return fail(c, BHRAY_E_STATE, "%s: ray batches under mesh lensing are not built", name);
+    if (c->mesh_lensing && (!c->lens_rays || path_call)) return fail(c, BHRAY_E_STATE, "%s: ray batches under mesh lensing are not built", name);
     return BHRAY_OK;
 }
 
@@ -1352,7 +1355,8 @@ int enqueue_rays(bhray_dev* c, const float4* d_rays, uint32_t n, float4* d_out, 
         F.need = (uint8_t*)paths->d_points; F.stamp = (const uint32_t*)paths->d_counts;
         F.radius = (int)paths->stride_log2; F.stamp_value = paths->max_points;
     }
-    const TraceVariant v{P.method, P.model_count > 0 ? 1 : 0, false, false, 0, false, true, d_records != nullptr, paths != nullptr};
+    // models: as a frame's (frame_variant) - lensed when the setting in force has BHRAY_LENS_RAYS and a usable visible model exists; the entry points refuse paths under lensing
+    const TraceVariant v{P.method, P.model_count > 0 ? ((c->mesh_lensing && c->lens_rays && !paths) ? 2 : 1) : 0, false, false, 0, false, true, d_records != nullptr, paths != nullptr};
     int ctx_grid = c->num_cus * trace_blocks_per_cu(v);
     if (c->grid_override > 0) ctx_grid = c->grid_override;
     const int grid = (int)bhray_trace_grid_for(n, 1, (uint32_t)ctx_grid, c->level_grid_gen, 0, c->level_grid_floor);      // n is exact: no margin
@@ -1372,7 +1376,7 @@ int dev_trace_rays(bhray_dev* c, const bhray_ray* rays, uint32_t n, float* out, 
     if (n > BHRAY_MAX_RAYS_PER_CALL || (n != 0 && (!rays || (!out && !sky16 && !records && !paths)))) return fail(c, BHRAY_E_INVALID, "bhray_trace_rays: bad arguments");
     if (paths && (paths->max_points < 2u || paths->stride_log2 > BHRAY_MAX_PATH_STRIDE_LOG2 || (uint64_t)n * paths->max_points > BHRAY_MAX_PATH_POINTS_PER_CALL ||
                   (n != 0 && (!paths->points || !paths->counts)))) return fail(c, BHRAY_E_INVALID, "bhray_trace_rays_paths: bad arguments");
-    { int rc = rays_refused(c, "bhray_trace_rays"); if (rc) return rc; }
+    { int rc = rays_refused(c, "bhray_trace_rays", paths != nullptr); if (rc) return rc; }
     if (n == 0) return BHRAY_OK;
     for (uint32_t i = 0; i < n; i++) {                            // before anything is enqueued
         const float* o = rays[i].origin; const float* d = rays[i].direction;
@@ -1472,7 +1476,7 @@ int dev_trace_rays_device(bhray_dev* c, const void* d_rays, uint32_t n, void* d_
     if (paths && (paths->max_points < 2u || paths->stride_log2 > BHRAY_MAX_PATH_STRIDE_LOG2 || (uint64_t)n * paths->max_points > BHRAY_MAX_PATH_POINTS_PER_CALL ||
                   (n != 0 && (!paths->points || !paths->counts || !d_records)) || ((uintptr_t)paths->points & 15u) || ((uintptr_t)paths->counts & 3u)))
         return fail(c, BHRAY_E_INVALID, "bhray_trace_rays_paths_device: bad arguments");
-    { int rc = rays_refused(c, "bhray_trace_rays_device"); if (rc) return rc; }
+    { int rc = rays_refused(c, "bhray_trace_rays_device", paths != nullptr); if (rc) return rc; }
     if (n == 0) return BHRAY_OK;
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = ensure_query(c); if (rc) return rc; }

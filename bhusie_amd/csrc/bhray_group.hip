@@ -281,6 +281,7 @@ struct bhray_ctx {
     uint64_t st_counter = 0; uint32_t st_pending = 0; int st_method = 0; int st_models = 0;
     uint8_t u_cam[32] = {0}, u_bh[132] = {0}, u_det[32] = {0}; bool have_uniforms = false;
     bool mesh_lensing = false;             // bhray_set_mesh_lensing (part of the kernel variant: ctx_variant)
+    int32_t lensing_word = 0;              // ... its whole argument, as the engines are told (BHRAY_LENS_RAYS is theirs to read: DESIGN.md §25)
     float m_pos[BHRAY_MAX_MODELS][3] = {{0}}; int32_t m_vis[BHRAY_MAX_MODELS] = {0}; bool m_dirty[BHRAY_MAX_MODELS] = {false}, m_usable[BHRAY_MAX_MODELS] = {false};
     bool single = true;                    // one partition, no gather: every call goes straight to parts[0].dev
     bool gather = false;
@@ -1542,6 +1543,7 @@ int bhray_set_mesh_lensing(bhray_ctx* c, int32_t on) {
     if (on != 0 && (c->cfg.flags & (BHRAY_F_LITERAL | BHRAY_F_EVAL_FMA)))
         return gfail(c, BHRAY_E_STATE, "mesh lensing has no kernel for BHRAY_F_LITERAL / BHRAY_F_EVAL_FMA (no executed shader text to pin one against)");
     c->mesh_lensing = on != 0;
+    c->lensing_word = on;
     if (c->threaded) return BHRAY_OK;
     for (Part& p : c->parts) if (p.dev) DEV(c, p.dev, dev_set_mesh_lensing(p.dev, on));
     return BHRAY_OK;
@@ -1753,7 +1755,7 @@ int bhray_render(bhray_ctx* c) {
         if (c->st_pending == 0) { c->st_method = method; c->st_models = models; }
         RenderCmd cmd;
         memcpy(cmd.cam, c->u_cam, 32); memcpy(cmd.bh, c->u_bh, 132); memcpy(cmd.det, c->u_det, 32);
-        cmd.lensing = c->mesh_lensing ? 1 : 0;
+        cmd.lensing = c->lensing_word;
         for (uint32_t mi = 0; mi < BHRAY_MAX_MODELS; mi++) { memcpy(cmd.mpos[mi], c->m_pos[mi], 12); cmd.mvis[mi] = c->m_vis[mi]; cmd.mset[mi] = c->m_dirty[mi]; c->m_dirty[mi] = false; }
         cmd.si = (int)(c->st_counter % c->nslots); cmd.sub = c->st_pending;
         cmd.bound = c->bound; c->bound = nullptr;

@@ -167,10 +167,11 @@ constexpr bool operator==(const TraceVariant& a, const TraceVariant& b) {
 // The build that runs when `asked` is asked for - the only place that knows the fallbacks.  Every build of a variant computes the same pixels, bit for bit, so a
 // fallback costs time only.  What is instantiated is exactly the set of variants that resolve to themselves (bhray_kernels.hip: trace_kernel_ptr).
 constexpr TraceVariant trace_resolve(TraceVariant v) {
-    // ray lists: the contract's evaluation only (the API refuses the others), latency build, general hole position, no counting; flat-space models (lensing is refused)
+    // ray lists: the contract's evaluation only (the API refuses the others), latency build, general hole position, no counting; models in flat space (1) or lensed (2:
+    // bhray_set_mesh_lensing's BHRAY_LENS_RAYS) for ray lists and records - a path request folds to flat-space models (the API refuses paths under lensing)
     if (v.paths) v.records = true;                                            // the path kernels are record kernels
     if (v.records) v.rays = true;                                             // the record kernels are ray-list kernels
-    if (v.rays) { v.models = v.models != 0 ? 1 : 0; v.count = false; v.dense = false; v.eval = 0; v.origin = false; return v; }
+    if (v.rays) { if (v.paths && v.models == 2) v.models = 1; v.count = false; v.dense = false; v.eval = 0; v.origin = false; return v; }
     if (v.models == 2 && v.eval == 0) { v.dense = false; v.origin = false; return v; }   // lensed meshes: the latency general build, counting or not
     if (v.models == 2) v.models = 1;                                          // no lensed kernel under another evaluation (refused at bhray_set_mesh_lensing): flat-space models
     if (v.count || (v.eval != 0 && v.models != 0)) v.dense = false;           // dense builds exist where throughput is reported (trace_variant_exists, bhray_kernels.hip)
@@ -192,9 +193,14 @@ static_assert(trace_resolve({1, 0, true,  false, 0, true }) == TraceVariant{1, 0
 static_assert(trace_resolve({1, 0, false, true,  1, true }) == TraceVariant{1, 0, false, true,  1, false}, "trace_resolve");   // and for another evaluation
 static_assert(trace_resolve({1, 0, false, true,  2, false}) == TraceVariant{1, 0, false, true,  2, false}, "trace_resolve");   // an already-resolved variant resolves to itself
 static_assert(trace_resolve({1, 0, true,  true,  0, true,  true}) == TraceVariant{1, 0, false, false, 0, false, true}, "trace_resolve");   // a ray list: latency, general, not counting
-static_assert(trace_resolve({0, 2, false, true,  0, false, true}) == TraceVariant{0, 1, false, false, 0, false, true}, "trace_resolve");   // ... and flat-space models
+static_assert(trace_resolve({0, 2, false, true,  0, false, true}) == TraceVariant{0, 2, false, false, 0, false, true}, "trace_resolve");   // ... and lensed models stay lensed
 static_assert(!(trace_resolve({1, 0, false, false, 0, false, true}) == trace_resolve({1, 0, false, false, 0, false, false})), "trace_resolve: the ray-list kernels are builds of their own");
-static_assert(trace_resolve({1, 2, true,  true,  0, true,  false, true}) == TraceVariant{1, 1, false, false, 0, false, true, true}, "trace_resolve");   // records imply a ray list, and resolve as one
+static_assert(trace_resolve({1, 2, true,  true,  0, true,  false, true}) == TraceVariant{1, 2, false, false, 0, false, true, true}, "trace_resolve");   // records imply a ray list, and resolve as one: lensed models stay lensed
+static_assert(trace_resolve({1, 1, true,  true,  0, true,  false, true}) == TraceVariant{1, 1, false, false, 0, false, true, true}, "trace_resolve");   // ... flat-space models flat
+static_assert(trace_resolve({0, 2, false, false, 0, false, true, true, false}) == TraceVariant{0, 2, false, false, 0, false, true, true, false}, "trace_resolve: the lensed record kernels are builds of their own");
+static_assert(!(trace_resolve({1, 2, false, false, 0, false, true}) == trace_resolve({1, 1, false, false, 0, false, true})), "trace_resolve: the lensed ray-list kernels are builds of their own");
+static_assert(trace_resolve({1, 2, false, false, 2, false, true}) == TraceVariant{1, 2, false, false, 0, false, true}, "trace_resolve");   // (a ray list's evaluation is the contract's: the API refuses the others before a launch)
+static_assert(trace_resolve({0, 2, false, false, 0, false, true, true, true}) == TraceVariant{0, 1, false, false, 0, false, true, true, true}, "trace_resolve: no lensed path kernel - a path request folds to flat-space models");
 static_assert(!(trace_resolve({0, 0, false, false, 0, false, true, true}) == trace_resolve({0, 0, false, false, 0, false, true, false})), "trace_resolve: the record kernels are builds of their own");
 static_assert(trace_resolve({0, 1, false, false, 0, false, true, false}) == TraceVariant{0, 1, false, false, 0, false, true, false}, "trace_resolve");   // a ray list without records stays what it was
 static_assert(trace_resolve({1, 2, true,  true,  0, true,  false, false, true}) == TraceVariant{1, 1, false, false, 0, false, true, true, true}, "trace_resolve");   // paths imply records, and resolve as a ray list

@@ -1421,9 +1421,10 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
     constexpr int REL_BATCH = (METHOD == 0 && DENSE && !MODELS) ? BHRAY_REL_BATCH_EULER_DENSE : BHRAY_REL_BATCH;
     constexpr int REFILL_MIN = (METHOD == 0 && DENSE && !MODELS) ? BHRAY_REFILL_MIN_EULER_DENSE : BHRAY_REFILL_MIN;
     static_assert(!LENSED || (MODELS && !DENSE && EVAL == 0 && !ORIGIN), "the lensed-mesh kernels: mesh variant, latency build, the contract's evaluation, general hole position");
-    static_assert(!RAYS || (!COUNT && !DENSE && EVAL == 0 && !ORIGIN && !LENSED), "the ray-list kernels: latency build, the contract's evaluation, general hole position, no counting, flat-space models");
+    static_assert(!RAYS || (!COUNT && !DENSE && EVAL == 0 && !ORIGIN), "the ray-list kernels: latency build, the contract's evaluation, general hole position, no counting; models in flat space, or lensed (DESIGN.md §25)");
     static_assert(!RECORDS || RAYS, "the record kernels are ray-list kernels");
     static_assert(!PATHS || RECORDS, "the path kernels are record kernels");
+    static_assert(!(LENSED && PATHS), "no path kernel under mesh lensing (the API refuses the call: DESIGN.md §25)");
     constexpr bool UNIFIED = BHRAY_UNIFIED != 0 && EVAL == 0 && (!MODELS || BHRAY_UNIFIED_MESH != 0) && !COUNT && !LENSED && !PATHS;           // the unified march (bhray_step_u.inc) in the contract kernels that do not count (the lensed-mesh kernels: the general step, whose ppos / pdir a paused lane keeps)
     constexpr bool ONE_TEST = UNIFIED && !MODELS && (((BHRAY_ONE_TEST & 1) != 0 && !DENSE) || ((BHRAY_ONE_TEST & 2) != 0 && DENSE));
     // the RK step's error estimate behind a wave-uniform bound (next_ray_rk_t): 0 the full text, 1 skipped where R11.1's bound holds, 2 the full text and that bound's counters,
@@ -1691,6 +1692,7 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                     // closest_render_state after the black hole (ray.wgsl:367-374): its t where it hit (always < seg), else t_max = seg
                     Hit rs; rs.hit = kind != 0; rs.t = kind != 0 ? cold.pend_t() : seg; rs.color = f3(0.0f, 0.0f, 0.0f); rs.opacity = kind != 0 ? 1.0f : 0.0f;
                     bool mesh_won = false;
+                    [[maybe_unused]] int win_model = 0, win_slot = 0;           // RECORDS: as in the flat phase - the model that holds the nearest hit, the winning triangle's bvh_lookup slot in it
                     const F3 inv = f3(rcp_rn(pdir.x), rcp_rn(pdir.y), rcp_rn(pdir.z));
                     const bool finite = fabsf(inv.x) < INFINITY && fabsf(inv.y) < INFINITY && fabsf(inv.z) < INFINITY;
                     for (int mi = 0; mi < P.model_count; mi++) {
@@ -1698,8 +1700,15 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                             Hit r; F3 nrm;
                             r.hit = false;
                             // every model with the full range (t_min, seg): no model's hit (nor the black hole's) bounds another's traversal
+                            // (RECORDS: the call with its slot output in an arm of its own - the lensed frame kernels keep the text, and the compiler figures, they had)
+                            if constexpr (RECORDS) {
+                                int slot = 0;
+                                if (lens_model_reachable(P.models[mi], ppos, inv, finite, seg)) trace_ray_model<COUNT, BVH_WW, true>(P.models[mi], bvh_lds, ppos, pdir, t_min, seg, r, nrm, cnt, &err, &slot);
+                                if (r.hit && r.t < rs.t) { win_model = mi; win_slot = slot; }
+                            } else {
                             if (lens_model_reachable(P.models[mi], ppos, inv, finite, seg)) trace_ray_model<COUNT, BVH_WW>(P.models[mi], bvh_lds, ppos, pdir, t_min, seg, r, nrm, cnt, &err);
                             else if (COUNT) cnt[6]++;                             // counted as the visit it replaces (as in the flat phase)
+                            }
                             if (r.hit && r.t < rs.t) {                            // strictly nearer; on a tie the earlier candidate stays
                                 rs = r; mesh_won = true;
                                 const F3 light = normalize(f3(0.2f, 0.2f, -1.0f));
@@ -1718,6 +1727,14 @@ __global__ BHRAY_TRACE_KERNEL_ATTR __launch_bounds__(BHRAY_TRACE_THREADS, MODELS
                             const F3 cc = f3(clamp_(rs.color.x, 0.0f, 1.0f), clamp_(rs.color.y, 0.0f, 1.0f), clamp_(rs.color.z, 0.0f, 1.0f));
                             cold.set_color(cold.color() + cc * (amount * rs.opacity));
                             amount *= 1.0f - rs.opacity;
+                            // RECORDS: a paused lane is kept out of the step's horizon arm and of the flat phase, so what they would have recorded is recorded here - a mesh (the
+                            // triangle through the model's bvh_lookup, once) or the horizon that stands (kind 1); the disk that stands is the shade phase's, below
+                            if constexpr (RECORDS) {
+                                if (!HIT_GET()) {
+                                    if (mesh_won) record_first_hit(records, cold.pix(), cpos, (uint32_t)BHRAY_HIT_MESH | ((uint32_t)win_model << 8), P.models[win_model].lookup[win_slot]);
+                                    else record_first_hit(records, cold.pix(), cpos, (uint32_t)BHRAY_HIT_HORIZON, -1);
+                                }
+                            }
                             HIT_SET(1);
                         }
                         if (amount < 0.005f) mode = M_FINISH; else it++;
@@ -2263,7 +2280,7 @@ hipError_t launch_classify(const FrameParams* Pb, const FrameLaunch* Fb, int nb,
 }
 
 // Which builds of trace_kernel<METHOD, MODELS, COUNT, DENSE, EVAL, ORIGIN, LENSED> exist (16 x 2 integrators general builds + 2 x 2 ORIGIN builds + 2 x 2 lensed-mesh builds
-// + 2 x 2 ray-list builds + 2 x 2 record builds + 2 x 2 path builds = 52 instantiations; 48 before the paths, 44 before the records, 40 before the ray lists, 36 in round 11, 32 in round 9, 48 in round 5, 72 in round 3).
+// + 2 x 2 ray-list builds + 2 x 2 record builds + 2 x 2 path builds + 2 x 2 lensed ray-list / record builds = 56 instantiations; 52 before those, 48 before the paths, 44 before the records, 40 before the ray lists, 36 in round 11, 32 in round 9, 48 in round 5, 72 in round 3).
 // eval: 0 the numerics contract, 1 BHRAY_F_LITERAL, 2 BHRAY_F_EVAL_FMA.  Every variant has a build for lone launches (the latency build);
 // the build for a saturated device (dense) exists where throughput is reported: not for counting kernels (BHRAY_F_COUNTERS is a diagnosis
 // mode: the same counts whichever build marches) and, of the two measurement-only evaluations, not for the mesh variant.  A launch that
@@ -2277,7 +2294,7 @@ constexpr bool trace_variant_exists(int eval, bool models, bool dense, bool coun
 // latency build, counting or not) and what a launch gets that asks for a build that does not exist: trace_resolve (bhray_internal.h).  The builds instantiated are the variants
 // that resolve to themselves.  The loop order is the order the kernels stand in the code object (lensed first, then per integrator the evaluations 1, 2, 0, mesh / counting /
 // ORIGIN / dense before their opposites): kept, so the object does not change.
-struct TraceBuilds { int n; TraceVariant v[52]; };
+struct TraceBuilds { int n; TraceVariant v[56]; };
 constexpr TraceBuilds trace_builds() {
     TraceBuilds t{};
     for (int lensed = 1; lensed >= 0; lensed--) for (int method = 0; method < 2; method++) for (int e = 1; e <= 3; e++) for (int mesh = 1; mesh >= lensed; mesh--)
@@ -2300,10 +2317,15 @@ constexpr TraceBuilds trace_builds() {
         const TraceVariant v{method, mesh, false, false, 0, false, true, true, true};
         if (trace_resolve(v) == v) t.v[t.n++] = v;
     }
+    // the lensed ray-list and record kernels (trace_kernel's LENSED with RAYS / RECORDS): both integrators x {ray list, records}, behind them; no lensed path kernel
+    for (int method = 0; method < 2; method++) for (int records = 0; records < 2; records++) {
+        const TraceVariant v{method, 2, false, false, 0, false, true, records != 0};
+        if (trace_resolve(v) == v) t.v[t.n++] = v;
+    }
     return t;
 }
 constexpr TraceBuilds TRACE_BUILDS = trace_builds();
-static_assert(TRACE_BUILDS.n == 36 + (BHRAY_ORIGIN_KERNEL != 0 && BHRAY_UNIFIED != 0 ? 4 : 0) + 4 + 4 + 4, "instantiations of trace_kernel (the last twelve: the ray-list kernels, then the record kernels, then the path kernels)");
+static_assert(TRACE_BUILDS.n == 36 + (BHRAY_ORIGIN_KERNEL != 0 && BHRAY_UNIFIED != 0 ? 4 : 0) + 4 + 4 + 4 + 4, "instantiations of trace_kernel (the last sixteen: the ray-list kernels, then the record kernels, then the path kernels, then the lensed ray-list and record kernels)");
 constexpr bool trace_variant_exists_agrees() {     // trace_variant_exists is trace_resolve's rule for the dense builds
     for (int i = 0; i < 24; i++) {
         const TraceVariant v{0, i & 1, (i & 2) != 0, (i & 4) != 0, i >> 3, false};

@@ -3,12 +3,12 @@
 // as raw little-endian f32 RGBA (row 0 = top).  Usage:
 //   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--stars-seeded N SEED] [--pick X Y] [--path X Y [--path-stride S]]
 // --spp N: instead of the ladder's frame, a supersampled still - the mean of N jittered samples per frame pixel, sky resolved, accumulated on the GPU
-//   (Renderer::render_still: bhray_accum_*); written the same way.  Not with --lensed-mesh, --devices or --panorama.
+//   (Renderer::render_still: bhray_accum_*); written the same way.  Not with --devices or --panorama.
 // --spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]: an adaptive still instead - every pixel takes MIN samples, then R more (4 by default) for as long as the
 //   relative standard error of its mean compressed luminance, with D (0.01 by default) added to the mean, exceeds TOL, and at most MAX
 //   (Renderer::render_still_adaptive: bhray_accum_add_adaptive); written the same way, followed by one line
 //   adaptive rounds=N rays=N mean_count=F
-//   Not with --spp, --lensed-mesh, --devices or --panorama.
+//   Not with --spp, --devices or --panorama.
 // --still-camera pinhole|equirect|fisheye FOV, --lens RADIUS FOCUS (with --spp or --spp-adaptive): the still's camera model, evaluated on the GPU (bhray_accum_set_camera,
 //   DESIGN.md §21) - a 360 x 180 degree panorama over the frame, an equidistant fisheye of full opening angle FOV (radians, 0 < FOV <= 2 pi), or the pinhole (the
 //   default); --lens gives the pinhole a thin lens of aperture radius RADIUS > 0 focused at distance FOCUS > 0 (depth of field) and goes with no other projection.
@@ -20,14 +20,16 @@
 // --path X Y [--path-stride S]: after the frame, the pick line of pixel (X, Y) and then the light path behind it, one line per point - that pixel's pinhole ray through
 //   bhray_trace_rays_paths (Renderer::ray_path), a point every 2^S iterations (S = 0 by default) and the end point:
 //   ITERATION X Y Z
-// Not with --lensed-mesh, --devices or --panorama.
+// Not with --lensed-mesh (paths under mesh lensing are not built: an error), --devices or --panorama.
 // --pick X Y: after the frame, one line with the record of its pixel (X, Y) - that pixel's pinhole ray through bhray_trace_rays_records (Renderer::pick):
 //   pick X Y hit=none|horizon|disk|mesh model=M triangle=T position=PX PY PZ iterations=I closest=C transmittance=A
-// Not with --lensed-mesh, --devices or --panorama.
+// Not with --devices or --panorama.
 // --panorama W H: instead of the pinhole frame, a 360 x 180 degree panorama of W x H pixels from the camera's position, its centre column looking along the camera's forward
-// (bhusie::equirect_rays through Renderer::render_rays: bhray_trace_rays); written the same way.  Not with --lensed-mesh or --devices.
+// (bhusie::equirect_rays through Renderer::render_rays: bhray_trace_rays); written the same way.  Not with --devices.
 // --pose: every --obj mesh is turned by the Euler rotation (RX, RY, RZ) about its own origin on the GPU (bhray_pose_from_euler + bhray_set_model_pose); needs --bvh device.
 // --lensed-mesh: the meshes are tested on every step inside the relativity sphere too (bhray_set_mesh_lensing): a mesh inside the sphere is visible.
+//   Together with --spp, --spp-adaptive (and their --still-camera, --lens, --filter, --stars-seeded), --panorama or --pick the ray batches behind those are lensed too
+//   (Renderer::lens_ray_batches: BHRAY_LENS_FRAMES | BHRAY_LENS_RAYS): the still, the panorama and the picked record show the lensed mesh.
 // --bvh device: every mesh's tree is built on the GPU (bhray_upload_model_build) instead of by the reference's host builder (the default).
 // --obj: repeatable; the i-th mesh goes to model slot i (Renderer::add_model), at the position its OBJ loader gives it.
 // --devices: row-tile the frame over several GPUs from this one process (RCCL gather to the first one, inside libbhray).
@@ -266,6 +268,7 @@ int main(int argc, char** argv) {
     if (spp && pano_w) { std::fprintf(stderr, "--spp samples the pixels of the pinhole frame: not with --panorama\n"); return 2; }
     if (path_x >= 0 && pano_w) { std::fprintf(stderr, "--path names a pixel of the pinhole frame: not with --panorama\n"); return 2; }
     if (pick_x >= 0 && pano_w) { std::fprintf(stderr, "--pick names a pixel of the pinhole frame: not with --panorama\n"); return 2; }
+    if (path_x >= 0 && lensed) { std::fprintf(stderr, "--path under --lensed-mesh is not built (bhray_trace_rays_paths is refused while mesh lensing is on)\n"); return 2; }
     if (posed && !bvh_device) { std::fprintf(stderr, "--pose needs --bvh device (a pose is applied to a tree built on the GPU)\n"); return 2; }
     try {
         std::unique_ptr<bhusie::Renderer> rp(devices.empty() ? new bhusie::Renderer({bw, bh}, 3, levels) : new bhusie::Renderer({bw, bh}, 3, levels, devices));
@@ -286,6 +289,7 @@ int main(int argc, char** argv) {
         }
         r.ray_details.integration_method = rk ? 1 : 0;
         r.mesh_lensing = lensed;
+        r.lens_ray_batches = lensed && (spp || adaptive || pano_w || pick_x >= 0);        // the stills, the panorama and the pick trace ray batches: lensed too (BHRAY_LENS_RAYS)
         std::vector<float> out;
         std::vector<uint32_t> counts;
         bhray_accum_adaptive_info ainfo{};

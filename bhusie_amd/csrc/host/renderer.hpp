@@ -194,6 +194,7 @@ public:
     void set_model_pose(uint32_t index, const float* pose_3x4) { check(bhray_set_model_pose(ctx_, index, pose_3x4), ctx_); }
     void set_model_transform(uint32_t index, const float position[3], int32_t visible) { check(bhray_set_model_transform(ctx_, index, position, visible), ctx_); }
     void set_mesh_lensing(bool on) { check(bhray_set_mesh_lensing(ctx_, on ? 1 : 0), ctx_); }   // lensed meshes: from the next pass on
+    void set_mesh_lensing_word(int32_t on) { check(bhray_set_mesh_lensing(ctx_, on), ctx_); }    // ... the setting's whole word: BHRAY_LENS_FRAMES | BHRAY_LENS_RAYS lenses the ray batches too
     void set_materials(const void* material_uniforms_128) { check(bhray_set_materials(ctx_, material_uniforms_128, 128), ctx_); }   // mod.rs:389 (ignored by the shader)
     void set_uniforms(const bhray_camera_uniform& c, const bhray_black_hole_uniform& b, const bhray_details& d) { check(bhray_set_uniforms(ctx_, &c, &b, &d), ctx_); }
     void pass() { check(bhray_render(ctx_), ctx_); }                                            // ray_pipeline.rs:301-309
@@ -384,6 +385,7 @@ public:
     BlackHole black_hole;
     RayDetails ray_details;
     bool mesh_lensing = false;      // lensed meshes (bhray_set_mesh_lensing): models are tested inside the relativity sphere too; applied before each render
+    bool lens_ray_batches = false;  // ... and, with it, in ray batches too (BHRAY_LENS_RAYS): render_rays, pick and the stills trace lensed; ray_path throws the ctx's error
     explicit Renderer(int device = 0) : ray_pipeline_({72, 41}, 3, 4, device) {}               // mod.rs:177-179
     Renderer(std::pair<uint32_t, uint32_t> base, uint32_t multiplier, uint32_t levels, int device = 0) : ray_pipeline_(base, multiplier, levels, device) {}
     Renderer(std::pair<uint32_t, uint32_t> base, uint32_t multiplier, uint32_t levels, const std::vector<int>& devices) : ray_pipeline_(base, multiplier, levels, devices) {}
@@ -477,10 +479,14 @@ public:
         return out;
     }
 private:
-    void apply_lensing() { if (mesh_lensing != lensing_applied_) { ray_pipeline_.set_mesh_lensing(mesh_lensing); lensing_applied_ = mesh_lensing; } }
+    // the ctx is told BHRAY_LENS_FRAMES | BHRAY_LENS_RAYS, BHRAY_LENS_FRAMES or 0; compared is the word last sent, not its truth (1 and 3 are different settings)
+    void apply_lensing() {
+        const int32_t word = mesh_lensing ? (lens_ray_batches ? (BHRAY_LENS_FRAMES | BHRAY_LENS_RAYS) : BHRAY_LENS_FRAMES) : 0;
+        if (word != lensing_applied_) { ray_pipeline_.set_mesh_lensing_word(word); lensing_applied_ = word; }
+    }
     RayPipeline ray_pipeline_;
     uint32_t models_ = 0;
-    bool lensing_applied_ = false;  // what the ctx was last told (its default: off)
+    int32_t lensing_applied_ = 0;   // the word the ctx was last told (its default: off)
 };
 
 }  // namespace bhusie

@@ -91,6 +91,7 @@ assert PATH_POINT_DTYPE.itemsize == C.sizeof(BhrayPathPoint) == 16
 MAX_PATH_STRIDE_LOG2 = 16                   # BHRAY_MAX_PATH_STRIDE_LOG2
 MAX_PATH_POINTS_PER_CALL = 1 << 24          # BHRAY_MAX_PATH_POINTS_PER_CALL
 HIT_NONE, HIT_HORIZON, HIT_DISK, HIT_MESH, HIT_UNUSABLE = 0, 1, 2, 3, 255      # BHRAY_HIT_*: bits 0-7 of bhray_ray_record.hit (bits 8-15: the model slot of a MESH hit)
+LENS_FRAMES, LENS_RAYS = 1, 2                                                   # BHRAY_LENS_*: the bits of bhray_set_mesh_lensing's `on` (frames; also ray batches, records and stills)
 
 
 class BhrayAccumAdaptive(C.Structure):      # bhray_accum_adaptive: the parameters of bhray_accum_add_adaptive

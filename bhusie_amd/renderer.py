@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import lib
-from .layouts import (BhrayFxaaDetails, BhrayMixDetails, DIAG_DISPLAY_FXAA_ONLY, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters, BhrayRay, BhrayRayRecord, BhrayPathPoint, PATH_POINT_DTYPE, HIT_MESH, HIT_UNUSABLE,
+from .layouts import (BhrayFxaaDetails, BhrayMixDetails, DIAG_DISPLAY_FXAA_ONLY, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters, BhrayRay, BhrayRayRecord, BhrayPathPoint, PATH_POINT_DTYPE, HIT_MESH, HIT_UNUSABLE, LENS_FRAMES, LENS_RAYS,
                       BhrayAccumAdaptive, BhrayAccumAdaptiveInfo, BhrayStar, BhrayStarParams, BhrayStillFilter, FILTER_BOX, FILTER_TENT, FILTER_CUBIC,
                       BhrayGatherInfo, BhrayModelBuildInfo, BhrayModelDesc, BhrayRebalanceInfo, BhrayTiming, check)
 from .model import NODE_DTYPE, Model
@@ -462,8 +462,10 @@ class RayPass:
 
     def set_mesh_lensing(self, on):
         """Lensed meshes (bhray_set_mesh_lensing): from the next render on, models are also tested on every integrator step inside the
-        relativity sphere.  Off by default; BhrayError (BHRAY_E_STATE) for on on a literal / eval_fma ctx."""
-        check(self._L.bhray_set_mesh_lensing(self._h, 1 if on else 0), self._h, self._L)
+        relativity sphere.  Off by default; BhrayError (BHRAY_E_STATE) for on on a literal / eval_fma ctx.  `on` is True / False (LENS_FRAMES / 0), or the
+        setting's word: an integer >= 2 is passed through - LENS_FRAMES | LENS_RAYS lenses the ray batches, the records and the stills as well."""
+        word = int(on) if isinstance(on, (int, np.integer)) and not isinstance(on, bool) and int(on) >= 2 else (1 if on else 0)
+        check(self._L.bhray_set_mesh_lensing(self._h, word), self._h, self._L)
 
     # -- ray batches (bhray_trace_rays, DESIGN.md §15)
     @staticmethod
@@ -896,7 +898,8 @@ class Renderer:
         self.models: list[Model] = []                        # scene.models: slot i of the ctx holds models[i]
         self._device_built: list[bool] = []                  # ... and whether its tree was built on the GPU (add_model(build="device"))
         self.mesh_lensing = False                            # lensed meshes (RayPass.set_mesh_lensing): applied before each render
-        self._lensing_applied = False                        # what the ctx was last told (its default: off)
+        self.lens_ray_batches = False                        # ... and, with it, ray batches too (LENS_RAYS): render_rays, render_records, pick, the stills
+        self._lensing_applied = 0                            # the word the ctx was last told (its default: off)
         self.still_info = None                               # what the last adaptive still did (render_still(adaptive=...)): rounds, active_last, rays, reach
         self.sky_filter = False                              # footprint-filtered sky pass (RayPass.set_sky_filter): applied before save_image's display pass
         self._sky_filter_applied = False
@@ -950,9 +953,7 @@ class Renderer:
     def render(self, dt: float = 0.0):
         self.ray_details.time += dt                          # mod.rs:382
         self.ray_pass.set_uniforms(self.camera.uniform(), self.black_hole.uniform(), self.ray_details.uniform())
-        if bool(self.mesh_lensing) != self._lensing_applied:
-            self.ray_pass.set_mesh_lensing(self.mesh_lensing)
-            self._lensing_applied = bool(self.mesh_lensing)
+        self._apply_lensing()
         self.ray_pass.render()
 
     def read_hdr(self):
@@ -968,9 +969,7 @@ class Renderer:
         if rec.shape[0] != h * w:
             raise ValueError(f"render_rays: {rec.shape[0]} rays for a {w}x{h} image")
         self.ray_pass.set_uniforms(self.camera.uniform(), self.black_hole.uniform(), self.ray_details.uniform())
-        if bool(self.mesh_lensing) != self._lensing_applied:
-            self.ray_pass.set_mesh_lensing(self.mesh_lensing)
-            self._lensing_applied = bool(self.mesh_lensing)
+        self._apply_lensing()
         six = rec[:, [0, 1, 2, 4, 5, 6]]
         usable = np.isfinite(six).all(axis=1) & (rec[:, 4:7] != 0.0).any(axis=1)
         img = np.zeros((h * w, 4), dtype=np.float16 if resolve_sky else np.float32)
@@ -980,11 +979,21 @@ class Renderer:
             img[usable] = got[1] if resolve_sky else got
         return img.reshape(h, w, 4)
 
+    def _lensing_word(self) -> int:
+        """what the ctx is to be told: LENS_FRAMES | LENS_RAYS, LENS_FRAMES, or 0"""
+        if not self.mesh_lensing:
+            return 0
+        return (LENS_FRAMES | LENS_RAYS) if self.lens_ray_batches else LENS_FRAMES
+
+    def _apply_lensing(self):
+        word = self._lensing_word()
+        if word != self._lensing_applied:                    # the value last sent, not its truth: 1 and 3 are different settings
+            self.ray_pass.set_mesh_lensing(word)
+            self._lensing_applied = word
+
     def _apply_uniforms(self):
         self.ray_pass.set_uniforms(self.camera.uniform(), self.black_hole.uniform(), self.ray_details.uniform())
-        if bool(self.mesh_lensing) != self._lensing_applied:
-            self.ray_pass.set_mesh_lensing(self.mesh_lensing)
-            self._lensing_applied = bool(self.mesh_lensing)
+        self._apply_lensing()
 
     def render_records(self, rays, shape):
         """The record layers of an image seen through caller-supplied rays (render_rays' rays and rules): an (h, w) structured array (RAY_RECORD_DTYPE) -

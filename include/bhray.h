@@ -436,7 +436,16 @@ int bhray_set_uniforms(bhray_ctx* ctx, const void* camera_uniform_32,
  * are launched first (a batch runs one kernel variant).  Off, and on with no usable visible model, every frame keeps
  * the bits it has without this call.  BHRAY_E_STATE for on != 0 on a ctx created with BHRAY_F_LITERAL or
  * BHRAY_F_EVAL_FMA (no executed shader text exists to pin such a kernel against).  With one process per GPU every
- * rank calls it alike.  bhray_rebalance's wave-step measure does not see the traversal work of lensed frames.       */
+ * rank calls it alike.  bhray_rebalance's wave-step measure does not see the traversal work of lensed frames.
+ * `on` is a word of two bits.  Any non-zero value lenses the frames: 1, 2 and 3 give the same frames,
+ * bit for bit.  Bit 1 (BHRAY_LENS_RAYS) extends the setting to the rays a caller supplies: with it bhray_trace_rays,
+ * bhray_trace_rays_device, bhray_trace_rays_sky, bhray_trace_rays_records[_device] and everything bhray_accum_add /
+ * bhray_accum_add_adaptive trace run the same test on every step inside the sphere, under the same semantics.  With it
+ * clear (on = 1, what `on != 0` has always meant) every one of them is refused while lensing is on (BHRAY_E_STATE), as
+ * before: a flat-space answer would not match the ctx's frames.  bhray_trace_rays_paths[_device] is refused while
+ * lensing is on with either bit.  A batch is traced under the setting in force when it is enqueued.                   */
+#define BHRAY_LENS_FRAMES 1   /* what `on != 0` has always meant */
+#define BHRAY_LENS_RAYS   2   /* also: ray batches, ray records and everything bhray_accum_* traces */
 int bhray_set_mesh_lensing(bhray_ctx* ctx, int32_t on);
 
 /* Ray batches (not in the reference, whose shader only traces the rays create_ray makes of its pinhole
@@ -456,7 +465,10 @@ int bhray_set_mesh_lensing(bhray_ctx* ctx, int32_t on);
  * (0, 0, 0, -1).
  * n == 0: BHRAY_OK, nothing happens.  n > BHRAY_MAX_RAYS_PER_CALL, a NULL ctx or a NULL array: BHRAY_E_INVALID.
  * BHRAY_E_STATE: before the first bhray_set_uniforms; on a ctx created with BHRAY_F_LITERAL or BHRAY_F_EVAL_FMA (no
- * such kernels exist: the rule of bhray_set_mesh_lensing); while mesh lensing is on; on a ctx with device_count >= 2.
+ * such kernels exist: the rule of bhray_set_mesh_lensing); while mesh lensing is on without BHRAY_LENS_RAYS; on a ctx
+ * with device_count >= 2.  While mesh lensing is on with BHRAY_LENS_RAYS the models are tested on every step of a ray
+ * inside the relativity sphere too (bhray_set_mesh_lensing's semantics), so pinhole_rays give the LENSED levels = 1
+ * frame, bit for bit; with no usable visible model every result has the bits it has with lensing off.
  * A BHRAY_F_COUNTERS ctx runs the kernels that do not count: its counters do not move.
  * bhray_trace_rays launches the staged frames first (they keep the uniforms they were staged with), copies the rays
  * in, traces, copies the results out and returns when `out_rgba32f` is complete.
@@ -480,8 +492,9 @@ int bhray_trace_rays_sky(bhray_ctx* ctx, const bhray_ray* rays, uint32_t n, floa
 /* Ray records (not in the reference): bhray_trace_rays, and per ray what trace_ray knew when its loop
  * ended - what the ray hit FIRST, where, how close it came to the hole, how many iterations it took and how much
  * light it had left.  "First accepted hit" is the first time crs.hit is true in trace_ray's loop (ray.wgsl:570, where
- * the shader sets hit = true): the horizon, the disk, or - in flat space, the only place the shader tests them - a
- * mesh; a disk hit followed by the horizon records DISK.
+ * the shader sets hit = true): the horizon, the disk, or a mesh - in flat space, the only place the shader tests them,
+ * and under mesh lensing with BHRAY_LENS_RAYS also on a step's segment inside the relativity sphere, where a mesh that
+ * is strictly nearer than the step's horizon or disk hit is that hit; a disk hit followed by the horizon records DISK.
  *   position       curr.position right after that hit (ray.wgsl:571: curr + prev.direction * t); no hit: curr.position
  *                  when the loop ended
  *   hit            bits 0-7 BHRAY_HIT_*; bits 8-15 the model slot (MESH only, else 0); bits 16-31 zero
@@ -495,8 +508,8 @@ int bhray_trace_rays_sky(bhray_ctx* ctx, const bhray_ray* rays, uint32_t n, floa
  * synchronisation, BHRAY_F_COUNTERS - and the results are bit for bit bhray_trace_rays' for the same rays.  d_records
  * must be 16-byte aligned (BHRAY_E_INVALID).  The device form answers an unusable ray with hit = BHRAY_HIT_UNUSABLE,
  * triangle = -1 and every other word zero, beside the result (0, 0, 0, -1).
- * Not built: records under mesh lensing, on a ctx with device_count >= 2 (both BHRAY_E_STATE, as bhray_trace_rays), and
- * for the pixels of a ladder frame (copied and interpolated pixels have no ray); the path length is not recorded (the path: below). */
+ * Refused as bhray_trace_rays is (BHRAY_E_STATE): under mesh lensing without BHRAY_LENS_RAYS, on a ctx with
+ * device_count >= 2.  No records exist for the pixels of a ladder frame (copied and interpolated pixels have no ray); the path length is not recorded (the path: below). */
 enum { BHRAY_HIT_NONE = 0, BHRAY_HIT_HORIZON = 1, BHRAY_HIT_DISK = 2, BHRAY_HIT_MESH = 3, BHRAY_HIT_UNUSABLE = 255 };
 typedef struct bhray_ray_record {
     float    position[3];
@@ -529,7 +542,8 @@ int bhray_trace_rays_records_device(bhray_ctx* ctx, const void* d_rays, uint32_t
  * max_points < 2; stride_log2 > BHRAY_MAX_PATH_STRIDE_LOG2; n * max_points > BHRAY_MAX_PATH_POINTS_PER_CALL; for
  * n != 0 a NULL out_points / out_counts (out_rgba32f and out_records of the host form may be NULL); in the device form
  * a NULL d_out_rgba32f / d_records, a d_points or d_records that is not 16-byte aligned, a d_counts that is not 4-byte
- * aligned.  Not built: paths under mesh lensing or on a ctx with device_count >= 2 (BHRAY_E_STATE, as above).         */
+ * aligned.  Not built: paths under mesh lensing - with or without BHRAY_LENS_RAYS - or on a ctx with device_count >= 2
+ * (BHRAY_E_STATE, as above).                                                                                          */
 typedef struct bhray_path_point { float position[3]; uint32_t iteration; } bhray_path_point;   /* 16 bytes */
 #define BHRAY_MAX_PATH_STRIDE_LOG2     16
 #define BHRAY_MAX_PATH_POINTS_PER_CALL (1u << 24)      /* n * max_points: 256 MiB of points */
@@ -567,7 +581,8 @@ int bhray_trace_rays_paths_device(bhray_ctx* ctx, const void* d_rays, uint32_t n
  * scene may change between calls - `time`, the camera: motion blur, depth of field -; a caller that does not want that
  * clears with bhray_accum_begin.  bhray_accum_read and bhray_accum_read_display wait and deliver frame_h rows.
  * BHRAY_E_STATE, as for bhray_trace_rays: before the first bhray_set_uniforms (bhray_accum_add), on a ctx created with
- * BHRAY_F_LITERAL or BHRAY_F_EVAL_FMA, while mesh lensing is on (bhray_accum_add), on a ctx with device_count >= 2 or a
+ * BHRAY_F_LITERAL or BHRAY_F_EVAL_FMA, while mesh lensing is on without BHRAY_LENS_RAYS (bhray_accum_add; with it the
+ * samples are traced lensed, under the setting in force at each call), on a ctx with device_count >= 2 or a
  * gather; and on a row-partitioned ctx (row_world > 1).  A frame of more than BHRAY_MAX_RAYS_PER_CALL pixels:
  * BHRAY_E_INVALID.  Every call that waits for the outstanding ray batches - the uploads, the poses, bhray_sync,
  * bhray_destroy - waits for the accumulation too, and a device fault surfaces as a batch's does.                    */
