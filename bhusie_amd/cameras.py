@@ -6,6 +6,7 @@ pinhole_rays    the shader's create_ray (ray.wgsl:269-285), operation by operati
 equirect_rays   a 360 x 180 degree panorama: the centre column looks along `forward`
 fisheye_rays    an equidistant fisheye of opening angle `fov` about `forward`; pixels outside the image circle get a zero direction (not traced: alpha -1)
 still_rays      the rays of sample s of the accumulation image under a StillCamera (bhray_accum_set_camera): what the device generates, bit for bit
+boost_rays      any of these records seen by a moving Observer: Lorentz aberration of the directions and the beam factors D^4, bit for bit
 
 All three use create_ray's basis: plane_up = (0, -1, 0), right = normalize(cross(forward, plane_up)), up = normalize(cross(forward, right)) - `up` is the direction in
 which the image's rows increase.  Directions are unit as a binary32 normalise leaves them (v * (1 / sqrt(dot(v, v)))), which is what the trace kernels expect.
@@ -283,3 +284,54 @@ def still_rays(camera, cfg, still_camera: StillCamera | None, s: int) -> np.ndar
     d = _normalize(v.astype(F))
     d = np.where(inside[..., None], d, F(0.0)).astype(F)
     return _records(pos, d.reshape(h * w, 3))
+
+
+@dataclass(frozen=True)
+class Observer:
+    """The moving observer of a still (bhray_observer): `velocity` is beta, the observer's velocity in the static frame, world axes, units of c
+    (|beta| <= 0.99); beaming: also scale every sample by the bolometric D^4.  A zero velocity is no observer."""
+    velocity: tuple = (0.0, 0.0, 0.0)
+    beaming: bool = True
+
+    @property
+    def at_rest(self) -> bool:
+        return all(F(v) == F(0.0) for v in self.velocity)
+
+    def struct(self):
+        """the bhray_observer the library takes"""
+        import ctypes as C
+        from .layouts import BhrayObserver
+        vx, vy, vz = (float(v) for v in self.velocity)
+        return BhrayObserver(C.sizeof(BhrayObserver), (C.c_float * 3)(vx, vy, vz), 1 if self.beaming else 0)
+
+
+def boost_rays(rays, observer: Observer | None):
+    """(rays', beam): the (n, 8) records `rays`, their directions given in the observer's rest frame, with the directions aberrated into the static frame, and the
+    (n,) beam factors D^4 - include/bhray.h's rule (bhray_observer_boost_rays), one rounded binary32 operation at a time.  Origins are unchanged; an all-zero
+    direction, a None observer or a zero velocity leaves the record unchanged with beam 1."""
+    rays = np.ascontiguousarray(rays, dtype=F).reshape(-1, 8)
+    out = rays.copy()
+    beam = np.ones(rays.shape[0], dtype=F)
+    if observer is None or observer.at_rest:
+        return out, beam
+    b = np.array([F(v) for v in observer.velocity], dtype=F)
+    bb = F(F(F(b[0] * b[0]) + F(b[1] * b[1])) + F(b[2] * b[2]))
+    if not np.all(np.isfinite(b)) or bb > F(0.9801):
+        raise ValueError(f"boost_rays: the velocity {tuple(observer.velocity)} is not finite or faster than 0.99 c")
+    ig = np.sqrt(F(F(1.0) - bb), dtype=F)
+    g = F(F(1.0) / ig)
+    k = F(g / F(g + F(1.0)))
+    n = rays[:, 4:7]
+    live = ~np.all(n == F(0.0), axis=1)
+    with np.errstate(all="ignore"):
+        c = _dot(b[None, :], n).astype(F)
+        a = ((k * c).astype(F) - F(1.0)).astype(F)
+        q = (F(1.0) / (F(1.0) - c).astype(F)).astype(F)
+        v = ((((n * ig).astype(F) + (b[None, :] * a[:, None]).astype(F)).astype(F)) * q[:, None]).astype(F)
+        d = _normalize(v)
+        D = (ig * q).astype(F)
+        D2 = (D * D).astype(F)
+        B = (D2 * D2).astype(F)
+    out[live, 4:7] = d[live]
+    beam[live] = B[live]
+    return out, beam

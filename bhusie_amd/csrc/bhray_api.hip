@@ -27,6 +27,7 @@
 #include "bhray_skyfilter.h"
 #include "bhray_stars.h"
 #include "bhray_accum_stars.h"
+#include "bhray_observer.h"
 
 using namespace bhray;
 
@@ -243,6 +244,8 @@ struct bhray_dev {
     bhray_still_filter a_filter{(uint32_t)sizeof(bhray_still_filter), BHRAY_FILTER_BOX, 2.0f, 1.0f / 3.0f, 1.0f / 3.0f};
     // point stars in stills (dev_accum_set_stars): read by every dev_accum_add at the time of the call; acts only while a catalogue is in force (stars)
     bool a_stars = false;
+    // the moving observer (dev_accum_set_observer): read like a_cam; an all-zero velocity is "no observer"
+    bhray_observer a_obs{(uint32_t)sizeof(bhray_observer), {0.0f, 0.0f, 0.0f}, 1u};
     bhray::ReadRing reads;                 // tickets of the asynchronous hand-off (dev_read_async)
     std::string err;
 };
@@ -1582,7 +1585,10 @@ int dev_accum_add(bhray_dev* c, uint32_t samples) {
     accum_gen_args(c, g);
     const bool still = !still_camera_is_default(c->a_cam);        // another projection or a lens: bhray_stillcam.hip's generator in accum_gen_kernel's place
     StillGen sg;
-    if (still) still_gen_fill(sg, c->cfg, c->cam, c->a_cam);
+    const bool moving = !observer_at_rest(c->a_obs);              // an observer in force: bhray_observer.hip's generator, through still_gen_fill of whichever camera
+    ObserverDev ob{};
+    if (moving) observer_fill(ob, c->a_obs);
+    if (moving || still) still_gen_fill(sg, c->cfg, c->cam, c->a_cam);
     const bool filtered = c->a_filter.kind != BHRAY_FILTER_BOX;   // a tent or a cubic: bhray_accum_filter.hip's stencil in accum_add_kernel's place
     AccumFilter af;
     if (filtered) accum_filter_fill(af, c->a_filter);
@@ -1595,14 +1601,16 @@ int dev_accum_add(bhray_dev* c, uint32_t samples) {
     for (uint32_t left = samples; left != 0;) {                   // in stream order: launch i + 1 rewrites the staging behind launch i's add
         const uint32_t k = std::min(left, kmax);
         g.s0 = c->a_samples; g.k = k;
-        if (still) { sg.a.s0 = g.s0; sg.a.k = k; HIPCHK(c, launch_still_gen(sg, c->a_rays, c->q_stream)); }
+        if (moving) { sg.a.s0 = g.s0; sg.a.k = k; HIPCHK(c, launch_observer_gen(sg, ob, c->a_rays, c->q_stream)); }
+        else if (still) { sg.a.s0 = g.s0; sg.a.k = k; HIPCHK(c, launch_still_gen(sg, c->a_rays, c->q_stream)); }
         else HIPCHK(c, launch_accum_gen(g, c->a_rays, c->q_stream));
         { int rc = enqueue_rays(c, c->a_rays, k * g.npix, c->a_res); if (rc) return rc; }
-        const float4* res = c->a_res;
+        float4* res = c->a_res;
         if (starred) {                                            // the starred images T go where the launch's records were: dead in stream order until the next generator
             HIPCHK(c, launch_accum_stars(c->stars, sky, c->a_res, c->a_rays, c->cfg.frame_w, c->cfg.frame_h, k, star_wrap, c->q_stream));
             res = c->a_rays;
         }
+        if (moving && c->a_obs.beaming == 1u) HIPCHK(c, launch_observer_beam(sg, ob, sky, res, c->q_stream));   // D^4 onto whichever buffer the add reads
         if (filtered) HIPCHK(c, launch_accum_filter_add(sky, af, res, c->a_sum, c->cfg.frame_w, c->cfg.frame_h, g.s0, k, c->q_stream));
         else HIPCHK(c, launch_accum_add(sky, res, c->a_sum, g.npix, k, c->q_stream));
         c->a_samples += k; left -= k;
@@ -1653,17 +1661,19 @@ int adaptive_select(bhray_dev* c, const bhray_accum_adaptive& a, uint32_t& n, ui
 }
 
 // `count` more samples for the n listed pixels (list == nullptr: every pixel), in chunks of launch_rays / n sub-samples: gen, trace, add; the last add advances issued
-// (sg != nullptr: the still camera's list generator in adapt_gen_kernel's place)
-int adaptive_round(bhray_dev* c, AccumGen& g, StillGen* sg, const TexDev& sky, const uint32_t* list, uint32_t n, uint32_t count) {
+// (sg != nullptr: the still camera's list generator in adapt_gen_kernel's place; ob != nullptr, then with sg: the observer's, and its beam stage when `beam`)
+int adaptive_round(bhray_dev* c, AccumGen& g, StillGen* sg, const ObserverDev* ob, bool beam, const TexDev& sky, const uint32_t* list, uint32_t n, uint32_t count) {
     const uint32_t launch_rays = c->a_launch_rays ? c->a_launch_rays : ACCUM_LAUNCH_RAYS;
     const uint32_t kmax = std::max<uint32_t>(1u, launch_rays / n);
     { int rc = accum_staging(c, (size_t)std::min(count, kmax) * n); if (rc) return rc; }
     for (uint32_t j0 = 0; j0 < count;) {                          // in stream order: chunk i + 1 rewrites the staging behind chunk i's add
         const uint32_t k = std::min(count - j0, kmax);
         g.k = k;
-        if (sg) { sg->a.k = k; HIPCHK(c, launch_still_gen_list(*sg, list, n, j0, c->a_state, c->a_rays, c->q_stream)); }
+        if (ob) { sg->a.k = k; HIPCHK(c, launch_observer_gen_list(*sg, *ob, list, n, j0, c->a_state, c->a_rays, c->q_stream)); }
+        else if (sg) { sg->a.k = k; HIPCHK(c, launch_still_gen_list(*sg, list, n, j0, c->a_state, c->a_rays, c->q_stream)); }
         else HIPCHK(c, launch_adapt_gen(g, list, n, j0, c->a_state, c->a_rays, c->q_stream));
         { int rc = enqueue_rays(c, c->a_rays, k * n, c->a_res); if (rc) return rc; }
+        if (ob && beam) HIPCHK(c, launch_observer_beam_list(*sg, *ob, sky, list, n, j0, c->a_state, c->a_res, c->q_stream));   // before j0 moves: the generator's indices
         j0 += k;
         HIPCHK(c, launch_adapt_add(sky, c->a_res, list, n, k, j0 == count ? count : 0u, c->a_sum, c->a_state, c->q_stream));
     }
@@ -1692,11 +1702,16 @@ int dev_accum_add_adaptive(bhray_dev* c, const bhray_accum_adaptive* params, bhr
     accum_gen_args(c, g);
     StillGen sgen;
     StillGen* sg = nullptr;
-    if (!still_camera_is_default(c->a_cam)) { still_gen_fill(sgen, c->cfg, c->cam, c->a_cam); sg = &sgen; }
+    const bool moving = !observer_at_rest(c->a_obs);              // an observer in force: its generators, through still_gen_fill of whichever camera
+    if (moving || !still_camera_is_default(c->a_cam)) { still_gen_fill(sgen, c->cfg, c->cam, c->a_cam); sg = &sgen; }
+    ObserverDev obd{};
+    const ObserverDev* ob = nullptr;
+    if (moving) { observer_fill(obd, c->a_obs); ob = &obd; }
+    const bool beam = moving && c->a_obs.beaming == 1u;
     TexDev sky; sky.rgba = c->tex[BHRAY_TEX_SKY]; sky.w = c->tex_w[BHRAY_TEX_SKY]; sky.h = c->tex_h[BHRAY_TEX_SKY];
     bhray_accum_adaptive_info I{};
     if (c->a_mode == 0) {                                         // the first round: every pixel, no test
-        { int rc = adaptive_round(c, g, sg, sky, nullptr, g.npix, a.min_samples); if (rc) return rc; }
+        { int rc = adaptive_round(c, g, sg, ob, beam, sky, nullptr, g.npix, a.min_samples); if (rc) return rc; }
         c->a_mode = 2; c->a_min = a.min_samples; c->a_round = a.round_samples; c->a_samples = a.min_samples;
         I.rounds = 1; I.rays = (uint64_t)g.npix * a.min_samples;
     }
@@ -1705,7 +1720,7 @@ int dev_accum_add_adaptive(bhray_dev* c, const bhray_accum_adaptive* params, bhr
         { int rc = adaptive_select(c, a, n, top); if (rc) return rc; }
         I.active_last = n;
         if (n == 0) break;
-        { int rc = adaptive_round(c, g, sg, sky, c->a_list, n, a.round_samples); if (rc) return rc; }
+        { int rc = adaptive_round(c, g, sg, ob, beam, sky, c->a_list, n, a.round_samples); if (rc) return rc; }
         c->a_samples = std::max(c->a_samples, top + a.round_samples);
         I.rounds++; I.rays += (uint64_t)n * a.round_samples;
     }
@@ -1798,7 +1813,15 @@ int dev_accum_sample_rays(bhray_dev* c, uint32_t s, bhray_ray* out) {
     float4* d = nullptr;
     HIPCHK(c, hipMalloc(&d, (size_t)g.npix * sizeof(bhray_ray)));
     hipError_t e;
-    if (still_camera_is_default(c->a_cam)) e = launch_accum_gen(g, d, c->q_stream);
+    if (!observer_at_rest(c->a_obs)) {                            // the observer's generator
+        StillGen sg;
+        still_gen_fill(sg, c->cfg, c->cam, c->a_cam);
+        sg.a.s0 = s; sg.a.k = 1;
+        ObserverDev ob;
+        observer_fill(ob, c->a_obs);
+        e = launch_observer_gen(sg, ob, d, c->q_stream);
+    }
+    else if (still_camera_is_default(c->a_cam)) e = launch_accum_gen(g, d, c->q_stream);
     else {
         StillGen sg;
         still_gen_fill(sg, c->cfg, c->cam, c->a_cam);
@@ -1817,6 +1840,14 @@ int dev_accum_set_camera(bhray_dev* c, const bhray_still_camera* cam) {
     if (!c) return BHRAY_E_INVALID;
     if (const char* why = still_camera_error(cam)) return fail(c, BHRAY_E_INVALID, "bhray_accum_set_camera: %s", why);
     if (cam) c->a_cam = *cam; else bhray_still_camera_default(&c->a_cam);
+    return BHRAY_OK;
+}
+
+// validates and stores: no device call, no image touched (NULL: at rest)
+int dev_accum_set_observer(bhray_dev* c, const bhray_observer* obs) {
+    if (!c) return BHRAY_E_INVALID;
+    if (const char* why = observer_error(obs)) return fail(c, BHRAY_E_INVALID, "bhray_accum_set_observer: %s", why);
+    if (obs) c->a_obs = *obs; else bhray_observer_default(&c->a_obs);
     return BHRAY_OK;
 }
 

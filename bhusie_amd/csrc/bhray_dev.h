@@ -128,6 +128,7 @@ int  dev_accum_read_display(bhray_dev* c, uint8_t* dst_rgba8, size_t pitch, cons
 int  dev_accum_sample_rays(bhray_dev* c, uint32_t s, bhray_ray* out);   // the generated records of sample s: frame_w * frame_h
 int  dev_accum_set_launch_rays(bhray_dev* c, uint32_t max_rays);        // rays per trace launch of dev_accum_add; 0: the default
 int  dev_accum_set_camera(bhray_dev* c, const bhray_still_camera* cam); // still cameras: validates and stores; NULL: pinhole, no lens
+int  dev_accum_set_observer(bhray_dev* c, const bhray_observer* obs);   // the moving observer: validates and stores; NULL: at rest
 int  dev_accum_set_filter(bhray_dev* c, const bhray_still_filter* filter); // still pixel filters: validates and stores; NULL: the box
 int  dev_accum_set_stars(bhray_dev* c, int32_t on);        // point stars in stills: validates and stores; 0 (the default) or 1
 // adaptive stills: min_samples for every pixel, then rounds of select - wait for the count - sample the failing pixels, until a selection is empty; blocks

@@ -1703,6 +1703,12 @@ int bhray_accum_set_stars(bhray_ctx* c, int32_t on) {
     for (Part& p : c->parts) if (p.dev) DEV(c, p.dev, dev_accum_set_stars(p.dev, on));
     return BHRAY_OK;
 }
+// The moving observer: state of every local engine, accepted on any ctx - what cannot accumulate refuses bhray_accum_add as before.
+int bhray_accum_set_observer(bhray_ctx* c, const bhray_observer* obs) {
+    if (!c) return BHRAY_E_INVALID;
+    for (Part& p : c->parts) if (p.dev) DEV(c, p.dev, dev_accum_set_observer(p.dev, obs));
+    return BHRAY_OK;
+}
 int bhray_accum_set_launch_rays(bhray_ctx* c, uint32_t max_rays) {
     if (!c) return BHRAY_E_INVALID;
     ENTER(c);

@@ -93,7 +93,11 @@ OFF(bhray_star_params, struct_size, 0); OFF(bhray_star_params, gain, 4); OFF(bhr
 SZ(bhray_star_pixel_info, 32);
 OFF(bhray_star_pixel_info, state, 0); OFF(bhray_star_pixel_info, tested, 12); OFF(bhray_star_pixel_info, area, 24);
 static_assert(BHRAY_MAX_STARS == (1u << 22) && BHRAY_STARS_MAX_CELLS == 64u, "BHRAY_MAX_STARS / BHRAY_STARS_MAX_CELLS");
-static_assert(BHRAY_MAX_PATH_STRIDE_LOG2 == 16 && BHRAY_MAX_PATH_POINTS_PER_CALL == (1u << 24), "BHRAY_MAX_PATH_*");
+// the moving observer of bhray_accum_set_observer
+SZ(bhray_observer, 20);
+OFF(bhray_observer, struct_size, 0); OFF(bhray_observer, velocity, 4); OFF(bhray_observer, beaming, 16);
+static_assert(BHRAY_OBSERVER_MAX_SPEED2 == 0.9801f, "BHRAY_OBSERVER_MAX_SPEED2");
+static_assert(BHRAY_MAX_PATH_STRIDE_LOG2 == 16&& BHRAY_MAX_PATH_POINTS_PER_CALL == (1u << 24), "BHRAY_MAX_PATH_*");
 static_assert(BHRAY_HIT_NONE == 0 && BHRAY_HIT_HORIZON == 1 && BHRAY_HIT_DISK == 2 && BHRAY_HIT_MESH == 3 && BHRAY_HIT_UNUSABLE == 255, "BHRAY_HIT_*");
 
 // not reference layouts, but ABI the bindings restate (bhusie_amd/layouts.py)

@@ -1,7 +1,7 @@
 // bhray_render — minimal C++ host program over renderer.hpp: renders one frame of the reference's default scene
 // (camera (0,0,-19), hole at the origin, disk 2..10, R = 20; camera.rs:10-16, blackhole.rs:16-28) and writes the HDR frame
 // as raw little-endian f32 RGBA (row 0 = top).  Usage:
-//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--stars-seeded N SEED] [--pick X Y] [--path X Y [--path-stride S]]
+//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--stars-seeded N SEED] [--observer VX VY VZ [--no-beaming]] [--pick X Y] [--path X Y [--path-stride S]]
 // --spp N: instead of the ladder's frame, a supersampled still - the mean of N jittered samples per frame pixel, sky resolved, accumulated on the GPU
 //   (Renderer::render_still: bhray_accum_*); written the same way.  Not with --devices or --panorama.
 // --spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]: an adaptive still instead - every pixel takes MIN samples, then R more (4 by default) for as long as the
@@ -17,6 +17,9 @@
 //   scaled to half width RADIUS (1 <= RADIUS <= 2.5).
 // --stars-seeded N SEED (with --spp; not with --spp-adaptive or --lens): a seeded catalogue of N point stars (bhusie::star_catalogue, 1 <= N <= BHRAY_MAX_STARS) lensed into
 //   every sample's image of the still (bhray_set_stars + bhray_accum_set_stars): pixel-sharp stars at sub-pixel accuracy, --filter their point spread function.
+// --observer VX VY VZ [--no-beaming] (with --spp or --spp-adaptive): the still as an observer moving with velocity (VX, VY, VZ) sees it - static frame, world axes, units
+//   of c, at most 0.99 - (bhray_accum_set_observer): every look direction is Lorentz-aberrated on the GPU and every sample scaled by the bolometric D^4;
+//   --no-beaming keeps the aberration alone.  A zero velocity is no observer.
 // --path X Y [--path-stride S]: after the frame, the pick line of pixel (X, Y) and then the light path behind it, one line per point - that pixel's pinhole ray through
 //   bhray_trace_rays_paths (Renderer::ray_path), a point every 2^S iterations (S = 0 by default) and the end point:
 //   ITERATION X Y Z
@@ -177,13 +180,15 @@ int main(int argc, char** argv) {
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
         return 0;
     }
-    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--stars-seeded N SEED] [--pick X Y] [--path X Y [--path-stride S]]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--stars-seeded N SEED] [--observer VX VY VZ [--no-beaming]] [--pick X Y] [--path X Y [--path-stride S]]\n", argv[0]); return 2; }
     uint32_t bw = 72, bh = 41, levels = 4, disk = 256, pano_w = 0, pano_h = 0;
     long pick_x = -1, pick_y = -1, path_x = -1, path_y = -1, path_stride = 0, spp = 0;
     bool rk = false, bvh_device = false, lensed = false, posed = false, adaptive = false;
     long a_min = 0, a_max = 0, a_round = 4, stars_n = 0, stars_seed = 0;
     double a_tol = 0.0, a_dark = 0.01;
-    bool still_given = false, lens_given = false, filter_given = false;
+    bool still_given = false, lens_given = false, filter_given = false, observer_given = false, no_beaming = false;
+    bhray_observer observer{};
+    bhray_observer_default(&observer);
     bhray_still_filter filter{};
     bhray_still_filter_default(&filter);
     bhray_still_camera still{};
@@ -249,6 +254,15 @@ int main(int argc, char** argv) {
             stars_n = std::strtol(argv[++i], &e1, 10); stars_seed = std::strtol(argv[++i], &e2, 10);
             if (*e1 || *e2 || stars_n < 1 || stars_n > (long)BHRAY_MAX_STARS || stars_seed < 0) { std::fprintf(stderr, "--stars-seeded needs 1 <= N <= %u and SEED >= 0\n", BHRAY_MAX_STARS); return 2; }
         }
+        else if (!std::strcmp(argv[i], "--observer") && i + 3 < argc) {
+            observer_given = true;
+            for (int a = 0; a < 3; a++) observer.velocity[a] = (float)std::atof(argv[++i]);
+            const float* v = observer.velocity;
+            if (!std::isfinite(v[0]) || !std::isfinite(v[1]) || !std::isfinite(v[2]) || (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2] > BHRAY_OBSERVER_MAX_SPEED2) {
+                std::fprintf(stderr, "--observer needs a finite velocity of at most 0.99 (units of c)\n"); return 2;
+            }
+        }
+        else if (!std::strcmp(argv[i], "--no-beaming")) no_beaming = true;
         else if (!std::strcmp(argv[i], "--pick") && i + 2 < argc) { pick_x = std::atol(argv[++i]); pick_y = std::atol(argv[++i]); if (pick_x < 0 || pick_y < 0) { std::fprintf(stderr, "--pick needs X >= 0 and Y >= 0\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--path") && i + 2 < argc) { path_x = std::atol(argv[++i]); path_y = std::atol(argv[++i]); if (path_x < 0 || path_y < 0) { std::fprintf(stderr, "--path needs X >= 0 and Y >= 0\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--path-stride") && i + 1 < argc) { path_stride = std::atol(argv[++i]); if (path_stride < 0 || path_stride > BHRAY_MAX_PATH_STRIDE_LOG2) { std::fprintf(stderr, "--path-stride needs 0 <= S <= %d\n", BHRAY_MAX_PATH_STRIDE_LOG2); return 2; } }
@@ -264,6 +278,8 @@ int main(int argc, char** argv) {
     if (stars_n && adaptive) { std::fprintf(stderr, "--stars-seeded lights a pixel from sample s of its neighbours: not with --spp-adaptive, whose pixels take different samples\n"); return 2; }
     if (stars_n && lens_given) { std::fprintf(stderr, "--stars-seeded needs footprints: not with --lens, whose neighbouring pixels look through different lens points\n"); return 2; }
     if (stars_n && !spp) { std::fprintf(stderr, "--stars-seeded in this mode is the star field of a still: give --spp\n"); return 2; }
+    if (observer_given && !spp && !adaptive) { std::fprintf(stderr, "--observer is the observer of a still: give --spp or --spp-adaptive\n"); return 2; }
+    if (no_beaming && !observer_given) { std::fprintf(stderr, "--no-beaming goes with --observer\n"); return 2; }
     if (lens_given && still.projection != BHRAY_STILL_PINHOLE) { std::fprintf(stderr, "--lens goes with the pinhole projection only\n"); return 2; }
     if (spp && pano_w) { std::fprintf(stderr, "--spp samples the pixels of the pinhole frame: not with --panorama\n"); return 2; }
     if (path_x >= 0 && pano_w) { std::fprintf(stderr, "--path names a pixel of the pinhole frame: not with --panorama\n"); return 2; }
@@ -290,6 +306,7 @@ int main(int argc, char** argv) {
         r.ray_details.integration_method = rk ? 1 : 0;
         r.mesh_lensing = lensed;
         r.lens_ray_batches = lensed && (spp || adaptive || pano_w || pick_x >= 0);        // the stills, the panorama and the pick trace ray batches: lensed too (BHRAY_LENS_RAYS)
+        if (observer_given) { observer.beaming = no_beaming ? 0u : 1u; r.observer = observer; }
         std::vector<float> out;
         std::vector<uint32_t> counts;
         bhray_accum_adaptive_info ainfo{};

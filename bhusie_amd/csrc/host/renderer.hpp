@@ -282,6 +282,12 @@ public:
     // point stars in stills (bhray_accum_set_stars): with on and a catalogue in force (set_stars), every sample image of accumulate() receives the
     // catalogue's stars before it is summed, from the next call on.  accumulate() under a lens and accumulate_adaptive() are then refused.
     void set_still_stars(bool on) { check(bhray_accum_set_stars(ctx_, on ? 1 : 0), ctx_); }
+    // the moving observer of a still (bhray_accum_set_observer): every look direction of accumulate() / accumulate_adaptive() aberrated by the velocity
+    // (static frame, world axes, units of c) and, with beaming, every sample scaled by D^4, from the next call on; a zero velocity: at rest.  struct_size is filled in here.
+    void set_still_observer(bhray_observer observer) {
+        observer.struct_size = (uint32_t)sizeof(bhray_observer);
+        check(bhray_accum_set_observer(ctx_, &observer), ctx_);
+    }
     bhray_ctx* ctx() { return ctx_; }
 private:
     bhray_config cfg_;
@@ -385,6 +391,7 @@ public:
     BlackHole black_hole;
     RayDetails ray_details;
     bool mesh_lensing = false;      // lensed meshes (bhray_set_mesh_lensing): models are tested inside the relativity sphere too; applied before each render
+    bhray_observer observer{(uint32_t)sizeof(bhray_observer), {0.0f, 0.0f, 0.0f}, 1u};   // the moving observer of the stills; zero velocity: at rest; applied before each still
     bool lens_ray_batches = false;  // ... and, with it, in ray batches too (BHRAY_LENS_RAYS): render_rays, pick and the stills trace lensed; ray_path throws the ctx's error
     explicit Renderer(int device = 0) : ray_pipeline_({72, 41}, 3, 4, device) {}               // mod.rs:177-179
     Renderer(std::pair<uint32_t, uint32_t> base, uint32_t multiplier, uint32_t levels, int device = 0) : ray_pipeline_(base, multiplier, levels, device) {}
@@ -441,6 +448,7 @@ public:
         ray_pipeline_.set_still_camera(still_camera);
         ray_pipeline_.set_still_filter(still_filter);
         ray_pipeline_.set_still_stars(stars);
+        ray_pipeline_.set_still_observer(observer);
         return ray_pipeline_.accumulate(samples);
     }
     // an adaptive still of the current scene (RayPipeline::accumulate_adaptive): params.struct_size is filled in here
@@ -452,6 +460,7 @@ public:
         ray_pipeline_.set_still_camera(still_camera);
         ray_pipeline_.set_still_filter(nullptr);                  // an adaptive still has no filter but the box
         ray_pipeline_.set_still_stars(false);                     // and no point stars
+        ray_pipeline_.set_still_observer(observer);
         return ray_pipeline_.accumulate_adaptive(params, info, counts);
     }
     // what is under frame pixel (x, y): the record of that pixel's pinhole ray under the current scene (hit & 0xff: BHRAY_HIT_*; (hit >> 8) & 0xff: the model slot of a mesh hit)

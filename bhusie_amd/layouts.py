@@ -126,6 +126,14 @@ class BhrayStillFilter(C.Structure):        # bhray_still_filter: the accumulati
 
 assert C.sizeof(BhrayStillFilter) == 20 and BhrayStillFilter.c.offset == 16
 
+
+class BhrayObserver(C.Structure):           # bhray_observer: the moving observer of a still (bhray_accum_set_observer)
+    _fields_ = [("struct_size", C.c_uint32), ("velocity", C.c_float * 3), ("beaming", C.c_uint32)]
+
+
+assert C.sizeof(BhrayObserver) == 20 and BhrayObserver.beaming.offset == 16
+OBSERVER_MAX_SPEED2 = 0.9801                # BHRAY_OBSERVER_MAX_SPEED2
+
 MAX_STARS, STARS_MAX_CELLS = 1 << 22, 64                    # BHRAY_MAX_STARS, BHRAY_STARS_MAX_CELLS
 
 
@@ -335,6 +343,9 @@ SYMBOLS = {
     "bhray_stars_resolve_host": (C.c_int, [vp, u32, u32, vp, u32, P(BhrayStarParams), vp]),
     "bhray_accum_set_stars": (C.c_int, [vp, i32]),
     "bhray_accum_stars_resolve_host": (C.c_int, [vp, u32, u32, i32, vp, u32, P(BhrayStarParams), vp]),
+    "bhray_accum_set_observer": (C.c_int, [vp, P(BhrayObserver)]),
+    "bhray_observer_default": (None, [P(BhrayObserver)]),
+    "bhray_observer_boost_rays": (C.c_int, [P(BhrayObserver), vp, u32, vp, vp]),
     "bhray_post_defaults": (C.c_int, [P(BhrayFxaaDetails), P(BhrayMixDetails)]),
     "bhray_bloom_sizes": (C.c_int, [u32, u32, P(u32), P(u32)]),
     "bhray_set_post_uniforms": (C.c_int, [vp, vp, vp]),
@@ -383,6 +394,7 @@ DIAG_SYMBOLS = {
     "bhray_accum_sample_rays": (C.c_int, [vp, u32, P(BhrayRay)]),
     "bhray_accum_set_launch_rays": (C.c_int, [vp, u32]),
     "bhray_still_sample_rays_host": (C.c_int, [P(BhrayConfig), vp, P(BhrayStillCamera), u32, P(BhrayRay)]),
+    "bhray_observer_sample_rays_host": (C.c_int, [P(BhrayConfig), vp, P(BhrayStillCamera), P(BhrayObserver), u32, vp, vp]),
     "bhray_accum_active_pixels": (C.c_int, [vp, P(BhrayAccumAdaptive), P(u32), u32, P(u32)]),
     "bhray_read_sky_pyramid_level": (C.c_int, [vp, u32, vp, sz]),
     "bhray_diag_display_image": (C.c_int, [C.c_int, vp, u32, u32, vp, vp, u32, vp, vp, sz]),

@@ -576,7 +576,8 @@ class RayPass:
         return out
 
     def accum_sample_rays(self, s: int) -> np.ndarray:
-        """The records the device generates for sample s under the current uniforms: (frame_h * frame_w, 8) float32 (bhray_diag.h)."""
+        """The records the device generates for sample s under the current uniforms, the still camera and the observer in force: (frame_h * frame_w, 8) float32
+        (bhray_diag.h)."""
         out = np.empty((int(self.cfg.frame_w) * int(self.cfg.frame_h), 8), dtype=np.float32)
         check(self._L.bhray_accum_sample_rays(self._h, int(s), out.ctypes.data_as(C.POINTER(BhrayRay))), self._h, self._L)
         return out
@@ -606,6 +607,19 @@ class RayPass:
         sub-pixel accuracy and a filter of accum_set_filter is its point spread function.  Off (the default), or without a catalogue, every image keeps its bits.
         accum_add under a lens and accum_add_adaptive are then refused (BHRAY_E_STATE).  Validates and stores only."""
         check(self._L.bhray_accum_set_stars(self._h, int(on)), self._h, self._L)
+
+    def accum_set_observer(self, velocity=None, beaming=True):
+        """The moving observer of the accumulation image from the next accum_add / accum_add_adaptive on (bhray_accum_set_observer): `velocity` is
+        beta, the observer's velocity in the static frame, world axes, units of c (|beta| <= 0.99) - or a cameras.Observer, whose own `beaming` then holds.  Every
+        generated look direction is Lorentz-aberrated on the device; beaming: every resolved sample is also scaled by the bolometric D^4.  None, or a zero velocity:
+        at rest - every image keeps its bits.  Validates and stores only; an observer the library refuses: BhrayError (BHRAY_E_INVALID)."""
+        from .cameras import Observer
+        if velocity is None:
+            check(self._L.bhray_accum_set_observer(self._h, None), self._h, self._L)
+            return
+        obs = velocity if isinstance(velocity, Observer) else Observer(tuple(float(v) for v in velocity), bool(beaming))
+        s = obs.struct()
+        check(self._L.bhray_accum_set_observer(self._h, C.byref(s)), self._h, self._L)
 
     # -- adaptive stills: each pixel sampled until the error of its mean is under a bound (bhray_accum_add_adaptive, DESIGN.md §20)
     @staticmethod
@@ -1045,7 +1059,7 @@ class Renderer:
                 "closest": float(r["closest"]), "transmittance": float(r["transmittance"]),
                 "path": pts["position"][0, :k].copy(), "path_iterations": pts["iteration"][0, :k].copy()}
 
-    def _accumulate(self, samples: int, shutter: float, camera=None, filter=None, stars=False):
+    def _accumulate(self, samples: int, shutter: float, camera=None, filter=None, stars=False, observer=None):
         samples = int(samples)
         if samples < 1:
             raise ValueError(f"render_still: samples must be at least 1, got {samples}")
@@ -1053,6 +1067,7 @@ class Renderer:
         self.ray_pass.accum_set_camera(camera)
         self.ray_pass.accum_set_filter(filter)
         self.ray_pass.accum_set_stars(bool(stars))
+        self.ray_pass.accum_set_observer(observer)
         self.ray_pass.accum_begin()
         if not shutter > 0.0:
             self.ray_pass.accum_add(samples)
@@ -1066,7 +1081,8 @@ class Renderer:
         finally:
             self.ray_details.time = t0
 
-    def render_still(self, samples: int = 16, shutter: float = 0.0, adaptive: AdaptiveStill | None = None, camera=None, filter=None, stars: bool = False) -> np.ndarray:
+    def render_still(self, samples: int = 16, shutter: float = 0.0, adaptive: AdaptiveStill | None = None, camera=None, filter=None, stars: bool = False,
+                     observer=None) -> np.ndarray:
         """A supersampled still of the current scene (RayPass.accum_*): the mean of `samples` jittered samples per frame pixel, sky resolved,
         (frame_h, frame_w, 4) float32.  Sample 0 is the pixel centre, so samples=1 is the frame a `levels = 1` ladder renders, after the sky pass in binary32.
         shutter > 0: motion blur - sample s is rendered at ray_details.time + shutter * s / samples (the disk turns with `time`); ray_details.time is left as it was.
@@ -1079,9 +1095,12 @@ class Renderer:
         with `adaptive` (ValueError).  The ctx keeps the filter of the last still.
         stars: the catalogue of set_stars lensed into every sample's image: pixel-sharp stars at sub-pixel accuracy, with `filter` as their point
         spread function.  Without a catalogue it changes nothing.  Not with `adaptive` (ValueError) or a camera with a lens (BhrayError).  The ctx keeps the
-        switch of the last still."""
+        switch of the last still.
+        observer: a cameras.Observer - the still as a moving observer sees it: Observer((vx, vy, vz)) aberrates every look direction by the
+        velocity (static frame, world axes, units of c), and with beaming (the default) scales every sample by D^4; goes with `adaptive`, every camera, the filters and
+        the stars.  None: at rest.  The ctx keeps the observer of the last still."""
         if adaptive is None:
-            self._accumulate(samples, shutter, camera, filter, stars)
+            self._accumulate(samples, shutter, camera, filter, stars, observer)
             return self.ray_pass.accum_read()
         if stars:
             raise ValueError("render_still: an adaptive still has no point stars (a round's pixels take different samples)")
@@ -1093,6 +1112,7 @@ class Renderer:
         self.ray_pass.accum_set_camera(camera)
         self.ray_pass.accum_set_filter(None)
         self.ray_pass.accum_set_stars(False)
+        self.ray_pass.accum_set_observer(observer)
         self.ray_pass.accum_begin()
         self.still_info = self.ray_pass.accum_add_adaptive(**adaptive.as_kwargs())
         return self.ray_pass.accum_read()
@@ -1101,11 +1121,11 @@ class Renderer:
         """The sample-count heat map of the last adaptive still: (frame_h, frame_w) uint32."""
         return self.ray_pass.accum_read_counts()
 
-    def save_still(self, path, samples: int = 16, camera=None, filter=None, stars: bool = False):
-        """save_image for a supersampled still: the mean of `samples` samples per pixel through the display pass, written with alpha 255.  camera, filter, stars: as
-        render_still's."""
+    def save_still(self, path, samples: int = 16, camera=None, filter=None, stars: bool = False, observer=None):
+        """save_image for a supersampled still: the mean of `samples` samples per pixel through the display pass, written with alpha 255.  camera, filter, stars,
+        observer: as render_still's."""
         from PIL import Image
-        self._accumulate(samples, 0.0, camera, filter, stars)
+        self._accumulate(samples, 0.0, camera, filter, stars, observer)
         img = self.ray_pass.accum_read_display()
         img[..., 3] = 255
         Image.fromarray(img, "RGBA").save(path)

@@ -955,6 +955,55 @@ int  bhray_accum_set_stars(bhray_ctx* ctx, int32_t on);
 int  bhray_accum_stars_resolve_host(const float* results_rgba32f, uint32_t w, uint32_t h, int32_t wrap_x, const bhray_star* stars,
                                     uint32_t n, const bhray_star_params* params, float* add_rgba32f);
 
+/* Moving observer for stills: Lorentz aberration of every generated look direction and, optionally, the bolometric
+ * Doppler beam D^4 of every resolved sample.  Every camera above is at rest relative to the hole; the observer gives the still camera a
+ * velocity.  It acts before the trace and behind it, never in it.
+ *
+ * Per-ctx state like bhray_accum_set_camera: bhray_accum_set_observer only validates and stores, needs no device, touches no image and
+ * is accepted in every state, multi-device ctxs included (the refusals of bhray_accum_add stay on bhray_accum_add); each bhray_accum_add
+ * / bhray_accum_add_adaptive reads it at the time of the call.  NULL: at rest.  BHRAY_E_INVALID, the observer in force untouched: a
+ * struct_size other than sizeof(bhray_observer); a velocity component that is not finite; bb > BHRAY_OBSERVER_MAX_SPEED2 (bb below);
+ * beaming > 1.  An all-zero velocity means no observer, exactly as NULL does, whatever `beaming` says: the generators of the still camera
+ * run as without this call, no stage is launched, every image keeps its bits (the rule below renormalises, so at beta = 0 it would still
+ * move last bits).  bhray_observer_default fills in zero velocity and beaming 1.  The observer plays no part in frames (bhray_render)
+ * or in bhray_trace_rays*: their callers boost their own ray lists with bhray_observer_boost_rays.
+ *
+ * The rule, binary32, one rounded operation at a time in the order written, no FMA; 1 / x and sqrt are IEEE.  Once per call, with
+ * b = velocity:  bb = (bx*bx + by*by) + bz*bz;  ig = sqrtf(1 - bb);  g = 1 / ig;  k = g / (g + 1).
+ * Per record: (origin, n') is the record of sample s of the pixel under the still camera in force (above), every projection and the thin
+ * lens included; n' is the look direction in the observer's rest frame.  An all-zero n' (outside a fisheye's circle) passes unchanged
+ * with beam 1.  Otherwise
+ *     c  = (bx*n'x + by*n'y) + bz*n'z
+ *     a  = k*c - 1
+ *     q  = 1 / (1 - c)
+ *     v  = ((n' * ig) + (b * a)) * q                 per component
+ *     n  = v * (1 / sqrtf((vx*vx + vy*vy) + vz*vz))
+ *     D  = ig * q                                     nu_observed / nu_static = 1 / (gamma (1 - b.n'))
+ *     D2 = D*D ; beam = D2*D2
+ * and the record is (origin, n): the exact aberration n = (n'/gamma + b (gamma/(gamma+1) b.n' - 1)) / (1 - b.n') of a look direction.
+ * The origin is unchanged.  Known property: under a thin lens the lens offsets are rest-frame lengths used as they are.
+ *
+ * Beaming (beaming == 1) is one more stage of a launch, behind the star stage of bhray_accum_set_stars if that runs and before the add
+ * (box, filter or adaptive).  For every record r of the launch, B = the beam of that record (the same function, the same bits as the
+ * generator's).  In place, v = img[r]: if v.w == 0.0f, v = the accumulation's resolve of v (binary32 sky^4, alpha 1); v.x = v.x*B,
+ * v.y = v.y*B, v.z = v.z*B; v.w is kept.  A record whose rest-frame direction is all zero is not touched.  A NaN or infinite colour
+ * stays so and is skipped downstream as before.  sum.w, the mean, the adaptive test (which sees beamed values), both reads and the
+ * display read are unchanged.  The star stage sees static-frame escape directions, so footprints and fluxes stay as specified above, and
+ * D^4 is the factor of their surface brightness too.  Every existing refusal holds, stars under a lens included; none is added.
+ *
+ * bhray_observer_boost_rays is host arithmetic, no device: out[i] = in[i] with its direction, given in the observer's rest frame, put
+ * through the per-record rule (an all-zero direction, a NULL observer or a zero velocity: unchanged, beam 1); out may be in; out_beam may
+ * be NULL.  BHRAY_E_INVALID: an observer the setter refuses, or n > 0 with a NULL in or out.                                          */
+typedef struct bhray_observer {
+    uint32_t struct_size;   /* = sizeof(bhray_observer) */
+    float    velocity[3];   /* beta: the observer's velocity in the static frame, world axes, units of c */
+    uint32_t beaming;       /* 0: aberration only; 1: also scale every sample by D^4 (bolometric) */
+} bhray_observer;           /* 20 B */
+#define BHRAY_OBSERVER_MAX_SPEED2 0.9801f   /* |beta| <= 0.99 */
+int  bhray_accum_set_observer(bhray_ctx* ctx, const bhray_observer* obs);   /* NULL = at rest */
+void bhray_observer_default(bhray_observer* obs);                           /* zero velocity, beaming 1 */
+int  bhray_observer_boost_rays(const bhray_observer* obs, const bhray_ray* in, uint32_t n, bhray_ray* out, float* out_beam /* may be NULL */);
+
 /* Display pass — the rest of the reference's GPU frame after the sky pass (mod.rs:209-324, run at 425-431): 5 bloom-down and
  * 5 bloom-up passes (bloom_down.wgsl, bloom_up.wgsl), mix (mix.wgsl), ACES tone mapping (hdr.wgsl) and FXAA (fxaa.wgsl) into the
  * Rgba8UnormSrgb target the reference's `Save Image` copies out (texture_to_output_buffer, mod.rs:491-526): frame_w x frame_h x 4

@@ -172,10 +172,17 @@ int bhray_read_model_vertices(bhray_ctx* ctx, uint32_t model_index, float* point
  * The accumulation image (bhray_accum_*)
  * ---------------------------------------------------------------------------------------- */
 /* The records the generator kernel writes for sample s under the current uniforms and the still camera in force
- * (bhray_accum_set_camera): frame_w * frame_h of them, row 0 the top, x fastest.  Needs no bhray_accum_begin; s >=
- * BHRAY_ACCUM_MAX_SAMPLES or a NULL out: BHRAY_E_INVALID; the refused states of bhray_accum_add apart from mesh lensing
- * (the generator does not trace).  Waits.                                                                             */
+ * (bhray_accum_set_camera): frame_w * frame_h of them, row 0 the top, x fastest.  With an observer in force
+ * (bhray_accum_set_observer, a velocity other than zero) they are the boosted records the observer's generator writes;
+ * without one they are unchanged.  Needs no bhray_accum_begin; s >= BHRAY_ACCUM_MAX_SAMPLES or a NULL out:
+ * BHRAY_E_INVALID; the refused states of bhray_accum_add apart from mesh lensing (the generator does not trace).  Waits. */
 int bhray_accum_sample_rays(bhray_ctx* ctx, uint32_t s, bhray_ray* out);
+/* bhray_still_sample_rays_host (below) under an observer: the function the observer's kernels call,
+ * compiled for the host - the boosted records into out_rays and each record's beam D^4 into out_beam (may be NULL).
+ * observer NULL or of zero velocity: the still camera's records, beam 1.  Needs no ctx and no device.  BHRAY_E_INVALID:
+ * what bhray_still_sample_rays_host refuses, or an observer that bhray_accum_set_observer refuses.                    */
+int bhray_observer_sample_rays_host(const bhray_config* cfg, const void* camera_uniform_32, const bhray_still_camera* camera, const bhray_observer* observer, uint32_t s,
+                                    bhray_ray* out_rays, float* out_beam);
 /* The same records by host arithmetic: the function the still-camera kernels call, compiled for the
  * host, over the frame of `cfg`, the 32 bytes of a bhray_camera_uniform and `camera` (NULL: the default; then the
  * records are those of the pinhole generator).  Needs no ctx and no device.  BHRAY_E_INVALID: a NULL cfg, uniform or
