@@ -18,6 +18,7 @@
 
 #include "bhray_accum.h"
 #include "bhray_accum_filter.h"
+#include "bhray_accum_passes.h"
 #include "bhray_adapt.h"
 #include "bhray_stillcam.h"
 #include "bhray_bvh_core.h"
@@ -230,6 +231,12 @@ struct bhray_dev {
     float4* a_rays = nullptr; float4* a_res = nullptr;       // one launch's generated records (2 float4 each) and results: grow-only (the stream is idle when they grow)
     size_t a_cap = 0;                      // rays that staging holds
     uint32_t a_samples = 0;                // sample indices enqueued since the last begin: the next add starts there
+    // still passes (dev_accum_set_passes): nothing below is allocated while every accumulation's set is 0
+    uint32_t a_passes_next = 0;            // the stored set: dev_accum_begin copies it
+    uint32_t a_passes = 0;                 // the set of the current accumulation (0 before the first begin)
+    float4* a_pass[ACCUM_PASS_COUNT] = {}; // one sum plane per pass, frame_w * frame_h: allocated by the first begin that carries the pass
+    float4* a_rec = nullptr; size_t a_rec_cap = 0;           // one launch's ray records (2 float4 each), beside a_rays / a_res: grow-only
+    float4* a_pimg = nullptr; size_t a_pimg_cap = 0;         // one pass's sample images of a launch under a tent or a cubic: grow-only
     uint32_t a_launch_rays = 0;            // dev_accum_set_launch_rays: rays per trace launch (0: BHRAY_ACCUM_LAUNCH_RAYS)
     bool a_begun = false;
     // adaptive stills (dev_accum_add_adaptive): allocated by the first adaptive call or selection; everything runs on q_stream
@@ -511,7 +518,8 @@ void dev_destroy(bhray_dev* c) {
     if (c->q_dpts) (void)hipFree(c->q_dpts);
     if (c->q_hcnt) (void)hipHostFree(c->q_hcnt);
     if (c->q_dcnt) (void)hipFree(c->q_dcnt);
-    for (void* p : {(void*)c->a_sum, (void*)c->a_mean, (void*)c->a_mean16, (void*)c->a_scratch, (void*)c->a_disp, (void*)c->a_rays, (void*)c->a_res, (void*)c->a_state, (void*)c->a_list, (void*)c->a_ctl}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)c->a_sum, (void*)c->a_mean, (void*)c->a_mean16, (void*)c->a_scratch, (void*)c->a_disp, (void*)c->a_rays, (void*)c->a_res, (void*)c->a_state, (void*)c->a_list, (void*)c->a_ctl, (void*)c->a_rec, (void*)c->a_pimg,
+                    (void*)c->a_pass[0], (void*)c->a_pass[1], (void*)c->a_pass[2], (void*)c->a_pass[3]}) if (p) (void)hipFree(p);
     if (c->a_hctl) (void)hipHostFree(c->a_hctl);
     for (hipEvent_t e : {c->q_begin, c->q_done, c->q_uploaded}) if (e) (void)hipEventDestroy(e);
     if (c->q_stream) (void)hipStreamDestroy(c->q_stream);
@@ -1546,6 +1554,25 @@ int accum_staging(bhray_dev* c, size_t need) {
     c->a_cap = need;
     return BHRAY_OK;
 }
+
+// still passes: a_rec holds `need` records and, under a tent or a cubic, a_pimg `need` texels: grow-only, behind a wait for the stream
+int accum_pass_staging(bhray_dev* c, size_t need, bool filtered) {
+    if (need > c->a_rec_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->q_stream));
+        if (c->a_rec) (void)hipFree(c->a_rec);
+        c->a_rec = nullptr; c->a_rec_cap = 0;
+        HIPCHK(c, hipMalloc(&c->a_rec, need * sizeof(bhray_ray_record)));
+        c->a_rec_cap = need;
+    }
+    if (filtered && need > c->a_pimg_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->q_stream));
+        if (c->a_pimg) (void)hipFree(c->a_pimg);
+        c->a_pimg = nullptr; c->a_pimg_cap = 0;
+        HIPCHK(c, hipMalloc(&c->a_pimg, need * sizeof(float4)));
+        c->a_pimg_cap = need;
+    }
+    return BHRAY_OK;
+}
 }  // namespace
 
 int dev_accum_begin(bhray_dev* c) {
@@ -1559,6 +1586,12 @@ int dev_accum_begin(bhray_dev* c) {
     if (!c->a_mean) HIPCHK(c, hipMalloc(&c->a_mean, npix * sizeof(float4)));
     HIPCHK(c, hipMemsetAsync(c->a_sum, 0, npix * sizeof(float4), c->q_stream));          // behind the samples of the accumulation before
     if (c->a_state) HIPCHK(c, hipMemsetAsync(c->a_state, 0, npix * sizeof(uint4), c->q_stream));
+    for (uint32_t b = 0; b < ACCUM_PASS_COUNT; b++) {             // still passes: the set is fixed here; one cleared plane per pass
+        if (!((c->a_passes_next >> b) & 1u)) continue;
+        if (!c->a_pass[b]) HIPCHK(c, hipMalloc(&c->a_pass[b], npix * sizeof(float4)));
+        HIPCHK(c, hipMemsetAsync(c->a_pass[b], 0, npix * sizeof(float4), c->q_stream));
+    }
+    c->a_passes = c->a_passes_next;
     c->a_samples = 0;
     c->a_mode = 0; c->a_min = c->a_round = 0;
     c->a_begun = true;
@@ -1595,6 +1628,10 @@ int dev_accum_add(bhray_dev* c, uint32_t samples) {
     const uint32_t launch_rays = c->a_launch_rays ? c->a_launch_rays : ACCUM_LAUNCH_RAYS;
     const uint32_t kmax = std::max<uint32_t>(1u, launch_rays / g.npix);                   // a small frame takes several samples per launch: the device stays filled
     { int rc = accum_staging(c, (size_t)std::min(samples, kmax) * g.npix); if (rc) return rc; }
+    const uint32_t passes = c->a_passes;                          // still passes: 0 - every launch below is the one it was
+    if (passes) { int rc = accum_pass_staging(c, (size_t)std::min(samples, kmax) * g.npix, filtered); if (rc) return rc; }
+    AccumPassPlanes planes;
+    for (uint32_t b = 0; b < ACCUM_PASS_COUNT; b++) planes.plane[b] = (passes >> b) & 1u ? c->a_pass[b] : nullptr;
     TexDev sky; sky.rgba = c->tex[BHRAY_TEX_SKY]; sky.w = c->tex_w[BHRAY_TEX_SKY]; sky.h = c->tex_h[BHRAY_TEX_SKY];
     // a whole 360 degree panorama is periodic in x (lon(x + lw) = lon(x) + 2 pi): its first and last columns are neighbours for the stars' footprints
     const int star_wrap = c->a_cam.projection == BHRAY_STILL_EQUIRECT && c->cfg.crop_x == 0 && c->cfg.frame_w == c->cfg.level_w[c->cfg.levels - 1];
@@ -1604,7 +1641,15 @@ int dev_accum_add(bhray_dev* c, uint32_t samples) {
         if (moving) { sg.a.s0 = g.s0; sg.a.k = k; HIPCHK(c, launch_observer_gen(sg, ob, c->a_rays, c->q_stream)); }
         else if (still) { sg.a.s0 = g.s0; sg.a.k = k; HIPCHK(c, launch_still_gen(sg, c->a_rays, c->q_stream)); }
         else HIPCHK(c, launch_accum_gen(g, c->a_rays, c->q_stream));
-        { int rc = enqueue_rays(c, c->a_rays, k * g.npix, c->a_res); if (rc) return rc; }
+        { int rc = enqueue_rays(c, c->a_rays, k * g.npix, c->a_res, passes ? (void*)c->a_rec : nullptr); if (rc) return rc; }
+        if (passes && !filtered) HIPCHK(c, launch_accum_passes_add(c->a_res, c->a_rec, c->a_rays, planes, passes, g.npix, k, c->q_stream));
+        else if (passes) {                                        // before the star stage: it overwrites the ray staging, whose directions the escape pass reads
+            for (uint32_t b = 0; b < ACCUM_PASS_COUNT; b++) {
+                if (!((passes >> b) & 1u)) continue;
+                HIPCHK(c, launch_accum_passes_form(c->a_res, c->a_rec, c->a_rays, 1u << b, c->a_pimg, (size_t)k * g.npix, c->q_stream));
+                HIPCHK(c, launch_accum_filter_add(sky, af, c->a_pimg, c->a_pass[b], c->cfg.frame_w, c->cfg.frame_h, g.s0, k, c->q_stream));
+            }
+        }
         float4* res = c->a_res;
         if (starred) {                                            // the starred images T go where the launch's records were: dead in stream order until the next generator
             HIPCHK(c, launch_accum_stars(c->stars, sky, c->a_res, c->a_rays, c->cfg.frame_w, c->cfg.frame_h, k, star_wrap, c->q_stream));
@@ -1687,6 +1732,8 @@ int dev_accum_add_adaptive(bhray_dev* c, const bhray_accum_adaptive* params, bhr
     { int rc = accum_refused(c, "bhray_accum_add_adaptive"); if (rc) return rc; }
     { int rc = rays_refused(c, "bhray_accum_add_adaptive"); if (rc) return rc; }
     if (c->a_mode == 1) return fail(c, BHRAY_E_STATE, "bhray_accum_add_adaptive: this accumulation holds bhray_accum_add's samples; bhray_accum_begin starts another");
+    if (c->a_passes) return fail(c, BHRAY_E_STATE, "bhray_accum_add_adaptive: this accumulation carries still passes (bhray_accum_set_passes): the adaptive adder works over a "
+                                                   "pixel list, and no list form of the passes is built");
     if (c->a_filter.kind != BHRAY_FILTER_BOX)
         return fail(c, BHRAY_E_STATE, "bhray_accum_add_adaptive: a still filter other than the box is in force (bhray_accum_set_filter): a round's pixels take different samples");
     if (c->a_stars && c->stars.stars)
@@ -1774,6 +1821,37 @@ int dev_accum_read(bhray_dev* c, float* dst, size_t pitch) {
     if (!dst || pitch < rowb) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, launch_accum_mean(c->a_sum, c->a_mean, nullptr, c->cfg.frame_w * c->cfg.frame_h, c->q_stream));
+    { int rc = query_wait(c); if (rc) return rc; }
+    HIPCHK(c, hipMemcpy2D(dst, pitch, c->a_mean, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost));
+    return BHRAY_OK;
+}
+
+// still passes: validates and stores - no device call; the next dev_accum_begin takes the set
+int dev_accum_set_passes(bhray_dev* c, uint32_t passes) {
+    if (!c) return BHRAY_E_INVALID;
+    if (passes & ~(uint32_t)BHRAY_PASS_ALL) return fail(c, BHRAY_E_INVALID, "bhray_accum_set_passes: unknown pass bits 0x%x", passes & ~(uint32_t)BHRAY_PASS_ALL);
+    c->a_passes_next = passes;
+    return BHRAY_OK;
+}
+
+int dev_accum_passes(const bhray_dev* c, uint32_t* passes) {
+    if (!c || !passes) return BHRAY_E_INVALID;
+    *passes = c->a_begun ? c->a_passes : 0u;
+    return BHRAY_OK;
+}
+
+// the mean of one pass's plane: dev_accum_read's kernel and copy over that plane
+int dev_accum_read_pass(bhray_dev* c, uint32_t pass, float* dst, size_t pitch) {
+    if (!c) return BHRAY_E_INVALID;
+    if (!c->a_begun) return fail(c, BHRAY_E_STATE, "bhray_accum_read_pass: bhray_accum_begin has not been called");
+    if (pass == 0 || (pass & (pass - 1)) != 0 || (pass & c->a_passes) != pass)
+        return fail(c, BHRAY_E_INVALID, "bhray_accum_read_pass: pass 0x%x is not one pass of this accumulation's set 0x%x", pass, c->a_passes);
+    const size_t rowb = (size_t)c->cfg.frame_w * sizeof(float4);
+    if (!dst || pitch < rowb) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
+    uint32_t b = 0;
+    while (!((pass >> b) & 1u)) b++;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_accum_mean(c->a_pass[b], c->a_mean, nullptr, c->cfg.frame_w * c->cfg.frame_h, c->q_stream));
     { int rc = query_wait(c); if (rc) return rc; }
     HIPCHK(c, hipMemcpy2D(dst, pitch, c->a_mean, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost));
     return BHRAY_OK;

@@ -130,6 +130,9 @@ int  dev_accum_set_launch_rays(bhray_dev* c, uint32_t max_rays);        // rays 
 int  dev_accum_set_camera(bhray_dev* c, const bhray_still_camera* cam); // still cameras: validates and stores; NULL: pinhole, no lens
 int  dev_accum_set_observer(bhray_dev* c, const bhray_observer* obs);   // the moving observer: validates and stores; NULL: at rest
 int  dev_accum_set_filter(bhray_dev* c, const bhray_still_filter* filter); // still pixel filters: validates and stores; NULL: the box
+int  dev_accum_set_passes(bhray_dev* c, uint32_t passes);  // still passes: validates and stores; the next dev_accum_begin takes the set
+int  dev_accum_passes(const bhray_dev* c, uint32_t* passes);   // the set of the current accumulation; 0 before dev_accum_begin
+int  dev_accum_read_pass(bhray_dev* c, uint32_t pass, float* dst_rgba32f, size_t pitch);   // the mean of one pass's plane, like dev_accum_read
 int  dev_accum_set_stars(bhray_dev* c, int32_t on);        // point stars in stills: validates and stores; 0 (the default) or 1
 // adaptive stills: min_samples for every pixel, then rounds of select - wait for the count - sample the failing pixels, until a selection is empty; blocks
 int  dev_accum_add_adaptive(bhray_dev* c, const bhray_accum_adaptive* params, bhray_accum_adaptive_info* info);

@@ -1709,6 +1709,26 @@ int bhray_accum_set_observer(bhray_ctx* c, const bhray_observer* obs) {
     for (Part& p : c->parts) if (p.dev) DEV(c, p.dev, dev_accum_set_observer(p.dev, obs));
     return BHRAY_OK;
 }
+// Still passes: the set is state of every local engine, accepted on any ctx - what cannot accumulate refuses bhray_accum_begin as before.
+int bhray_accum_set_passes(bhray_ctx* c, uint32_t passes) {
+    if (!c) return BHRAY_E_INVALID;
+    if (passes & ~(uint32_t)BHRAY_PASS_ALL) return gfail(c, BHRAY_E_INVALID, "bhray_accum_set_passes: unknown pass bits");   // before any engine stores it
+    for (Part& p : c->parts) if (p.dev) DEV(c, p.dev, dev_accum_set_passes(p.dev, passes));
+    return BHRAY_OK;
+}
+int bhray_accum_passes(const bhray_ctx* c, uint32_t* passes) {
+    if (!c || !passes) return BHRAY_E_INVALID;
+    *passes = 0;                                                  // a ctx that cannot accumulate carries no pass
+    if (c->cfg.device_count >= 2 || !c->single) return BHRAY_OK;
+    return dev_accum_passes(c->parts[0].dev, passes);
+}
+int bhray_accum_read_pass(bhray_ctx* c, uint32_t pass, float* dst, size_t pitch) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_accum_read_pass"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_accum_read_pass(c->parts[0].dev, pass, dst, pitch));
+    return BHRAY_OK;
+}
 int bhray_accum_set_launch_rays(bhray_ctx* c, uint32_t max_rays) {
     if (!c) return BHRAY_E_INVALID;
     ENTER(c);

@@ -1,7 +1,7 @@
 // bhray_render — minimal C++ host program over renderer.hpp: renders one frame of the reference's default scene
 // (camera (0,0,-19), hole at the origin, disk 2..10, R = 20; camera.rs:10-16, blackhole.rs:16-28) and writes the HDR frame
 // as raw little-endian f32 RGBA (row 0 = top).  Usage:
-//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--stars-seeded N SEED] [--observer VX VY VZ [--no-beaming]] [--pick X Y] [--path X Y [--path-stride S]]
+//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--stars-seeded N SEED] [--observer VX VY VZ [--no-beaming]] [--passes coverage,geometry,position,escape] [--pick X Y] [--path X Y [--path-stride S]]
 // --spp N: instead of the ladder's frame, a supersampled still - the mean of N jittered samples per frame pixel, sky resolved, accumulated on the GPU
 //   (Renderer::render_still: bhray_accum_*); written the same way.  Not with --devices or --panorama.
 // --spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]: an adaptive still instead - every pixel takes MIN samples, then R more (4 by default) for as long as the
@@ -20,6 +20,9 @@
 // --observer VX VY VZ [--no-beaming] (with --spp or --spp-adaptive): the still as an observer moving with velocity (VX, VY, VZ) sees it - static frame, world axes, units
 //   of c, at most 0.99 - (bhray_accum_set_observer): every look direction is Lorentz-aberrated on the GPU and every sample scaled by the bolometric D^4;
 //   --no-beaming keeps the aberration alone.  A zero velocity is no observer.
+// --passes LIST (with --spp; not with --spp-adaptive or --panorama): LIST names, separated by commas, the per-pixel maps the still carries beside its colour
+//   (bhray_accum_set_passes) - coverage (horizon, disk, mesh shares), geometry (closest approach, iterations, transmittance), position (the disk / mesh hit
+//   point, premultiplied by its coverage), escape (the mean escape direction).  Each goes to OUT.f32.<name> as raw f32 RGBA, the format of OUT.f32 itself.
 // --path X Y [--path-stride S]: after the frame, the pick line of pixel (X, Y) and then the light path behind it, one line per point - that pixel's pinhole ray through
 //   bhray_trace_rays_paths (Renderer::ray_path), a point every 2^S iterations (S = 0 by default) and the end point:
 //   ITERATION X Y Z
@@ -47,12 +50,14 @@
 // (mod.rs:382), every frame handed to host memory - in its three hand-off forms, and prints one JSON object (bench.py embeds it as `dropin`).
 // Textures: the disk texture comes from the reference's own generator (bhray_generate_disk_texture); the LUT and the sky
 // are flat grey here (this program demonstrates the host surface, the tests use the seeded assets).
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <string>
 
 #include "renderer.hpp"
 
@@ -180,13 +185,16 @@ int main(int argc, char** argv) {
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
         return 0;
     }
-    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--stars-seeded N SEED] [--observer VX VY VZ [--no-beaming]] [--pick X Y] [--path X Y [--path-stride S]]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--stars-seeded N SEED] [--observer VX VY VZ [--no-beaming]] [--passes coverage,geometry,position,escape] [--pick X Y] [--path X Y [--path-stride S]]\n", argv[0]); return 2; }
     uint32_t bw = 72, bh = 41, levels = 4, disk = 256, pano_w = 0, pano_h = 0;
     long pick_x = -1, pick_y = -1, path_x = -1, path_y = -1, path_stride = 0, spp = 0;
     bool rk = false, bvh_device = false, lensed = false, posed = false, adaptive = false;
     long a_min = 0, a_max = 0, a_round = 4, stars_n = 0, stars_seed = 0;
     double a_tol = 0.0, a_dark = 0.01;
     bool still_given = false, lens_given = false, filter_given = false, observer_given = false, no_beaming = false;
+    uint32_t passes = 0;
+    bool passes_given = false;
+    static const struct { const char* name; uint32_t bit; } pass_names[] = {{"coverage", BHRAY_PASS_COVERAGE}, {"geometry", BHRAY_PASS_GEOMETRY}, {"position", BHRAY_PASS_POSITION}, {"escape", BHRAY_PASS_ESCAPE}};
     bhray_observer observer{};
     bhray_observer_default(&observer);
     bhray_still_filter filter{};
@@ -263,6 +271,19 @@ int main(int argc, char** argv) {
             }
         }
         else if (!std::strcmp(argv[i], "--no-beaming")) no_beaming = true;
+        else if (!std::strcmp(argv[i], "--passes") && i + 1 < argc) {
+            passes_given = true;
+            const std::string list = argv[++i];
+            for (size_t a = 0; a <= list.size();) {
+                const size_t e = std::min(list.find(',', a), list.size());
+                const std::string name = list.substr(a, e - a);
+                uint32_t bit = 0;
+                for (const auto& pn : pass_names) if (name == pn.name) bit = pn.bit;
+                if (!bit) { std::fprintf(stderr, "--passes needs a comma-separated list of coverage, geometry, position, escape\n"); return 2; }
+                passes |= bit;
+                a = e + 1;
+            }
+        }
         else if (!std::strcmp(argv[i], "--pick") && i + 2 < argc) { pick_x = std::atol(argv[++i]); pick_y = std::atol(argv[++i]); if (pick_x < 0 || pick_y < 0) { std::fprintf(stderr, "--pick needs X >= 0 and Y >= 0\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--path") && i + 2 < argc) { path_x = std::atol(argv[++i]); path_y = std::atol(argv[++i]); if (path_x < 0 || path_y < 0) { std::fprintf(stderr, "--path needs X >= 0 and Y >= 0\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--path-stride") && i + 1 < argc) { path_stride = std::atol(argv[++i]); if (path_stride < 0 || path_stride > BHRAY_MAX_PATH_STRIDE_LOG2) { std::fprintf(stderr, "--path-stride needs 0 <= S <= %d\n", BHRAY_MAX_PATH_STRIDE_LOG2); return 2; } }
@@ -279,6 +300,9 @@ int main(int argc, char** argv) {
     if (stars_n && lens_given) { std::fprintf(stderr, "--stars-seeded needs footprints: not with --lens, whose neighbouring pixels look through different lens points\n"); return 2; }
     if (stars_n && !spp) { std::fprintf(stderr, "--stars-seeded in this mode is the star field of a still: give --spp\n"); return 2; }
     if (observer_given && !spp && !adaptive) { std::fprintf(stderr, "--observer is the observer of a still: give --spp or --spp-adaptive\n"); return 2; }
+    if (passes_given && adaptive) { std::fprintf(stderr, "--passes sums every sample of a launch's pixels: not with --spp-adaptive, whose adder works over a pixel list\n"); return 2; }
+    if (passes_given && pano_w) { std::fprintf(stderr, "--passes are the maps of a still over the pinhole frame: not with --panorama\n"); return 2; }
+    if (passes_given && !spp) { std::fprintf(stderr, "--passes are the maps of a still: give --spp\n"); return 2; }
     if (no_beaming && !observer_given) { std::fprintf(stderr, "--no-beaming goes with --observer\n"); return 2; }
     if (lens_given && still.projection != BHRAY_STILL_PINHOLE) { std::fprintf(stderr, "--lens goes with the pinhole projection only\n"); return 2; }
     if (spp && pano_w) { std::fprintf(stderr, "--spp samples the pixels of the pinhole frame: not with --panorama\n"); return 2; }
@@ -307,6 +331,7 @@ int main(int argc, char** argv) {
         r.mesh_lensing = lensed;
         r.lens_ray_batches = lensed && (spp || adaptive || pano_w || pick_x >= 0);        // the stills, the panorama and the pick trace ray batches: lensed too (BHRAY_LENS_RAYS)
         if (observer_given) { observer.beaming = no_beaming ? 0u : 1u; r.observer = observer; }
+        r.still_passes = passes;
         std::vector<float> out;
         std::vector<uint32_t> counts;
         bhray_accum_adaptive_info ainfo{};
@@ -329,6 +354,15 @@ int main(int argc, char** argv) {
         if (!f) { std::perror(argv[1]); return 1; }
         std::fwrite(out.data(), sizeof(float), out.size(), f);
         std::fclose(f);
+        for (const auto& pn : pass_names) {                        // the still's passes beside it: OUT.<name>, the same raw floats
+            if (!(passes & pn.bit)) continue;
+            const std::string path = std::string(argv[1]) + "." + pn.name;
+            const std::vector<float> plane = r.still_pass(pn.bit);
+            FILE* g = std::fopen(path.c_str(), "wb");
+            if (!g) { std::perror(path.c_str()); return 1; }
+            std::fwrite(plane.data(), sizeof(float), plane.size(), g);
+            std::fclose(g);
+        }
         std::printf("%ux%u\n", res.first, res.second);
         if (adaptive) {
             double total = 0.0;

@@ -288,6 +288,15 @@ public:
         observer.struct_size = (uint32_t)sizeof(bhray_observer);
         check(bhray_accum_set_observer(ctx_, &observer), ctx_);
     }
+    // still passes (bhray_accum_set_passes): the per-pixel maps the NEXT accumulate() carries beside its colour - an OR of BHRAY_PASS_*; 0: none.
+    // accumulate_adaptive() is refused in an accumulation that carries passes.
+    void set_still_passes(uint32_t passes) { check(bhray_accum_set_passes(ctx_, passes), ctx_); }
+    // one pass of the current accumulation (bhray_accum_read_pass): the mean over its samples under its filter, RGBA32F, 4 f32 per pixel
+    std::vector<float> still_pass(uint32_t pass) {
+        std::vector<float> out((size_t)cfg_.frame_w * cfg_.frame_h * 4);
+        check(bhray_accum_read_pass(ctx_, pass, out.data(), (size_t)cfg_.frame_w * 16), ctx_);
+        return out;
+    }
     bhray_ctx* ctx() { return ctx_; }
 private:
     bhray_config cfg_;
@@ -392,6 +401,7 @@ public:
     RayDetails ray_details;
     bool mesh_lensing = false;      // lensed meshes (bhray_set_mesh_lensing): models are tested inside the relativity sphere too; applied before each render
     bhray_observer observer{(uint32_t)sizeof(bhray_observer), {0.0f, 0.0f, 0.0f}, 1u};   // the moving observer of the stills; zero velocity: at rest; applied before each still
+    uint32_t still_passes = 0;      // still passes: the BHRAY_PASS_* maps render_still carries beside its colour (still_pass reads them); applied before each still
     bool lens_ray_batches = false;  // ... and, with it, in ray batches too (BHRAY_LENS_RAYS): render_rays, pick and the stills trace lensed; ray_path throws the ctx's error
     explicit Renderer(int device = 0) : ray_pipeline_({72, 41}, 3, 4, device) {}               // mod.rs:177-179
     Renderer(std::pair<uint32_t, uint32_t> base, uint32_t multiplier, uint32_t levels, int device = 0) : ray_pipeline_(base, multiplier, levels, device) {}
@@ -449,8 +459,11 @@ public:
         ray_pipeline_.set_still_filter(still_filter);
         ray_pipeline_.set_still_stars(stars);
         ray_pipeline_.set_still_observer(observer);
+        ray_pipeline_.set_still_passes(still_passes);
         return ray_pipeline_.accumulate(samples);
     }
+    // one pass of the last render_still (still_passes; RayPipeline::still_pass): BHRAY_PASS_COVERAGE, _GEOMETRY, _POSITION or _ESCAPE
+    std::vector<float> still_pass(uint32_t pass) { return ray_pipeline_.still_pass(pass); }
     // an adaptive still of the current scene (RayPipeline::accumulate_adaptive): params.struct_size is filled in here
     std::vector<float> render_still_adaptive(bhray_accum_adaptive params, bhray_accum_adaptive_info* info = nullptr, std::vector<uint32_t>* counts = nullptr,
                                              const bhray_still_camera* still_camera = nullptr) {
@@ -461,6 +474,7 @@ public:
         ray_pipeline_.set_still_filter(nullptr);                  // an adaptive still has no filter but the box
         ray_pipeline_.set_still_stars(false);                     // and no point stars
         ray_pipeline_.set_still_observer(observer);
+        ray_pipeline_.set_still_passes(0);                        // and no passes
         return ray_pipeline_.accumulate_adaptive(params, info, counts);
     }
     // what is under frame pixel (x, y): the record of that pixel's pinhole ray under the current scene (hit & 0xff: BHRAY_HIT_*; (hit >> 8) & 0xff: the model slot of a mesh hit)

@@ -118,6 +118,8 @@ class BhrayStillCamera(C.Structure):        # bhray_still_camera: the accumulati
 assert C.sizeof(BhrayStillCamera) == 20 and BhrayStillCamera.focus_distance.offset == 16
 
 FILTER_BOX, FILTER_TENT, FILTER_CUBIC = 0, 1, 2             # BHRAY_FILTER_*
+PASS_COVERAGE, PASS_GEOMETRY, PASS_POSITION, PASS_ESCAPE, PASS_ALL = 1, 2, 4, 8, 0xF     # BHRAY_PASS_*: the still passes (bhray_accum_set_passes)
+PASS_NAMES = {"coverage": PASS_COVERAGE, "geometry": PASS_GEOMETRY, "position": PASS_POSITION, "escape": PASS_ESCAPE}
 
 
 class BhrayStillFilter(C.Structure):        # bhray_still_filter: the accumulation image's reconstruction filter (bhray_accum_set_filter)
@@ -344,6 +346,10 @@ SYMBOLS = {
     "bhray_accum_set_stars": (C.c_int, [vp, i32]),
     "bhray_accum_stars_resolve_host": (C.c_int, [vp, u32, u32, i32, vp, u32, P(BhrayStarParams), vp]),
     "bhray_accum_set_observer": (C.c_int, [vp, P(BhrayObserver)]),
+    "bhray_accum_set_passes": (C.c_int, [vp, u32]),
+    "bhray_accum_passes": (C.c_int, [vp, P(u32)]),
+    "bhray_accum_read_pass": (C.c_int, [vp, u32, vp, sz]),
+    "bhray_accum_pass_values": (C.c_int, [vp, vp, vp, u32, u32, vp]),
     "bhray_observer_default": (None, [P(BhrayObserver)]),
     "bhray_observer_boost_rays": (C.c_int, [P(BhrayObserver), vp, u32, vp, vp]),
     "bhray_post_defaults": (C.c_int, [P(BhrayFxaaDetails), P(BhrayMixDetails)]),

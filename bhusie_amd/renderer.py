@@ -14,7 +14,7 @@ import numpy as np
 
 from ._lib import lib
 from .layouts import (BhrayFxaaDetails, BhrayMixDetails, DIAG_DISPLAY_FXAA_ONLY, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters, BhrayRay, BhrayRayRecord, BhrayPathPoint, PATH_POINT_DTYPE, HIT_MESH, HIT_UNUSABLE, LENS_FRAMES, LENS_RAYS,
-                      BhrayAccumAdaptive, BhrayAccumAdaptiveInfo, BhrayStar, BhrayStarParams, BhrayStillFilter, FILTER_BOX, FILTER_TENT, FILTER_CUBIC,
+                      BhrayAccumAdaptive, BhrayAccumAdaptiveInfo, BhrayStar, BhrayStarParams, BhrayStillFilter, FILTER_BOX, FILTER_TENT, FILTER_CUBIC, PASS_COVERAGE, PASS_GEOMETRY, PASS_POSITION, PASS_ESCAPE, PASS_ALL, PASS_NAMES,
                       BhrayGatherInfo, BhrayModelBuildInfo, BhrayModelDesc, BhrayRebalanceInfo, BhrayTiming, check)
 from .model import NODE_DTYPE, Model
 from .scene import BlackHole, Camera, RayDetails
@@ -186,6 +186,20 @@ def accum_stars_resolve_host(results, stars, params=None, wrap_x=False) -> np.nd
     out = np.empty_like(f)
     check(lib().bhray_accum_stars_resolve_host(f.ctypes.data, f.shape[1], f.shape[0], int(bool(wrap_x)), a.ctypes.data, n, C.byref(params) if params is not None else None,
                                                out.ctypes.data))
+    return out
+
+
+def accum_pass_values(results, records, rays, pass_bit: int) -> np.ndarray:
+    """What every sample contributes to one still pass (bhray_accum_pass_values, DESIGN.md §27: host arithmetic through the function the kernels call, no device):
+    (n, 4) float32 - (v, 1) for a taken sample, zeros for a skipped one.  results: (n, 4) trace results; records: n records of RAY_RECORD_DTYPE; rays: (n, 8), read
+    for PASS_ESCAPE only (None otherwise).  pass_bit: exactly one PASS_* bit (BhrayError otherwise)."""
+    r = np.ascontiguousarray(results, dtype=np.float32).reshape(-1, 4)
+    q = np.ascontiguousarray(records, dtype=RAY_RECORD_DTYPE).reshape(-1)
+    d = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8) if rays is not None else None
+    if q.shape[0] != r.shape[0] or (d is not None and d.shape[0] != r.shape[0]):
+        raise ValueError("accum_pass_values: results, records and rays must hold the same number of samples")
+    out = np.empty_like(r)
+    check(lib().bhray_accum_pass_values(r.ctypes.data, q.ctypes.data, d.ctypes.data if d is not None else None, r.shape[0], int(pass_bit), out.ctypes.data))
     return out
 
 
@@ -620,6 +634,28 @@ class RayPass:
         obs = velocity if isinstance(velocity, Observer) else Observer(tuple(float(v) for v in velocity), bool(beaming))
         s = obs.struct()
         check(self._L.bhray_accum_set_observer(self._h, C.byref(s)), self._h, self._L)
+
+    # -- still passes: coverage, geometry, position and escape maps beside the colour (bhray_accum_set_passes)
+    def accum_set_passes(self, passes: int = 0):
+        """The passes the next accum_begin's accumulation carries beside its colour: an OR of PASS_COVERAGE / PASS_GEOMETRY / PASS_POSITION / PASS_ESCAPE (layouts),
+        0 (the default) for none.  Each pass is one more sum plane over the same samples and the same filter; accum_add_adaptive is refused in an accumulation that
+        carries one (BHRAY_E_STATE).  Validates and stores only: the running accumulation keeps its set.  Unknown bits: BhrayError (BHRAY_E_INVALID)."""
+        check(self._L.bhray_accum_set_passes(self._h, int(passes)), self._h, self._L)
+
+    def accum_passes(self) -> int:
+        """The set of the current accumulation (0 before accum_begin)."""
+        n = C.c_uint32()
+        check(self._L.bhray_accum_passes(self._h, C.byref(n)), self._h, self._L)
+        return int(n.value)
+
+    def accum_read_pass(self, pass_bit: int) -> np.ndarray:
+        """The mean of one pass over the samples taken so far: (frame_h, frame_w, 4) float32 - (x / w, y / w, z / w, 1), zeros where the pixel took no sample.
+        COVERAGE: the horizon, disk and mesh shares; GEOMETRY: closest approach, iterations, transmittance; POSITION: the disk / mesh hit point premultiplied by its
+        coverage; ESCAPE: the mean escape direction (its length: the unobstructed share).  Waits.  A pass the accumulation does not carry: BhrayError (BHRAY_E_INVALID)."""
+        w, h = int(self.cfg.frame_w), int(self.cfg.frame_h)
+        out = np.empty((h, w, 4), dtype=np.float32)
+        check(self._L.bhray_accum_read_pass(self._h, int(pass_bit), out.ctypes.data, w * 16), self._h, self._L)
+        return out
 
     # -- adaptive stills: each pixel sampled until the error of its mean is under a bound (bhray_accum_add_adaptive, DESIGN.md §20)
     @staticmethod
@@ -1059,7 +1095,7 @@ class Renderer:
                 "closest": float(r["closest"]), "transmittance": float(r["transmittance"]),
                 "path": pts["position"][0, :k].copy(), "path_iterations": pts["iteration"][0, :k].copy()}
 
-    def _accumulate(self, samples: int, shutter: float, camera=None, filter=None, stars=False, observer=None):
+    def _accumulate(self, samples: int, shutter: float, camera=None, filter=None, stars=False, observer=None, passes=0):
         samples = int(samples)
         if samples < 1:
             raise ValueError(f"render_still: samples must be at least 1, got {samples}")
@@ -1068,6 +1104,7 @@ class Renderer:
         self.ray_pass.accum_set_filter(filter)
         self.ray_pass.accum_set_stars(bool(stars))
         self.ray_pass.accum_set_observer(observer)
+        self.ray_pass.accum_set_passes(self._pass_bits(passes))
         self.ray_pass.accum_begin()
         if not shutter > 0.0:
             self.ray_pass.accum_add(samples)
@@ -1081,8 +1118,33 @@ class Renderer:
         finally:
             self.ray_details.time = t0
 
+    @staticmethod
+    def _pass_bits(passes) -> int:
+        """an OR of PASS_* bits from an int, a pass name, or an iterable of names and bits"""
+        if passes is None:
+            return 0
+        if isinstance(passes, str):
+            passes = [p for p in passes.split(",") if p]
+        if isinstance(passes, (int, np.integer)):
+            return int(passes)
+        bits = 0
+        for p in passes:
+            if isinstance(p, str):
+                if p not in PASS_NAMES:
+                    raise ValueError(f"unknown still pass {p!r}: one of {', '.join(PASS_NAMES)}")
+                bits |= PASS_NAMES[p]
+            else:
+                bits |= int(p)
+        return bits
+
+    def still_pass(self, name_or_bit) -> np.ndarray:
+        """One pass of the last still rendered with `passes` (RayPass.accum_read_pass): "coverage", "geometry", "position", "escape" or the PASS_*
+        bit - (frame_h, frame_w, 4) float32, the mean over the still's samples under its filter.  A pass the still does not carry: BhrayError (BHRAY_E_INVALID)."""
+        bit = self._pass_bits(name_or_bit)
+        return self.ray_pass.accum_read_pass(bit)
+
     def render_still(self, samples: int = 16, shutter: float = 0.0, adaptive: AdaptiveStill | None = None, camera=None, filter=None, stars: bool = False,
-                     observer=None) -> np.ndarray:
+                     observer=None, passes=0) -> np.ndarray:
         """A supersampled still of the current scene (RayPass.accum_*): the mean of `samples` jittered samples per frame pixel, sky resolved,
         (frame_h, frame_w, 4) float32.  Sample 0 is the pixel centre, so samples=1 is the frame a `levels = 1` ladder renders, after the sky pass in binary32.
         shutter > 0: motion blur - sample s is rendered at ray_details.time + shutter * s / samples (the disk turns with `time`); ray_details.time is left as it was.
@@ -1098,10 +1160,14 @@ class Renderer:
         switch of the last still.
         observer: a cameras.Observer - the still as a moving observer sees it: Observer((vx, vy, vz)) aberrates every look direction by the
         velocity (static frame, world axes, units of c), and with beaming (the default) scales every sample by D^4; goes with `adaptive`, every camera, the filters and
-        the stars.  None: at rest.  The ctx keeps the observer of the last still."""
+        the stars.  None: at rest.  The ctx keeps the observer of the last still.
+        passes: the per-pixel maps the still carries beside its colour - an OR of PASS_COVERAGE / PASS_GEOMETRY / PASS_POSITION / PASS_ESCAPE, or
+        their names ("coverage,escape", ["geometry"]); still_pass(name) then delivers each.  The colour keeps its bits.  Not with `adaptive` (ValueError).  0: none."""
         if adaptive is None:
-            self._accumulate(samples, shutter, camera, filter, stars, observer)
+            self._accumulate(samples, shutter, camera, filter, stars, observer, passes)
             return self.ray_pass.accum_read()
+        if self._pass_bits(passes):
+            raise ValueError("render_still: an adaptive still carries no passes (its adder works over a pixel list)")
         if stars:
             raise ValueError("render_still: an adaptive still has no point stars (a round's pixels take different samples)")
         if filter is not None and filter.kind != FILTER_BOX:
@@ -1113,6 +1179,7 @@ class Renderer:
         self.ray_pass.accum_set_filter(None)
         self.ray_pass.accum_set_stars(False)
         self.ray_pass.accum_set_observer(observer)
+        self.ray_pass.accum_set_passes(0)
         self.ray_pass.accum_begin()
         self.still_info = self.ray_pass.accum_add_adaptive(**adaptive.as_kwargs())
         return self.ray_pass.accum_read()
@@ -1121,11 +1188,11 @@ class Renderer:
         """The sample-count heat map of the last adaptive still: (frame_h, frame_w) uint32."""
         return self.ray_pass.accum_read_counts()
 
-    def save_still(self, path, samples: int = 16, camera=None, filter=None, stars: bool = False, observer=None):
+    def save_still(self, path, samples: int = 16, camera=None, filter=None, stars: bool = False, observer=None, passes=0):
         """save_image for a supersampled still: the mean of `samples` samples per pixel through the display pass, written with alpha 255.  camera, filter, stars,
-        observer: as render_still's."""
+        observer, passes: as render_still's (still_pass delivers the passes afterwards)."""
         from PIL import Image
-        self._accumulate(samples, 0.0, camera, filter, stars, observer)
+        self._accumulate(samples, 0.0, camera, filter, stars, observer, passes)
         img = self.ray_pass.accum_read_display()
         img[..., 3] = 255
         Image.fromarray(img, "RGBA").save(path)

@@ -1004,6 +1004,58 @@ int  bhray_accum_set_observer(bhray_ctx* ctx, const bhray_observer* obs);   /* N
 void bhray_observer_default(bhray_observer* obs);                           /* zero velocity, beaming 1 */
 int  bhray_observer_boost_rays(const bhray_observer* obs, const bhray_ray* in, uint32_t n, bhray_ray* out, float* out_beam /* may be NULL */);
 
+/* Still passes (not in the reference): per-pixel maps of a still beside its colour - what every sample hit, how close
+ * it came to the hole, where it ended and in which direction it left - summed over the same samples, under the same reconstruction
+ * filter, on the device.  A compositor gets mattes whose edges are the colour's edges and a direction map; a scientific user the
+ * shadow's outline with sub-pixel coverage, the closest-approach map and the iteration (cost) map.
+ *
+ * bhray_accum_set_passes is per-ctx state like the still camera: it validates and stores, is accepted in every state and needs no
+ * device; a bit outside BHRAY_PASS_ALL: BHRAY_E_INVALID, the stored set untouched.  bhray_accum_begin fixes the stored set for the
+ * accumulation it starts and allocates (first use) and clears one RGBA32F sum plane per pass; a later bhray_accum_set_passes does not
+ * change the running accumulation.  bhray_accum_passes answers the set of the CURRENT accumulation (0 before bhray_accum_begin and on
+ * a ctx that cannot accumulate).  With the set 0 - the default - a still runs exactly the launches it ran without this interface: the
+ * same kernels, the same buffers, the same bits, nothing allocated.  With passes, every launch of bhray_accum_add traces through the
+ * record kernels (bhray_trace_rays_records', whose results are bit for bit those of the kernels without records, so the colour keeps
+ * its bits) and the pass work runs directly behind the trace, before the star stage, the beam and the add.
+ *
+ * The rule - all of it binary32, every operation rounded on its own in the order written, no FMA.  Per traced sample: R is the trace's
+ * result (before the sky resolve, the star stage and the beam), Q its record (bhray_ray_record; kind = Q.hit & 0xff), d the direction
+ * words of the ray as it was traced (under an observer: the boosted direction).
+ *   taken    The sample is SKIPPED for all passes iff R.x, R.y or R.z is not finite.  This is the passes' own rule, stated on R alone:
+ *            it differs from the colour's rule (stated on the resolved, starred, beamed colour) only where the resolve, a star's flux
+ *            or the beam makes a finite result non-finite - such a sample is in the passes and not in the colour.
+ *   values   a taken sample contributes (v, 1):
+ *            BHRAY_PASS_COVERAGE  v = (kind == HORIZON, kind == DISK, kind == MESH) as 1.0f / 0.0f; the escaped share is the remainder.
+ *            BHRAY_PASS_GEOMETRY  v = (Q.closest, float(Q.iterations), Q.transmittance); the conversion is one round-to-nearest-even.
+ *            BHRAY_PASS_POSITION  v = Q.position when kind is DISK or MESH, else zeros: premultiplied by coverage, as positions in
+ *                                 mattes are - the reader divides by the disk plus mesh coverage.
+ *            BHRAY_PASS_ESCAPE    R.w == 0: v = (R.x, R.y, R.z), the final direction of a ray that entered the sphere, left it and
+ *                                 hit nothing.  Otherwise, kind == NONE: v = d - the shader resolved the sky itself (i <= 5,
+ *                                 ray.wgsl:583) because the ray left the loop at once: exact for a ray that never entered the sphere;
+ *                                 for one that grazed it within five iterations this is the generated direction, not the feathered
+ *                                 one.  Otherwise zeros.  The mean vector's direction is the lens map, its length the unobstructed share.
+ *            A BHRAY_HIT_UNUSABLE sample (a fisheye sample outside the image circle) is taken: v = 0 in every pass, a finite black
+ *            sample as in the colour image.
+ *   sum      the colour's rule.  Box: plane[p] = plane[p] + (v, 1) in increasing s, whatever the grouping of samples into calls and
+ *            launches.  TENT / CUBIC: the stencil of bhray_accum_set_filter with the same ten weights over V(x', y') = (v, 1) for a
+ *            taken sample inside the frame and (0, 0, 0, 0) otherwise.
+ *   mean     bhray_accum_read_pass delivers (x / w, y / w, z / w, 1), zeros where w == 0 - bhray_accum_read's operation - as frame_h
+ *            rows of RGBA32F.
+ * bhray_accum_read_pass: BHRAY_E_STATE before bhray_accum_begin; BHRAY_E_INVALID for a `pass` that is not exactly one bit of the
+ * current accumulation's set.  bhray_accum_add_adaptive in an accumulation that carries passes: BHRAY_E_STATE, nothing enqueued (its
+ * adder works over a pixel list; a list form of the passes is not built).  Every existing refusal holds; passes go with every still
+ * camera, both filters, bhray_accum_set_stars, the observer and BHRAY_LENS_RAYS.
+ * bhray_accum_pass_values is host arithmetic through the function the kernels call - no ctx, no device: out[i] = (v, 1) of `pass`
+ * (exactly one bit) for a taken sample, (0, 0, 0, 0) for a skipped one.  rays may be NULL for every pass except BHRAY_PASS_ESCAPE.
+ * BHRAY_E_INVALID: another `pass`, or n > 0 with a NULL array it needs.                                                              */
+enum { BHRAY_PASS_COVERAGE = 1u << 0, BHRAY_PASS_GEOMETRY = 1u << 1, BHRAY_PASS_POSITION = 1u << 2, BHRAY_PASS_ESCAPE = 1u << 3,
+       BHRAY_PASS_ALL = 0xfu };
+int bhray_accum_set_passes(bhray_ctx* ctx, uint32_t passes);          /* validates and stores; in force from the next bhray_accum_begin */
+int bhray_accum_passes(const bhray_ctx* ctx, uint32_t* passes);       /* the set of the CURRENT accumulation (0 before bhray_accum_begin) */
+int bhray_accum_read_pass(bhray_ctx* ctx, uint32_t pass, float* dst_rgba32f, size_t row_pitch_bytes);   /* frame_h rows, like bhray_accum_read */
+int bhray_accum_pass_values(const float* results_rgba32f, const bhray_ray_record* records, const bhray_ray* rays, uint32_t n,
+                            uint32_t pass, float* out_rgba32f);      /* host arithmetic through the function the kernel calls; no ctx, no device */
+
 /* Display pass — the rest of the reference's GPU frame after the sky pass (mod.rs:209-324, run at 425-431): 5 bloom-down and
  * 5 bloom-up passes (bloom_down.wgsl, bloom_up.wgsl), mix (mix.wgsl), ACES tone mapping (hdr.wgsl) and FXAA (fxaa.wgsl) into the
  * Rgba8UnormSrgb target the reference's `Save Image` copies out (texture_to_output_buffer, mod.rs:491-526): frame_w x frame_h x 4
