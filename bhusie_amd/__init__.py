@@ -24,4 +24,4 @@ from .scene import Camera, BlackHole, RayDetails  # noqa: F401
 from .model import Model, load_model  # noqa: F401
 from . import cameras  # noqa: F401
 from .cameras import StillCamera, Observer  # noqa: F401
-from .renderer import RAY_RECORD_DTYPE, AdaptiveStill, StillFilter, RayPass, Renderer, PinnedFrame, ladder_from_base, ladder_for_frame, comm_unique_id, post_defaults, bloom_sizes, display_image, sky_pyramid_sizes, star_array, star_grid_size, star_cells, stars_resolve_host, accum_stars_resolve_host, accum_pass_values, PASS_COVERAGE, PASS_GEOMETRY, PASS_POSITION, PASS_ESCAPE, PASS_ALL, PASS_NAMES, stars_pixel_info_host, STAR_PIXEL_INFO_DTYPE, partition_rows, config_partition_rows, balance_slabs, rebalance_slabs, pose_from_euler  # noqa: F401
+from .renderer import RAY_RECORD_DTYPE, AdaptiveStill, StillFilter, StillDenoise, accum_denoise_host, RayPass, Renderer, PinnedFrame, ladder_from_base, ladder_for_frame, comm_unique_id, post_defaults, bloom_sizes, display_image, sky_pyramid_sizes, star_array, star_grid_size, star_cells, stars_resolve_host, accum_stars_resolve_host, accum_pass_values, PASS_COVERAGE, PASS_GEOMETRY, PASS_POSITION, PASS_ESCAPE, PASS_ALL, PASS_NAMES, stars_pixel_info_host, STAR_PIXEL_INFO_DTYPE, partition_rows, config_partition_rows, balance_slabs, rebalance_slabs, pose_from_euler  # noqa: F401

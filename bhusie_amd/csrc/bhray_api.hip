@@ -19,6 +19,7 @@
 #include "bhray_accum.h"
 #include "bhray_accum_filter.h"
 #include "bhray_accum_passes.h"
+#include "bhray_accum_denoise.h"
 #include "bhray_adapt.h"
 #include "bhray_stillcam.h"
 #include "bhray_bvh_core.h"
@@ -237,6 +238,9 @@ struct bhray_dev {
     float4* a_pass[ACCUM_PASS_COUNT] = {}; // one sum plane per pass, frame_w * frame_h: allocated by the first begin that carries the pass
     float4* a_rec = nullptr; size_t a_rec_cap = 0;           // one launch's ray records (2 float4 each), beside a_rays / a_res: grow-only
     float4* a_pimg = nullptr; size_t a_pimg_cap = 0;         // one pass's sample images of a launch under a tent or a cubic: grow-only
+    // denoised stills (dev_accum_read_denoised): the filter's working images, frame_w * frame_h texels each, allocated by the first read that needs them
+    float4* a_dn[2] = {};                  // the two ping-pong images (r, g, b, t)
+    float4* a_dng[3] = {};                 // the packed guide means: (coverage xyz, closest), position xyz, escape xyz
     uint32_t a_launch_rays = 0;            // dev_accum_set_launch_rays: rays per trace launch (0: BHRAY_ACCUM_LAUNCH_RAYS)
     bool a_begun = false;
     // adaptive stills (dev_accum_add_adaptive): allocated by the first adaptive call or selection; everything runs on q_stream
@@ -519,7 +523,8 @@ void dev_destroy(bhray_dev* c) {
     if (c->q_hcnt) (void)hipHostFree(c->q_hcnt);
     if (c->q_dcnt) (void)hipFree(c->q_dcnt);
     for (void* p : {(void*)c->a_sum, (void*)c->a_mean, (void*)c->a_mean16, (void*)c->a_scratch, (void*)c->a_disp, (void*)c->a_rays, (void*)c->a_res, (void*)c->a_state, (void*)c->a_list, (void*)c->a_ctl, (void*)c->a_rec, (void*)c->a_pimg,
-                    (void*)c->a_pass[0], (void*)c->a_pass[1], (void*)c->a_pass[2], (void*)c->a_pass[3]}) if (p) (void)hipFree(p);
+                    (void*)c->a_pass[0], (void*)c->a_pass[1], (void*)c->a_pass[2], (void*)c->a_pass[3],
+                    (void*)c->a_dn[0], (void*)c->a_dn[1], (void*)c->a_dng[0], (void*)c->a_dng[1], (void*)c->a_dng[2]}) if (p) (void)hipFree(p);
     if (c->a_hctl) (void)hipHostFree(c->a_hctl);
     for (hipEvent_t e : {c->q_begin, c->q_done, c->q_uploaded}) if (e) (void)hipEventDestroy(e);
     if (c->q_stream) (void)hipStreamDestroy(c->q_stream);
@@ -1870,6 +1875,98 @@ int dev_accum_read_display(bhray_dev* c, uint8_t* dst, size_t pitch, const bhray
     if (!c->a_scratch) HIPCHK(c, hipMalloc(&c->a_scratch, display_scratch_bytes(c->cfg.frame_w, c->cfg.frame_h)));
     if (!c->a_disp) HIPCHK(c, hipMalloc(&c->a_disp, (size_t)npix * sizeof(uint32_t)));
     HIPCHK(c, launch_accum_mean(c->a_sum, c->a_mean, c->a_mean16, npix, c->q_stream));
+    HIPCHK(c, launch_display(c->a_mean16, c->a_scratch, c->a_disp, c->cfg.frame_w, c->cfg.frame_h, *fx, *mx, c->q_stream));
+    { int rc = query_wait(c); if (rc) return rc; }
+    HIPCHK(c, hipMemcpy2D(dst, pitch, c->a_disp, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost));
+    return BHRAY_OK;
+}
+
+// Denoised stills: prepare, then one a-trous launch per iteration, on the query stream behind the samples.  Reads a_sum and the pass planes, writes
+// a_mean and the filter's own images: no accumulation state changes.  The answer is left in *result; with `display`, its RGBA16F rounding in a_mean16.
+namespace {
+// ev (may be nullptr): 2 + iterations events, recorded before the prepare launch and behind every launch (dev_accum_denoise_times).
+int accum_denoise_enqueue(bhray_dev* c, const char* name, const bhray_still_denoise* p, bool display, float4** result, hipEvent_t* ev = nullptr) {
+    if (c->a_passes == 0) return fail(c, BHRAY_E_STATE, "%s: this accumulation carries no still passes (bhray_accum_set_passes before bhray_accum_begin): the filter has no guide", name);
+    if (c->a_mode == 2) return fail(c, BHRAY_E_STATE, "%s: this accumulation is adaptive", name);
+    bhray_still_denoise defaults;
+    if (!p) { bhray_still_denoise_default(&defaults); p = &defaults; }
+    if (const char* why = still_denoise_error(p, c->a_passes)) return fail(c, BHRAY_E_INVALID, "%s: %s (the set is 0x%x)", name, why, c->a_passes);
+    DenoiseRule rule;
+    denoise_rule_fill(rule, p, c->a_passes);
+    const uint32_t npix = c->cfg.frame_w * c->cfg.frame_h;
+    HIPCHK(c, hipSetDevice(c->device));
+    for (int i = 0; i < 2; i++) if (!c->a_dn[i]) HIPCHK(c, hipMalloc(&c->a_dn[i], (size_t)npix * sizeof(float4)));
+    const uint32_t needs[3] = {DENOISE_NEEDS_G0, DENOISE_NEEDS_G1, DENOISE_NEEDS_G2};
+    for (int i = 0; i < 3; i++) if ((rule.guides & needs[i]) && !c->a_dng[i]) HIPCHK(c, hipMalloc(&c->a_dng[i], (size_t)npix * sizeof(float4)));
+    if (display && !c->a_mean16) HIPCHK(c, hipMalloc(&c->a_mean16, (size_t)npix * sizeof(uint2)));
+    AccumPassPlanes planes;
+    for (uint32_t b = 0; b < ACCUM_PASS_COUNT; b++) planes.plane[b] = (rule.guides >> b) & 1u ? c->a_pass[b] : nullptr;
+    float4* g[3];
+    for (int i = 0; i < 3; i++) g[i] = (rule.guides & needs[i]) ? c->a_dng[i] : nullptr;
+    if (ev) HIPCHK(c, hipEventRecord(ev[0], c->q_stream));
+    HIPCHK(c, launch_denoise_prepare(c->a_sum, planes, rule.guides, c->a_mean, c->a_dn[0], g[0], g[1], g[2], npix, c->q_stream));
+    if (ev) HIPCHK(c, hipEventRecord(ev[1], c->q_stream));
+    for (uint32_t it = 0; it < p->iterations; it++) {
+        const bool last = it + 1 == p->iterations;
+        HIPCHK(c, launch_denoise_atrous(rule, c->a_dn[it & 1], g[0], g[1], g[2], c->a_mean, c->a_dn[(it + 1) & 1], last && display ? c->a_mean16 : nullptr,
+                                        c->cfg.frame_w, c->cfg.frame_h, 1u << it, last, c->q_stream));
+        if (ev) HIPCHK(c, hipEventRecord(ev[2 + it], c->q_stream));
+    }
+    *result = c->a_dn[p->iterations & 1];
+    return BHRAY_OK;
+}
+}  // namespace
+
+int dev_accum_read_denoised(bhray_dev* c, const bhray_still_denoise* p, float* dst, size_t pitch) {
+    if (!c) return BHRAY_E_INVALID;
+    if (!c->a_begun) return fail(c, BHRAY_E_STATE, "bhray_accum_read_denoised: bhray_accum_begin has not been called");
+    const size_t rowb = (size_t)c->cfg.frame_w * sizeof(float4);
+    if (!dst || pitch < rowb) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
+    float4* result = nullptr;
+    { int rc = accum_denoise_enqueue(c, "bhray_accum_read_denoised", p, false, &result); if (rc) return rc; }
+    { int rc = query_wait(c); if (rc) return rc; }
+    HIPCHK(c, hipMemcpy2D(dst, pitch, result, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost));
+    return BHRAY_OK;
+}
+
+// bhray_diag.h: the launches of dev_accum_read_denoised with an event between them; delivers no image
+int dev_accum_denoise_times(bhray_dev* c, const bhray_still_denoise* p, float ms[6]) {
+    if (!c) return BHRAY_E_INVALID;
+    if (!ms) return fail(c, BHRAY_E_INVALID, "bhray_accum_denoise_times: NULL ms");
+    if (!c->a_begun) return fail(c, BHRAY_E_STATE, "bhray_accum_denoise_times: bhray_accum_begin has not been called");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipEvent_t ev[2 + BHRAY_DENOISE_MAX_ITERATIONS] = {};
+    int rc = BHRAY_OK;
+    for (hipEvent_t& e : ev) if (hipEventCreate(&e) != hipSuccess) rc = fail(c, BHRAY_E_HIP, "bhray_accum_denoise_times: hipEventCreate failed");
+    float4* result = nullptr;
+    if (!rc) rc = accum_denoise_enqueue(c, "bhray_accum_denoise_times", p, false, &result, ev);
+    if (!rc) rc = query_wait(c);
+    if (!rc) {
+        const uint32_t iterations = p ? p->iterations : 0;        // nullptr: the defaults'
+        bhray_still_denoise d;
+        bhray_still_denoise_default(&d);
+        const uint32_t n = iterations ? iterations : d.iterations;
+        for (uint32_t i = 0; i < 1 + BHRAY_DENOISE_MAX_ITERATIONS; i++) {
+            ms[i] = 0.0f;
+            if (i < 1 + n && hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]) != hipSuccess) rc = fail(c, BHRAY_E_HIP, "bhray_accum_denoise_times: hipEventElapsedTime failed");
+        }
+    }
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    return rc;
+}
+
+// denoised mean -> RGBA16F (the last a-trous launch) -> the display pass (launch_display, unchanged) with the ctx's post uniforms -> RGBA8
+int dev_accum_read_display_denoised(bhray_dev* c, const bhray_still_denoise* p, uint8_t* dst, size_t pitch, const bhray_fxaa_details* fx, const bhray_mix_details* mx) {
+    if (!c || !fx || !mx) return BHRAY_E_INVALID;
+    if (!c->a_begun) return fail(c, BHRAY_E_STATE, "bhray_accum_read_display_denoised: bhray_accum_begin has not been called");
+    { int rc = display_whole_frame(c); if (rc) return rc; }
+    const size_t rowb = (size_t)c->cfg.frame_w * sizeof(uint32_t);
+    if (!dst || pitch < rowb) return fail(c, BHRAY_E_INVALID, "bad destination / pitch");
+    float4* result = nullptr;
+    { int rc = accum_denoise_enqueue(c, "bhray_accum_read_display_denoised", p, true, &result); if (rc) return rc; }
+    const uint32_t npix = c->cfg.frame_w * c->cfg.frame_h;
+    if (!c->a_scratch) HIPCHK(c, hipMalloc(&c->a_scratch, display_scratch_bytes(c->cfg.frame_w, c->cfg.frame_h)));
+    if (!c->a_disp) HIPCHK(c, hipMalloc(&c->a_disp, (size_t)npix * sizeof(uint32_t)));
     HIPCHK(c, launch_display(c->a_mean16, c->a_scratch, c->a_disp, c->cfg.frame_w, c->cfg.frame_h, *fx, *mx, c->q_stream));
     { int rc = query_wait(c); if (rc) return rc; }
     HIPCHK(c, hipMemcpy2D(dst, pitch, c->a_disp, rowb, rowb, c->cfg.frame_h, hipMemcpyDeviceToHost));

@@ -133,6 +133,10 @@ int  dev_accum_set_filter(bhray_dev* c, const bhray_still_filter* filter); // st
 int  dev_accum_set_passes(bhray_dev* c, uint32_t passes);  // still passes: validates and stores; the next dev_accum_begin takes the set
 int  dev_accum_passes(const bhray_dev* c, uint32_t* passes);   // the set of the current accumulation; 0 before dev_accum_begin
 int  dev_accum_read_pass(bhray_dev* c, uint32_t pass, float* dst_rgba32f, size_t pitch);   // the mean of one pass's plane, like dev_accum_read
+// denoised stills: dev_accum_read / dev_accum_read_display behind the a-trous filter guided by the passes; p == nullptr: the defaults
+int  dev_accum_read_denoised(bhray_dev* c, const bhray_still_denoise* p, float* dst_rgba32f, size_t pitch);
+int  dev_accum_denoise_times(bhray_dev* c, const bhray_still_denoise* p, float ms[6]);   // bhray_diag.h: its launches' times from events; no image
+int  dev_accum_read_display_denoised(bhray_dev* c, const bhray_still_denoise* p, uint8_t* dst_rgba8, size_t pitch, const bhray_fxaa_details* fx, const bhray_mix_details* mx);
 int  dev_accum_set_stars(bhray_dev* c, int32_t on);        // point stars in stills: validates and stores; 0 (the default) or 1
 // adaptive stills: min_samples for every pixel, then rounds of select - wait for the count - sample the failing pixels, until a selection is empty; blocks
 int  dev_accum_add_adaptive(bhray_dev* c, const bhray_accum_adaptive* params, bhray_accum_adaptive_info* info);

@@ -1729,6 +1729,28 @@ int bhray_accum_read_pass(bhray_ctx* c, uint32_t pass, float* dst, size_t pitch)
     DEV(c, c->parts[0].dev, dev_accum_read_pass(c->parts[0].dev, pass, dst, pitch));
     return BHRAY_OK;
 }
+// Denoised stills: the reads of the accumulation image behind the a-trous filter guided by the still passes.
+int bhray_accum_read_denoised(bhray_ctx* c, const bhray_still_denoise* p, float* dst, size_t pitch) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_accum_read_denoised"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_accum_read_denoised(c->parts[0].dev, p, dst, pitch));
+    return BHRAY_OK;
+}
+int bhray_accum_denoise_times(bhray_ctx* c, const bhray_still_denoise* p, float ms[6]) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_accum_denoise_times"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_accum_denoise_times(c->parts[0].dev, p, ms));
+    return BHRAY_OK;
+}
+int bhray_accum_read_display_denoised(bhray_ctx* c, const bhray_still_denoise* p, uint8_t* dst, size_t pitch) {
+    if (!c) return BHRAY_E_INVALID;
+    ENTER(c);
+    { int rc = rays_entry(c, "bhray_accum_read_display_denoised"); if (rc) return rc; }
+    DEV(c, c->parts[0].dev, dev_accum_read_display_denoised(c->parts[0].dev, p, dst, pitch, &c->post_fxaa, &c->post_mix));
+    return BHRAY_OK;
+}
 int bhray_accum_set_launch_rays(bhray_ctx* c, uint32_t max_rays) {
     if (!c) return BHRAY_E_INVALID;
     ENTER(c);

@@ -101,6 +101,10 @@ static_assert(BHRAY_MAX_PATH_STRIDE_LOG2 == 16&& BHRAY_MAX_PATH_POINTS_PER_CALL 
 static_assert(BHRAY_HIT_NONE == 0 && BHRAY_HIT_HORIZON == 1 && BHRAY_HIT_DISK == 2 && BHRAY_HIT_MESH == 3 && BHRAY_HIT_UNUSABLE == 255, "BHRAY_HIT_*");
 // the still passes of bhray_accum_set_passes: one bit and one sum plane each
 static_assert(BHRAY_PASS_COVERAGE == 1 && BHRAY_PASS_GEOMETRY == 2 && BHRAY_PASS_POSITION == 4 && BHRAY_PASS_ESCAPE == 8 && BHRAY_PASS_ALL == 15, "BHRAY_PASS_*");
+// the parameters of the denoised stills
+static_assert(sizeof(bhray_still_denoise) == 32, "bhray_still_denoise");
+OFF(bhray_still_denoise, struct_size, 0); OFF(bhray_still_denoise, iterations, 4); OFF(bhray_still_denoise, guides, 8); OFF(bhray_still_denoise, sigma_colour, 12); OFF(bhray_still_denoise, sigma_escape, 28);
+static_assert(BHRAY_DENOISE_MAX_ITERATIONS == 5u, "BHRAY_DENOISE_MAX_ITERATIONS");
 
 // not reference layouts, but ABI the bindings restate (bhusie_amd/layouts.py)
 static_assert(sizeof(bhray_counters) == 104, "bhray_counters");

@@ -1,7 +1,7 @@
 // bhray_render — minimal C++ host program over renderer.hpp: renders one frame of the reference's default scene
 // (camera (0,0,-19), hole at the origin, disk 2..10, R = 20; camera.rs:10-16, blackhole.rs:16-28) and writes the HDR frame
 // as raw little-endian f32 RGBA (row 0 = top).  Usage:
-//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--stars-seeded N SEED] [--observer VX VY VZ [--no-beaming]] [--passes coverage,geometry,position,escape] [--pick X Y] [--path X Y [--path-stride S]]
+//   bhray_render OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,2,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--stars-seeded N SEED] [--observer VX VY VZ [--no-beaming]] [--passes coverage,geometry,position,escape] [--denoise [ITERATIONS]] [--pick X Y] [--path X Y [--path-stride S]]
 // --spp N: instead of the ladder's frame, a supersampled still - the mean of N jittered samples per frame pixel, sky resolved, accumulated on the GPU
 //   (Renderer::render_still: bhray_accum_*); written the same way.  Not with --devices or --panorama.
 // --spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]: an adaptive still instead - every pixel takes MIN samples, then R more (4 by default) for as long as the
@@ -23,6 +23,9 @@
 // --passes LIST (with --spp; not with --spp-adaptive or --panorama): LIST names, separated by commas, the per-pixel maps the still carries beside its colour
 //   (bhray_accum_set_passes) - coverage (horizon, disk, mesh shares), geometry (closest approach, iterations, transmittance), position (the disk / mesh hit
 //   point, premultiplied by its coverage), escape (the mean escape direction).  Each goes to OUT.f32.<name> as raw f32 RGBA, the format of OUT.f32 itself.
+// --denoise [ITERATIONS] (with --spp; not with --spp-adaptive or --panorama): the still is written through the edge-avoiding a-trous filter guided by its passes
+//   (bhray_accum_read_denoised) in place of the plain mean; ITERATIONS (1 .. 5, the library's default when left out) levels at tap spacing 1, 2, 4, 8,
+//   16 pixels, every other parameter the library's default.  Without --passes the still carries all four passes for it (none is written); with --passes, those.
 // --path X Y [--path-stride S]: after the frame, the pick line of pixel (X, Y) and then the light path behind it, one line per point - that pixel's pinhole ray through
 //   bhray_trace_rays_paths (Renderer::ray_path), a point every 2^S iterations (S = 0 by default) and the end point:
 //   ITERATION X Y Z
@@ -185,7 +188,7 @@ int main(int argc, char** argv) {
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
         return 0;
     }
-    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--stars-seeded N SEED] [--observer VX VY VZ [--no-beaming]] [--passes coverage,geometry,position,escape] [--pick X Y] [--path X Y [--path-stride S]]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s OUT.f32 [--rk] [--base W H] [--levels N] [--disk-size S] [--obj mesh.obj]... [--bvh reference|device] [--pose RX RY RZ] [--lensed-mesh] [--devices 0,1,...] [--panorama W H] [--spp N] [--spp-adaptive MIN MAX TOL [--spp-round R] [--spp-dark D]] [--still-camera pinhole|equirect|fisheye FOV] [--lens RADIUS FOCUS] [--filter tent RADIUS|cubic RADIUS B C] [--stars-seeded N SEED] [--observer VX VY VZ [--no-beaming]] [--passes coverage,geometry,position,escape] [--denoise [ITERATIONS]] [--pick X Y] [--path X Y [--path-stride S]]\n", argv[0]); return 2; }
     uint32_t bw = 72, bh = 41, levels = 4, disk = 256, pano_w = 0, pano_h = 0;
     long pick_x = -1, pick_y = -1, path_x = -1, path_y = -1, path_stride = 0, spp = 0;
     bool rk = false, bvh_device = false, lensed = false, posed = false, adaptive = false;
@@ -193,7 +196,9 @@ int main(int argc, char** argv) {
     double a_tol = 0.0, a_dark = 0.01;
     bool still_given = false, lens_given = false, filter_given = false, observer_given = false, no_beaming = false;
     uint32_t passes = 0;
-    bool passes_given = false;
+    bool passes_given = false, denoise_given = false;
+    bhray_still_denoise denoise{};
+    bhray_still_denoise_default(&denoise);
     static const struct { const char* name; uint32_t bit; } pass_names[] = {{"coverage", BHRAY_PASS_COVERAGE}, {"geometry", BHRAY_PASS_GEOMETRY}, {"position", BHRAY_PASS_POSITION}, {"escape", BHRAY_PASS_ESCAPE}};
     bhray_observer observer{};
     bhray_observer_default(&observer);
@@ -284,6 +289,14 @@ int main(int argc, char** argv) {
                 a = e + 1;
             }
         }
+        else if (!std::strcmp(argv[i], "--denoise")) {
+            denoise_given = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {
+                const long n = std::atol(argv[++i]);
+                if (n < 1 || n > (long)BHRAY_DENOISE_MAX_ITERATIONS) { std::fprintf(stderr, "--denoise needs 1 <= ITERATIONS <= %u\n", BHRAY_DENOISE_MAX_ITERATIONS); return 2; }
+                denoise.iterations = (uint32_t)n;
+            }
+        }
         else if (!std::strcmp(argv[i], "--pick") && i + 2 < argc) { pick_x = std::atol(argv[++i]); pick_y = std::atol(argv[++i]); if (pick_x < 0 || pick_y < 0) { std::fprintf(stderr, "--pick needs X >= 0 and Y >= 0\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--path") && i + 2 < argc) { path_x = std::atol(argv[++i]); path_y = std::atol(argv[++i]); if (path_x < 0 || path_y < 0) { std::fprintf(stderr, "--path needs X >= 0 and Y >= 0\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--path-stride") && i + 1 < argc) { path_stride = std::atol(argv[++i]); if (path_stride < 0 || path_stride > BHRAY_MAX_PATH_STRIDE_LOG2) { std::fprintf(stderr, "--path-stride needs 0 <= S <= %d\n", BHRAY_MAX_PATH_STRIDE_LOG2); return 2; } }
@@ -303,6 +316,9 @@ int main(int argc, char** argv) {
     if (passes_given && adaptive) { std::fprintf(stderr, "--passes sums every sample of a launch's pixels: not with --spp-adaptive, whose adder works over a pixel list\n"); return 2; }
     if (passes_given && pano_w) { std::fprintf(stderr, "--passes are the maps of a still over the pinhole frame: not with --panorama\n"); return 2; }
     if (passes_given && !spp) { std::fprintf(stderr, "--passes are the maps of a still: give --spp\n"); return 2; }
+    if (denoise_given && adaptive) { std::fprintf(stderr, "--denoise is guided by the passes of a still: not with --spp-adaptive, which carries none\n"); return 2; }
+    if (denoise_given && pano_w) { std::fprintf(stderr, "--denoise filters a still over the pinhole frame: not with --panorama\n"); return 2; }
+    if (denoise_given && !spp) { std::fprintf(stderr, "--denoise filters a still: give --spp\n"); return 2; }
     if (no_beaming && !observer_given) { std::fprintf(stderr, "--no-beaming goes with --observer\n"); return 2; }
     if (lens_given && still.projection != BHRAY_STILL_PINHOLE) { std::fprintf(stderr, "--lens goes with the pinhole projection only\n"); return 2; }
     if (spp && pano_w) { std::fprintf(stderr, "--spp samples the pixels of the pinhole frame: not with --panorama\n"); return 2; }
@@ -331,7 +347,7 @@ int main(int argc, char** argv) {
         r.mesh_lensing = lensed;
         r.lens_ray_batches = lensed && (spp || adaptive || pano_w || pick_x >= 0);        // the stills, the panorama and the pick trace ray batches: lensed too (BHRAY_LENS_RAYS)
         if (observer_given) { observer.beaming = no_beaming ? 0u : 1u; r.observer = observer; }
-        r.still_passes = passes;
+        r.still_passes = denoise_given && !passes ? (uint32_t)BHRAY_PASS_ALL : passes;
         std::vector<float> out;
         std::vector<uint32_t> counts;
         bhray_accum_adaptive_info ainfo{};
@@ -346,6 +362,7 @@ int main(int argc, char** argv) {
         } else if (spp) {
             if (stars_n > 0) r.ray_pipeline().set_stars(bhusie::star_catalogue((uint32_t)stars_n, (uint32_t)stars_seed));
             out = r.render_still((uint32_t)spp, &still, filter_given ? &filter : nullptr, stars_n > 0);
+            if (denoise_given) out = r.still_denoised(&denoise);   // in place of the plain mean
         } else {
             r.render(0.0f);
             out = r.ray_pipeline().output();

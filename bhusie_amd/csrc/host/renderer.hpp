@@ -297,6 +297,16 @@ public:
         check(bhray_accum_read_pass(ctx_, pass, out.data(), (size_t)cfg_.frame_w * 16), ctx_);
         return out;
     }
+    // denoised stills (bhray_accum_read_denoised): the current accumulation's image through the a-trous filter guided by its passes, RGBA32F;
+    // null: the library's defaults.  struct_size is filled in here.  The accumulation must carry passes (set_still_passes) and must not be adaptive.
+    std::vector<float> accumulation_denoised(const bhray_still_denoise* denoise = nullptr) {
+        std::vector<float> out((size_t)cfg_.frame_w * cfg_.frame_h * 4);
+        if (!denoise) { check(bhray_accum_read_denoised(ctx_, nullptr, out.data(), (size_t)cfg_.frame_w * 16), ctx_); return out; }
+        bhray_still_denoise d = *denoise;
+        d.struct_size = (uint32_t)sizeof(bhray_still_denoise);
+        check(bhray_accum_read_denoised(ctx_, &d, out.data(), (size_t)cfg_.frame_w * 16), ctx_);
+        return out;
+    }
     bhray_ctx* ctx() { return ctx_; }
 private:
     bhray_config cfg_;
@@ -462,6 +472,9 @@ public:
         ray_pipeline_.set_still_passes(still_passes);
         return ray_pipeline_.accumulate(samples);
     }
+    // the last render_still denoised (RayPipeline::accumulation_denoised): that still must have carried passes (still_passes != 0).  Reads only: the
+    // plain still, its passes and further denoised reads with other parameters stay available.
+    std::vector<float> still_denoised(const bhray_still_denoise* denoise = nullptr) { return ray_pipeline_.accumulation_denoised(denoise); }
     // one pass of the last render_still (still_passes; RayPipeline::still_pass): BHRAY_PASS_COVERAGE, _GEOMETRY, _POSITION or _ESCAPE
     std::vector<float> still_pass(uint32_t pass) { return ray_pipeline_.still_pass(pass); }
     // an adaptive still of the current scene (RayPipeline::accumulate_adaptive): params.struct_size is filled in here

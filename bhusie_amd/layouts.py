@@ -129,6 +129,15 @@ class BhrayStillFilter(C.Structure):        # bhray_still_filter: the accumulati
 assert C.sizeof(BhrayStillFilter) == 20 and BhrayStillFilter.c.offset == 16
 
 
+class BhrayStillDenoise(C.Structure):       # bhray_still_denoise: the parameters of a denoised read of the accumulation image (bhray_accum_read_denoised)
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("guides", C.c_uint32), ("sigma_colour", C.c_float), ("sigma_coverage", C.c_float),
+                ("sigma_closest", C.c_float), ("sigma_position", C.c_float), ("sigma_escape", C.c_float)]
+
+
+assert C.sizeof(BhrayStillDenoise) == 32 and BhrayStillDenoise.sigma_escape.offset == 28
+DENOISE_MAX_ITERATIONS = 5                  # BHRAY_DENOISE_MAX_ITERATIONS
+
+
 class BhrayObserver(C.Structure):           # bhray_observer: the moving observer of a still (bhray_accum_set_observer)
     _fields_ = [("struct_size", C.c_uint32), ("velocity", C.c_float * 3), ("beaming", C.c_uint32)]
 
@@ -350,6 +359,10 @@ SYMBOLS = {
     "bhray_accum_passes": (C.c_int, [vp, P(u32)]),
     "bhray_accum_read_pass": (C.c_int, [vp, u32, vp, sz]),
     "bhray_accum_pass_values": (C.c_int, [vp, vp, vp, u32, u32, vp]),
+    "bhray_still_denoise_default": (None, [P(BhrayStillDenoise)]),
+    "bhray_accum_read_denoised": (C.c_int, [vp, P(BhrayStillDenoise), vp, sz]),
+    "bhray_accum_read_display_denoised": (C.c_int, [vp, P(BhrayStillDenoise), vp, sz]),
+    "bhray_accum_denoise_host": (C.c_int, [vp, P(vp), u32, u32, P(BhrayStillDenoise), vp]),
     "bhray_observer_default": (None, [P(BhrayObserver)]),
     "bhray_observer_boost_rays": (C.c_int, [P(BhrayObserver), vp, u32, vp, vp]),
     "bhray_post_defaults": (C.c_int, [P(BhrayFxaaDetails), P(BhrayMixDetails)]),
@@ -398,6 +411,7 @@ DIAG_SYMBOLS = {
     "bhray_read_model_bvh": (C.c_int, [vp, u32, vp, u32, vp, u32, P(u32), P(u32)]),
     "bhray_read_model_vertices": (C.c_int, [vp, u32, vp, u32, vp, u32, P(u32), P(u32)]),
     "bhray_accum_sample_rays": (C.c_int, [vp, u32, P(BhrayRay)]),
+    "bhray_accum_denoise_times": (C.c_int, [vp, P(BhrayStillDenoise), P(C.c_float)]),
     "bhray_accum_set_launch_rays": (C.c_int, [vp, u32]),
     "bhray_still_sample_rays_host": (C.c_int, [P(BhrayConfig), vp, P(BhrayStillCamera), u32, P(BhrayRay)]),
     "bhray_observer_sample_rays_host": (C.c_int, [P(BhrayConfig), vp, P(BhrayStillCamera), P(BhrayObserver), u32, vp, vp]),

@@ -14,7 +14,7 @@ import numpy as np
 
 from ._lib import lib
 from .layouts import (BhrayFxaaDetails, BhrayMixDetails, DIAG_DISPLAY_FXAA_ONLY, MAX_MODELS, PARTITION_SLABS, F_COUNTERS, F_EVAL_FMA, F_GATHER_SKY, F_LITERAL, F_TEMPORAL, F_TIMING, F_TIMING_SPARSE, GATHER_RCCL, TEX_DISK, TEX_SKY, TEX_TEMP_LUT, BhrayConfig, BhrayCounters, BhrayRay, BhrayRayRecord, BhrayPathPoint, PATH_POINT_DTYPE, HIT_MESH, HIT_UNUSABLE, LENS_FRAMES, LENS_RAYS,
-                      BhrayAccumAdaptive, BhrayAccumAdaptiveInfo, BhrayStar, BhrayStarParams, BhrayStillFilter, FILTER_BOX, FILTER_TENT, FILTER_CUBIC, PASS_COVERAGE, PASS_GEOMETRY, PASS_POSITION, PASS_ESCAPE, PASS_ALL, PASS_NAMES,
+                      BhrayAccumAdaptive, BhrayAccumAdaptiveInfo, BhrayStar, BhrayStarParams, BhrayStillFilter, BhrayStillDenoise, FILTER_BOX, FILTER_TENT, FILTER_CUBIC, PASS_COVERAGE, PASS_GEOMETRY, PASS_POSITION, PASS_ESCAPE, PASS_ALL, PASS_NAMES,
                       BhrayGatherInfo, BhrayModelBuildInfo, BhrayModelDesc, BhrayRebalanceInfo, BhrayTiming, check)
 from .model import NODE_DTYPE, Model
 from .scene import BlackHole, Camera, RayDetails
@@ -70,6 +70,42 @@ class StillFilter:
 
     def __repr__(self):
         return f"StillFilter(kind={self.kind}, radius={self.radius}, b={self.b}, c={self.c})"
+
+
+class StillDenoise:
+    """The parameters of a denoised read of a still (Renderer.render_still(denoise=...), RayPass.accum_read_denoised; bhray_still_denoise): an
+    edge-avoiding a-trous filter of `iterations` levels (1 .. 5: tap spacing 1, 2, 4, 8, 16 pixels) over the colour mean, guided by the still's passes.  guides: 0 -
+    every pass the still carries - or a non-empty subset of them (PASS_* bits).  Each sigma is the difference at which a tap's weight reaches zero: of the compressed
+    luminance, of the coverage vector, of the closest approach, of the premultiplied hit position and of the escape vector.  A sigma left None takes the library's
+    default (bhray_still_denoise_default), and so does iterations."""
+
+    def __init__(self, iterations: int | None = None, guides: int = 0, sigma_colour: float | None = None, sigma_coverage: float | None = None,
+                 sigma_closest: float | None = None, sigma_position: float | None = None, sigma_escape: float | None = None):
+        d = BhrayStillDenoise()
+        lib().bhray_still_denoise_default(C.byref(d))
+        self.iterations = int(d.iterations if iterations is None else iterations)
+        self.guides = int(guides)
+        self.sigma_colour = float(d.sigma_colour if sigma_colour is None else sigma_colour)
+        self.sigma_coverage = float(d.sigma_coverage if sigma_coverage is None else sigma_coverage)
+        self.sigma_closest = float(d.sigma_closest if sigma_closest is None else sigma_closest)
+        self.sigma_position = float(d.sigma_position if sigma_position is None else sigma_position)
+        self.sigma_escape = float(d.sigma_escape if sigma_escape is None else sigma_escape)
+
+    def struct(self) -> BhrayStillDenoise:
+        """the bhray_still_denoise the library takes"""
+        return BhrayStillDenoise(C.sizeof(BhrayStillDenoise), self.iterations, self.guides, self.sigma_colour, self.sigma_coverage, self.sigma_closest,
+                                 self.sigma_position, self.sigma_escape)
+
+    def __repr__(self):
+        return (f"StillDenoise(iterations={self.iterations}, guides={self.guides}, sigma_colour={self.sigma_colour}, sigma_coverage={self.sigma_coverage}, "
+                f"sigma_closest={self.sigma_closest}, sigma_position={self.sigma_position}, sigma_escape={self.sigma_escape})")
+
+
+def _denoise_struct(denoise):
+    """None (the library's defaults), True (the same), a StillDenoise or a BhrayStillDenoise -> the struct to pass, or None"""
+    if denoise is None or denoise is True:
+        return None
+    return denoise.struct() if hasattr(denoise, "struct") else denoise
 
 
 def ladder_from_base(base=(72, 41), multiplier=3, levels=4) -> BhrayConfig:
@@ -200,6 +236,29 @@ def accum_pass_values(results, records, rays, pass_bit: int) -> np.ndarray:
         raise ValueError("accum_pass_values: results, records and rays must hold the same number of samples")
     out = np.empty_like(r)
     check(lib().bhray_accum_pass_values(r.ctypes.data, q.ctypes.data, d.ctypes.data if d is not None else None, r.shape[0], int(pass_bit), out.ctypes.data))
+    return out
+
+
+def accum_denoise_host(colour, guides, denoise=None) -> np.ndarray:
+    """The denoiser's rule on the host (bhray_accum_denoise_host, DESIGN.md §28: host arithmetic through the functions the kernels call, no device).  colour: the
+    (h, w, 4) float32 colour mean; guides: {PASS_* bit: (h, w, 4) float32 pass mean} - the planes present are the set; denoise: a StillDenoise or None (the defaults).
+    Returns the (h, w, 4) float32 denoised mean.  BhrayError where the parameters are refused."""
+    c = np.ascontiguousarray(colour, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 4:
+        raise ValueError("accum_denoise_host: colour must be (h, w, 4)")
+    planes, keep = (C.c_void_p * 4)(), []
+    for bit, g in dict(guides).items():
+        bit = int(bit)
+        if bit not in (PASS_COVERAGE, PASS_GEOMETRY, PASS_POSITION, PASS_ESCAPE):
+            raise ValueError(f"accum_denoise_host: {bit} is not one PASS_* bit")
+        a = np.ascontiguousarray(g, dtype=np.float32)
+        if a.shape != c.shape:
+            raise ValueError("accum_denoise_host: a guide plane must have the colour's shape")
+        keep.append(a)
+        planes[bit.bit_length() - 1] = a.ctypes.data
+    st = _denoise_struct(denoise)
+    out = np.empty_like(c)
+    check(lib().bhray_accum_denoise_host(c.ctypes.data, planes, c.shape[1], c.shape[0], C.byref(st) if st is not None else None, out.ctypes.data))
     return out
 
 
@@ -587,6 +646,33 @@ class RayPass:
         w, h = int(self.cfg.frame_w), int(self.cfg.frame_h)
         out = np.empty((h, w, 4), dtype=np.uint8)
         check(self._L.bhray_accum_read_display(self._h, out.ctypes.data, w * 4), self._h, self._L)
+        return out
+
+    # -- denoised stills: the reads behind an edge-avoiding a-trous filter guided by the passes (bhray_accum_read_denoised)
+    def accum_read_denoised(self, denoise=None) -> np.ndarray:
+        """accum_read's image denoised: a StillDenoise, or None for the library's defaults.  The accumulation must carry passes (accum_set_passes) and must not be
+        adaptive (BhrayError, BHRAY_E_STATE).  Changes no accumulation state: accum_add may continue and accum_read keeps its bits.  Waits."""
+        w, h = int(self.cfg.frame_w), int(self.cfg.frame_h)
+        out = np.empty((h, w, 4), dtype=np.float32)
+        st = _denoise_struct(denoise)
+        check(self._L.bhray_accum_read_denoised(self._h, C.byref(st) if st is not None else None, out.ctypes.data, w * 16), self._h, self._L)
+        return out
+
+    def accum_denoise_times(self, denoise=None) -> list:
+        """The device time of accum_read_denoised's launches in milliseconds, from events (bhray_diag.h): [prepare, a-trous at spacing 1, 2, ...], one entry per
+        iteration.  Delivers no image and changes no accumulation state.  Waits."""
+        ms = (C.c_float * 6)()
+        st = _denoise_struct(denoise)
+        check(self._L.bhray_accum_denoise_times(self._h, C.byref(st) if st is not None else None, ms), self._h, self._L)
+        n = st.iterations if st is not None else StillDenoise().iterations
+        return [float(v) for v in ms[:1 + n]]
+
+    def accum_read_display_denoised(self, denoise=None) -> np.ndarray:
+        """accum_read_display's image of the denoised mean: uint8 (frame_h, frame_w, 4).  Waits."""
+        w, h = int(self.cfg.frame_w), int(self.cfg.frame_h)
+        out = np.empty((h, w, 4), dtype=np.uint8)
+        st = _denoise_struct(denoise)
+        check(self._L.bhray_accum_read_display_denoised(self._h, C.byref(st) if st is not None else None, out.ctypes.data, w * 4), self._h, self._L)
         return out
 
     def accum_sample_rays(self, s: int) -> np.ndarray:
@@ -1144,7 +1230,7 @@ class Renderer:
         return self.ray_pass.accum_read_pass(bit)
 
     def render_still(self, samples: int = 16, shutter: float = 0.0, adaptive: AdaptiveStill | None = None, camera=None, filter=None, stars: bool = False,
-                     observer=None, passes=0) -> np.ndarray:
+                     observer=None, passes=0, denoise=None) -> np.ndarray:
         """A supersampled still of the current scene (RayPass.accum_*): the mean of `samples` jittered samples per frame pixel, sky resolved,
         (frame_h, frame_w, 4) float32.  Sample 0 is the pixel centre, so samples=1 is the frame a `levels = 1` ladder renders, after the sky pass in binary32.
         shutter > 0: motion blur - sample s is rendered at ray_details.time + shutter * s / samples (the disk turns with `time`); ray_details.time is left as it was.
@@ -1162,10 +1248,18 @@ class Renderer:
         velocity (static frame, world axes, units of c), and with beaming (the default) scales every sample by D^4; goes with `adaptive`, every camera, the filters and
         the stars.  None: at rest.  The ctx keeps the observer of the last still.
         passes: the per-pixel maps the still carries beside its colour - an OR of PASS_COVERAGE / PASS_GEOMETRY / PASS_POSITION / PASS_ESCAPE, or
-        their names ("coverage,escape", ["geometry"]); still_pass(name) then delivers each.  The colour keeps its bits.  Not with `adaptive` (ValueError).  0: none."""
+        their names ("coverage,escape", ["geometry"]); still_pass(name) then delivers each.  The colour keeps its bits.  Not with `adaptive` (ValueError).  0: none.
+        denoise: a StillDenoise, or True for the library's defaults - the still is delivered through the a-trous filter guided by its passes; with
+        passes == 0 all four passes are switched on.  None or False: the plain mean.  Not with `adaptive` (ValueError)."""
+        if denoise is False:
+            denoise = None
+        if denoise is not None and adaptive is not None:
+            raise ValueError("render_still: an adaptive still is not denoised (it carries no passes)")
         if adaptive is None:
+            if denoise is not None and self._pass_bits(passes) == 0:
+                passes = PASS_ALL
             self._accumulate(samples, shutter, camera, filter, stars, observer, passes)
-            return self.ray_pass.accum_read()
+            return self.ray_pass.accum_read() if denoise is None else self.ray_pass.accum_read_denoised(denoise)
         if self._pass_bits(passes):
             raise ValueError("render_still: an adaptive still carries no passes (its adder works over a pixel list)")
         if stars:
@@ -1188,12 +1282,16 @@ class Renderer:
         """The sample-count heat map of the last adaptive still: (frame_h, frame_w) uint32."""
         return self.ray_pass.accum_read_counts()
 
-    def save_still(self, path, samples: int = 16, camera=None, filter=None, stars: bool = False, observer=None, passes=0):
+    def save_still(self, path, samples: int = 16, camera=None, filter=None, stars: bool = False, observer=None, passes=0, denoise=None):
         """save_image for a supersampled still: the mean of `samples` samples per pixel through the display pass, written with alpha 255.  camera, filter, stars,
-        observer, passes: as render_still's (still_pass delivers the passes afterwards)."""
+        observer, passes, denoise: as render_still's (still_pass delivers the passes afterwards)."""
         from PIL import Image
+        if denoise is False:
+            denoise = None
+        if denoise is not None and self._pass_bits(passes) == 0:
+            passes = PASS_ALL
         self._accumulate(samples, 0.0, camera, filter, stars, observer, passes)
-        img = self.ray_pass.accum_read_display()
+        img = self.ray_pass.accum_read_display() if denoise is None else self.ray_pass.accum_read_display_denoised(denoise)
         img[..., 3] = 255
         Image.fromarray(img, "RGBA").save(path)
 

@@ -1056,6 +1056,57 @@ int bhray_accum_read_pass(bhray_ctx* ctx, uint32_t pass, float* dst_rgba32f, siz
 int bhray_accum_pass_values(const float* results_rgba32f, const bhray_ray_record* records, const bhray_ray* rays, uint32_t n,
                             uint32_t pass, float* out_rgba32f);      /* host arithmetic through the function the kernel calls; no ctx, no device */
 
+/* Denoised stills (not in the reference): a read-time, edge-avoiding a-trous filter over the accumulation image, guided
+ * by the still passes.  The one sample source that is random per pixel is the thin lens; a lens still of a few samples is grainy, and
+ * the passes beside its sum say where its edges are.  bhray_accum_read_denoised delivers what bhray_accum_read delivers, filtered; it is
+ * a pure function of the colour mean and the pass means of the current accumulation: it changes no accumulation state,
+ * bhray_accum_add may continue afterwards, and bhray_accum_read keeps its bits.  With these entry points uncalled nothing is allocated
+ * and every existing launch sequence is unchanged.  Everything is enqueued on the accumulation's stream behind the samples; only the
+ * read waits.
+ *
+ * The rule - all of it binary32, every operation rounded on its own in the order written, no FMA.
+ *   inputs   C_0[p] is the colour mean exactly as bhray_accum_read delivers it (alpha 1, or 0 where the pixel took no sample);
+ *            M_g[p] the mean of guide pass g exactly as bhray_accum_read_pass delivers it.  Guides are never filtered.
+ *   valid    valid_i(p) iff C_i[p].w == 1 and C_i[p].x, .y and .z are finite (the exponent bits are not all ones).
+ *   t        t_i(p), the adaptive stills' compressed luminance of C_i[p]:  Y = (0.2126f * r + 0.7152f * g) + 0.0722f * b;
+ *            Y = Y < 0 ? 0 : Y;  t = Y >= 0x1p100f ? 1.0f : Y / (1.0f + Y).
+ *   E        the stop function E(d2, s2):  q = d2 / s2;  u = 1.0f - q;  E = u > 0 ? u * u : 0 (a NaN gives 0).  Each
+ *            s2 = sigma * sigma is formed once on the host.
+ *   step     iteration i = 0 .. iterations - 1 with tap spacing step = 1 << i.  A pixel that is not valid keeps its value:
+ *            C_{i+1}[p] = C_i[p].  For a valid pixel p = (x, y):  acc = (0, 0, 0), ws = 0; then for b = -2 .. 2 (outer) and
+ *            a = -2 .. 2 (inner), q = (x + a * step, y + b * step), skipped when q is outside the frame or not valid_i:
+ *              w = h[|a|] * h[|b|], h = {0.375f, 0.25f, 0.0625f};
+ *              w = w * E((t_i(p) - t_i(q))^2, s2_colour);
+ *              then for each guide of the set in bit order, w = w * E(d2, s2_guide) with
+ *                BHRAY_PASS_COVERAGE  d2 = (dx * dx + dy * dy) + dz * dz over the xyz of M[p] - M[q];
+ *                BHRAY_PASS_GEOMETRY  d2 = d * d, d the difference of .x (the closest approach) only;
+ *                BHRAY_PASS_POSITION  d2 as for coverage, over the position means, premultiplied as they are;
+ *                BHRAY_PASS_ESCAPE    d2 as for coverage, over the escape means;
+ *              acc.c = acc.c + w * C_i[q].c for c = x, y, z;  ws = ws + w.
+ *            C_{i+1}[p] = ws > 0 ? (acc.x / ws, acc.y / ws, acc.z / ws, 1) : C_i[p].
+ *   answer   C_iterations, frame_h rows of RGBA32F.  bhray_accum_read_display_denoised rounds it to RGBA16F (nearest even) and runs
+ *            bhray_accum_read_display's display pass over it unchanged.
+ * guides == 0 means every pass of the current accumulation's set; otherwise it is a non-empty subset of that set.
+ * Refusals: every refusal of bhray_accum_read / bhray_accum_read_display holds (before bhray_accum_begin: BHRAY_E_STATE; a bad
+ * destination or pitch; a frame under 32 x 32 for the display form).  BHRAY_E_STATE in an accumulation whose pass set is 0 and in an
+ * adaptive accumulation.  BHRAY_E_INVALID, nothing launched: a wrong struct_size, iterations outside 1 .. 5, guides with a bit outside
+ * the current set, a sigma that is not finite or not > 0.
+ * bhray_accum_denoise_host is host arithmetic through the functions the kernels call - no ctx, no device: colour and every plane of
+ * guide are w * h RGBA32F texels (the means as the reads deliver them); plane i belongs to bit 1u << i, NULL where absent, and the
+ * present planes are "the set".  BHRAY_E_INVALID: a NULL colour, guide or out, w or h of 0, no plane present, or p as above.          */
+#define BHRAY_DENOISE_MAX_ITERATIONS 5u
+typedef struct bhray_still_denoise {
+    uint32_t struct_size;     /* = sizeof(bhray_still_denoise) */
+    uint32_t iterations;      /* 1 .. 5: a-trous levels, tap spacing 1, 2, 4, 8, 16 pixels */
+    uint32_t guides;          /* 0: every pass of the current accumulation's set; else a non-empty subset of it */
+    float sigma_colour, sigma_coverage, sigma_closest, sigma_position, sigma_escape;   /* each finite and > 0 */
+} bhray_still_denoise;
+void bhray_still_denoise_default(bhray_still_denoise* p);   /* 2 iterations, every guide; the sigmas of DESIGN.md §28 */
+int  bhray_accum_read_denoised(bhray_ctx* ctx, const bhray_still_denoise* p /* NULL = defaults */, float* dst_rgba32f, size_t row_pitch_bytes);
+int  bhray_accum_read_display_denoised(bhray_ctx* ctx, const bhray_still_denoise* p, uint8_t* dst_rgba8, size_t row_pitch_bytes);
+int  bhray_accum_denoise_host(const float* colour_rgba32f, const float* const guide_rgba32f[4] /* plane i = bit 1u << i, NULL = absent */,
+                              uint32_t w, uint32_t h, const bhray_still_denoise* p, float* out_rgba32f);   /* host arithmetic, no ctx, no device */
+
 /* Display pass — the rest of the reference's GPU frame after the sky pass (mod.rs:209-324, run at 425-431): 5 bloom-down and
  * 5 bloom-up passes (bloom_down.wgsl, bloom_up.wgsl), mix (mix.wgsl), ACES tone mapping (hdr.wgsl) and FXAA (fxaa.wgsl) into the
  * Rgba8UnormSrgb target the reference's `Save Image` copies out (texture_to_output_buffer, mod.rs:491-526): frame_w x frame_h x 4

@@ -193,6 +193,11 @@ int bhray_still_sample_rays_host(const bhray_config* cfg, const void* camera_uni
  * into one launch.  0 restores the default, 2^22; more than BHRAY_MAX_RAYS_PER_CALL: BHRAY_E_INVALID.  The image
  * does not depend on it.                                                                                             */
 int bhray_accum_set_launch_rays(bhray_ctx* ctx, uint32_t max_rays);
+/* The launches of bhray_accum_read_denoised with a HIP event between them, no image delivered: ms[0] is the
+ * prepare launch, ms[1 + i] the a-trous launch of iteration i (tap spacing 1 << i), 0 for the iterations p does not ask
+ * for.  Milliseconds of device time.  Refuses what bhray_accum_read_denoised refuses; a NULL ms: BHRAY_E_INVALID.  Changes
+ * no accumulation state.  Waits.                                                                                       */
+int bhray_accum_denoise_times(bhray_ctx* ctx, const bhray_still_denoise* p, float ms[6]);
 /* One selection of bhray_accum_add_adaptive under `params` without sampling: the frame pixels
  * (y * frame_w + x) with issued < max_samples that are not converged, in the order the selection kernel compacted them
  * (unspecified between blocks).  *n is their number, the first min(*n, cap) go to out (out may be NULL when cap is
